@@ -94,8 +94,50 @@ def parse():
                          "torch: the model wrapped in torch DistributedDataParallel(find_unused_parameters=True) exactly as the "
                          "reference does (alignn/train.py:207), per-tensor fused AdamW, eager steps - the reference's wrap beside ours")
     ap.add_argument("--eager-steps", type=int, default=5,
-                    help="extra informational run of this many eagerly launched steps on the resident batch (0: skip)")
+                    help="the same --steps K steps also launched eagerly on the resident batch, before any capture (0: skip); "
+                         "the faster of the two launch modes is the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed - prediction, "
+                         "loss, parameter gradients, updated parameters (alignn_ff: + forces and stresses) - as DIR/<name>.npy "
+                         "(rank 0)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def host_outputs(model, outs, loss):
+    """float32 host copies of what one training step hands its caller: the model outputs, the loss, the parameter gradients
+    and the parameters after the optimizer step (both flat, in model.parameters() order; no gradient: zeros)."""
+    import numpy as np
+
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outs.items()}
+    arrays["loss"] = loss.detach().float().reshape(1).cpu().numpy()
+    params = list(model.parameters())
+    arrays["grads"] = torch.cat([(p_.grad if p_.grad is not None else torch.zeros_like(p_)).detach().float().reshape(-1)
+                                 for p_ in params]).cpu().numpy()
+    arrays["params"] = torch.cat([p_.detach().float().reshape(-1) for p_ in params]).cpu().numpy()
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+
+
+def write_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array; past DUMP_BUDGET_BYTES in all, the arrays of more than 2^20 values are cut to a fixed
+    sample (seeded, sorted positions) of the same share of each."""
+    import numpy as np
+
+    total = sum(a.nbytes for a in arrays.values())
+    big = sum(a.nbytes for a in arrays.values() if a.size > 1 << 20)
+    keep = 1.0 if total <= DUMP_BUDGET_BYTES else max(DUMP_BUDGET_BYTES - (total - big), 0) / float(big)
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if keep < 1.0 and a.size > 1 << 20:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, int(flat.size * keep), replace=False))
+            a = flat[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def spawn_ranks(n):
@@ -588,6 +630,10 @@ def main():
             sync.sync()
         opt.step()  # (FlatAdamW: packs the gradients, all-reduces the packed buffer, updates)
 
+    # --dump-outputs: the outputs of the latest step (device tensors; copied to the host after the timed loop only)
+    dump = args.dump_outputs is not None and rank == 0
+    last_out = {}
+    dumped = None
     if args.model == "alignn_ff":
         # SURVEY 8(d) cfg 4: loss = L1(energy) + L1(forces) + L1(stress), differentiating THROUGH the forces
         f_tgt = torch.randn(raw.num_nodes, 3, generator=torch.Generator().manual_seed(7 + rank)).to(dev)
@@ -600,13 +646,18 @@ def main():
             loss = l1(o["out"], target) + l1(o["grad"], f_tgt) + l1(o["stresses"], s_tgt)
             (loss if loss_scale == 1.0 else loss * loss_scale).backward()
             reduce_and_update()
+            if dump:
+                last_out.update(pred=o["out"].detach(), forces=o["grad"].detach(), stresses=o["stresses"].detach())
             return loss
     else:
         def step():
             zero_grad()
-            loss = torch.nn.functional.l1_loss(predict(batch), target)
+            pred = predict(batch)
+            loss = torch.nn.functional.l1_loss(pred, target)
             (loss if loss_scale == 1.0 else loss * loss_scale).backward()
             reduce_and_update()
+            if dump:
+                last_out.update(pred=pred.detach())
             return loss
 
     main_prio = os.environ.get("ALIGNN_BENCH_MAIN_PRIORITY")
@@ -633,7 +684,7 @@ def main():
     # enqueued by two C calls (alignn_amd/cmodel.py), or from Python (ALIGNN_AMD_CMODEL=0)
     eager_step = step
     eager = None
-    n_eager = max(args.eager_steps, args.steps) if args.eager_steps > 0 else 0  # (K steps: the same protocol as the replays)
+    n_eager = args.steps if args.eager_steps > 0 else 0  # (K steps: the same protocol as the replays)
     if n_eager > 0 and os.environ.get("ALIGNN_BENCH_EAGER", "0") != "1":
         for _ in range(2):
             eager_step()
@@ -772,8 +823,13 @@ def main():
                     o_ = model(batch)
                     l1_ = torch.nn.functional.l1_loss
                     g_loss = l1_(o_["out"], target) + l1_(o_["grad"], f_tgt) + l1_(o_["stresses"], s_tgt)
+                    if dump:  # (static outputs: every replay rewrites them)
+                        last_out.update(pred=o_["out"].detach(), forces=o_["grad"].detach(), stresses=o_["stresses"].detach())
                 else:
-                    g_loss = torch.nn.functional.l1_loss(predict(batch), target)
+                    g_pred = predict(batch)
+                    g_loss = torch.nn.functional.l1_loss(g_pred, target)
+                    if dump:
+                        last_out.update(pred=g_pred.detach())
                 (g_loss if loss_scale == 1.0 else g_loss * loss_scale).backward()
             ops.reset_amax_arena()
             g_grads = [p_.grad for p_ in params]  # static buffers the replays write into (None: parameter unused)
@@ -804,6 +860,11 @@ def main():
     t_enq = time.perf_counter() - t0  # host time to ENQUEUE the steps (no device sync inside)
     fence()
     dt = time.perf_counter() - t0
+    # (the last step of THIS loop whichever launch mode is the headline: the eager and the replayed steps compute bit-identical
+    # results, and this step is the same training step in every run with the same arguments)
+    if dump:
+        dumped = write_outputs(args.dump_outputs, host_outputs(model, last_out, loss))
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
     multi = None
     if world > 1:
         dt_rank = dt
@@ -1082,6 +1143,8 @@ def main():
             "streamed_batches": streamed,
             "loss": round(float(loss.item()), 6),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if not args.no_cpu_baseline and world == 1:
             if args.model == "alignn_ff":
                 out["cpu_baseline"] = cpu_baseline_ff(n_atoms, sample=min(B, args.cpu_graphs or 4))

@@ -112,6 +112,13 @@ def _bench(args, env_extra, timeout=900):
     return json.loads(lines[0]), r.stderr
 
 
+def _ranks_for_the_rehearsal():
+    """Eight ranks, one per GPU, where eight GPUs are visible.  Where fewer are, the ranks share cuda:0 beside this test
+    process, and four ranks keep the processes holding that one device few: the same launch path and the same assertions,
+    on 4 x --batch graphs."""
+    return 8 if torch.cuda.device_count() >= 8 else 4
+
+
 SMALL = ["--steps", "3", "--warmup", "1", "--batch", "8", "--atoms", "20", "--no-cpu-baseline", "--eager-steps", "2",
          "--streamed-steps", "0"]
 
@@ -133,14 +140,16 @@ def test_bench_two_ranks_on_one_gpu_with_hipgraph_capture_beside_the_collective(
 
 
 def test_eight_ranks_on_one_gpu_rehearsal_of_the_drivers_scaling_run():
-    """The launch shape of the driver's 8-GPU scaling run, rehearsed on the one GPU of this box: ``bench.py --gpus 8`` self-
-    spawned, eight ranks sharing the device (gloo collectives), 8 crystals per rank, eagerly launched steps AND hipGraph
-    replays beside the packed-gradient all-reduce.  Every rank is counted, nothing deadlocks, and after the timed steps every
-    rank holds BIT-identical parameters (the data-parallel invariant: a rank that missed or raced a collective would drift)."""
-    out, err = _bench(["--gpus", "8"] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
-    assert out["n_gpus"] == 8 and out["config"]["global_batch"] == 64 and out["config"]["parallelism"] == "dp8"
+    """The launch shape of the driver's 8-GPU scaling run, rehearsed: ``bench.py --gpus 8`` self-spawned (``--gpus 4`` sharing
+    cuda:0 on a box with fewer than eight GPUs: _ranks_for_the_rehearsal), gloo collectives, 8 crystals per rank, eagerly
+    launched steps AND hipGraph replays beside the packed-gradient all-reduce.  Every rank is counted, nothing deadlocks, and
+    after the timed steps every rank holds BIT-identical parameters (the data-parallel invariant: a rank that missed or raced
+    a collective would drift)."""
+    n = _ranks_for_the_rehearsal()
+    out, err = _bench(["--gpus", str(n)] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
+    assert out["n_gpus"] == n and out["config"]["global_batch"] == 8 * n and out["config"]["parallelism"] == f"dp{n}"
     mg = out["multi_gpu"]
-    assert mg["ranks_seen"] == 8 and mg["collectives_per_step"] == 1
+    assert mg["ranks_seen"] == n and mg["collectives_per_step"] == 1
     assert mg["parameters_bit_equal_across_ranks"] is True, mg
     assert mg["rank_host_enqueue_ms_per_step_min"] <= mg["rank_host_enqueue_ms_per_step_max"]
     assert out["replayed_steps"] is not None and out["replayed_steps"]["ms_per_step"] > 0, (out["step_launch"], err[-1500:])
@@ -151,28 +160,32 @@ def test_eight_ranks_on_one_gpu_rehearsal_of_the_drivers_scaling_run():
 def test_eight_ranks_molecules_sharded_by_cost_rehearsal():
     """``bench.py --gpus 8 --kind molecule`` splits ONE global batch of irregular molecules with
     ``ddp.shard_by_cost`` on the line-graph rows T (every rank computes the same partition, nothing is communicated) and reports
-    the rows and graphs each rank owns and each rank's own forward + backward time.  Eight ranks on this box's one GPU, gloo."""
-    out, err = _bench(["--gpus", "8", "--kind", "molecule", "--steps", "3", "--warmup", "1", "--batch", "16", "--no-cpu-baseline",
-                       "--eager-steps", "2", "--streamed-steps", "0"], {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
-    assert out["n_gpus"] == 8 and out["config"]["global_batch"] == 128
+    the rows and graphs each rank owns and each rank's own forward + backward time.  Eight ranks (four sharing one GPU:
+    _ranks_for_the_rehearsal), gloo."""
+    n = _ranks_for_the_rehearsal()
+    out, err = _bench(["--gpus", str(n), "--kind", "molecule", "--steps", "3", "--warmup", "1", "--batch", "16",
+                       "--no-cpu-baseline", "--eager-steps", "2", "--streamed-steps", "0"], {"ALIGNN_BENCH_BACKEND": "gloo"},
+                      timeout=1500)
+    assert out["n_gpus"] == n and out["config"]["global_batch"] == 16 * n
     mg = out["multi_gpu"]
     sh = mg["sharding"]
-    assert mg["ranks_seen"] == 8 and mg["parameters_bit_equal_across_ranks"] is True, mg
-    assert sum(sh["graphs_per_rank"]) == 128 and sum(mg["rank_graphs"]) == 128
+    assert mg["ranks_seen"] == n and mg["parameters_bit_equal_across_ranks"] is True, mg
+    assert sum(sh["graphs_per_rank"]) == 16 * n and sum(mg["rank_graphs"]) == 16 * n
     assert mg["rank_T"] == sh["T_per_rank"] and sh["T_min"] == min(mg["rank_T"]) and sh["T_max"] == max(mg["rank_T"])
     # the cost-based split is what it is for: tighter than the contiguous split a sampler would make
     assert sh["T_max_over_mean"] <= sh["contiguous_split_T_max_over_mean"] and sh["T_max_over_mean"] < 1.05, sh
-    assert len(mg["rank_fwd_bwd_ms"]) == 8 and min(mg["rank_fwd_bwd_ms"]) > 0 and mg["rank_fwd_bwd_ms_max_over_min"] >= 1.0
+    assert len(mg["rank_fwd_bwd_ms"]) == n and min(mg["rank_fwd_bwd_ms"]) > 0 and mg["rank_fwd_bwd_ms_max_over_min"] >= 1.0
     assert out["loss"] == out["loss"]
 
 
 def test_eight_ranks_with_the_references_ddp_wrap_rehearsal():
     """``--ddp torch`` wraps the model in torch DistributedDataParallel(find_unused_parameters=True) as the
-    reference does (alignn/train.py:207) instead of the one flat all-reduce: eight ranks on one GPU, gloo, eager steps; the
-    replicas stay bit-identical."""
-    out, err = _bench(["--gpus", "8", "--ddp", "torch"] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
+    reference does (alignn/train.py:207) instead of the one flat all-reduce: eight ranks (four sharing one GPU:
+    _ranks_for_the_rehearsal), gloo, eager steps; the replicas stay bit-identical."""
+    n = _ranks_for_the_rehearsal()
+    out, err = _bench(["--gpus", str(n), "--ddp", "torch"] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
     mg = out["multi_gpu"]
-    assert out["n_gpus"] == 8 and mg["ranks_seen"] == 8 and mg["collectives_per_step"] is None
+    assert out["n_gpus"] == n and mg["ranks_seen"] == n and mg["collectives_per_step"] is None
     assert "DistributedDataParallel" in mg["gradient_exchange"] and "DistributedDataParallel" in out["optimizer"]
     assert mg["parameters_bit_equal_across_ranks"] is True, mg
     assert out["step_launch"] == "eager" and out["loss"] == out["loss"]
