@@ -7,5 +7,6 @@ from .alignn import ALIGNN, ALIGNNConfig, ALIGNNConv, EdgeGatedGraphConv, MLPLay
 from .alignn_atomwise import ALIGNNAtomWise, ALIGNNAtomWiseConfig  # noqa: F401
 from .ealignn_atomwise import eALIGNNAtomWise, eALIGNNAtomWiseConfig  # noqa: F401
 from .graph import CSRGraph, GraphBatch, build_csr  # noqa: F401
+from .relax import RelaxResult, relax  # noqa: F401
 
 __version__ = "0.1.0"

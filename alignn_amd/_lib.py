@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libalignn_hip.so")
 LIB_PATH = os.environ.get("ALIGNN_AMD_LIB_PATH", LIB_PATH)  # (A/B runs of differently compiled libraries: tools/gpu/*.sh)
 
-_p, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+_p, _i32, _i64, _f32, _f64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); must mirror include/alignn_hip.h (tests/test_abi.py checks the set)
 SIGNATURES = {
@@ -161,6 +161,9 @@ SIGNATURES = {
     "alignn_ff_fc_grad": (_i32, [_p, _f32, _i32, _p, _p, _p, _p, _p, _p, _i32, _i32, _p]),
     "alignn_add_inplace": (_i32, [_p, _p, _i64, _p]),
     "alignn_add3": (_i32, [_p, _p, _p, _p, _i64, _p]),
+    # batched FIRE relaxation (csrc/relax.hip)
+    "alignn_fire_step": (_i32, [_p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f64, _i32, _f64, _f64, _i32, _f64,
+                                _f64, _f64, _f64, _p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

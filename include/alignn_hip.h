@@ -898,6 +898,25 @@ int alignn_radius_emit(const float* lat, const float* cart, const int32_t* graph
                        const int32_t* crystal_level, const int64_t* offset, int64_t* u, int64_t* v, float* r, int32_t* image,
                        alignn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched structure relaxation (csrc/relax.hip; alignn_amd/relax.py is the host loop): one FIRE step at fixed cell, ASE's
+ * ase/optimize/fire.py as alignn/ff/ff.py:373-415 runs it (optimize_lattice=False, downhill_check=False), preceded by the
+ * convergence test of Optimizer.run (max_i |F_i|^2 < fmax^2) on the forces of the current positions.  float64.  One
+ * workgroup per ACTIVE structure k < n_active; structure s = active[k] owns atoms [atom_ptr[s], atom_ptr[s+1]) of the
+ * full-batch arrays positions / velocities / frac / forces_out [N][3], and forces [.][3] rows [force_ptr[k], force_ptr[k+1])
+ * of the evaluation of the active batch (energy[k] its energy).  Per structure: state[s] = {dt, a}, istate[s] = {Nsteps,
+ * steps taken}.  A structure is recorded (forces_out, energy_out[s], fmax_out[s] = max_i |F_i|), then either retired
+ * (status[1+k] = 1: converged, 2: `steps` steps taken; -1: force rows of another count than its atoms, nothing written) or
+ * stepped (status[1+k] = 0): positions += dr (|dr| over the structure clipped to maxstep), frac = positions inv_lattice[s]
+ * wrapped into [0, 1).  status[0] = number of structures stepped.  Fixed-order reductions: a structure's step is
+ * bit-identical whatever else shares the launch.
+ * ------------------------------------------------------------------------------------------ */
+int alignn_fire_step(const double* forces, const double* energy, const int32_t* force_ptr, const int32_t* active, int n_active,
+                     const int32_t* atom_ptr, const double* inv_lattice, double* positions, double* velocities, double* frac,
+                     double* forces_out, double* energy_out, double* state, int32_t* istate, double* fmax_out, int32_t* status,
+                     double fmax, int steps, double maxstep, double dtmax, int nmin, double finc, double fdec, double astart,
+                     double fa, alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,160 @@
+"""The executable specification of ``alignn_amd.relax`` (csrc/relax.hip): a float64 numpy restatement of the FIRE optimiser and
+of the run loop the reference drives it with (``ForceField.optimize_atoms``, alignn/ff/ff.py:373-415: ``FIRE(atoms).run(fmax,
+steps)`` with ``optimize_lattice=False``, ``downhill_check=False``).  ASE is not a dependency of this project, so ``FireRef``
+and ``run_ref`` follow ASE's published ``ase/optimize/fire.py`` (``FIRE.step``) and ``ase/optimize/optimize.py``
+(``Optimizer.run`` / ``Dynamics.irun`` / ``Optimizer.converged``) line by line; the checks below pin them to steps computed by
+hand on a 1-D harmonic well.  The GPU tests (test_gpu_relax.py) hold the kernel and the batched relaxer to this restatement."""
+
+import numpy as np
+import pytest
+
+from alignn_amd.relax import RelaxResult, relax  # the batched relaxer this file specifies
+
+# ASE's FIRE defaults
+DEFAULTS = dict(dt=0.1, maxstep=0.2, dtmax=1.0, Nmin=5, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, a=0.1)
+
+
+class FireRef:
+    """ase/optimize/fire.py FIRE.step, downhill_check=False, one structure; ``r`` [n, 3] Cartesian positions."""
+
+    def __init__(self, r, dt=0.1, maxstep=0.2, dtmax=1.0, Nmin=5, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, a=0.1):
+        self.r = np.array(r, dtype=np.float64)
+        self.v = None  # FIRE.initialize
+        self.dt, self.maxstep, self.dtmax, self.Nmin = dt, maxstep, dtmax, Nmin
+        self.finc, self.fdec, self.astart, self.fa, self.a = finc, fdec, astart, fa, a
+        self.Nsteps = 0
+
+    def step(self, f):
+        f = np.asarray(f, dtype=np.float64)
+        if self.v is None:
+            self.v = np.zeros((len(self.r), 3))
+        else:
+            vf = np.vdot(f, self.v)
+            if vf > 0.0:
+                self.v = (1.0 - self.a) * self.v + self.a * f / np.sqrt(np.vdot(f, f)) * np.sqrt(np.vdot(self.v, self.v))
+                if self.Nsteps > self.Nmin:
+                    self.dt = min(self.dt * self.finc, self.dtmax)
+                    self.a *= self.fa
+                self.Nsteps += 1
+            else:
+                self.v[:] *= 0.0
+                self.a = self.astart
+                self.dt *= self.fdec
+                self.Nsteps = 0
+        self.v += self.dt * f
+        dr = self.dt * self.v
+        normdr = np.sqrt(np.vdot(dr, dr))
+        if normdr > self.maxstep:
+            dr = self.maxstep * dr / normdr
+        self.r = self.r + dr
+
+
+def converged(f, fmax):
+    """Optimizer.converged: max over atoms of |F_i|^2 below fmax^2."""
+    return bool((np.asarray(f) ** 2).sum(axis=1).max() < fmax ** 2)
+
+
+def run_ref(r0, energy_forces, fmax=0.1, steps=100, **fire):
+    """Optimizer.run(fmax, steps): evaluate, then step while not converged and fewer than ``steps`` steps were taken.
+    ``energy_forces(r) -> (e, f)``.  -> dict(r, e, f, n_steps, converged, n_evals, traj: positions after each step)."""
+    opt = FireRef(r0, **{**DEFAULTS, **fire})
+    e, f = energy_forces(opt.r)
+    n_evals, n_steps, traj = 1, 0, [opt.r.copy()]
+    conv = converged(f, fmax)
+    while not conv and n_steps < steps:
+        opt.step(f)
+        n_steps += 1
+        traj.append(opt.r.copy())
+        e, f = energy_forces(opt.r)
+        n_evals += 1
+        conv = converged(f, fmax)
+    return dict(r=opt.r, e=e, f=np.asarray(f, dtype=np.float64), n_steps=n_steps, converged=conv, n_evals=n_evals, traj=traj,
+                opt=opt)
+
+
+def well(k, x0=0.0):
+    """1-D harmonic well along x for one atom: E = k (x - x0)^2 / 2, F = -k (x - x0)."""
+
+    def ef(r):
+        d = r[:, 0] - x0
+        f = np.zeros_like(r)
+        f[:, 0] = -k * d
+        return 0.5 * k * float(d @ d), f
+
+    return ef
+
+
+def test_first_step_has_no_mixing():
+    opt = FireRef([[1.0, 0.0, 0.0]])
+    opt.step(well(1.0)(opt.r)[1])  # f = -1: v = 0 + 0.1 * -1, dr = 0.1 * v
+    assert opt.v[0, 0] == pytest.approx(-0.1, abs=1e-15) and opt.r[0, 0] == pytest.approx(0.99, abs=1e-15)
+    assert (opt.dt, opt.a, opt.Nsteps) == (0.1, 0.1, 0)
+
+
+def test_second_step_mixes():
+    opt = FireRef([[1.0, 0.0, 0.0]])
+    ef = well(1.0)
+    opt.step(ef(opt.r)[1])
+    opt.step(ef(opt.r)[1])
+    # f = -0.99, v = -0.1, P = 0.099 > 0: v = 0.9 (-0.1) + 0.1 (-0.99 / 0.99) 0.1 = -0.1; Nsteps 1 (not > Nmin: dt kept);
+    # v += 0.1 (-0.99) -> -0.199; x = 0.99 - 0.0199
+    assert opt.Nsteps == 1 and opt.dt == 0.1 and opt.a == 0.1
+    assert opt.v[0, 0] == pytest.approx(-0.199, abs=1e-15) and opt.r[0, 0] == pytest.approx(0.9701, abs=1e-15)
+    # across directions the mix turns v toward F, keeping |v|: v = [1, 0, 0], f = [1, 1, 0]
+    o2 = FireRef([[0.0, 0.0, 0.0]])
+    o2.v = np.array([[1.0, 0.0, 0.0]])
+    o2.step(np.array([[1.0, 1.0, 0.0]]))
+    c = 0.1 / np.sqrt(2.0)
+    assert o2.v[0] == pytest.approx([0.9 + c + 0.1, c + 0.1, 0.0], abs=1e-15)
+
+
+def test_dt_grows_after_nmin_downhill_steps():
+    opt = FireRef([[1.0, 0.0, 0.0]])
+    ef = well(1.0)
+    for k in range(1, 8):  # step 1 starts the velocity, steps 2..7 are downhill with Nsteps 0..5 (not > Nmin = 5)
+        opt.step(ef(opt.r)[1])
+        assert opt.dt == 0.1 and opt.a == 0.1 and opt.Nsteps == k - 1
+    opt.step(ef(opt.r)[1])  # step 8: Nsteps 6 > 5
+    assert opt.dt == pytest.approx(0.11, abs=1e-15) and opt.a == pytest.approx(0.099, abs=1e-15) and opt.Nsteps == 7
+    for _ in range(40):
+        opt.step(ef(opt.r)[1])
+        assert opt.dt <= 1.0  # dtmax
+
+
+def test_maxstep_clip_then_uphill_reset():
+    opt = FireRef([[0.1, 0.0, 0.0]])
+    ef = well(300.0)
+    opt.step(ef(opt.r)[1])  # f = -30, v = -3, dr = -0.3 -> clipped to -0.2
+    assert opt.v[0, 0] == pytest.approx(-3.0, abs=1e-14) and opt.r[0, 0] == pytest.approx(-0.1, abs=1e-15)
+    opt.step(ef(opt.r)[1])  # f = +30 against v = -3: P < 0 -> v = 0, a = astart, dt = 0.05, Nsteps = 0; v = 1.5, dr = 0.075
+    assert (opt.a, opt.Nsteps) == (0.1, 0) and opt.dt == pytest.approx(0.05, abs=1e-16)
+    assert opt.v[0, 0] == pytest.approx(1.5, abs=1e-14) and opt.r[0, 0] == pytest.approx(-0.025, abs=1e-15)
+    # the clip is on the norm over the WHOLE structure: two atoms each moving 0.15 clip together (0.212 > 0.2)
+    two = FireRef(np.zeros((2, 3)))
+    two.step(np.array([[15.0, 0.0, 0.0], [0.0, -15.0, 0.0]]))
+    assert np.linalg.norm(two.r) == pytest.approx(0.2, abs=1e-15) and two.r[0, 0] == pytest.approx(-two.r[1, 1], abs=1e-16)
+
+
+def test_convergence_is_checked_before_stepping():
+    ef = well(1.0)
+    res = run_ref([[0.05, 0.0, 0.0]], ef, fmax=0.1)  # |F| = 0.05 < fmax: no step, one evaluation
+    assert res["n_steps"] == 0 and res["n_evals"] == 1 and res["converged"] and res["r"][0, 0] == 0.05
+    res = run_ref([[1.0, 0.0, 0.0]], ef, fmax=0.1, steps=0)  # steps = 0: evaluated once, not converged
+    assert res["n_steps"] == 0 and res["n_evals"] == 1 and not res["converged"]
+    res = run_ref([[1.0, 0.0, 0.0]], ef, fmax=0.0, steps=7)  # fmax = 0 never converges: exactly `steps` steps
+    assert res["n_steps"] == 7 and res["n_evals"] == 8 and not res["converged"]
+    res = run_ref([[1.0, 0.0, 0.0]], ef, fmax=1e-3, steps=500)
+    assert res["converged"] and abs(res["f"][0, 0]) < 1e-3 and res["n_evals"] == res["n_steps"] + 1
+    assert abs(res["r"][0, 0]) < 1e-3
+
+
+def test_relax_module_exists():
+    """The batched relaxer this restatement specifies is part of the package's public surface."""
+    import alignn_amd
+
+    assert alignn_amd.relax is relax and set(RelaxResult.__dataclass_fields__) >= {
+        "positions", "energies", "forces", "fmax", "converged", "n_steps", "n_evals"}
+    with pytest.raises(ValueError):
+        relax(None, [np.eye(3)], [np.zeros((1, 3)), np.zeros((1, 3))], forces_fn=lambda lat, pos: None)
+    with pytest.raises(TypeError):
+        relax(object(), [np.eye(3)], [np.zeros((1, 3))])
