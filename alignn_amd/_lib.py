@@ -164,6 +164,8 @@ SIGNATURES = {
     # batched FIRE relaxation (csrc/relax.hip)
     "alignn_fire_step": (_i32, [_p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f64, _i32, _f64, _f64, _i32, _f64,
                                 _f64, _f64, _f64, _p]),
+    "alignn_fire_cell_step": (_i32, [_p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                     _p, _f64, _i32, _f64, _f64, _i32, _f64, _f64, _f64, _f64, _p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

@@ -157,6 +157,329 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(
     }
 }
 
+// ---- FIRE with ASE's ExpCellFilter (optimize_lattice=True; ase/constraints.py, 3.22.1, default arguments) --------------------
+// Generalised positions of a structure of n atoms: n atom rows X_a = positions F^-T and three cell rows X_c = c logm(F),
+// c = n, F the deformation gradient of the current cell C = C0 F^T.  Generalised forces: atom rows f F; cell rows the
+// virial W = -V sym(stress) (the "naive" force) or, when it points too far from it, the exact gradient -d E / d logm(F), the
+// Frechet derivative of expm at L = X_c / c applied to W expm(-L); either one / c.  FIRE and the convergence test then run
+// over all n + 3 rows.  X_c is kept as state instead of recomputing logm(F) from the cell every step (the round trip is the
+// identity to rounding: tests/test_relax_cell.py).
+
+// row-major 3x3: c = a b
+__device__ __forceinline__ void mm3(const double* a, const double* b, double* c) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+}
+
+constexpr int EXPM_TAYLOR = 18;  // with |X| <= 1/2 after scaling the remainder is below 1e-22 of |expm|
+
+// squarings s with |A| / 2^s <= 1/2 (|.| any bound of the infinity norm); a non-finite norm gives NaN anyway
+__device__ __forceinline__ int expm_squarings(double nrm) {
+    if (!(nrm > 0.5)) return 0;
+    return min(ilogb(nrm) + 2, 1100);  // nrm < 2^(ilogb + 1): nrm / 2^(ilogb + 2) < 1/2
+}
+
+// expm of the 6x6 block upper-triangular [[L, B], [0, L]] as its blocks (E11 = expm(L), E12 = the Frechet derivative of expm
+// at L in the direction B): scaling and squaring of a Taylor polynomial, every product done blockwise (three 3x3 products
+// instead of one 6x6).  B = 0 gives the 3x3 expm(L) in E11.
+__device__ void expm_block(const double* L, const double* B, double* E11, double* E12) {
+    double nrm = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double r = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) r += fabs(L[3 * i + j]) + fabs(B[3 * i + j]);
+        nrm = fmax(nrm, r);
+    }
+    const int s = expm_squarings(nrm);
+    const double sc = ldexp(1.0, -s);
+    double X11[9], X12[9], T11[9], T12[9], U[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        X11[i] = L[i] * sc;
+        X12[i] = B[i] * sc;
+        E11[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        E12[i] = 0.0;
+    }
+    // Horner: P <- I + X P / k, k = K .. 1
+    for (int k = EXPM_TAYLOR; k >= 1; --k) {
+        mm3(X11, E11, T11);
+        mm3(X11, E12, T12);
+        mm3(X12, E11, U);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            E11[i] = ((i % 4 == 0) ? 1.0 : 0.0) + T11[i] / k;
+            E12[i] = (T12[i] + U[i]) / k;
+        }
+    }
+    for (int q = 0; q < s; ++q) {  // [[P, Q], [0, P]]^2 = [[P P, P Q + Q P], [0, P P]]
+        mm3(E11, E11, T11);
+        mm3(E11, E12, T12);
+        mm3(E12, E11, U);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            E11[i] = T11[i];
+            E12[i] = T12[i] + U[i];
+        }
+    }
+}
+
+__device__ __forceinline__ void expm3(const double* L, double* E) {
+    const double Z[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double unused[9];
+    expm_block(L, Z, E, unused);
+}
+
+// the filter's cell rows (before the division by c) from the current cell C, the stress S (eV/A^3, ASE sign) and L = X_c / c;
+// Ssym (the symmetrised stress) is returned as well
+__device__ void cell_force(const double* C, const double* S, const double* L, double* G, double* Ssym) {
+    const double det = C[0] * (C[4] * C[8] - C[5] * C[7]) - C[1] * (C[3] * C[8] - C[5] * C[6]) + C[2] * (C[3] * C[7] - C[4] * C[6]);
+    const double V = fabs(det);
+    double W[9];  // the virial; naive force
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Ssym[3 * i + j] = i == j ? S[3 * i + j] : (S[3 * i + j] + S[3 * j + i]) / 2;
+            W[3 * i + j] = -V * Ssym[3 * i + j];
+        }
+    // exact force: -expm([[L, -W expm(-L)], [0, L]])[0:3, 3:6], symmetrised; the upper-right block is linear in W, so it is
+    // computed for W scaled by a power of two to below one
+    double mL[9], Em[9], Bm[9], E11[9], E12[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) mL[i] = -L[i];
+    expm3(mL, Em);
+    mm3(W, Em, Bm);
+    double bmax = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) bmax = fmax(bmax, fabs(Bm[i]));
+    const int be = bmax > 0.0 && bmax <= 1.7e308 ? ilogb(bmax) + 1 : 0;  // bmax / 2^be in [1/2, 1)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Bm[i] = -ldexp(Bm[i], -be);
+    expm_block(L, Bm, E11, E12);
+    double E[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) E[i] = -ldexp(E12[i], be);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i + 1; j < 3; ++j) {
+            const double f = 0.5 * (E[3 * i + j] + E[3 * j + i]);
+            E[3 * i + j] = f;
+            E[3 * j + i] = f;
+        }
+    // ASE's switch: the naive force when numpy.isclose holds everywhere (rtol 1e-5, atol 1e-8, against the naive one) or the
+    // cosine of the two exceeds 0.8 (a NaN cosine does not)
+    bool close = true;
+    double en = 0.0, ee = 0.0, nn = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        close = close && (E[i] == W[i] || fabs(E[i] - W[i]) <= 1e-8 + 1e-5 * fabs(W[i]));
+        en += E[i] * W[i];
+        ee += E[i] * E[i];
+        nn += W[i] * W[i];
+    }
+    const bool naive = close || en / sqrt(ee * nn) > 0.8;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) G[i] = naive ? W[i] : E[i];
+}
+
+__global__ __launch_bounds__(FIRE_BLOCK) void fire_cell_step_kernel(
+    const double* __restrict__ forces, const double* __restrict__ energy, const double* __restrict__ stress,
+    const int32_t* __restrict__ force_ptr, const int32_t* __restrict__ active, const int32_t* __restrict__ atom_ptr,
+    const double* __restrict__ lattice0, const double* __restrict__ inv_lattice0, double* __restrict__ xa,
+    double* __restrict__ pos, double* __restrict__ vel, double* __restrict__ frac, double* __restrict__ xc,
+    double* __restrict__ cell_vel, double* __restrict__ defgrad, double* __restrict__ lattice, double* __restrict__ forces_out,
+    double* __restrict__ energy_out, double* __restrict__ stress_out, double* __restrict__ state, int32_t* __restrict__ istate,
+    double* __restrict__ fmax_out, int32_t* __restrict__ status, double fmax_tol, int steps, double maxstep, double dtmax,
+    int nmin, double finc, double fdec, double astart, double fa) {
+    __shared__ double sh[4][FIRE_WAVES];
+    __shared__ double Fsh[9];
+    const int k = blockIdx.x;
+    const int s = active[k];
+    const int beg = atom_ptr[s], n = atom_ptr[s + 1] - beg;
+    const int fbeg = force_ptr[k];
+    if (force_ptr[k + 1] - fbeg != n) {  // forces of another shape than the structure: touch nothing
+        if (threadIdx.x == 0) status[1 + k] = -1;
+        return;
+    }
+    const double c = (double)n;  // ExpCellFilter's cell_factor
+    const double* Fo = forces + 3 * (int64_t)fbeg;
+    double* XA = xa + 3 * (int64_t)beg;
+    double* V = vel + 3 * (int64_t)beg;
+    double* XC = xc + 9 * (int64_t)s;
+    double* VC = cell_vel + 9 * (int64_t)s;
+    const int taken = istate[2 * s + 1];
+    double D[9];  // deformation gradient of the evaluated cell
+#pragma unroll
+    for (int i = 0; i < 9; ++i) D[i] = defgrad[9 * (int64_t)s + i];
+
+    // stage 1 (thread 0): the cell rows of the filter forces
+    double G[9], vc[9];
+    if (threadIdx.x == 0) {
+        double L[9], Ssym[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) L[i] = XC[i] / c;
+        cell_force(lattice + 9 * (int64_t)s, stress + 9 * (int64_t)k, L, G, Ssym);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            G[i] /= c;
+            vc[i] = VC[i];
+            stress_out[9 * (int64_t)s + i] = Ssym[i];
+        }
+    }
+
+    // stage 2: record, reduce over the n + 3 rows (the cell rows are thread 0's last), test convergence
+    double red[4] = {0.0, 0.0, 0.0, 0.0};  // G.v, |G|^2, |v|^2, max |G_i|^2
+    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
+        double f[3], fi2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            f[j] = Fo[3 * i + j];
+            forces_out[3 * ((int64_t)beg + i) + j] = f[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double g = f[0] * D[j] + f[1] * D[3 + j] + f[2] * D[6 + j];  // (f F)_j
+            const double v = V[3 * i + j];
+            red[0] += g * v;
+            fi2 += g * g;
+            red[2] += v * v;
+        }
+        red[1] += fi2;
+        red[3] = fmax(red[3], fi2);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            double fi2 = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                red[0] += G[3 * r + j] * vc[3 * r + j];
+                fi2 += G[3 * r + j] * G[3 * r + j];
+                red[2] += vc[3 * r + j] * vc[3 * r + j];
+            }
+            red[1] += fi2;
+            red[3] = fmax(red[3], fi2);
+        }
+    }
+    block_reduce<4, true>(red, sh);
+    const int converged = red[3] < fmax_tol * fmax_tol;
+    if (threadIdx.x == 0) {
+        energy_out[s] = energy[k];
+        fmax_out[s] = sqrt(red[3]);
+        const int flag = converged ? 1 : (taken >= steps ? 2 : 0);
+        status[1 + k] = flag;
+        if (!flag) atomicAdd(status, 1);  // (an integer count: order-independent)
+    }
+    if (converged || taken >= steps) return;
+
+    // stage 3: ASE FIRE.step over the n + 3 rows
+    double dt = state[2 * s], a = state[2 * s + 1];
+    int nsteps = istate[2 * s];
+    bool zero_v = taken == 0;
+    double mix_v = 1.0, mix_f = 0.0;
+    if (!zero_v) {
+        if (red[0] > 0.0) {
+            mix_v = 1.0 - a;
+            mix_f = a / sqrt(red[1]) * sqrt(red[2]);
+            if (nsteps > nmin) {
+                dt = fmin(dt * finc, dtmax);
+                a *= fa;
+            }
+            nsteps += 1;
+        } else {
+            zero_v = true;
+            a = astart;
+            dt *= fdec;
+            nsteps = 0;
+        }
+    }
+    double dr2[1] = {0.0};
+    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
+        double f[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) f[j] = Fo[3 * i + j];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double g = f[0] * D[j] + f[1] * D[3 + j] + f[2] * D[6 + j];
+            double v = zero_v ? 0.0 : mix_v * V[3 * i + j] + mix_f * g;
+            v += dt * g;
+            V[3 * i + j] = v;
+            const double d = dt * v;
+            dr2[0] += d * d;
+        }
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            double v = zero_v ? 0.0 : mix_v * vc[i] + mix_f * G[i];
+            v += dt * G[i];
+            vc[i] = v;
+            const double d = dt * v;
+            dr2[0] += d * d;
+        }
+    }
+    block_reduce<1, false>(dr2, sh);
+
+    // stage 4: clipped move; F = expm(X_c / c), C = C0 F^T (thread 0), then positions X_a F^T and frac = X_a inv(C0) wrapped
+    const double normdr = sqrt(dr2[0]);
+    const bool clip = normdr > maxstep;
+    if (threadIdx.x == 0) {
+        double L[9], Fn[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            double d = dt * vc[i];
+            if (clip) d = maxstep * d / normdr;
+            const double x = XC[i] + d;
+            XC[i] = x;
+            VC[i] = vc[i];
+            L[i] = x / c;
+        }
+        expm3(L, Fn);
+        const double* C0 = lattice0 + 9 * (int64_t)s;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                lattice[9 * (int64_t)s + 3 * i + j] = C0[3 * i] * Fn[3 * j] + C0[3 * i + 1] * Fn[3 * j + 1] + C0[3 * i + 2] * Fn[3 * j + 2];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            defgrad[9 * (int64_t)s + i] = Fn[i];
+            Fsh[i] = Fn[i];
+        }
+    }
+    __syncthreads();
+    double Fn[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Fn[i] = Fsh[i];
+    const double* Li = inv_lattice0 + 9 * (int64_t)s;
+    double* R = pos + 3 * (int64_t)beg;
+    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
+        double x[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double d = dt * V[3 * i + j];
+            if (clip) d = maxstep * d / normdr;
+            x[j] = XA[3 * i + j] + d;
+            XA[3 * i + j] = x[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            R[3 * i + j] = x[0] * Fn[3 * j] + x[1] * Fn[3 * j + 1] + x[2] * Fn[3 * j + 2];
+            frac[3 * ((int64_t)beg + i) + j] = wrap01(x[0] * Li[j] + x[1] * Li[3 + j] + x[2] * Li[6 + j]);
+        }
+    }
+    if (threadIdx.x == 0) {
+        state[2 * s] = dt;
+        state[2 * s + 1] = a;
+        istate[2 * s] = nsteps;
+        istate[2 * s + 1] = taken + 1;
+    }
+}
+
 }  // namespace
 
 extern "C" int alignn_fire_step(const double* forces, const double* energy, const int32_t* force_ptr, const int32_t* active,
@@ -173,6 +496,26 @@ extern "C" int alignn_fire_step(const double* forces, const double* energy, cons
     fire_step_kernel<<<n_active, FIRE_BLOCK, 0, st>>>(forces, energy, force_ptr, active, atom_ptr, inv_lattice, positions,
                                                       velocities, frac, forces_out, energy_out, state, istate, fmax_out, status,
                                                       fmax_tol, steps, maxstep, dtmax, nmin, finc, fdec, astart, fa);
+    ALIGNN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int alignn_fire_cell_step(const double* forces, const double* energy, const double* stress, const int32_t* force_ptr,
+                                     const int32_t* active, int n_active, const int32_t* atom_ptr, const double* lattice0,
+                                     const double* inv_lattice0, double* xa, double* positions, double* velocities, double* frac,
+                                     double* xc, double* cell_velocities, double* defgrad, double* lattice, double* forces_out,
+                                     double* energy_out, double* stress_out, double* state, int32_t* istate, double* fmax_out,
+                                     int32_t* status, double fmax, int steps, double maxstep, double dtmax, int nmin, double finc,
+                                     double fdec, double astart, double fa, alignn_stream_t stream) {
+    if (n_active < 0 || !status) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    if (e != hipSuccess) return (int)e;
+    if (n_active == 0) return 0;
+    fire_cell_step_kernel<<<n_active, FIRE_BLOCK, 0, st>>>(
+        forces, energy, stress, force_ptr, active, atom_ptr, lattice0, inv_lattice0, xa, positions, velocities, frac, xc,
+        cell_velocities, defgrad, lattice, forces_out, energy_out, stress_out, state, istate, fmax_out, status, fmax, steps, maxstep,
+        dtmax, nmin, finc, fdec, astart, fa);
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }

@@ -15,6 +15,11 @@ around ``AlignnAtomwiseCalculator`` (alignn/ff/calculators.py:280-370), one host
 Positions, velocities, ``dt``, ``a`` and ``Nsteps`` of every structure stay on the device in float64.  A structure's step
 depends only on its own forces and state (fixed-order reductions): its trajectory is the same bits whether it is relaxed
 alone or beside others.
+
+``optimize_lattice=True`` relaxes the cells too, as ``optimize_atoms``' default does: ASE's ``ExpCellFilter`` around the atoms,
+its n + 3 generalised rows per structure (atom rows in the starting cell, cell rows ``n logm(F)`` of the deformation gradient
+``F``) driven by the same FIRE in ``alignn_fire_cell_step``.  The model's per-crystal stresses enter as the calculator gives
+them (``stress * stress_weight / 160.21766208``, eV/A^3).
 """
 
 from __future__ import annotations
@@ -32,7 +37,9 @@ __all__ = ["relax", "RelaxResult"]
 @dataclass
 class RelaxResult:
     """Per structure, in the input order.  ``energies`` / ``forces`` / ``fmax`` are those of the final positions (the last
-    evaluation); ``n_steps`` counts FIRE steps taken; ``n_evals`` counts batched force evaluations (model calls)."""
+    evaluation); ``n_steps`` counts FIRE steps taken; ``n_evals`` counts batched force evaluations (model calls).  With
+    ``optimize_lattice``, ``fmax`` is the largest of the n + 3 filter rows, ``forces`` stay the atoms' Cartesian forces, and
+    ``lattices`` / ``stresses`` are the final cells and the stresses of the last evaluation."""
 
     positions: List[torch.Tensor]  # [n_i, 3] float64, Cartesian, not wrapped into the cell
     energies: torch.Tensor  # [B] float64
@@ -41,6 +48,8 @@ class RelaxResult:
     converged: torch.Tensor  # [B] bool
     n_steps: torch.Tensor  # [B] int64
     n_evals: int
+    lattices: Optional[torch.Tensor] = None  # [B, 3, 3] float64: the final cells (optimize_lattice only)
+    stresses: Optional[torch.Tensor] = None  # [B, 3, 3] float64, eV/A^3, ASE's sign, symmetrised (optimize_lattice only)
 
 
 def _wrap(frac: torch.Tensor) -> torch.Tensor:
@@ -52,8 +61,10 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
           steps: int = 100, dt: float = 0.1, maxstep: float = 0.2, dtmax: float = 1.0, Nmin: int = 5, finc: float = 1.1,
           fdec: float = 0.5, astart: float = 0.1, fa: float = 0.99, a: float = 0.1, cutoff: float = 8.0, max_neighbors: int = 12,
           neighbor_strategy: str = "k-nearest", intensive: bool = True, force_multiplier: float = 1.0,
-          forces_fn: Optional[Callable] = None, device=None) -> RelaxResult:
-    """Relax the atomic positions of B crystals at fixed cell with FIRE until max_i |F_i| < ``fmax`` or ``steps`` steps.
+          forces_fn: Optional[Callable] = None, device=None, optimize_lattice: bool = False,
+          stress_weight: float = 1.0) -> RelaxResult:
+    """Relax the atomic positions of B crystals with FIRE until max_i |F_i| < ``fmax`` or ``steps`` steps; at fixed cell, or
+    with the cells too when ``optimize_lattice``.
 
     ``lattices``: B cells [3, 3] (rows a, b, c); ``positions``: B Cartesian [n_i, 3]; ``atom_features``: B [n_i, F] (the
     model's ``atom_input_features``).  ``model``: an ``ALIGNNAtomWise`` with ``calculate_gradient=True`` in eval mode; energies
@@ -65,7 +76,14 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
     concatenated forces as they are to be used (no multiplier applied).
 
     ``dt`` ... ``a``: FIRE's parameters, ASE's defaults (ase/optimize/fire.py).  Runs on the GPU (the model's device, else
-    ``device``, else the current one)."""
+    ``device``, else the current one).
+
+    ``optimize_lattice``: relax the cells as well, through ASE's ``ExpCellFilter`` (default arguments).  The reference's
+    ``optimize_atoms`` defaults to ``optimize_lattice=True``; here the default stays ``False``.  The model must then predict
+    per-crystal stresses (``stresswise_weight != 0``, ``batch_stress=True``), used as ``stress * stress_weight /
+    160.21766208`` (the calculator's ``stress_wt``, 1.0 in ``ForceField``); ``forces_fn`` must return ``(energy, forces,
+    stress [B', 3, 3])`` with the stress in eV/A^3 and ASE's sign (d E / d strain / volume), used as given.  The cells and
+    positions it gets change from step to step."""
     B = len(positions)
     if B == 0 or len(lattices) != B:
         raise ValueError(f"relax: {len(lattices)} lattices for {B} position arrays (need the same number, at least one)")
@@ -82,6 +100,9 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
             raise ValueError("relax: the model is in training mode; call model.eval() first")
         if atom_features is None or len(atom_features) != B:
             raise ValueError("relax: the model needs atom_features, one [n_i, F] array per structure")
+        if optimize_lattice and (model.config.stresswise_weight == 0 or not model.config.batch_stress):
+            raise ValueError("relax: optimize_lattice needs per-crystal stresses: a model with stresswise_weight != 0 and "
+                             "batch_stress=True")
         dev = model.fc.weight.device
     else:
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -119,6 +140,13 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
         state = torch.tensor([[float(dt), float(a)]] * B, dtype=torch.float64, device=dev)  # dt, a
         istate = torch.zeros(B, 2, dtype=torch.int32, device=dev)  # Nsteps, steps taken
         status = torch.empty(1 + B, dtype=torch.int32, device=dev)
+        if optimize_lattice:  # ExpCellFilter's state: X_a, X_c = n logm(F), cell velocities, F, the current cell
+            xa = pos.clone()
+            xc = torch.zeros(B, 3, 3, dtype=torch.float64, device=dev)
+            cvel = torch.zeros_like(xc)
+            defgrad = torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous()
+            lat_cur = lat.clone()
+            stress_all = torch.zeros_like(xc)
         # fixed per-structure views: the same lattice tensors every step keep neighbors' lattice tables cached
         lat_v = [lat[s] for s in range(B)]
         pos_v = [pos[ptr_h[s]:ptr_h[s + 1]] for s in range(B)]
@@ -140,8 +168,15 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
                 force_ptr = torch.tensor(fp, dtype=torch.int32, device=dev)
                 n_act_t = torch.tensor(n_act, dtype=torch.float32, device=dev)
                 changed = False
+            if optimize_lattice:
+                # fresh tensors every step: the kernel writes lat_cur through a raw pointer (no version bump), which the
+                # lattice-table cache of neighbors would not see
+                lat_now = lat_cur.clone()
+                lat_act = [lat_now[s] for s in active]
+            else:
+                lat_act = [lat_v[s] for s in active]
             if forces_fn is None:
-                batch = neighbors.crystal_batch([lat_v[s] for s in active], [frac_v[s] for s in active],
+                batch = neighbors.crystal_batch(lat_act, [frac_v[s] for s in active],
                                                 atom_features=[feats[s] for s in active], device=dev, cutoff=cutoff,
                                                 max_neighbors=max_neighbors, line_graph=line_graph,
                                                 neighbor_strategy=neighbor_strategy)
@@ -150,8 +185,19 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
                 out = res["out"].detach().reshape(-1).float()
                 energy = ((out * n_act_t) if intensive else out).double()
                 forces = (res["grad"].detach().reshape(-1, 3) * force_multiplier).double()
+                if optimize_lattice:  # the calculator: voigt (symmetrised) stress * stress_wt / 160.21766208, float32
+                    st = res["stresses"].detach().reshape(-1, 3, 3).float()
+                    stress = ((st + st.transpose(1, 2)) / 2 * stress_weight / 160.21766208).double()
+            elif optimize_lattice:
+                out = forces_fn(lat_act, [pos_v[s] for s in active])
+                if not isinstance(out, (tuple, list)) or len(out) != 3:
+                    raise ValueError("relax: with optimize_lattice, forces_fn must return (energy, forces, stress)")
+                energy, forces, stress = out
+                energy = torch.as_tensor(energy).to(dev, torch.float64).reshape(-1)
+                forces = torch.as_tensor(forces).to(dev, torch.float64).reshape(-1, 3)
+                stress = torch.as_tensor(stress).to(dev, torch.float64)
             else:
-                energy, forces = forces_fn([lat_v[s] for s in active], [pos_v[s] for s in active])
+                energy, forces = forces_fn(lat_act, [pos_v[s] for s in active])
                 energy = torch.as_tensor(energy).to(dev, torch.float64).reshape(-1)
                 forces = torch.as_tensor(forces).to(dev, torch.float64).reshape(-1, 3)
             if energy.numel() != Ba or forces.shape[0] != fp[-1]:
@@ -159,12 +205,24 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
                                  f"{Ba} structures / {fp[-1]} atoms")
             energy, forces = energy.contiguous(), forces.contiguous()
             n_evals += 1
-            _lib.check(lib.alignn_fire_step(forces.data_ptr(), energy.data_ptr(), force_ptr.data_ptr(), act_t.data_ptr(), Ba,
-                                            atom_ptr.data_ptr(), inv.data_ptr(), pos.data_ptr(), vel.data_ptr(), frac.data_ptr(),
-                                            forces_all.data_ptr(), energy_all.data_ptr(), state.data_ptr(), istate.data_ptr(),
-                                            fmax_all.data_ptr(), status.data_ptr(), float(fmax), int(steps), float(maxstep),
-                                            float(dtmax), int(Nmin), float(finc), float(fdec), float(astart), float(fa),
-                                            _lib.stream()), "fire_step")
+            if optimize_lattice:
+                if stress.shape != (Ba, 3, 3):
+                    raise ValueError(f"relax: evaluation returned stresses of shape {tuple(stress.shape)} for {Ba} structures")
+                stress = stress.contiguous()
+                _lib.check(lib.alignn_fire_cell_step(
+                    forces.data_ptr(), energy.data_ptr(), stress.data_ptr(), force_ptr.data_ptr(), act_t.data_ptr(), Ba,
+                    atom_ptr.data_ptr(), lat.data_ptr(), inv.data_ptr(), xa.data_ptr(), pos.data_ptr(), vel.data_ptr(),
+                    frac.data_ptr(), xc.data_ptr(), cvel.data_ptr(), defgrad.data_ptr(), lat_cur.data_ptr(), forces_all.data_ptr(),
+                    energy_all.data_ptr(), stress_all.data_ptr(), state.data_ptr(), istate.data_ptr(), fmax_all.data_ptr(),
+                    status.data_ptr(), float(fmax), int(steps), float(maxstep), float(dtmax), int(Nmin), float(finc), float(fdec),
+                    float(astart), float(fa), _lib.stream()), "fire_cell_step")
+            else:
+                _lib.check(lib.alignn_fire_step(forces.data_ptr(), energy.data_ptr(), force_ptr.data_ptr(), act_t.data_ptr(), Ba,
+                                                atom_ptr.data_ptr(), inv.data_ptr(), pos.data_ptr(), vel.data_ptr(), frac.data_ptr(),
+                                                forces_all.data_ptr(), energy_all.data_ptr(), state.data_ptr(), istate.data_ptr(),
+                                                fmax_all.data_ptr(), status.data_ptr(), float(fmax), int(steps), float(maxstep),
+                                                float(dtmax), int(Nmin), float(finc), float(fdec), float(astart), float(fa),
+                                                _lib.stream()), "fire_step")
             st = status[:1 + Ba].tolist()  # the one host read of a step
             if st[0] == Ba:
                 continue
@@ -178,4 +236,5 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
         return RelaxResult(positions=[p.clone() for p in pos_v], energies=energy_all,
                            forces=[forces_all[ptr_h[s]:ptr_h[s + 1]].clone() for s in range(B)], fmax=fmax_all,
                            converged=torch.tensor([f == 1 for f in flag], device=dev), n_steps=istate[:, 1].long(),
-                           n_evals=n_evals)
+                           n_evals=n_evals, lattices=lat_cur.clone() if optimize_lattice else None,
+                           stresses=stress_all if optimize_lattice else None)

@@ -917,6 +917,24 @@ int alignn_fire_step(const double* forces, const double* energy, const int32_t* 
                      double fmax, int steps, double maxstep, double dtmax, int nmin, double finc, double fdec, double astart,
                      double fa, alignn_stream_t stream);
 
+/* One FIRE step with ASE's ExpCellFilter (ase/constraints.py, default arguments: optimize_lattice=True of ff.py:373-415):
+ * alignn_fire_step over n + 3 generalised rows per structure of n atoms.  Besides the per-atom arrays above, structure s
+ * owns xa [N][3] (atom rows X_a = positions F^-T; positions [N][3] are written as X_a F^T), and [B][3][3] row-major:
+ * xc (X_c = n logm(F)), cell_velocities, defgrad (F), lattice (C = lattice0 F^T), lattice0 (the starting cell C0),
+ * inv_lattice0 (its inverse), stress_out.  stress [n_active][3][3] is the evaluation's stress (eV/A^3, ASE's sign), row k
+ * for active[k]; it is symmetrised (stress_out[s]) and turned into the cell rows: the virial W = -|det C| stress, or the
+ * exact gradient -expm([[L, -W expm(-L)], [0, L]])[0:3, 3:6] (symmetrised, L = X_c / n) where the two point apart
+ * (cosine <= 0.8 and not numpy-isclose), divided by n.  Atom rows: forces F.  Convergence and fmax_out over all n + 3
+ * rows; frac = xa inv_lattice0 wrapped into [0, 1).  Initial state: xa = positions, xc = cell_velocities = 0, defgrad = I,
+ * lattice = lattice0. */
+int alignn_fire_cell_step(const double* forces, const double* energy, const double* stress, const int32_t* force_ptr,
+                          const int32_t* active, int n_active, const int32_t* atom_ptr, const double* lattice0,
+                          const double* inv_lattice0, double* xa, double* positions, double* velocities, double* frac, double* xc,
+                          double* cell_velocities, double* defgrad, double* lattice, double* forces_out, double* energy_out,
+                          double* stress_out, double* state, int32_t* istate, double* fmax_out, int32_t* status, double fmax,
+                          int steps, double maxstep, double dtmax, int nmin, double finc, double fdec, double astart, double fa,
+                          alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
