@@ -7,6 +7,11 @@ with one flat all-reduce.
 
 workload = BASELINE.json configs[1]: default ALIGNNConfig (4 ALIGNN + 4 GCN layers, hidden 256),
 batch_size 64, synthetic JARVIS-DFT-shaped periodic crystals (60 atoms, kNN-12 within 8 A).
+
+A plain run does what the headline figure needs: set-up, warm-up, the eagerly launched and the replayed steps (the faster
+is the headline), --dump-outputs, the line.  --full adds everything else: per-kernel and roofline timings, host calibration,
+the streamed-batch timing, the CPU baseline, the other BASELINE configs, and at N > 1 the standalone all-reduce, per-rank
+forward + backward times and the cross-rank parameter check.
 """
 
 from __future__ import annotations
@@ -72,18 +77,25 @@ def parse():
                          "(both informational)")
     ap.add_argument("--kind", default="crystal", choices=["crystal", "molecule"],
                     help="molecule = BASELINE configs[4] shape (QM9-like, 9-27 atoms, no periodic images); not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline and per-kernel timings, "
+                         "angle_embedding, host_calibration, streamed_batches, cpu_baseline, other_configs and the multi_gpu "
+                         "extras (standalone all-reduce, per-rank forward + backward, parameter bit-equality across ranks); "
+                         "--no-cpu-baseline, --cpu-graphs, --no-micro and --other-configs shape a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--streamed-steps", type=int, default=8,
-                    help="extra informational run with a fresh batch per step through alignn_amd.loader (0: skip)")
+                    help="training steps with a fresh batch per step through alignn_amd.loader before the timed steps (0: "
+                         "skip); they advance the model the timed steps start from, so they run in every mode, and --full "
+                         "reports their time as `streamed_batches`")
     ap.add_argument("--cpu-graphs", type=int, default=None,
-                    help="graphs in the CPU-baseline sample (default: the same batch as the GPU run)")
+                    help="graphs in the CPU-baseline sample (default: the same batch as the GPU run; --full only)")
     ap.add_argument("--no-micro", action="store_true",
-                    help="skip the stand-alone micro-timings of the projection kernels (PMC passes: everything left in the "
-                         "profile is then step work)")
+                    help="skip the stand-alone micro-timings of the projection kernels of a --full run (PMC passes: "
+                         "everything left in the profile is then step work)")
     ap.add_argument("--other-configs", type=int, default=None,
                     help="1: after the headline run also the force-field (BASELINE configs[3]) and molecule (configs[4]) "
                          "workloads, 5 replayed steps each in a child process, and put their lines under `other_configs` "
-                         "(default: on for the plain `python bench.py` headline run at N=1, off otherwise)")
+                         "(--full only; default: on for the headline workload at N=1, off otherwise)")
     ap.add_argument("--shard", default="auto", choices=["auto", "cost", "rank"],
                     help="N > 1: how the GLOBAL batch (N x --batch graphs) is split.  rank: every rank generates its own --batch "
                          "graphs (regular crystals: all ranks alike); cost: one global batch, split with ddp.shard_by_cost on the "
@@ -100,7 +112,10 @@ def parse():
                     help="after the timed steps, write what the last timed step computed - prediction, "
                          "loss, parameter gradients, updated parameters (alignn_ff: + forces and stresses) - as DIR/<name>.npy "
                          "(rank 0)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.other_configs or args.cpu_graphs is not None):
+        ap.error("--other-configs 1 and --cpu-graphs belong to a --full run")
+    return args
 
 
 DUMP_BUDGET_BYTES = 64 << 20
@@ -461,7 +476,7 @@ def other_config_lines():
     out = {}
     for name, extra in runs.items():
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "5", "--warmup", "2", "--streamed-steps", "0",
-               "--eager-steps", "3", "--other-configs", "0"] + extra
+               "--eager-steps", "3", "--full", "--other-configs", "0"] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
@@ -706,15 +721,16 @@ def main():
     # ---- the dominant kernel INSIDE a training step (measured here, before any hipGraph exists in the process - see the
     # note on eager steps above): HIP events around every T-row launch of the f16x3 NT kernel during
     # one eagerly launched step (the weight-gradient GEMMs of the previous layer run beside it on the side stream, as
-    # in every real step) - reported in `roofline.in_step` next to the stand-alone micro-timing
+    # in every real step) - reported in `roofline.in_step` next to the stand-alone micro-timing.  A plain run takes the
+    # same training step untimed: the timed steps start from the parameters and optimizer state it leaves.
     in_step = None
     if args.model in ("alignn", "alignn_ff"):  # (every rank runs the step: it contains the gradient all-reduce)
-        if rank == 0:
+        if rank == 0 and args.full:
             ops.KERNEL_TIMER = {"min_rows": raw.num_triplets, "events": []}
         try:
             eager_step()
             torch.cuda.synchronize()
-            ev = ops.KERNEL_TIMER["events"] if rank == 0 else []
+            ev = ops.KERNEL_TIMER["events"] if ops.KERNEL_TIMER is not None else []
         finally:
             ops.KERNEL_TIMER = None
         # T-row launches of the f16x3 NT kernel family by epilogue variant; algorithmic (compulsory, unique-footprint)
@@ -759,7 +775,8 @@ def main():
 
     # ---- streamed batches (informational, N=1): a FRESH batch every step through alignn_amd.loader - one pinned
     # 2.4 MB buffer per batch over PCIe, CSR + L(g) + cosines rebuilt on a staging stream under the previous step.
-    # `value` above stays the resident-input number the contract asks for; this is the PCIe-inclusive rate.
+    # `value` above stays the resident-input number the contract asks for; this is the PCIe-inclusive rate.  These steps
+    # train the model, so a plain run takes them too and only leaves `streamed_batches` out.
     streamed = None
     if world == 1 and args.streamed_steps > 0 and args.model == "alignn":
         from alignn_amd import loader
@@ -786,11 +803,12 @@ def main():
             sstep()
         fence()
         sdt = (time.perf_counter() - t0) / args.streamed_steps
-        streamed = {"ms_per_step": round(sdt * 1e3, 3), "graphs_per_s": round(B / sdt, 1), "steps": args.streamed_steps,
-                    "host_to_device_bytes_per_batch": packed[0].nbytes,
-                    "what": "fresh 64-crystal batch every step: one pinned buffer H2D, canonical CSR + line graph + "
-                            "bond cosines rebuilt on a staging stream (alignn_amd/loader.py)"}
-        log(f"streamed batches: {sdt * 1e3:.2f} ms/step, {B / sdt:.1f} graphs/s")
+        if args.full:
+            streamed = {"ms_per_step": round(sdt * 1e3, 3), "graphs_per_s": round(B / sdt, 1), "steps": args.streamed_steps,
+                        "host_to_device_bytes_per_batch": packed[0].nbytes,
+                        "what": "fresh 64-crystal batch every step: one pinned buffer H2D, canonical CSR + line graph + "
+                                "bond cosines rebuilt on a staging stream (alignn_amd/loader.py)"}
+            log(f"streamed batches: {sdt * 1e3:.2f} ms/step, {B / sdt:.1f} graphs/s")
 
     # ---- forward + loss + backward of the timed steps as ONE hipGraph (the library never allocates or synchronises and
     # launches only on the current stream; the side-stream weight gradients are joined inside the capture).  Same ~520
@@ -874,76 +892,78 @@ def main():
         # every rank is counted over the SAME backend the gradients travel on (RCCL for real runs)
         seen = torch.ones(1, device=dev)
         dist.all_reduce(seen)
-        # the gradient all-reduce on its own: HIP events around the collective of the last timed step (FlatAdamW) and a
-        # stand-alone loop over the same buffer
-        ar_in_step = None
-        evs = getattr(opt, "last_allreduce_events", None)
-        if evs is not None:
-            torch.cuda.synchronize()
-            ar_in_step = evs[0].elapsed_time(evs[1])
-        buf = opt.flat_grad.clone() if getattr(opt, "flat_grad", None) is not None else torch.zeros(4026753, device=dev)
-        for _ in range(3):
-            dist.all_reduce(buf)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            dist.all_reduce(buf)
-        e1.record()
-        torch.cuda.synchronize()
         # what the HOST of every rank needed to enqueue a step (eight ranks share one host: the margin the eager headline has)
         he = torch.tensor([t_enq / args.steps * 1e3, -t_enq / args.steps * 1e3], device=dev, dtype=torch.float64)
         dist.all_reduce(he, op=dist.ReduceOp.MAX)
-        # data parallelism keeps the replicas identical: every rank must hold bit-identical parameters after the timed steps
-        # (the all-reduced gradient is the same tensor everywhere; a rank that missed a collective or raced one would drift)
-        bits = torch.cat([p_.detach().reshape(-1) for p_ in model.parameters()]).view(torch.int32).to(torch.int64)
-        chk = torch.stack([bits.sum(), (bits * (torch.arange(bits.numel(), device=dev) % 8191 + 1)).sum()])
-        lo, hi = chk.clone(), chk.clone()
-        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         multi = {"ranks_seen": int(seen.item()), "backend": backend, "rank_ms_per_step_max": round(dt / args.steps * 1e3, 3),
                  "rank_host_enqueue_ms_per_step_max": round(float(he[0].item()), 3),
                  "rank_host_enqueue_ms_per_step_min": round(-float(he[1].item()), 3),
-                 "parameters_bit_equal_across_ranks": bool(torch.equal(lo, hi)),
                  "rank0_cpu_binding": binding,
                  "rank_ms_per_step_min": round(dt_min / args.steps * 1e3, 3), "rank0_ms_per_step": round(dt_rank / args.steps * 1e3, 3),
-                 "allreduce_bytes": buf.numel() * buf.element_size(),
-                 "allreduce_ms_in_step_incl_divide": None if ar_in_step is None else round(ar_in_step, 4),
-                 "allreduce_ms_standalone": round(e0.elapsed_time(e1) / 10, 4),
                  "collectives_per_step": None if ddp_torch else 1}
-        # per-rank time of the timed steps (each rank's own clock around its K steps) and the rows it owned: where the batch is
-        # irregular (molecules) the skew between ranks IS the load imbalance the cost-based split is there to remove
-        # (inside the timed steps the collective makes every rank wait for the slowest: the imbalance shows in forward + backward
-        # ALONE - three eagerly launched passes without the gradient exchange, each rank's own HIP events)
-        import contextlib
+        if args.full:
+            # the gradient all-reduce on its own: HIP events around the collective of the last timed step (FlatAdamW) and a
+            # stand-alone loop over the same buffer
+            ar_in_step = None
+            evs = getattr(opt, "last_allreduce_events", None)
+            if evs is not None:
+                torch.cuda.synchronize()
+                ar_in_step = evs[0].elapsed_time(evs[1])
+            buf = opt.flat_grad.clone() if getattr(opt, "flat_grad", None) is not None else torch.zeros(4026753, device=dev)
+            for _ in range(3):
+                dist.all_reduce(buf)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                dist.all_reduce(buf)
+            e1.record()
+            torch.cuda.synchronize()
+            # data parallelism keeps the replicas identical: every rank must hold bit-identical parameters after the timed
+            # steps (the all-reduced gradient is the same tensor everywhere; a rank that missed a collective or raced one
+            # would drift)
+            bits = torch.cat([p_.detach().reshape(-1) for p_ in model.parameters()]).view(torch.int32).to(torch.int64)
+            chk = torch.stack([bits.sum(), (bits * (torch.arange(bits.numel(), device=dev) % 8191 + 1)).sum()])
+            lo, hi = chk.clone(), chk.clone()
+            dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+            multi.update({"parameters_bit_equal_across_ranks": bool(torch.equal(lo, hi)),
+                          "allreduce_bytes": buf.numel() * buf.element_size(),
+                          "allreduce_ms_in_step_incl_divide": None if ar_in_step is None else round(ar_in_step, 4),
+                          "allreduce_ms_standalone": round(e0.elapsed_time(e1) / 10, 4)})
+            # per-rank time of the timed steps (each rank's own clock around its K steps) and the rows it owned: where the
+            # batch is irregular (molecules) the skew between ranks IS the load imbalance the cost-based split is there to
+            # remove (inside the timed steps the collective makes every rank wait for the slowest: the imbalance shows in
+            # forward + backward ALONE - three eagerly launched passes without the gradient exchange, each rank's own HIP events)
+            import contextlib
 
-        def fwd_bwd_only():
-            zero_grad()
-            with (model.no_sync() if ddp_torch else contextlib.nullcontext()):
-                if args.model == "alignn_ff":
-                    o_ = model(batch)
-                    l1_ = torch.nn.functional.l1_loss
-                    (l1_(o_["out"], target) + l1_(o_["grad"], f_tgt) + l1_(o_["stresses"], s_tgt)).backward()
-                else:
-                    torch.nn.functional.l1_loss(predict(batch), target).backward()
+            def fwd_bwd_only():
+                zero_grad()
+                with (model.no_sync() if ddp_torch else contextlib.nullcontext()):
+                    if args.model == "alignn_ff":
+                        o_ = model(batch)
+                        l1_ = torch.nn.functional.l1_loss
+                        (l1_(o_["out"], target) + l1_(o_["grad"], f_tgt) + l1_(o_["stresses"], s_tgt)).backward()
+                    else:
+                        torch.nn.functional.l1_loss(predict(batch), target).backward()
 
-        fwd_bwd_only()
-        torch.cuda.synchronize()
-        f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        f0.record()
-        for _ in range(3):
             fwd_bwd_only()
-        f1.record()
-        torch.cuda.synchronize()
-        zero_grad()
-        own_ms = f0.elapsed_time(f1) / 3
-        mine_ms = torch.tensor([own_ms, float(raw.num_triplets), float(B)], device=dev, dtype=torch.float64)
-        allr = [torch.zeros_like(mine_ms) for _ in range(world)]
-        dist.all_gather(allr, mine_ms)
-        multi["rank_fwd_bwd_ms"] = [round(float(a[0]), 3) for a in allr]
-        multi["rank_T"] = [int(a[1]) for a in allr]
-        multi["rank_graphs"] = [int(a[2]) for a in allr]
-        multi["rank_fwd_bwd_ms_max_over_min"] = round(max(multi["rank_fwd_bwd_ms"]) / max(min(multi["rank_fwd_bwd_ms"]), 1e-9), 4)
+            torch.cuda.synchronize()
+            f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            f0.record()
+            for _ in range(3):
+                fwd_bwd_only()
+            f1.record()
+            torch.cuda.synchronize()
+            zero_grad()
+            own_ms = f0.elapsed_time(f1) / 3
+            mine_ms = torch.tensor([own_ms, float(raw.num_triplets), float(B)], device=dev, dtype=torch.float64)
+            allr = [torch.zeros_like(mine_ms) for _ in range(world)]
+            dist.all_gather(allr, mine_ms)
+            multi["rank_fwd_bwd_ms"] = [round(float(a[0]), 3) for a in allr]
+            multi["rank_T"] = [int(a[1]) for a in allr]
+            multi["rank_graphs"] = [int(a[2]) for a in allr]
+            multi["rank_fwd_bwd_ms_max_over_min"] = round(max(multi["rank_fwd_bwd_ms"]) / max(min(multi["rank_fwd_bwd_ms"]), 1e-9), 4)
         multi["sharding"] = sharding if sharding is not None else {"by": "rank: every rank generates its own --batch graphs"}
         multi["gradient_exchange"] = ("torch DistributedDataParallel(find_unused_parameters=True), as alignn/train.py:207" if ddp_torch
                                       else "one all-reduce of the packed gradient buffer (alignn_amd/optim.py FlatAdamW)")
@@ -991,8 +1011,9 @@ def main():
         # which lifts it off the 157 TF fp32-MFMA roof and makes it HBM-bound: algorithmic bytes per launch =
         # read z + write C = 2*T*H*4 (the 256 KiB of sliced weights stay in L2).  Timed live with HIP events on
         # the launch stream.  The six-product bf16 variant (used when max|z| is unknown) and the exact-fp32 MFMA
-        # kernel are timed beside it for reference.
-        if not args.no_micro:
+        # kernel are timed beside it for reference.  (--full only, as are angle_embedding and host_calibration)
+        micro = args.full and not args.no_micro
+        if micro:
             zt = torch.randn(T, H, device=dev)
             w = torch.randn(H, H, device=dev) / 16
             bz = torch.randn(H, device=dev)
@@ -1000,12 +1021,12 @@ def main():
             ws = ops.split_bf16x3(w)
             wh, z_amax = ops.split_f16x2(w), ops.absmax(zt)
         angle_emb = None
-        if not args.no_micro and args.model == "alignn":
+        if micro and args.model == "alignn":
             try:
                 angle_emb = angle_embedding_timings(model, batch.h)
             except Exception as exc:  # (informational: never fails the line)
                 angle_emb = {"error": repr(exc)[:200]}
-        if args.no_micro:
+        if not micro:
             t_h3 = t_x6 = t_f32 = float("nan")
         else:
             t_h3 = time_kernel(lambda: ops.gemm_nt_f16x3(zt, z_amax, wh, bz, out=buf))
@@ -1049,6 +1070,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,  # (False: the informational sections below are null or absent - see --full)
             "ms_per_step": round(ms, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -1111,7 +1133,7 @@ def main():
                     "TFLOPs": round(flops / (t_f32 * 1e-3) / 1e12, 1),
                     "frac_of_157.3TF": round(flops / (t_f32 * 1e-3) / 1e12 / MFMA_F32_PEAK_TF, 4),
                 },
-            ),
+            ) if args.full else None,
             "step_roofline": {
                 # ACHIEVED bandwidth first: what the schedule really moves - rocprofv3 FETCH_SIZE x2 + WRITE_SIZE summed over
                 # the launches of one step (profiles/pmc_traffic.json) - divided by the step time
@@ -1130,7 +1152,7 @@ def main():
                  "algorithmic_bytes_over_step_time_frac_of_8TBs"): round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                 "mfma_frac_of_157TF": round(step_flops / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF, 4),
             },
-            "host_calibration": host_calibration(dev),  # (+ gpu_copy_GBps: this GPU's streaming-copy rate)
+            "host_calibration": host_calibration(dev) if args.full else None,  # (+ gpu_copy_GBps: this GPU's streaming-copy rate)
             "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3),
             "optimizer": opt_desc,
             "multi_gpu": multi,
@@ -1145,7 +1167,7 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if args.model == "alignn_ff":
                 out["cpu_baseline"] = cpu_baseline_ff(n_atoms, sample=min(B, args.cpu_graphs or 4))
             elif args.model == "alignn":
@@ -1155,17 +1177,17 @@ def main():
         else:
             out["cpu_baseline"] = None
         want_other = args.other_configs
-        if want_other is None:  # the driver's plain command: headline workload on one GPU with its CPU baseline
+        if want_other is None:  # `--full` of the headline workload on one GPU with its CPU baseline
             want_other = int(world == 1 and args.model == "alignn" and args.kind == "crystal" and B == 64
                              and not args.no_cpu_baseline and os.environ.get("ALIGNN_BENCH_OTHER_CONFIGS", "1") != "0")
-        if want_other and world == 1:
+        if args.full and want_other and world == 1:
             torch.cuda.empty_cache()
             out["other_configs"] = other_config_lines()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if args.no_micro:  # (the skipped micro-timings are NaN placeholders: not valid JSON)
+        if args.full and args.no_micro:  # (the skipped micro-timings are NaN placeholders: not valid JSON)
             def scrub(o):
                 if isinstance(o, dict):
                     return {k: scrub(v) for k, v in o.items()}

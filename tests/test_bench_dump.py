@@ -44,6 +44,8 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["steps"] == 3 and out["ms_per_step"] > 0
+    # a plain run measures nothing beyond the headline (--full does)
+    assert out["full"] is False and out["roofline"] is None and out["cpu_baseline"] is None and "other_configs" not in out
     files = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
     assert set(files) == {"pred", "loss", "grads", "params"} == set(out["dumped_outputs"]["shapes"])
     assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())

@@ -33,6 +33,13 @@ def test_gpus_flag_must_match_the_launcher():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_options_of_the_full_run_need_full():
+    for extra in (["--other-configs", "1"], ["--cpu-graphs", "4"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + extra, capture_output=True,
+                           text=True, timeout=120)
+        assert r.returncode == 2 and "--full" in r.stderr, (extra, r.stderr[-500:])
+
+
 def test_gpus_8_rendezvous_counts_every_rank():
     """The driver's 8-GPU launch shape (one process per GPU): all eight ranks join the group on the loopback address and
     are counted (no GPU: they stop after the rendezvous)."""

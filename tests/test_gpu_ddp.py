@@ -146,7 +146,7 @@ def test_eight_ranks_on_one_gpu_rehearsal_of_the_drivers_scaling_run():
     after the timed steps every rank holds BIT-identical parameters (the data-parallel invariant: a rank that missed or raced
     a collective would drift)."""
     n = _ranks_for_the_rehearsal()
-    out, err = _bench(["--gpus", str(n)] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
+    out, err = _bench(["--gpus", str(n), "--full"] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
     assert out["n_gpus"] == n and out["config"]["global_batch"] == 8 * n and out["config"]["parallelism"] == f"dp{n}"
     mg = out["multi_gpu"]
     assert mg["ranks_seen"] == n and mg["collectives_per_step"] == 1
@@ -163,7 +163,7 @@ def test_eight_ranks_molecules_sharded_by_cost_rehearsal():
     the rows and graphs each rank owns and each rank's own forward + backward time.  Eight ranks (four sharing one GPU:
     _ranks_for_the_rehearsal), gloo."""
     n = _ranks_for_the_rehearsal()
-    out, err = _bench(["--gpus", str(n), "--kind", "molecule", "--steps", "3", "--warmup", "1", "--batch", "16",
+    out, err = _bench(["--gpus", str(n), "--full", "--kind", "molecule", "--steps", "3", "--warmup", "1", "--batch", "16",
                        "--no-cpu-baseline", "--eager-steps", "2", "--streamed-steps", "0"], {"ALIGNN_BENCH_BACKEND": "gloo"},
                       timeout=1500)
     assert out["n_gpus"] == n and out["config"]["global_batch"] == 16 * n
@@ -183,7 +183,7 @@ def test_eight_ranks_with_the_references_ddp_wrap_rehearsal():
     reference does (alignn/train.py:207) instead of the one flat all-reduce: eight ranks (four sharing one GPU:
     _ranks_for_the_rehearsal), gloo, eager steps; the replicas stay bit-identical."""
     n = _ranks_for_the_rehearsal()
-    out, err = _bench(["--gpus", str(n), "--ddp", "torch"] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
+    out, err = _bench(["--gpus", str(n), "--full", "--ddp", "torch"] + SMALL, {"ALIGNN_BENCH_BACKEND": "gloo"}, timeout=1500)
     mg = out["multi_gpu"]
     assert out["n_gpus"] == n and mg["ranks_seen"] == n and mg["collectives_per_step"] is None
     assert "DistributedDataParallel" in mg["gradient_exchange"] and "DistributedDataParallel" in out["optimizer"]
@@ -195,7 +195,7 @@ def test_eight_ranks_with_the_references_ddp_wrap_rehearsal():
 def test_bench_two_ranks_over_rccl():
     """The real thing wherever >= 2 GPUs are visible: one rank per GPU, RCCL all-reduce of the packed gradient buffer
     beside the replayed hipGraph; ranks_seen counted over RCCL itself."""
-    out, err = _bench(["--gpus", "2"] + SMALL, {})
+    out, err = _bench(["--gpus", "2", "--full"] + SMALL, {})
     mg = out["multi_gpu"]
     assert out["n_gpus"] == 2 and mg["ranks_seen"] == 2 and mg["backend"] == "nccl"
     assert mg["allreduce_ms_standalone"] > 0
