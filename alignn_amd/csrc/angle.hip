@@ -587,9 +587,6 @@ __device__ __forceinline__ int bfrag_idx(int rb, int jb, int s, int hl, int lane
 // scale, multiplied into a fresh accumulator and added to dW2's with the inverse scale - the fp32 addition the MFMA itself
 // would have made.
 constexpr int kDwThreads = 512, kDwTile = 256, kDwGrid = 256;
-#ifndef DW2_PIPE
-#define DW2_PIPE 0  // (measured: 314 us with the recompute issued one block ahead - 256 registers, 27 spilled - against 295 us without)
-#endif
 
 __global__ __launch_bounds__(kDwThreads, 1) void angle_sums_dw2_kernel(P p) {
     __shared__ L1Shared sh;
@@ -643,9 +640,9 @@ __global__ __launch_bounds__(kDwThreads, 1) void angle_sums_dw2_kernel(P p) {
     // one row block: recompute the wave's 32 features, gz and the sums, its share of G
     // (g: g_z of this row block on entry; refilled with the NEXT block's - of row0n / rbn - as soon as it has been consumed, so
     // one set of registers is both the operand and the prefetch: a second set spilled 85-91 registers)
-    // the wave's 32 features of row block rb, recomputed: issued one block AHEAD of its use (DW2_PIPE), so that the matrix
-    // pipe works on block rb + 1 while the vector pipe runs the element chain of block rb - with two waves per SIMD there is
-    // nobody else to fill either pipe
+    // the wave's 32 features of row block rb, recomputed at the top of its block.  (Issued one block ahead instead, so that the
+    // matrix pipe would work on block rb + 1 beside the element chain of block rb, it measured slower: 314 vs 295 us - 256
+    // registers, 27 spilled; profiles/README.md)
     auto recompute = [&](int rb) {
         f32x16 acc = zero16();
 #pragma unroll
@@ -656,11 +653,9 @@ __global__ __launch_bounds__(kDwThreads, 1) void angle_sums_dw2_kernel(P p) {
         }
         return acc;
     };
-    auto block = [&](auto full_c, int64_t row0, int rb, float (&g)[16], int64_t row0n, int rbn, f32x16& acc) {
+    auto block = [&](auto full_c, int64_t row0, int rb, float (&g)[16], int64_t row0n, int rbn) {
         constexpr bool FULL = decltype(full_c)::value;
-#if !DW2_PIPE
-        acc = recompute(rb);
-#endif
+        const f32x16 acc = recompute(rb);
         float gzv[16], s0 = 0.0f, s1 = 0.0f, mx = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -677,9 +672,6 @@ __global__ __launch_bounds__(kDwThreads, 1) void angle_sums_dw2_kernel(P p) {
             am1 = fmaxf(am1, fabsf(xh));
         }
         load_g(row0n, rbn, g);
-#if DW2_PIPE
-        if (rb < 7) acc = recompute(rb + 1);  // (acc's values are all in gzv / the sums by now)
-#endif
         c0 += (double)s0;
         c1 += (double)s1;
         am0 = fmaxf(am0, mx);
@@ -730,12 +722,8 @@ __global__ __launch_bounds__(kDwThreads, 1) void angle_sums_dw2_kernel(P p) {
         __syncthreads();
         const int64_t row0_next = row0 + (int64_t)gridDim.x * kDwTile;
         auto row_blocks = [&](auto full_c) {
-            f32x16 acc;
-#if DW2_PIPE
-            acc = recompute(0);
-#endif
 #pragma unroll 1
-            for (int rb = 0; rb < 8; ++rb) block(full_c, row0, rb, g0, rb < 7 ? row0 : row0_next, rb < 7 ? rb + 1 : 0, acc);
+            for (int rb = 0; rb < 8; ++rb) block(full_c, row0, rb, g0, rb < 7 ? row0 : row0_next, rb < 7 ? rb + 1 : 0);
         };
         if (full)
             row_blocks(std::true_type{});

@@ -54,7 +54,7 @@ __device__ __forceinline__ void pivot_merge4(float& na, float4& pa, float4& Sa, 
 }
 // `cnt`: values this wave accumulated (wave-uniform; lane 0 is active in every panel).  Writes slab [3][H] at `slab` and, for
 // the first feature panel, the block's row count at `count_out`.
-__device__ __forceinline__ void block_moments_store(const ShiftAcc& a, float cnt, float* slab, float* count_out, int H, int f,
+__device__ __forceinline__ void block_moments_write(const ShiftAcc& a, float cnt, float* slab, float* count_out, int H, int f,
                                                     bool active, bool first_panel,
                                                     float4 (*sh)[kWavesPerBlock][ALIGNN_WAVE], float* shn, int wave, int lane) {
     sh[0][wave][lane] = a.p;
@@ -194,10 +194,10 @@ __global__ __launch_bounds__(kThreads) void egc_gate_fwd_kernel(
         // (lane 0 is active in every panel and carries the wave's counts; an inactive lane of a partial last panel
         // accumulated nothing and stores nothing)
         if (e_partial)
-            block_moments_store(e_acc, e_cnt, e_partial + (size_t)blockIdx.x * 3 * H, e_partial + (size_t)gridDim.x * 3 * H + blockIdx.x,
+            block_moments_write(e_acc, e_cnt, e_partial + (size_t)blockIdx.x * 3 * H, e_partial + (size_t)gridDim.x * 3 * H + blockIdx.x,
                                 H, f, active, c0 == 0, sh, shn, wave, lane);
         if (n_partial)
-            block_moments_store(n_acc, n_cnt, n_partial + (size_t)blockIdx.x * 3 * H, n_partial + (size_t)gridDim.x * 3 * H + blockIdx.x,
+            block_moments_write(n_acc, n_cnt, n_partial + (size_t)blockIdx.x * 3 * H, n_partial + (size_t)gridDim.x * 3 * H + blockIdx.x,
                                 H, f, active, c0 == 0, sh, shn, wave, lane);
     }
     if (INFER) block_amax_commit(y_am, y_amax);

@@ -35,30 +35,9 @@
 #include "common.h"
 #include "../../include/alignn_hip.h"
 
-// Ablation / tracing switches of tools/dw_ablate.py (never defined in the shipped build).  DW_ABL bits: 1 no W-stage DMA,
-// 2 no epilogue-stage DMA, 4 no input-gradient products, 8 no weight-gradient products, 16 no stores of C, 32 no Y-stage DMA,
-// 64 no G-row DMA (timing only: results are garbage).  DW_TRACE: wave 0 of every workgroup stamps the phases of its third tile.
-#ifndef DW_ABL
-#define DW_ABL 0
-#endif
-#ifndef DW_TRACE
-#define DW_TRACE 0
-#endif
-#ifndef DW_NS
-#define DW_NS 4
-#endif
-#ifndef DW_IL
-#define DW_IL 0  // 1 (lock-step form): the DMA requests of a step are issued BETWEEN its products, one per three MFMAs (measured
-                 // slower: 714 vs 660 us, profiles/r06_dw_ablate.txt)
-#endif
-#ifndef DW_PP
-#define DW_PP 0  // 1: two teams of four waves alternate matrix and load segments (see the kernel; measured slower: 721 vs 660 us);
-                 // 0: all eight waves in lock-step
-#endif
-#if DW_TRACE
-__device__ unsigned long long dw_trace_buf[256 * 16];
-#endif
-
+// Every wave runs the whole tile in lock-step with the others: per step a barrier, the step's DMA requests, its operand reads,
+// its products.  Measured slower (profiles/r06_dw_ablate_il1.txt, us at T rows): the DMA requests issued between the
+// products, one per three MFMAs (714 vs 660), and two teams of four waves that alternate matrix and load segments (721 vs 660).
 #ifndef DW_GRID_DEFAULT
 #define DW_GRID_DEFAULT 224  // (profiles/r06_dw_grid_ab.txt - headline step, eager / replayed ms, three boxes: 256: 14.56-14.97 / 14.56-14.67; 224: 14.37-14.58 / 14.54-14.68; 192: 14.41-14.53 / 14.81-14.93; 160: 14.60)
 #endif
@@ -73,7 +52,7 @@ typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
 constexpr int H = 256;                   // features: N = K = 256
 constexpr int R = 64;                    // rows per tile
 constexpr int NW = 8, NTH = NW * 64;     // waves, threads
-constexpr int NS = DW_NS;                // ring slots
+constexpr int NS = 4;                    // ring slots
 constexpr int SLOT = 16384;
 constexpr int GBUF = 0;                                  // 64 rows x 1 KiB
 constexpr int RING = GBUF + R * 1024;                    // NS x 16 KiB
@@ -102,33 +81,25 @@ struct Sched {
     static constexpr int first(int s) { return s <= 4 ? s : s <= E0 ? 4 + 2 * (s - 4) : 20 + (s - E0) * cons(E0); }
     static constexpr int fill_lo(int s) { return (s == 0 ? first(STEPS - 1) - NSL : first(s - 1)) + NS; }
     static constexpr int fill_n(int s) { return s == 0 ? cons(STEPS - 1) : cons(s - 1); }
-    static constexpr int slot_ops(int n) {  // DMA instructions per wave for stage n (2; 0 under the ablation switches)
-        n = ((n % NSL) + NSL) % NSL;
-        if ((DW_ABL & 32) && n < 4) return 0;
-        if ((DW_ABL & 1) && n >= 4 && n < 20) return 0;
-        if ((DW_ABL & 2) && n >= 20) return 0;
-        return 2;
-    }
-    static constexpr int g_ops() { return (DW_ABL & 64) ? 0 : 8; }
-    static constexpr int store_ops() { return (DW_ABL & 16) ? 0 : STORES; }
+    static constexpr int SLOT_OPS = 2, G_OPS = 8;  // DMA instructions per wave: one stage, one tile's G rows
     static constexpr Sched make() {
         Sched r{};
         constexpr int TILES = 3;
         int end_op[(TILES + 1) * NSL + NS] = {};
         int g_end[TILES + 2] = {};
         int ops = 0;
-        g_end[0] = (ops += g_ops());
+        g_end[0] = (ops += G_OPS);
         r.prologue = fill_lo(0);
-        for (int n = 0; n < r.prologue; ++n) end_op[n] = (ops += slot_ops(n));
+        for (int n = 0; n < r.prologue; ++n) end_op[n] = (ops += SLOT_OPS);
         int w[TILES][STEPS] = {};
         int gw[TILES] = {};
         for (int t = 0; t < TILES; ++t) {
             gw[t] = ops - g_end[t];
             for (int s = 0; s < STEPS; ++s) {
                 if (cons(s) > 0) w[t][s] = ops - end_op[t * NSL + first(s) + cons(s) - 1];
-                for (int k = 0; k < fill_n(s); ++k) end_op[t * NSL + fill_lo(s) + k] = (ops += slot_ops(fill_lo(s) + k));
-                if (s == E0) g_end[t + 1] = (ops += g_ops());
-                if (s >= E0) ops += store_ops();
+                for (int k = 0; k < fill_n(s); ++k) end_op[t * NSL + fill_lo(s) + k] = (ops += SLOT_OPS);
+                if (s == E0) g_end[t + 1] = (ops += G_OPS);
+                if (s >= E0) ops += STORES;
             }
         }
         for (int s = 0; s < STEPS; ++s) r.w0[s] = w[0][s], r.ws[s] = w[2][s];
@@ -277,18 +248,15 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         dma16(base + tr.m0 * ld, col_b + (unsigned)(row * (int)ld) * 4u, dst);
     };
     auto issue_G = [&](const TileRef& tr) {
-        if constexpr (S::g_ops() == 0) return;
 #pragma unroll
         for (int i = 0; i < 8; ++i) row_dma(g.G, g.ldg, tr, wave * 8 + i, smem + GBUF + (wave * 8 + i) * 1024);
     };
     // stage n (0 .. NSL-1) of tile tr -> ring position n % NS
-    auto issue_slot = [&](auto nc, const TileRef& tr, int only = -1) {  // only: one of the stage's two instructions (-1: both)
+    auto issue_slot = [&](auto nc, const TileRef& tr) {
         constexpr int n = decltype(nc)::value;
-        if constexpr (S::slot_ops(n) == 0) return;
         unsigned char* dst = smem + RING + (n % NS) * SLOT;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if (only >= 0 && only != i) continue;
             const int lr = 2 * wave + i;  // row of the stage / KiB piece of the weight block
             if constexpr (n < 4) {
                 row_dma(g.Y, g.ldy, tr, 16 * n + lr, dst + lr * 1024);
@@ -341,17 +309,6 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         static_for<0, kSched<NE>.prologue>([&](auto nc) { issue_slot(nc, tr0); });
     }
 
-#if DW_TRACE
-    unsigned long long tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tr_w[3] = {0, 0, 0}, tr_b[3] = {0, 0, 0};
-    int tr_j = 0;
-#define DW_STAMP(i) do { if (tr_j == 2) tr_t[i] = __builtin_readcyclecounter(); } while (0)
-#define DW_WAIT(ph, stmt) do { const unsigned long long t0_ = __builtin_readcyclecounter(); stmt; if (tr_j == 2) tr_w[ph] += __builtin_readcyclecounter() - t0_; } while (0)
-#define DW_BARRIER(ph) do { const unsigned long long t0_ = __builtin_readcyclecounter(); block_barrier(); if (tr_j == 2) tr_b[ph] += __builtin_readcyclecounter() - t0_; } while (0)
-#else
-#define DW_STAMP(i) do { } while (0)
-#define DW_WAIT(ph, stmt) stmt
-#define DW_BARRIER(ph) block_barrier()
-#endif
     f16x8 yah[2], yal[2], ybh[4], ybl[4];  // operands of a weight-gradient step (16 rows): G^T blocks, Y blocks
     f16x8 wah[2], wal[2], wbh[2][2], wbl[2][2];  // operands of a pair of input-gradient k-steps
     int ta_off[2], tb_off[2], a_base, b_off[2];
@@ -374,24 +331,14 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             ybl[b] = tr_operand<(s % NS) * SLOT + 512>(p0, p1);
         }
     };
-    auto no_il = [](auto) {};
-    // (`between(k)`, k = 0, 1: called after the first and second of the three passes - the step's DMA requests go there, DW_IL)
-    auto y_mfma = [&](auto&& between) {
-        if constexpr (!(DW_ABL & 8)) {
+    auto y_mfma = [&]() {
 #define DW_PASS(AA, BB)                                                                       \
     _Pragma("unroll") for (int a = 0; a < 2; ++a) _Pragma("unroll") for (int b = 0; b < 4; ++b) \
         acc_dw[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AA[a], BB[b], acc_dw[a][b], 0, 0, 0);
-            DW_PASS(yal, ybh)
-            between(std::integral_constant<int, 0>{});
-            DW_PASS(yah, ybl)
-            between(std::integral_constant<int, 1>{});
-            DW_PASS(yah, ybh)
+        DW_PASS(yal, ybh)
+        DW_PASS(yah, ybl)
+        DW_PASS(yah, ybh)
 #undef DW_PASS
-        } else {
-            acc_dw[0][0][0] += (float)yah[0][0] + (float)ybh[0][0] + (float)yal[1][0] + (float)ybl[3][0];  // (keeps the operand reads)
-            between(std::integral_constant<int, 0>{});
-            between(std::integral_constant<int, 1>{});
-        }
     };
     auto w_reads = [&](auto ktc) {  // both k-steps of the pair that starts at kt
         constexpr int kt0 = decltype(ktc)::value;
@@ -410,43 +357,25 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
     };
-    // (`between(k)`, k = 0 .. 3: called after every third product of the twelve)
-    auto w_mfma = [&](auto&& between) {
+    auto w_mfma = [&]() {
         static_for<0, 2>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if constexpr (!(DW_ABL & 4)) {
-                acc_c[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbh[j][0], acc_c[0], 0, 0, 0);
-                acc_c[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbh[j][1], acc_c[1], 0, 0, 0);
-                acc_c[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbl[j][0], acc_c[0], 0, 0, 0);
-                between(std::integral_constant<int, 2 * j>{});
-                acc_c[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbl[j][1], acc_c[1], 0, 0, 0);
-                acc_c[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wal[j], wbh[j][0], acc_c[0], 0, 0, 0);
-                acc_c[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wal[j], wbh[j][1], acc_c[1], 0, 0, 0);
-                between(std::integral_constant<int, 2 * j + 1>{});
-            } else {
-                acc_c[0][0] += (float)wah[j][0] + (float)wal[j][0] + (float)wbh[j][0][0] + (float)wbl[j][1][0];  // (keeps the reads)
-                between(std::integral_constant<int, 2 * j>{});
-                between(std::integral_constant<int, 2 * j + 1>{});
-            }
+            acc_c[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbh[j][0], acc_c[0], 0, 0, 0);
+            acc_c[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbh[j][1], acc_c[1], 0, 0, 0);
+            acc_c[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbl[j][0], acc_c[0], 0, 0, 0);
+            acc_c[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[j], wbl[j][1], acc_c[1], 0, 0, 0);
+            acc_c[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wal[j], wbh[j][0], acc_c[0], 0, 0, 0);
+            acc_c[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wal[j], wbh[j][1], acc_c[1], 0, 0, 0);
         });
     };
-    // Two teams (DW_PP): waves 0-3 lead, waves 4-7 - their partners on the four SIMDs (tools/simd_map.hip: waves w and w + 4
-    // share one) - follow half an interval behind.  An interval has two barriers: in its first half the leaders fetch the
-    // operands of step s while the others multiply what they fetched in step s - 1; in its second half the leaders multiply and the
-    // others fetch.  On every SIMD one wave's matrix segment runs beside its partner's LDS segment (with all eight waves in
-    // lock-step a k-step took 720 cycles for 384 of matrix work: profiles/r06_dw_ablate_v3.txt).
-    // (the two teams run two COPIES of the tile loop, chosen once: with per-step team branches around the products hipcc copies
-    // the accumulators at every join - 2 500 registers spilled)
 
     // one tile; FIRST: the waits of the first tile count the prologue's operations instead of the previous tile's
-    auto tile_body = [&](auto first_c, auto lead_c) {
-        constexpr bool FIRST = decltype(first_c)::value, lead = decltype(lead_c)::value;
-        DW_STAMP(0);
+    auto tile_body = [&](auto first_c) {
+        constexpr bool FIRST = decltype(first_c)::value;
         const TileRef cur = tile_ref(tile), nxt = tile_ref(tile + grid);
         const int64_t m0 = cur.m0;
         // ---- the tile's G rows: the wave slices the 8 rows it requested itself, in place
-        DW_WAIT(0, (wait_vmcnt<FIRST ? kSched<NE>.g0 : kSched<NE>.gs>()));
-        DW_STAMP(1);
+        wait_vmcnt<FIRST ? kSched<NE>.g0 : kSched<NE>.gs>();
         {
             const int l = opaque_lane();  // (the eight swizzled write addresses are derived here, not carried through the kernel)
             const int wslot = l >> 1, wsub = (l & 1) * 8;
@@ -485,7 +414,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // slice the two rows of Y stage s this wave requested, in place (rows past the end of the matrix: zeros)
         auto y_convert = [&](auto sc) {
             constexpr int s = decltype(sc)::value;
-            DW_WAIT(0, (wait_vmcnt<FIRST ? kSched<NE>.w0[s] : kSched<NE>.ws[s]>()));
+            wait_vmcnt<FIRST ? kSched<NE>.w0[s] : kSched<NE>.ws[s]>();
             unsigned char* slot = smem + RING + (s % NS) * SLOT;
             const int ra = 2 * wave, rb = ra + 1;
             const int l = opaque_lane();
@@ -510,48 +439,14 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 issue_slot(std::integral_constant<int, n % S::NSL>{}, n >= S::NSL ? nxt : cur);
             });
         };
-        // ... one DMA instruction of them at a time (piece k of 2 fill_n(s)), fenced so that it stays between the products
-        auto fill_piece = [&](auto sc, auto kc) {
-            constexpr int s = decltype(sc)::value, k = decltype(kc)::value;
-            if constexpr (k < 2 * S::fill_n(s)) {
-                constexpr int n = S::fill_lo(s) + k / 2;
-                __builtin_amdgcn_sched_barrier(0);
-                issue_slot(std::integral_constant<int, n % S::NSL>{}, n >= S::NSL ? nxt : cur, k % 2);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        DW_STAMP(2);
         y_convert(std::integral_constant<int, 0>{});
         static_for<0, 4>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
-            DW_BARRIER(0);  // the planes of this stage (and, s == 0, of G) are complete; step s-1's ring position is free
-#if DW_PP
-            // the load segment of a team: DMA requests, operand reads, slicing of the next stage - beside the other team's products
-            if constexpr (lead) {
-                fills(sc);
-                y_reads(sc);
-                if constexpr (s < 3) y_convert(std::integral_constant<int, s + 1>{});
-            } else {
-                if constexpr (s > 0) y_mfma(no_il);  // (step s - 1's operands)
-            }
-            block_barrier();
-            if constexpr (lead) {
-                y_mfma(no_il);
-            } else {
-                fills(sc);
-                y_reads(sc);
-                if constexpr (s < 3) y_convert(std::integral_constant<int, s + 1>{});
-            }
-#elif DW_IL
-            y_reads(sc);
-            y_mfma([&](auto kc) { fill_piece(sc, kc); });
-            if constexpr (s < 3) y_convert(std::integral_constant<int, s + 1>{});
-#else
+            block_barrier();  // the planes of this stage (and, s == 0, of G) are complete; step s-1's ring position is free
             fills(sc);
             y_reads(sc);
-            y_mfma(no_il);
+            y_mfma();
             if constexpr (s < 3) y_convert(std::integral_constant<int, s + 1>{});
-#endif
         });
         // ---- input gradient: 16 k-steps over the weight image
 #pragma unroll
@@ -572,34 +467,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         static_for<4, S::E0>([&](auto sc) {
             constexpr int s = decltype(sc)::value, kt0 = 2 * (s - 4);  // two k-steps per barrier
-            if (s == 4) DW_STAMP(3);
-            DW_WAIT(1, (wait_vmcnt<FIRST ? kSched<NE>.w0[s] : kSched<NE>.ws[s]>()));
-            DW_BARRIER(1);
-#if DW_PP
-            if constexpr (lead) {
-                fills(sc);
-                w_reads(std::integral_constant<int, kt0>{});
-            } else {
-                if constexpr (kt0 == 0)
-                    y_mfma(no_il);  // (the last weight-gradient step's operands)
-                else
-                    w_mfma(no_il);  // (the previous pair's operands)
-            }
+            wait_vmcnt<FIRST ? kSched<NE>.w0[s] : kSched<NE>.ws[s]>();
             block_barrier();
-            if constexpr (lead) {
-                w_mfma(no_il);
-            } else {
-                fills(sc);
-                w_reads(std::integral_constant<int, kt0>{});
-            }
-#elif DW_IL
-            w_reads(std::integral_constant<int, kt0>{});
-            w_mfma([&](auto kc) { fill_piece(sc, kc); });
-#else
             fills(sc);
             w_reads(std::integral_constant<int, kt0>{});
-            w_mfma(no_il);
-#endif
+            w_mfma();
         });
         // ---- epilogue: the operands of each step in the ring
         // a step = 8 (4) rows x 64 columns per wave through its patch; lane (prow, pc4) takes rows prow (and prow + 4) at the
@@ -614,10 +486,8 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             constexpr int QR = 32 / S::EST;                      // rows per wave and step: 8 (quarters) or 4 (eighths)
             constexpr int q = QR == 8 ? e : e / 2, hf = e & 1;   // accumulator registers 4 q .. 4 q + 3 (eighths: of half-wave hf)
             constexpr int n_slot = 20 + e;                       // this step's stage (NE > 0)
-            if (e == 0) DW_STAMP(4);
-            if constexpr (NE > 0) DW_WAIT(2, (wait_vmcnt<FIRST ? kSched<NE>.w0[s] : kSched<NE>.ws[s]>()));
-            if constexpr (e == 0) DW_BARRIER(2);  // every wave has left the tile's planes and the last W stages
-            if constexpr (e == 0 && DW_PP && !lead) w_mfma(no_il);  // (the last pair's operands)
+            if constexpr (NE > 0) wait_vmcnt<FIRST ? kSched<NE>.w0[s] : kSched<NE>.ws[s]>();
+            if constexpr (e == 0) block_barrier();  // every wave has left the tile's planes and the last W stages
             fills(sc);
             if constexpr (e == 0) issue_G(nxt);
             const unsigned char* mine = smem + RING + (n_slot % NS) * SLOT + wave * 2048;  // this wave's rows of the stage
@@ -647,31 +517,19 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     s0 = f4_add(s0, gz);
                     s1 = f4_fma(gz, xc, s1);
                 }
-                if (!(DW_ABL & 16) || v.x == 12345.678f) f4_sts<true>(c_t + (rowc * (int)g.ldc + ecol), v);
+                f4_sts<true>(c_t + (rowc * (int)g.ldc + ecol), v);
                 if constexpr (BNRED) __builtin_amdgcn_sched_barrier(0);  // (one row's transcendental chain at a time: registers)
             }
         });
-        DW_STAMP(5);
-#if DW_TRACE
-        ++tr_j;
-#endif
     };
-    auto run_tiles = [&](auto lead_c) {
-        tile_body(std::true_type{}, lead_c);
+    // the workgroup's tiles (a lambda of its own: written straight into the kernel body, the same walk compiles to another
+    // register allocation)
+    auto run_tiles = [&]() {
+        tile_body(std::true_type{});
         tile += grid;
-        for (int j = 1; j < J; ++j, tile += grid) tile_body(std::false_type{}, lead_c);
+        for (int j = 1; j < J; ++j, tile += grid) tile_body(std::false_type{});
     };
-    if (!DW_PP || wave < 4)  // (wave-uniform: one scalar branch per kernel)
-        run_tiles(std::true_type{});
-    else
-        run_tiles(std::false_type{});
-#if DW_TRACE
-    if (threadIdx.x == 0 && blockIdx.x < 256) {
-        unsigned long long* o = dw_trace_buf + blockIdx.x * 16;
-        for (int i = 0; i < 6; ++i) o[i] = tr_t[i];
-        for (int i = 0; i < 3; ++i) o[6 + i] = tr_w[i], o[9 + i] = tr_b[i];
-    }
-#endif
+    run_tiles();
 
     wait_vmcnt<0>();  // (the phantom stages requested past the last tile: no DMA may outlive the workgroup's LDS allocation)
     // ---- the workgroup's dW partial -> slab blockIdx.x (accumulator layout: 32 consecutive columns per row and register)
@@ -753,12 +611,6 @@ inline int dw_grid(int64_t M) {
 inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
-
-#if DW_TRACE
-extern "C" int alignn_dw_trace_read(void* host, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(dw_trace_buf), bytes < sizeof(dw_trace_buf) ? bytes : sizeof(dw_trace_buf));
-}
-#endif
 
 extern "C" {
 

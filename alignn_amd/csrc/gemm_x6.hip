@@ -36,57 +36,9 @@
 #include "common.h"
 #include "../../include/alignn_hip.h"
 
-// Ablation switches for tools/ablate_x6.py (never defined in the shipped build)
-#ifndef X6_ABL_NOSLICE
-#define X6_ABL_NOSLICE 0
-#endif
-#ifndef X6_ABL_NOBLOAD
-#define X6_ABL_NOBLOAD 0
-#endif
-#ifndef X6_ABL_NOALOAD
-#define X6_ABL_NOALOAD 0
-#endif
-#ifndef X6_ABL_ONEMFMA
-#define X6_ABL_ONEMFMA 0
-#endif
-#ifndef X6_PERSIST
-#define X6_PERSIST 0  // 1: long products on 512 persistent workgroups (bit-identical, measured no faster: see PERSIST below)
-#endif
-#ifndef TN_PIPE
-#define TN_PIPE 0  // 1: software-pipelined stage loop of the f16x3 weight-gradient kernel (see gemm_tn_x6_kernel)
-#endif
-#ifndef X6_EPI_NOSYNC
-#define X6_EPI_NOSYNC 0  // 1: no per-round __syncthreads() in the epilogue (see there)
-#endif
-#ifndef X6_KPIPE
-#define X6_KPIPE 0  // 1: f16x3 k-loop with the stage hand-over in the middle of a step's MFMAs (see the k-loop)
-#endif
-#ifndef X6P_NT
-#define X6P_NT 1  // 0: plain (L2 write-back) stores in the persistent kernel's epilogue (experiment)
-#endif
-#ifndef X6_TRACE
-#define X6_TRACE 0  // 1: wave 0 of every workgroup stamps its phases with s_memtime (tools/x6_trace.py reads them)
-#endif
-#if X6_TRACE
-__device__ unsigned long long x6_trace_buf[8192 * 8];
-#define X6_STAMP(i)                                                                                   \
-    do {                                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.y == 0)                                 \
-            x6_trace_buf[blockIdx.x * 8 + (i)] = __builtin_readcyclecounter();                        \
-    } while (0)
-#else
-#define X6_STAMP(i) \
-    do {            \
-    } while (0)
-#endif
-#ifndef X6_ABL_NOSTORE
-#define X6_ABL_NOSTORE 0  // 1: epilogue without its global stores, 2: no epilogue at all
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -112,14 +64,8 @@ struct Sch {
     static constexpr int NPL = F16 ? 2 : 3;
     static constexpr int STAGE = Geo<RM_>::A_BYTES + NPL * B_PLANE;  // RM = 2: 32 KiB / 24 KiB
     static constexpr int B_DMA = NPL * B_PLANE / 1024 / (NT / 64);   // pieces per wave
-#ifdef X6_NSTAGE
-    static constexpr int NSTAGE = X6_NSTAGE;
-#else
     static constexpr int NSTAGE = 2;  // DMA ring depth (3 measured no faster for f16x3: the kernel is HBM-bound)
-#endif
     static constexpr int LDS = NSTAGE * STAGE > EPI_BYTES ? NSTAGE * STAGE : EPI_BYTES;  // two workgroups per CU
-    // persistent walk: ring of two stages, the transpose patches overlay stage 1 and run past the ring's end
-    static constexpr int LDS_PERSIST = 2 * STAGE > STAGE + EPI_BYTES ? 2 * STAGE : STAGE + EPI_BYTES;
 };
 
 template <int N>
@@ -176,12 +122,6 @@ __device__ __forceinline__ float trunc16(float x) { return __uint_as_float(__flo
 
 // slice 8 consecutive-k floats into the three bf16x8 MFMA operands
 __device__ __forceinline__ void slice8(const float4& lo, const float4& hi4, bf16x8& h, bf16x8& m, bf16x8& l) {
-#if X6_ABL_NOSLICE
-    h = __builtin_bit_cast(bf16x8, lo);
-    m = __builtin_bit_cast(bf16x8, hi4);
-    l = h;
-    return;
-#endif
     float x[8] = {lo.x, lo.y, lo.z, lo.w, hi4.x, hi4.y, hi4.z, hi4.w};
     uint4 hp, mp, lp;
     unsigned* hpp = reinterpret_cast<unsigned*>(&hp);
@@ -214,11 +154,6 @@ __device__ __forceinline__ float f16_scale(float amax) {
 // slice 8 consecutive-k floats (scaled by s) into the two fp16x8 MFMA operands - in two halves, so that the kernel
 // can start the ah products while the VALU still works on the low slice
 __device__ __forceinline__ void slice8_f16_hi(const float4& lo, const float4& hi4, float s, float (&xs)[8], f16x8& h) {
-#if X6_ABL_NOSLICE
-    h = __builtin_bit_cast(f16x8, lo);
-    xs[0] = hi4.x, xs[1] = hi4.y, xs[2] = hi4.z, xs[3] = hi4.w;
-    return;
-#endif
     const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi4.x, hi4.y, hi4.z, hi4.w};
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -227,10 +162,6 @@ __device__ __forceinline__ void slice8_f16_hi(const float4& lo, const float4& hi
     }
 }
 __device__ __forceinline__ void slice8_f16_lo(const float (&xs)[8], const f16x8& h, f16x8& l) {
-#if X6_ABL_NOSLICE
-    l = __builtin_bit_cast(f16x8, make_float4(xs[0], xs[1], xs[2], xs[3]));
-    return;
-#endif
     // l = RN_f16(xs - h) (the subtraction is exact in fp32).  As v_fma_mixlo/hi_f16 (fp32 fma of xs * 1.0 - h with the fp16
     // operand read straight out of the packed high slice, result rounded into one half of the destination): one
     // instruction per element where hipcc emits v_cvt_f32_f16 + v_pk_add_f32 + v_cvt_pk_f16_f32 (two per element) - and
@@ -265,17 +196,6 @@ __device__ __forceinline__ void dma16(const void* sbase, unsigned lane_off, unsi
                  : "memory");
 }
 
-// PERSIST: the launch has fewer workgroups than row tiles; a workgroup walks tiles blockIdx.x, +gridDim.x, ... and
-// DMA-prefetches the first k-stage of its NEXT tile before it issues the stores of the current one.  A one-tile
-// workgroup cannot retire (and free its LDS and registers for the next tile) before every store is acknowledged -
-// two thirds of the measured epilogue cost (profiles/r01_final_f16x3_ablation.txt); here the stores drain under the
-// next tile's first k-step.  vmcnt retires in issue order and counts stores, so that step waits with
-// vmcnt(<stores issued after the prefetch>) instead of vmcnt(0).  Needs an even number of k-steps (the last step
-// reads stage 1, stage 0 is free for the prefetch, the transpose patches overlay stage 1 onwards).
-// STATUS: compiled only with -DX6_PERSIST=1.  Results are bit-identical to the one-tile kernel (tools/ablate_x6.py,
-// ABL_CHECK=1, T x 256 x 256), but it measured no faster (374 vs 378 us, interleaved rounds): the second k-step's
-// vmcnt(0) still meets the stores one step later.  Kept as the base for a deeper walk (three stages: two prefetched
-// ahead of the stores) - see HISTORY.md section 8.
 // EPI == 1: the output C is a gradient g_y = dL/dy of a tensor y = r + silu(BatchNorm(xn)) (the edge output of the previous
 // line-graph convolution, or an MLPLayer output without r).  BatchNorm's backward needs the column sums
 // sum_rows gz and sum_rows gz*xhat (gz = g_y * silu'(z)) over ALL rows before anything else can happen - a separate
@@ -286,11 +206,13 @@ __device__ __forceinline__ void dma16(const void* sbase, unsigned lane_off, unsi
 // EPI is a set of flags: 1 = BNRED (above), 2 = GATHER (C[e] += P[src e].A + P[dst e].Bd, below), 4 = STATS (per-tile
 // column sums of C and C^2 into red_partial: the BatchNorm statistics of the tensor this product writes, so that no
 // separate pass has to read it back for them).
-template <bool HAS_ADD, bool F16, int RM_, bool PERSIST = false, int EPI = 0>
+// One row tile per workgroup.  (A walk of several row tiles per workgroup, with the next tile's first k-stage prefetched ahead
+// of the current tile's stores, measured no faster: 374 vs 378 us - the second k-step's vmcnt(0) still meets the stores;
+// profiles/README.md.)
+template <bool HAS_ADD, bool F16, int RM_, int EPI = 0>
 __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
     constexpr bool BNRED = (EPI & 1) != 0, GATHER = (EPI & 2) != 0, STATS = (EPI & 4) != 0;
     static_assert(!(BNRED && STATS), "one set of column sums per launch");
-    static_assert(EPI == 0 || !PERSIST, "the reduction epilogue exists for the one-tile kernel only");
     static_assert(!GATHER || !HAS_ADD, "the gather variant has its own two addends");
     // EPI == 2: C[e] = A-row . W + b  +  P[src e].A + P[dst e].Bd  - the u_add_v of the convolution
     // (alignn/models/alignn.py:100-101) folded into the projection that produces the third addend, so that m never
@@ -304,22 +226,11 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int il = lane & 31, half = lane >> 5;
-    const int64_t n_mt = (g.M + BM - 1) / BM;  // row tiles (PERSIST walks them; otherwise gridDim.x == n_mt)
-    int64_t tile = blockIdx.x;
-    int64_t m0 = tile * BM;
+    const int64_t tile = blockIdx.x;
+    const int64_t m0 = tile * BM;
     const int n0 = blockIdx.y * BN;
 
     f32x16 acc[RM][RN];
-
-#if X6_TRACE
-    if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.y == 0) {
-        unsigned id, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(id));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        x6_trace_buf[blockIdx.x * 8 + 7] = ((unsigned long long)xcc << 32) | id;
-    }
-    X6_STAMP(0);
-#endif
 
     // ---- DMA addressing (LDS image is lane-linear; the XOR swizzle lives in the SOURCE address)
     // A: piece q = wave*A_DMA + i holds tile positions p = q*64 + lane -> row p/4, stored chunk p%4, which is
@@ -349,15 +260,9 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
     const unsigned char* b_base = g.Ws + (int64_t)blockIdx.y * (NPL * B_PLANE) + (wave * B_DMA) * 1024;
     const unsigned b_lane = lane * 16;
     auto issue = [&](int kt, unsigned char* stage) {
-#if X6_ABL_NOALOAD
-        if (kt == 0)
-#endif
 #pragma unroll
         for (int i = 0; i < A_DMA; ++i)
             dma16<0>(a_base + kt * BK, a_lane[i], stage + (wave * A_DMA + i) * 1024);
-#if X6_ABL_NOBLOAD
-        if (kt == 0)
-#endif
 #pragma unroll
         for (int i = 0; i < B_DMA; ++i)
             dma16<0>(b_base + kt * kb_stride + i * 1024, b_lane, stage + A_BYTES + (wave * B_DMA + i) * 1024);
@@ -398,106 +303,24 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
         inv_sw = 1.0f / f16_scale(*g.w_amax);
     }
 
-    // DMA ring of NSTAGE stages: stage kt+NSTAGE-1 is issued at the top of step kt (into the slot every wave has
-    // finished reading), so a stage has NSTAGE-1 k-steps to land; COUNTED vmcnt - only the stage about to be read
-    // must have arrived, younger ones stay in flight across the barrier.
-    constexpr int NSTAGE = Sch<F16, RM_>::NSTAGE, PIECES = A_DMA + B_DMA;
-    static_assert(NSTAGE == 2 || NSTAGE == 3, "vmcnt cases below");
-    static_assert(!PERSIST || NSTAGE == 2, "the persistent walk prefetches into stage 0 of a two-stage ring");
-    constexpr int EPI_STORES = RM * (RN / 2) * 8;  // global stores per lane and tile, all issued after the prefetch
-    static_assert(EPI_STORES < 64, "vmcnt is a 6-bit counter");
+    // DMA ring of NSTAGE = 2 stages: stage kt+1 is issued at the top of step kt (into the slot every wave has finished
+    // reading), so a stage has one k-step to land and the stage about to be read is the only one in flight.
+    constexpr int NSTAGE = Sch<F16, RM_>::NSTAGE;
     const int nk = g.K / BK;
 #pragma unroll
     for (int s0 = 0; s0 < NSTAGE - 1; ++s0)
         if (s0 < nk) issue(s0, smem + s0 * STAGE_BYTES);
-    bool first = true;
-    for (;;) {  // row tiles of this workgroup (one iteration unless PERSIST)
 #pragma unroll
     for (int a = 0; a < RM; ++a)
 #pragma unroll
         for (int b = 0; b < RN; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    if constexpr (F16 && X6_KPIPE && !PERSIST) {
-        // Software-pipelined form of the loop below.  A wave's step there is a serial chain - wait for the stage, barrier,
-        // issue the next DMA, LDS reads, high slices, 24 MFMAs - of which only the MFMAs are hidden by the co-resident
-        // workgroup.  Here the stage hand-over sits in the MIDDLE of a step's products: after the first two passes of step
-        // kt (16 MFMAs in the pipe) the wave waits for stage kt+1, passes the barrier, issues the DMA of stage kt+NSTAGE
-        // into the slot of stage kt (every wave's LDS reads of it have completed: block_barrier() drains lgkmcnt) and
-        // reads the operands of step kt+1 - into the registers the finished passes have released - while the third pass
-        // runs.  Same products in the same order per accumulator: bit-identical.
-        f16x8 ah[RM], al[RM], bh[RN], bl[RN];
-        float xs[RM][8];
-        auto read_hi = [&](const unsigned char* stage) {
-#pragma unroll
-            for (int b = 0; b < RN; ++b) bh[b] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(stage + b_off[b]));
-#pragma unroll
-            for (int a = 0; a < RM; ++a)
-                slice8_f16_hi(*reinterpret_cast<const float4*>(stage + a_off0[a]),
-                              *reinterpret_cast<const float4*>(stage + a_off1[a]), sa, xs[a], ah[a]);
-        };
-        auto read_lo = [&](const unsigned char* stage) {
-#pragma unroll
-            for (int b = 0; b < RN; ++b)
-                bl[b] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(stage + b_off[b] + B_PLANE));
-        };
-#define X6_PASS(AA, BB)                                                                              \
-    _Pragma("unroll") for (int a = 0; a < RM; ++a) _Pragma("unroll") for (int b = 0; b < RN; ++b)    \
-        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AA[a], BB[b], acc[a][b], 0, 0, 0);
-        // stage 0: landed -> barrier -> DMA of stage NSTAGE-1 -> operands of step 0
-        if (NSTAGE == 3 && 1 < nk)
-            wait_vmcnt<PIECES>();
-        else
-            wait_vmcnt<0>();
-        block_barrier();
-        if (NSTAGE - 1 < nk) issue(NSTAGE - 1, smem + ((NSTAGE - 1) % NSTAGE) * STAGE_BYTES);
-        read_hi(smem);
-        read_lo(smem);
-        for (int kt = 0; kt < nk; ++kt) {
-            X6_PASS(ah, bh)
-#pragma unroll
-            for (int a = 0; a < RM; ++a) slice8_f16_lo(xs[a], ah[a], al[a]);
-            X6_PASS(al, bh)
-            const bool more = kt + 1 < nk;
-            const unsigned char* nstage = smem + ((kt + 1) % NSTAGE) * STAGE_BYTES;
-            float4 raw0[RM], raw1[RM];
-            if (more) {
-                if (NSTAGE == 3 && kt + 2 < nk)
-                    wait_vmcnt<PIECES>();
-                else
-                    wait_vmcnt<0>();
-                block_barrier();
-                if (kt + NSTAGE < nk) issue(kt + NSTAGE, smem + ((kt + NSTAGE) % NSTAGE) * STAGE_BYTES);
-#pragma unroll
-                for (int b = 0; b < RN; ++b)
-                    bh[b] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(nstage + b_off[b]));
-#pragma unroll
-                for (int a = 0; a < RM; ++a) {
-                    raw0[a] = *reinterpret_cast<const float4*>(nstage + a_off0[a]);
-                    raw1[a] = *reinterpret_cast<const float4*>(nstage + a_off1[a]);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            X6_PASS(ah, bl)
-            __builtin_amdgcn_sched_barrier(0);  // (the LDS latency of the reads above is spent under this pass)
-            if (more) {
-                read_lo(nstage);
-#pragma unroll
-                for (int a = 0; a < RM; ++a) slice8_f16_hi(raw0[a], raw1[a], sa, xs[a], ah[a]);
-            }
-        }
-#undef X6_PASS
-    } else
+    // (a software-pipelined f16x3 loop, with the stage hand-over between the second and third product pass, measured no
+    // faster: 350 vs 356 / 342 us; profiles/README.md)
     for (int kt = 0; kt < nk; ++kt) {
-        if (PERSIST && kt == 0 && !first)
-            wait_vmcnt<EPI_STORES>();  // stage 0 was prefetched BEFORE the previous tile's stores: leave those in flight
-        else if (NSTAGE == 3 && kt + 1 < nk)
-            wait_vmcnt<PIECES>();
-        else
-            wait_vmcnt<0>();
+        wait_vmcnt<0>();
         block_barrier();
-        if (kt == 0) X6_STAMP(1);
-        if (kt == 8) X6_STAMP(2);
         // (issuing these DMA pieces between the product passes instead - they cost a wave fewer issue cycles among
         // MFMAs than in front of LDS reads - measured 3.5 % SLOWER at T x 256 x 256)
         if (kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1, smem + ((kt + NSTAGE - 1) % NSTAGE) * STAGE_BYTES);
@@ -527,10 +350,8 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
             X6_PASS(ah, bh)
 #pragma unroll
             for (int a = 0; a < RM; ++a) slice8_f16_lo(xs[a], ah[a], al[a]);
-#if !X6_ABL_ONEMFMA
             X6_PASS(ah, bl)
             X6_PASS(al, bh)
-#endif
 #undef X6_PASS
         } else {
             bf16x8 ah[RM], am[RM], al[RM], bh[RN], bm[RN], bl[RN];
@@ -550,84 +371,43 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
 #define X6_PASS(AA, BB)                                                                              \
     _Pragma("unroll") for (int a = 0; a < RM; ++a) _Pragma("unroll") for (int b = 0; b < RN; ++b)    \
         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AA[a], BB[b], acc[a][b], 0, 0, 0);
-#if !X6_ABL_ONEMFMA
             X6_PASS(al, bh)
             X6_PASS(ah, bl)
             X6_PASS(am, bm)
             X6_PASS(am, bh)
             X6_PASS(ah, bm)
-#endif
             X6_PASS(ah, bh)
 #undef X6_PASS
         }
     }
 
-    X6_STAMP(3);
     // epilogue: per-wave LDS transpose of two 32x32 tiles at a time -> float4 row segments.  Per round: all LDS
     // traffic first, then all addend loads (rows clamped, no per-element branches), then the stores.
-    const int64_t next = tile + gridDim.x;
-    const bool has_next = PERSIST && next < n_mt;
-    if (has_next) {  // every wave has passed the last k-step's barrier, i.e. nobody reads stage 0 any more
-        set_rows(next * BM);
-        issue(0, smem);
-    }
     constexpr int PLD = 64 + 4;
-    float* patch = reinterpret_cast<float*>(smem + (PERSIST ? STAGE_BYTES : 0)) + wave * (32 * PLD);
+    float* patch = reinterpret_cast<float*>(smem) + wave * (32 * PLD);
     // EPI == 1: every lane's running column sums (4 columns x its rows, per 64-column half), behind the transpose patches
     float* red_acc = reinterpret_cast<float*>(smem + EPI_BYTES);
     static_assert(EPI_BYTES + (NT / 64) * (RN / 2) * 2 * 256 * 4 == EPI1_LDS, "LDS for the reduction slots (see launch_nt_rm)");
     const int prow = e_prow, pc4 = e_pc4;
-#if X6_ABL_NOSTORE == 2
-    if (acc[0][0][0] == 12345.678f)  // (keeps the accumulators alive)
-#endif
 #pragma unroll
     for (int ahb = 0; ahb < RM * (RN / 2); ++ahb) {
         const int a = ahb / (RN / 2), hb = ahb % (RN / 2);
         // the patches are private to a wave (LDS serves one wave's accesses in order): the only cross-wave hazard is
-        // the first overwrite of stage memory other waves may still be reading.  PERSIST must not use
-        // __syncthreads() here - its vmcnt(0) would drain the prefetch just issued.
-#if X6_EPI_NOSYNC
-        // one barrier in front of the first overwrite of stage memory; afterwards every wave works on its own patch
-        // (LDS serves one wave's accesses in order) and the stores of round r stay in flight under the transposes of
-        // round r+1 - __syncthreads() would drain them (it waits vmcnt(0)) four times per tile
-        if (ahb == 0) block_barrier();
-#else
-        if constexpr (PERSIST) {
-            if (ahb == 0) block_barrier();
-        } else {
-            __syncthreads();
-        }
-#endif
+        // the first overwrite of stage memory other waves may still be reading.  (One barrier in front of the first round
+        // only, so that the stores of round r stay in flight under the transposes of round r+1, measured within noise:
+        // 357 vs 363 us; profiles/README.md)
+        __syncthreads();
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 patch[((r & 3) + 8 * (r >> 2) + 4 * half) * PLD + b * 32 + il] = acc[a][2 * hb + b][r];
-#if !X6_EPI_NOSYNC
-        if constexpr (!PERSIST) __syncthreads();
-#endif
+        __syncthreads();
         const int col = n0 + wn * TN + hb * 64 + pc4;
         const int colc = col < g.N ? col : 0;
         const int64_t row0 = m0 + wm * TM + a * 32 + prow;
         float4 ov[BNRED ? 1 : 8], av[8], xv[BNRED ? 8 : 1];
-        if constexpr (PERSIST) {
-            // read the patch behind the compiler's back: it would put s_waitcnt vmcnt(0) in front of LDS reads that
-            // it cannot tell apart from the destination of the DMA prefetch in flight
-            v4f pv[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                asm volatile("ds_read_b128 %0, %1"
-                             : "=v"(pv[i])
-                             : "v"((unsigned)(size_t)(patch + (i * 4 + prow) * PLD + pc4))
-                             : "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(pv[4]), "+v"(pv[5]), "+v"(pv[6]),
-                           "+v"(pv[7])
-                         :
-                         : "memory");
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ov[BNRED ? 0 : i] = make_float4(pv[i].x, pv[i].y, pv[i].z, pv[i].w);
-        } else if constexpr (!BNRED) {
+        if constexpr (!BNRED) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) ov[i] = f4_ld(patch + (i * 4 + prow) * PLD + pc4);
         }
@@ -675,7 +455,7 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
             if constexpr (F16) v = f4_scale(f4_scale(v, inv_sa), inv_sw);
             v = f4_add(v, bias_v[hb]);
             if (HAS_ADD || GATHER) v = f4_add(v, av[i]);
-            if (row < g.M && col < g.N && (!X6_ABL_NOSTORE || v.x == 12345.678f)) {
+            if (row < g.M && col < g.N) {
                 if (g.stream_out)
                     f4_sts<true>(g.C + row * g.ldc + col, v);
                 else
@@ -733,42 +513,33 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
             }
         }
     }
-    X6_STAMP(4);
-#if X6_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    X6_STAMP(5);
-#endif
-    if (!has_next) break;
-    tile = next;
-    m0 = tile * BM;
-    first = false;
-    }  // row tiles
 }
 
-template <bool HAS_ADD, bool F16, int RM_, bool PERSIST = false>
+// (the unused last parameter keeps the kernel's symbol, and with it the code object, as it has been)
+template <bool HAS_ADD, bool F16, int RM_, bool = false>
 __global__ __launch_bounds__(NT) void gemm_nt_x6_kernel(X6Args g) {
-    gemm_nt_x6_body<HAS_ADD, F16, RM_, PERSIST, 0>(g);
+    gemm_nt_x6_body<HAS_ADD, F16, RM_>(g);
 }
 // the EPI == 1 variant needs more registers than the compiler's default target leaves for two waves per SIMD (it would
 // settle for one: 170 + 128 accumulator registers); pinning the occupancy makes it allocate within 256 (a handful of
 // spills with an addend).  Not applied to the plain kernel: there it measured 2.6 % slower (356 vs 347 us).
 template <bool HAS_ADD, int RM_>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gemm_nt_x6_bnred_kernel(X6Args g) {
-    gemm_nt_x6_body<HAS_ADD, true, RM_, false, 1>(g);
+    gemm_nt_x6_body<HAS_ADD, true, RM_, 1>(g);
 }
 template <int RM_, bool STATS>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gemm_nt_x6_gather_kernel(X6Args g) {
-    gemm_nt_x6_body<false, true, RM_, false, 2 | (STATS ? 4 : 0)>(g);
+    gemm_nt_x6_body<false, true, RM_, 2 | (STATS ? 4 : 0)>(g);
 }
 template <int RM_>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void gemm_nt_x6_stats_kernel(X6Args g) {
-    gemm_nt_x6_body<false, true, RM_, false, 4>(g);
+    gemm_nt_x6_body<false, true, RM_, 4>(g);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Persistent form of the f16x3 NT kernel for long products (>= 2 row tiles per resident workgroup; 128 x 256 tiles).
 // A one-tile workgroup spends its life in four serial phases - in-kernel s_memtime stamps at T x 256 x 256
-// (tools/x6_trace.py, profiles/r02_x6_phase_trace_onetile.txt): 11 % from entry until the first k-stage has landed, 62 % in the
+// (profiles/r02_x6_phase_trace_onetile.txt): 11 % from entry until the first k-stage has landed, 62 % in the
 // 16 k-steps, 23 % in the epilogue, 3 % waiting for its stores before it may retire - and only the co-resident
 // workgroup fills the gaps.  Here 512 workgroups walk the row tiles.  The DMA ring has THREE slots: while step s
 // multiplies out of slot s % 3, stages s+1 and s+2 are in flight - across tile boundaries too, so the first two
@@ -898,20 +669,6 @@ __device__ __forceinline__ void gemm_nt_f16p_body(const X6Args& g) {
             src_l = g.gsrc[row];
             dst_l = g.gdst[row];
         }
-        if (j == 1) X6_STAMP(0);
-#if X6_TRACE == 2
-        unsigned long long ph[5] = {0, 0, 0, 0, 0}, tp = __builtin_readcyclecounter();
-#define X6_PH(i)                                                    \
-    do {                                                            \
-        const unsigned long long tn_ = __builtin_readcyclecounter(); \
-        ph[i] += tn_ - tp;                                          \
-        tp = tn_;                                                   \
-    } while (0)
-#else
-#define X6_PH(i) \
-    do {         \
-    } while (0)
-#endif
         for (int kt = 0; kt < nk; ++kt) {
             const int s = j * nk + kt;
             // stage s has landed?  Steps 0 and 1 of a later tile were waited for before the previous epilogue.
@@ -921,13 +678,8 @@ __device__ __forceinline__ void gemm_nt_f16p_body(const X6Args& g) {
                 else
                     wait_vmcnt<0>();
             }
-            X6_PH(0);
             block_barrier();  // (also: every wave has left slot (s+2) % 3 - the reads of step s-1 or the patches)
-            X6_PH(1);
-            if (j == 2 && kt == 0) X6_STAMP(5);
-            if (j == 2 && kt == 2) X6_STAMP(6);
             if (issued < S) issue_next(slot == 0 ? 2 : slot - 1);  // stage s+2 -> slot (s+2) % 3
-            X6_PH(2);
             const unsigned char* stage = smem + slot * STAGE_BYTES;
             slot = slot == NS - 1 ? 0 : slot + 1;
             f16x8 ah[RM], al[RM], bh[RN], bl[RN];
@@ -945,32 +697,16 @@ __device__ __forceinline__ void gemm_nt_f16p_body(const X6Args& g) {
 #define X6_PASS(AA, BB)                                                                              \
     _Pragma("unroll") for (int a = 0; a < RM; ++a) _Pragma("unroll") for (int b = 0; b < RN; ++b)    \
         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AA[a], BB[b], acc[a][b], 0, 0, 0);
-#if X6_TRACE == 2
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            X6_PH(3);
-#endif
             X6_PASS(ah, bh)
 #pragma unroll
             for (int a = 0; a < RM; ++a) slice8_f16_lo(xs[a], ah[a], al[a]);
             X6_PASS(ah, bl)
             X6_PASS(al, bh)
 #undef X6_PASS
-#if X6_TRACE == 2
-            __builtin_amdgcn_sched_barrier(0);
-            X6_PH(4);
-#endif
         }
-#if X6_TRACE == 2
-        if (j == 1 && threadIdx.x == 0 && blockIdx.x < 512)
-            for (int i = 0; i < 5; ++i) x6_trace_buf[(4096 + blockIdx.x) * 8 + i] = ph[i];
-#endif
-        if (j == 1) X6_STAMP(1);
         // the two stages in flight belong to the next tile: have them landed before the first store goes out (see above)
         wait_vmcnt<0>();
-        if (j == 1) X6_STAMP(2);
         block_barrier();  // every wave has finished reading the last stage: its slot becomes the patches
-        if (j == 1) X6_STAMP(3);
         float* patch = reinterpret_cast<float*>(smem + (slot == 0 ? NS - 1 : slot - 1) * STAGE_BYTES + wave * PATCH_BYTES);
         // The epilogue has NO control flow around its memory operations (N is a multiple of 256 here; rows past the end are
         // clamped to the last row, whose values the clamped operand rows reproduce bit for bit, so the surplus stores
@@ -993,7 +729,8 @@ __device__ __forceinline__ void gemm_nt_f16p_body(const X6Args& g) {
         const int col0 = n0 + wn * TN + pc4_e;
         // operands of one HALF round (16 x 32 of the 32 x 32 tile: two float4 per lane and array), requested D half rounds
         // ahead of their use - the latency of these loads, not their volume, is what the fused epilogues cost
-        // (tools/x6p_trace.py: 9 k cycles for the plain epilogue, 54 k with a dependent index load + gather per half round)
+        // (profiles/r02_x6_phase_trace_persistent.txt: 9 k cycles for the plain epilogue, 54 k with a dependent index load +
+        // gather per half round)
         constexpr int D = (BNRED && HAS_ADD) ? 1 : 2, NH = 2 * RN * RM;  // look-ahead, half rounds per tile
         float4 av[(HAS_ADD || GATHER) ? D : 1][2], xv[BNRED ? D : 1][2], nst[BNRED ? 2 : 1][3], bias_b[2], s0, s1;
         auto row_of = [&](int a, int i) {
@@ -1067,7 +804,7 @@ __device__ __forceinline__ void gemm_nt_f16p_body(const X6Args& g) {
                 if (q + D < NH) load_half(q + D);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int i = 0; i < 2; ++i) f4_sts<X6P_NT != 0>(c_t + (row_of(a, 2 * h + i) * (int)g.ldc + col), v[i]);  // (write-once hint)
+                for (int i = 0; i < 2; ++i) f4_sts<true>(c_t + (row_of(a, 2 * h + i) * (int)g.ldc + col), v[i]);  // (write-once hint: plain stores measured slower, gather 431 vs 408 us)
                 if (a == RM - 1 && h == 1 && (BNRED || STATS)) {
                     // the wave's eight row groups (lane >> 3) hold the same four columns: fixed-order butterfly
 #pragma unroll
@@ -1087,7 +824,6 @@ __device__ __forceinline__ void gemm_nt_f16p_body(const X6Args& g) {
                 }
             }
         }
-        if (j == 1) X6_STAMP(4);
     }
 }
 
@@ -1216,7 +952,7 @@ __global__ __launch_bounds__(TNT) void gemm_tn_x6_kernel(TnArgs g) {
     const char* sbase = reinterpret_cast<const char*>(is_x ? g.X + k0 : g.G + n0);
     const int64_t ld_bytes = ld * 4;
 #define TN_LOAD(R, ST)                                                                                 \
-    if ((ST) < nst && (!X6_ABL_NOALOAD || (ST) < 2)) {                                                 \
+    if ((ST) < nst) {                                                                                  \
         const int64_t r0_ = rbeg + (int64_t)(ST) * TSTEP;                                              \
         if (r0_ + TSTEP <= g.M) {                                                                      \
             const char* p_ = sbase + r0_ * ld_bytes;                                                   \
@@ -1271,9 +1007,7 @@ __global__ __launch_bounds__(TNT) void gemm_tn_x6_kernel(TnArgs g) {
         bh[b] = *reinterpret_cast<const f16x8*>((buf) + b_off[b]);                                              \
         bl[b] = *reinterpret_cast<const f16x8*>((buf) + b_off[b] + TPLANE);                                     \
     }
-#define TN_MMA_F16                                                                                              \
-    if (!X6_ABL_ONEMFMA) { TN_PASS(f16, al, bh) TN_PASS(f16, ah, bl) }                                          \
-    TN_PASS(f16, ah, bh)
+#define TN_MMA_F16 TN_PASS(f16, al, bh) TN_PASS(f16, ah, bl) TN_PASS(f16, ah, bh)
 #define TN_MMA_BF16(buf)                                                                                        \
     {                                                                                                           \
         bf16x8 ah[TRM], am[TRM], al[TRM], bh[TRN], bm[TRN], bl[TRN];                                            \
@@ -1291,41 +1025,10 @@ __global__ __launch_bounds__(TNT) void gemm_tn_x6_kernel(TnArgs g) {
         TN_PASS(bf16, am, bh) TN_PASS(bf16, ah, bm) TN_PASS(bf16, ah, bh)                                       \
     }
 
-    if constexpr (F16 && TN_PIPE) {
-        // Software-pipelined stage loop (f16x3): THREE stages of this thread's column in flight in registers; the slices
-        // of stage s+1 are computed and written to the other LDS buffer in the shadow of the products of stage s (VALU
-        // and LDS-write instructions issue while the matrix pipe works through the 24 products), one barrier per stage.
-        // Same arithmetic in the same order as the two-stage loop: bit-identical.
-        float r0[TSTEP], r1[TSTEP], r2[TSTEP];
-        TN_LOAD(r0, 0)
-        TN_LOAD(r1, 1)
-        TN_LOAD(r2, 2)
-        if (nst > 0) {
-            if (nst > 2) wait_vmcnt<2 * TSTEP>(); else if (nst > 1) wait_vmcnt<TSTEP>(); else wait_vmcnt<0>();
-            TN_SLICE(r0, 0, smem)
-        }
-#define TN_PIPE_STEP(RNEXT, RFREE, ST)                                                                          \
-    if ((ST) < nst) {                                                                                           \
-        if ((ST) + 2 < nst) wait_vmcnt<TSTEP>(); else wait_vmcnt<0>(); /* stage ST+1 has landed */              \
-        block_barrier(); /* slices of stage ST visible; every wave is past its reads of stage ST-1 */          \
-        unsigned char* cur = smem + ((ST) & 1) * BUF;                                                           \
-        unsigned char* nxt = smem + (((ST) + 1) & 1) * BUF;                                                     \
-        TN_READ_F16(cur)                                                                                        \
-        if (!X6_ABL_ONEMFMA) { TN_PASS(f16, al, bh) }                                                           \
-        if ((ST) + 1 < nst) TN_SLICE(RNEXT, (ST) + 1, nxt)                                                      \
-        if (!X6_ABL_ONEMFMA) { TN_PASS(f16, ah, bl) }                                                           \
-        TN_PASS(f16, ah, bh)                                                                                    \
-        TN_LOAD(RFREE, (ST) + 3)                                                                                \
-    }
-        for (int st = 0; st < nst; st += 3) {
-            TN_PIPE_STEP(r1, r0, st)
-            TN_PIPE_STEP(r2, r1, st + 1)
-            TN_PIPE_STEP(r0, r2, st + 2)
-        }
-#undef TN_PIPE_STEP
-    } else {
-        float ra[TSTEP], rb[TSTEP];  // two stages of this thread's column in flight
-        // slice the landed stage into the LDS image, refill the registers with stage ST+2, hand over, multiply
+    // two stages of this thread's column in flight (three, with the next stage sliced under the current products, measured
+    // no faster: 480-492 vs 454-492 us; profiles/README.md)
+    float ra[TSTEP], rb[TSTEP];
+    // slice the landed stage into the LDS image, refill the registers with stage ST+2, hand over, multiply
 #define TN_STEP(R, ST, BUFI)                                                                                    \
     if ((ST) < nst) {                                                                                           \
         if ((ST) + 1 < nst)                                                                                     \
@@ -1343,14 +1046,13 @@ __global__ __launch_bounds__(TNT) void gemm_tn_x6_kernel(TnArgs g) {
             TN_MMA_BF16(buf)                                                                                    \
         }                                                                                                       \
     }
-        TN_LOAD(ra, 0)
-        TN_LOAD(rb, 1)
-        for (int st = 0; st < nst; st += 2) {
-            TN_STEP(ra, st, 0)
-            TN_STEP(rb, st + 1, 1)
-        }
-#undef TN_STEP
+    TN_LOAD(ra, 0)
+    TN_LOAD(rb, 1)
+    for (int st = 0; st < nst; st += 2) {
+        TN_STEP(ra, st, 0)
+        TN_STEP(rb, st + 1, 1)
     }
+#undef TN_STEP
 #undef TN_MMA_BF16
 #undef TN_MMA_F16
 #undef TN_READ_F16
@@ -1567,29 +1269,6 @@ int launch_nt_rm(const X6Args& g, hipStream_t st) {
         attr_set = true;
     }
     dim3 grid(alignn_ceil_div(g.M, Geo<RM_>::BM), g.Npad / BN);
-#if X6_PERSIST
-    // long products (>= 4 tiles per resident workgroup): 512 persistent workgroups (two per CU) walk the row tiles
-    if constexpr (RM_ == 2 && Sch<F16, RM_>::NSTAGE == 2) {
-        constexpr int kResident = 512;
-        const int ny = g.Npad / BN;
-        // (without addend only: the addend variant needs 292 registers per lane in this form - one wave per SIMD)
-        if (!g.addend && !g.red_partial && !g.gp && g.N == g.Npad && ((g.K / BK) & 1) == 0 && (int64_t)grid.x * ny >= 4 * kResident &&
-            ny <= kResident) {
-            constexpr int plds = Sch<F16, RM_>::LDS_PERSIST;
-            static bool pattr_set = false;
-            if (!pattr_set) {
-                hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_x6_kernel<false, F16, RM_, true>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, plds);
-                if (e != hipSuccess) return (int)e;
-                pattr_set = true;
-            }
-            hipLaunchKernelGGL((gemm_nt_x6_kernel<false, F16, RM_, true>), dim3(kResident / ny, ny), dim3(NT), plds,
-                               st, g);
-            ALIGNN_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-#endif
     if constexpr (F16) {
         constexpr int slds = Sch<F16, RM_>::LDS > EPI1_LDS ? Sch<F16, RM_>::LDS : EPI1_LDS;  // + the column-sum slots
         static bool fattr_set = false;
@@ -1649,14 +1328,8 @@ int launch_nt_rm(const X6Args& g, hipStream_t st) {
     return 0;
 }
 // ---- persistent f16x3 kernel (gemm_nt_f16p_body): long products only
-#ifndef X6_NO_PERSIST
-#define X6_NO_PERSIST 0  // 1: never dispatch the persistent kernel (A/B in tools/ablate_x6.py)
-#endif
 constexpr int kResidentP = 512;  // two workgroups per CU
 inline bool nt_persistent(int64_t M, int N, int K) {
-#if X6_NO_PERSIST || defined(X6_FORCE_RM)
-    return false;
-#endif
     const char* e = getenv("ALIGNN_AMD_X6_PERSIST");  // =0: one-tile kernels everywhere (read per call: A/B runs, tests)
     if (e != nullptr && e[0] == '0') return false;
     const int64_t tiles = alignn_ceil_div(M, 128) * (int64_t)(npad(N) / BN);
@@ -1711,9 +1384,6 @@ int launch_nt_p(const X6Args& g_in, hipStream_t st) {
 // tiles = one thin generation, on 793 half tiles - measured slower on every variant in round 3)
 inline int64_t rm1_below() { return 256; }
 inline int nt_block_rows(int64_t M, int N, int K) {
-#ifdef X6_FORCE_RM
-    return 64 * X6_FORCE_RM;
-#endif
     if (nt_persistent(M, N, K)) return 64;
     const int64_t tiles128 = alignn_ceil_div(M, 128) * (int64_t)(npad(N) / BN);
     return (K <= 64 || tiles128 < rm1_below()) ? 64 : 128;
@@ -1722,9 +1392,6 @@ template <bool F16>
 int launch_nt(const X6Args& g, hipStream_t st) {
     // 64-row tiles for shallow products and for products too short to give every CU one 128-row tile
     const int64_t tiles128 = alignn_ceil_div(g.M, 128) * (int64_t)(g.Npad / BN);
-#ifdef X6_FORCE_RM  // (tools/ablate_x6.py)
-    return launch_nt_rm<F16, X6_FORCE_RM>(g, st);
-#endif
     if constexpr (F16)
         if (nt_persistent(g.M, g.N, g.K)) {
             // measured per variant at T x 256 x 256, kernels interleaved (tools/x6_family_check.py): persistent -5 % plain,
@@ -1744,12 +1411,6 @@ inline bool nt_args_ok(const float* A, int64_t lda, const void* Wsplit, const fl
              (addend && ((ldadd & 3) || !a16(addend))));
 }
 }  // namespace
-
-#if X6_TRACE
-extern "C" int alignn_x6_trace_read(void* host, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(x6_trace_buf), bytes < sizeof(x6_trace_buf) ? bytes : sizeof(x6_trace_buf));
-}
-#endif
 
 extern "C" {
 
@@ -1860,7 +1521,7 @@ int alignn_gemm_tn_x6_partials(const float* G, int64_t ldg, const float* g_amax,
     tn::TnArgs g{G, ldg, X, ldx, (float*)workspace, M, N, K, tn::tn_chunk(M, N, K), N / tn::TBN, K / tn::TBK,
                  tn::tn_splits(M, N, K), g_amax, x_amax};
     static bool tn_attr = false;
-    if (!tn_attr && true) {
+    if (!tn_attr) {
         hipError_t e = hipFuncSetAttribute((const void*)tn::gemm_tn_x6_kernel<false>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, tn::TSch<false>::LDS);
         if (e == hipSuccess)

@@ -74,7 +74,8 @@ def newest_round():
 
 
 # other workloads of BASELINE.json benched beside the headline (bench.py `other_configs`): name -> (triplets, model); their PMC
-# passes are profiles/rNN_pmc_<name>_fetch_size.txt / _write_size.txt (tools/gpu/r6_pmc.sh with BARGS / SUFFIX)
+# passes are profiles/rNN_pmc_<name>_fetch_size.txt / _write_size.txt (the FETCH_SIZE / WRITE_SIZE passes of
+# tools/gpu/profile_set.sh, run with that workload's bench arguments)
 WORKLOADS = {"cfg3_ff": (561792, "alignn_ff"), "cfg4_mol": (909126, "alignn")}
 
 
