@@ -166,6 +166,10 @@ SIGNATURES = {
                                 _f64, _f64, _f64, _p]),
     "alignn_fire_cell_step": (_i32, [_p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                      _p, _f64, _i32, _f64, _f64, _i32, _f64, _f64, _f64, _f64, _p]),
+    # batched molecular dynamics (csrc/dynamics.hip)
+    "alignn_md_step": (_i32, [_p, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32,
+                              _i32, _f64, _f64, _f64, _i32, _f64, _p]),
+    "alignn_md_init_momenta": (_i32, [_p, _i32, _p, _p, _p, _p, _f64, _p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

@@ -109,3 +109,39 @@ __device__ __forceinline__ void block_amax_commit(float m, float* amax) {
     __syncthreads();  // the scratch array may be reused by a second commit
 }
 __device__ __forceinline__ float f4_absmax(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+
+// ---- float64 helpers of the per-structure integrators (relax.hip, dynamics.hip): one workgroup of WAVES waves per structure ----
+
+// sums over the workgroup of NV values per thread (the last one a max when LAST_MAX); every thread returns the same bits.
+// Fixed order (shuffle-down within a wave, then the wave partials in wave order): no float atomics, so a structure's result
+// does not depend on which other structures share the launch.  Every thread of the workgroup must call it (barriers).
+template <int NV, bool LAST_MAX, int WAVES>
+__device__ __forceinline__ void block_reduce(double (&v)[NV], double (*sh)[WAVES]) {
+    const int lane = threadIdx.x & (ALIGNN_WAVE - 1), wave = threadIdx.x / ALIGNN_WAVE;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const bool mx = LAST_MAX && j == NV - 1;
+#pragma unroll
+        for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) {
+            const double u = __shfl_down(v[j], o, ALIGNN_WAVE);
+            v[j] = mx ? fmax(v[j], u) : v[j] + u;
+        }
+        if (lane == 0) sh[j][wave] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const bool mx = LAST_MAX && j == NV - 1;
+        double s = sh[j][0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) s = mx ? fmax(s, sh[j][w]) : s + sh[j][w];
+        v[j] = s;
+    }
+    __syncthreads();  // (sh is reused by the next reduction)
+}
+
+// fractional coordinate wrapped into [0, 1)
+__device__ __forceinline__ double wrap01(double f) {
+    f -= floor(f);
+    return f < 1.0 ? f : 0.0;  // (-tiny - floor(-tiny) rounds to 1.0)
+}

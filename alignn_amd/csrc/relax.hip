@@ -18,37 +18,6 @@ namespace {
 constexpr int FIRE_BLOCK = 256;
 constexpr int FIRE_WAVES = FIRE_BLOCK / ALIGNN_WAVE;
 
-// sums over the workgroup of NV values per thread (the last one a max when LAST_MAX); every thread returns the same bits
-template <int NV, bool LAST_MAX>
-__device__ __forceinline__ void block_reduce(double (&v)[NV], double (*sh)[FIRE_WAVES]) {
-    const int lane = threadIdx.x & (ALIGNN_WAVE - 1), wave = threadIdx.x / ALIGNN_WAVE;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const bool mx = LAST_MAX && j == NV - 1;
-#pragma unroll
-        for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) {
-            const double u = __shfl_down(v[j], o, ALIGNN_WAVE);
-            v[j] = mx ? fmax(v[j], u) : v[j] + u;
-        }
-        if (lane == 0) sh[j][wave] = v[j];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const bool mx = LAST_MAX && j == NV - 1;
-        double s = sh[j][0];
-#pragma unroll
-        for (int w = 1; w < FIRE_WAVES; ++w) s = mx ? fmax(s, sh[j][w]) : s + sh[j][w];
-        v[j] = s;
-    }
-    __syncthreads();  // (sh is reused by the next reduction)
-}
-
-__device__ __forceinline__ double wrap01(double f) {
-    f -= floor(f);
-    return f < 1.0 ? f : 0.0;  // (-tiny - floor(-tiny) rounds to 1.0)
-}
-
 __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(
     const double* __restrict__ forces, const double* __restrict__ energy, const int32_t* __restrict__ force_ptr,
     const int32_t* __restrict__ active, const int32_t* __restrict__ atom_ptr, const double* __restrict__ inv_lattice,

@@ -935,6 +935,33 @@ int alignn_fire_cell_step(const double* forces, const double* energy, const doub
                           int steps, double maxstep, double dtmax, int nmin, double finc, double fdec, double astart, double fa,
                           alignn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched molecular dynamics at fixed cell (csrc/dynamics.hip; alignn_amd/dynamics.py is the host loop): ASE 3.22.1's
+ * VelocityVerlet (ensemble 0), Langevin (1) and NVTBerendsen (2) as alignn/ff/ff.py:419-550 runs them, float64, ASE units
+ * (eV, A, amu, A sqrt(amu / eV)).  One workgroup per structure s < n_structures; it owns atoms [atom_ptr[s], atom_ptr[s+1]) of
+ * masses [N], momenta / positions (Cartesian, unwrapped) / frac / velocities / rnd_vel [N][3], and forces [n_rows][3] rows of
+ * the same range (the evaluation at the current positions, energy[s] its energy).  n_rows must equal atom_ptr[n_structures],
+ * else status[0] = -1 and nothing is written.  One launch per evaluation t = 0 .. steps: finish step t (t > 0: the second
+ * half-kick with these forces), record frame t / interval when t % interval == 0 (epot / ekin / temperature [frames][B], KE =
+ * 0.5 sum p^2 / m, T = 2 KE / (3 n kB); traj_positions / traj_momenta [frames][N][3] unless NULL), then, unless t == steps,
+ * begin step t + 1 (Berendsen velocity scaling toward t0_kelvin[s] with time constant taut; the first half-kick; fixcm's
+ * momentum / noise corrections; the drift; frac = positions inv_lattice[s] wrapped into [0, 1)).  Langevin draws 6 normals
+ * per atom from Philox4x32-10 (key = seeds[s], counter (atom, t, block 0..2, 0)) and keeps velocities and rnd_vel between the
+ * two halves; noise_out [N][18] (tests; NULL otherwise) receives per atom xi[3], eta[3] and the 12 Philox words as doubles.
+ * Fixed-order reductions: a structure's trajectory is bit-identical whatever else shares the launch.
+ * ------------------------------------------------------------------------------------------ */
+int alignn_md_step(const double* forces, const double* energy, int64_t n_rows, const int32_t* atom_ptr, int n_structures,
+                   const double* masses, const double* inv_lattice, double* momenta, double* positions, double* frac,
+                   double* velocities, double* rnd_vel, const double* t0_kelvin, const uint64_t* seeds, double* epot, double* ekin,
+                   double* temperature, double* traj_positions, double* traj_momenta, double* noise_out, int32_t* status, int t,
+                   int interval, int steps, int ensemble, double dt, double friction, double taut, int fixcm, double kB,
+                   alignn_stream_t stream);
+
+/* Maxwell-Boltzmann momenta (ASE's MaxwellBoltzmannDistribution, no Stationary): momenta[i] = xi sqrt(m_i kB t_kelvin[s]) with
+ * xi three normals of the stream above (counter (atom, 0, block 0..1, 1)). */
+int alignn_md_init_momenta(const int32_t* atom_ptr, int n_structures, const double* masses, const double* t_kelvin,
+                           const uint64_t* seeds, double* momenta, double kB, alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
