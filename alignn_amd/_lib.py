@@ -170,6 +170,15 @@ SIGNATURES = {
     "alignn_md_step": (_i32, [_p, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32,
                               _i32, _f64, _f64, _f64, _i32, _f64, _p]),
     "alignn_md_init_momenta": (_i32, [_p, _i32, _p, _p, _p, _p, _f64, _p]),
+    # batched finite-displacement phonons (csrc/phonon.hip)
+    "alignn_phonon_displace": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _p]),
+    "alignn_phonon_fc_rows": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _f64, _p, _p]),
+    "alignn_phonon_symmetrize": (_i32, [_p, _p, _p, _p, _p, _i32, _i64, _p]),
+    "alignn_phonon_acoustic": (_i32, [_p, _p, _p, _p, _i32, _i32, _p]),
+    "alignn_phonon_mass_weight": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i64, _p]),
+    "alignn_phonon_eigh_max_dim": (_i32, []),
+    "alignn_phonon_eigh": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _p, _i32, _f64, _p, _p, _p, _p, _p, _p, _p]),
+    "alignn_phonon_dos": (_i32, [_p, _p, _i32, _i32, _f64, _p, _p, _p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

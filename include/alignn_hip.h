@@ -962,6 +962,52 @@ int alignn_md_step(const double* forces, const double* energy, int64_t n_rows, c
 int alignn_md_init_momenta(const int32_t* atom_ptr, int n_structures, const double* masses, const double* t_kelvin,
                            const uint64_t* seeds, double* momenta, double kB, alignn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched finite-displacement phonons (csrc/phonon.hip; alignn_amd/phonons.py is the host loop): ASE 3.22.1's Phonons as
+ * the reference's ase_phonon runs it (alignn/ff/ff.py:1337), float64.  Structure s has n_s = atom_ptr[s+1] - atom_ptr[s]
+ * atoms, m_s = 3 n_s, a supercell supercell[s] = (N0, N1, N2) of Ncell_s = N0 N1 N2 images (atom j = image n_s + b, image =
+ * (m0 N1 + m1) N2 + m2), and its force constants C [Ncell_s][m_s][m_s] at fc_off[s] of the fc buffers.
+ *
+ * _displace: for job k < n_jobs, jobs[k] = (s, d), d = 6a + 2i + sign (0: -delta, 1: +delta) moves atom a of image 0 along
+ * axis i.  Writes the supercell's n_s Ncell_s rows from row_off[k] of frac [.][3] (wrapped into [0, 1) with inv_supercell[s],
+ * the inverse of the supercell lattice) and, unless NULL, of cart [.][3] (Cartesian, unwrapped: positions + image offsets of
+ * the primitive lattice[s] + the displacement).
+ * _fc_rows: pair k: pairs[k] = (s, x = 3a + i); the minus supercell's forces are rows [pair_rows[k], + n_s Ncell_s) of forces,
+ * the plus supercell's the rows after.  Writes row x of every cell: (F- - F+) / (2 delta) after the drift correction (0 none,
+ * 1 Frederiksen: the supercell's force sum off atom a's row, 2 mean: sum / (n_s Ncell_s) off every row).
+ * _symmetrize (out of place), _acoustic (in place): one pass of ASE's Phonons.symmetrize / Phonons.acoustic (offset 0).
+ * _mass_weight: dyn = fc * (m_x^-1/2 m_y^-1/2) (masses [atoms] in amu).  max_elems = max_s Ncell_s m_s^2, max_atoms = max_s n_s.
+ * _eigh: one workgroup per (q < n_q, structure).  D(q) = sum_R dyn[R] exp(-2 pi i q.R) over the lattice points of rows
+ * [cell_ptr[s], cell_ptr[s+1]) of lattice_points [.][3] (int) paired with the cells of dyn at dyn_off[s] (dims[s] = m_s <=
+ * max_dim <= alignn_phonon_eigh_max_dim()), from its upper triangle; parallel cyclic Jacobi in LDS.  Writes per structure,
+ * ascending per q: freqs [n_q][m_s] at freq_off[s] (sign(l) scale sqrt(|l|)), eigvals (the same shape; NULL: not written),
+ * modes [n_q][m_s][m_s] complex (interleaved re, im; column r = the eigenvector of eigenvalue r; NULL: not computed) at
+ * mode_off[s] (in doubles).  status[0] = 1 when a (q, structure) hit the sweep cap; untouched otherwise.
+ * _dos: per structure s < n_structures over freqs [freq_off[s], freq_off[s+1]): energies [s][npts] = linspace(min - 3 width,
+ * max + 3 width, npts), weights [s][npts] = sum of unit Gaussians of `width` at those energies.
+ * Fixed-order reductions: a structure's results are bit-identical whatever else shares the launches.
+ * ------------------------------------------------------------------------------------------ */
+int alignn_phonon_displace(const double* positions, const int32_t* atom_ptr, const double* lattice, const double* inv_supercell,
+                           const int32_t* supercell, const int32_t* jobs, const int64_t* row_off, int n_jobs, double delta,
+                           double* frac, double* cart, alignn_stream_t stream);
+int alignn_phonon_fc_rows(const double* forces, const int32_t* pairs, const int64_t* pair_rows, int n_pairs,
+                          const int32_t* atom_ptr, const int32_t* supercell, const int64_t* fc_off, int drift, double delta,
+                          double* fc, alignn_stream_t stream);
+int alignn_phonon_symmetrize(const double* fc_in, double* fc_out, const int32_t* atom_ptr, const int32_t* supercell,
+                             const int64_t* fc_off, int n_structures, int64_t max_elems, alignn_stream_t stream);
+int alignn_phonon_acoustic(double* fc, const int32_t* atom_ptr, const int32_t* supercell, const int64_t* fc_off,
+                           int n_structures, int max_atoms, alignn_stream_t stream);
+int alignn_phonon_mass_weight(const double* fc, double* dyn, const double* masses, const int32_t* atom_ptr,
+                              const int32_t* supercell, const int64_t* fc_off, int n_structures, int64_t max_elems,
+                              alignn_stream_t stream);
+int alignn_phonon_eigh_max_dim(void);
+int alignn_phonon_eigh(const double* dyn, const int64_t* dyn_off, const int32_t* lattice_points, const int32_t* cell_ptr,
+                       const int32_t* dims, int n_structures, int max_dim, const double* qpoints, int n_q, double scale,
+                       double* freqs, const int64_t* freq_off, double* eigvals, double* modes, const int64_t* mode_off,
+                       int32_t* status, alignn_stream_t stream);
+int alignn_phonon_dos(const double* freqs, const int64_t* freq_off, int n_structures, int npts, double width, double* energies,
+                      double* weights, alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

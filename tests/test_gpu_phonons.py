@@ -1,0 +1,313 @@
+"""Batched phonons on the device (csrc/phonon.hip, alignn_amd/phonons.py) against the numpy restatement of ASE's Phonons in
+test_phonons_ref.py: (1) the displaced supercells bit for bit; (2) force constants from forces_fn forces for every drift,
+symmetrize and acoustic setting; (3) the Jacobi eigen launch against numpy.linalg.eigvalsh (random Hermitian, degenerate,
+diagonal and zero matrices; eigenvector residuals and orthonormality; D(q) from the upper triangle); (4) the analytic
+dispersion of spring crystals end to end; (5) a structure alone vs. in a batch, bit for bit; (6) the model path against one
+model(batch) per displaced supercell, and chunked; (7) the DOS."""
+
+import numpy as np
+import pytest
+import torch
+
+from alignn_amd import ALIGNNAtomWise, ALIGNNAtomWiseConfig, _lib, neighbors, phonons
+from alignn_amd.phonons import FREQ_SCALE, monkhorst_pack
+from alignn_amd.synthetic import make_crystal
+from tests.test_phonons_ref import (displaced_supercells, dos, dq, dynamical_matrices, force_constants, frequencies,
+                                    inv_supercell, lattice_points, sc_analytic, simple_cubic, spring_forces_of)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def _t(x, dtype=torch.float64):
+    return torch.tensor(np.asarray(x), dtype=dtype, device=DEV)
+
+
+def _rel(got, want):
+    return np.abs(np.asarray(got) - np.asarray(want)).max() / max(1e-300, np.abs(np.asarray(want)).max())
+
+
+def _structures(sizes, seed0):
+    lats, pos = [], []
+    for i, n in enumerate(sizes):
+        lat, frac, _ = make_crystal(max(n, 2), seed0 + i)
+        lats.append(np.asarray(lat, dtype=np.float64))
+        pos.append((np.asarray(frac, dtype=np.float64) @ lats[-1])[:n])
+    return lats, pos
+
+
+def pair_forces(sl, cart):
+    """A deterministic exponential pair repulsion over the images within one supercell of each other (float64 numpy)."""
+    sl, cart = np.asarray(sl, dtype=np.float64), np.asarray(cart, dtype=np.float64)
+    img = np.indices((3, 3, 3)).reshape(3, -1).T - 1.0
+    shifts = img @ sl
+    d = cart[None, :, None, :] + shifts[None, None, :, :] - cart[:, None, None, :]  # [i, j, image, 3]
+    r = np.sqrt((d * d).sum(-1))
+    r = np.where(r > 1e-9, r, np.inf)
+    g = -2.0 * np.exp(-r / 0.7) / 0.7 / r  # phi'(r) / r, phi = 2 exp(-r / 0.7)
+    return (g[..., None] * d).sum((1, 2))
+
+
+class NumpyForces:
+    """forces_fn through a numpy force function, one displaced supercell at a time: a supercell's forces do not depend on
+    what else is in the call."""
+
+    def __init__(self, fn):
+        self.fn, self.calls = fn, 0
+
+    def __call__(self, lats, poss):
+        self.calls += 1
+        fs = [self.fn(l.cpu().numpy(), p.cpu().numpy()) for l, p in zip(lats, poss)]
+        return torch.zeros(len(fs), device=DEV), _t(np.concatenate(fs))
+
+
+# --- (1) displaced supercells ------------------------------------------------------------------------------------------------
+def test_displaced_supercells_are_the_restatement_bit_for_bit():
+    lib = _lib.load()
+    sizes, scs = [1, 3, 5], [(2, 2, 2), (3, 1, 2), (2, 3, 4)]
+    lats, pos = _structures(sizes, 40)
+    B, delta = len(sizes), 0.0137
+    ncell = [int(np.prod(c)) for c in scs]
+    lat_d = _t(np.stack(lats))
+    dims = _t(scs, torch.int32)
+    inv = _t(np.stack([inv_supercell(lats[s], scs[s]) for s in range(B)]))
+    jobs, rows, r = [], [], 0
+    for s in range(B):
+        for d in range(6 * sizes[s]):
+            jobs.append((s, d))
+            rows.append(r)
+            r += sizes[s] * ncell[s]
+    frac = torch.full((r, 3), np.nan, dtype=torch.float64, device=DEV)
+    cart = torch.full((r, 3), np.nan, dtype=torch.float64, device=DEV)
+    # (every argument tensor bound to a name: a temporary's memory could be handed to the next one before the launch)
+    pos_d, ptr_d = _t(np.concatenate(pos)), _t(np.concatenate([[0], np.cumsum(sizes)]), torch.int32)
+    jobs_d, rows_d = _t(jobs, torch.int32), _t(rows, torch.int64)
+    _lib.check(lib.alignn_phonon_displace(
+        pos_d.data_ptr(), ptr_d.data_ptr(), lat_d.data_ptr(), inv.data_ptr(), dims.data_ptr(), jobs_d.data_ptr(),
+        rows_d.data_ptr(), len(jobs), delta, frac.data_ptr(), cart.data_ptr(), _lib.stream()), "phonon_displace")
+    frac, cart, inv_h = frac.cpu().numpy(), cart.cpu().numpy(), inv.cpu().numpy()
+    k = 0
+    for s in range(B):
+        for f, c in displaced_supercells(lats[s], pos[s], scs[s], delta, inv_h[s]):
+            o = rows[k]
+            assert np.array_equal(frac[o:o + len(f)], f) and np.array_equal(cart[o:o + len(c)], c), (s, k)
+            k += 1
+    assert (frac >= 0).all() and (frac < 1).all()
+
+
+# --- (2) force constants ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sc", [(2, 2, 2), (3, 3, 3), (2, 3, 4)])
+def test_force_constants_match_the_restatement(sc):
+    lats, pos = _structures([3], 70)
+    masses = [np.array([12.0, 30.0, 55.0])]
+    delta = 0.01
+    sl = lats[0] * np.array(sc, dtype=np.float64)[:, None]
+    cache = {}
+
+    def fn(l, c):
+        key = c.tobytes()
+        if key not in cache:
+            cache[key] = pair_forces(l, c)
+        return cache[key]
+
+    ff = NumpyForces(fn)
+    forces = [fn(sl, c) for _, c in displaced_supercells(lats[0], pos[0], sc, delta, inv_supercell(lats[0], sc))]
+    qs = np.random.default_rng(0).uniform(-0.5, 0.5, (5, 3))
+    for drift in ("frederiksen", "mean", None):
+        for n_sym in (0, 1, 3):
+            for ac in (True, False):
+                res = phonons(None, lats, pos, None, masses, supercell=sc, delta=delta, drift=drift, symmetrize=n_sym,
+                              acoustic=ac, qpoints=qs, dos_kpts=None, forces_fn=ff, device=DEV)
+                want = force_constants(forces, 3, sc, delta, drift, n_sym, ac)
+                got = res.force_constants[0].cpu().numpy()
+                assert _rel(got, want) <= 1e-12, (drift, n_sym, ac, _rel(got, want))
+                assert np.array_equal(res.lattice_points[0].numpy(), lattice_points(sc))
+                w = frequencies(dynamical_matrices(want, masses[0]), lattice_points(sc), qs)
+                assert np.abs(res.frequencies[0].cpu().numpy() - w).max() <= 1e-10 * np.abs(w).max()
+    assert res.n_supercells == 18 and res.frequencies[0].shape == (5, 9)
+
+
+# --- (3) the eigen launch -------------------------------------------------------------------------------------------------
+def _hermitian(rng, m, kind):
+    if kind == "zero":
+        return np.zeros((m, m), dtype=complex)
+    if kind == "diagonal":
+        return np.diag(rng.normal(size=m)).astype(complex)
+    if kind == "degenerate":
+        Q, _ = np.linalg.qr(rng.normal(size=(m, m)) + 1j * rng.normal(size=(m, m)))
+        lam = np.repeat(rng.normal(size=(m + 2) // 3), 3)[:m]  # every eigenvalue threefold (the last group maybe less)
+        return (Q * lam) @ Q.conj().T
+    X = rng.normal(size=(m, m)) + 1j * rng.normal(size=(m, m))
+    return X + X.conj().T
+
+
+def _eigh_launch(D_list, R_list, q, modes):
+    lib = _lib.load()
+    ms = [D.shape[1] for D in D_list]
+    K = len(q)
+    dyn = _t(np.concatenate([D.reshape(-1) for D in D_list]))
+    off = _t(np.concatenate([[0], np.cumsum([D.size for D in D_list])]), torch.int64)
+    R = _t(np.concatenate(R_list), torch.int32)
+    cptr = _t(np.concatenate([[0], np.cumsum([len(r) for r in R_list])]), torch.int32)
+    f_off = np.concatenate([[0], np.cumsum([K * m for m in ms])]).astype(np.int64)
+    m_off = 2 * np.concatenate([[0], np.cumsum([K * m * m for m in ms])]).astype(np.int64)
+    freqs = torch.full((int(f_off[-1]),), np.nan, dtype=torch.float64, device=DEV)
+    evals = torch.full((int(f_off[-1]),), np.nan, dtype=torch.float64, device=DEV)
+    vecs = torch.full((int(m_off[-1]),), np.nan, dtype=torch.float64, device=DEV) if modes else None
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ms_d, q_d, fo_d, mo_d = _t(ms, torch.int32), _t(q), _t(f_off, torch.int64), _t(m_off, torch.int64)
+    _lib.check(lib.alignn_phonon_eigh(
+        dyn.data_ptr(), off.data_ptr(), R.data_ptr(), cptr.data_ptr(), ms_d.data_ptr(), len(ms), max(ms), q_d.data_ptr(), K,
+        FREQ_SCALE, freqs.data_ptr(), fo_d.data_ptr(), evals.data_ptr(), _lib.ptr(vecs), mo_d.data_ptr(), status.data_ptr(),
+        _lib.stream()), "phonon_eigh")
+    assert status.item() == 0
+    f, e = freqs.cpu().numpy(), evals.cpu().numpy()
+    out = []
+    for s, m in enumerate(ms):
+        v = None
+        if modes:
+            v = vecs[m_off[s]:m_off[s + 1]].cpu().numpy().view(np.complex128).reshape(K, m, m)
+        out.append((f[f_off[s]:f_off[s + 1]].reshape(K, m), e[f_off[s]:f_off[s + 1]].reshape(K, m), v))
+    return out
+
+
+@pytest.mark.parametrize("modes", [False, True])
+def test_eigen_launch_against_eigvalsh(modes):
+    rng = np.random.default_rng(9)
+    # D(q) = D_0 + D_1 exp(-2 pi i q.R_1) with R_1 = (1, 0, 0), q = (1/4, 0, 0): D_0 - i D_1 (up to cos(pi/2) = 6e-17)
+    R = np.array([[0, 0, 0], [1, 0, 0]])
+    q = np.array([[0.25, 0.0, 0.0]])
+    cases = [(m, kind) for m in (3, 6, 24, 47, 96) for kind in ("random", "degenerate")]
+    cases += [(5, "diagonal"), (96, "diagonal"), (4, "zero"), (33, "zero")]
+    D_list, H_list = [], []
+    for m, kind in cases:
+        H = _hermitian(rng, m, kind)
+        D = np.stack([H.real, -H.imag])
+        if kind == "random":  # the lower triangle must not count: spoil it
+            D[:, np.tril_indices(m, -1)[0], np.tril_indices(m, -1)[1]] = rng.normal(size=(2, m * (m - 1) // 2))
+        D_list.append(D)
+        H_list.append(dq(D, R, q[0]))
+    out = _eigh_launch(D_list, [R] * len(cases), q, modes)
+    worst = 0.0
+    for (m, kind), H, (f, e, v) in zip(cases, H_list, out):
+        want = np.linalg.eigvalsh(H, UPLO="U")
+        fro = max(np.linalg.norm(H), 1e-300)
+        err = np.abs(e[0] - want).max()
+        worst = max(worst, err / fro)
+        assert err <= 1e-11 * fro or (kind == "zero" and err == 0.0), (m, kind, err / fro)
+        assert np.all(np.diff(e[0]) >= 0)
+        assert np.array_equal(f[0], np.sign(e[0]) * FREQ_SCALE * np.sqrt(np.abs(e[0])))
+        if modes:
+            U = np.triu(H, 1)
+            Hf = U + U.conj().T + np.diag(H.diagonal().real)
+            V = v[0]
+            assert np.abs(Hf @ V - V * e[0][None, :]).max() <= 1e-11 * max(fro, 1.0), (m, kind)
+            assert np.abs(V.conj().T @ V - np.eye(m)).max() <= 1e-11, (m, kind)
+    print(f"eigen launch: worst eigenvalue error / ||D||_F {worst:.2e}")
+
+
+def test_dynamical_matrix_assembly_over_many_cells():
+    rng = np.random.default_rng(4)
+    sc = (5, 6, 7)  # 210 cells: more than one staged chunk of phases
+    R = lattice_points(sc)
+    D_N = rng.normal(size=(len(R), 6, 6)) * np.exp(-np.abs(R).sum(1))[:, None, None]
+    qs = rng.uniform(-0.5, 0.5, (4, 3))
+    (f, e, _), = _eigh_launch([D_N], [R], qs, False)
+    for k, q in enumerate(qs):
+        H = dq(D_N, R, q)
+        assert np.abs(e[k] - np.linalg.eigvalsh(H, UPLO="U")).max() <= 1e-11 * np.linalg.norm(H)
+
+
+# --- (4) spring crystals end to end ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sc", [(3, 3, 3), (4, 4, 4)])
+def test_spring_crystal_dispersion_and_acoustic_gamma(sc):
+    lat, pos, shells = simple_cubic()
+    m = 26.98
+    qs = np.random.default_rng(1).uniform(-0.5, 0.5, (12, 3))
+    qs[0] = 0.0
+    ff = NumpyForces(spring_forces_of(shells))
+    res = phonons(None, [lat], [pos], None, [np.array([m])], supercell=sc, delta=1e-3, qpoints=qs, dos_kpts=None, forces_fn=ff,
+                  device=DEV)
+    w = res.frequencies[0].cpu().numpy()
+    want = np.array([np.sort(sc_analytic(q, lat[0, 0], shells[0][1], shells[1][1], m)) for q in qs])
+    assert np.abs(w - want).max() <= 1e-5 * np.abs(want).max()
+    assert np.abs(w[0]).max() <= 1e-8
+    more = res.frequencies_at(qs[1:4])[0].cpu().numpy()  # later q-points, no re-evaluation
+    assert np.array_equal(more, w[1:4]) and ff.calls == res.n_evals
+
+
+# --- (5) alone vs. batched ----------------------------------------------------------------------------------------------------
+def test_structure_alone_equals_its_slice_of_the_batch():
+    sizes, scs = [2, 1, 4, 3], [(2, 2, 2), (3, 3, 3), (2, 1, 3), (2, 3, 2)]
+    lats, pos = _structures(sizes, 500)
+    ms = [np.random.default_rng(i).uniform(5.0, 80.0, n) for i, n in enumerate(sizes)]
+    qs = np.random.default_rng(2).uniform(-0.5, 0.5, (6, 3))
+    kw = dict(delta=0.02, qpoints=qs, modes=True, dos_kpts=(4, 4, 4), dos_npts=40, dos_width=1e-3, device=DEV)
+    ff = NumpyForces(pair_forces)
+    both = phonons(None, lats, pos, None, ms, supercell=scs, forces_fn=ff, **kw)
+    chunked = phonons(None, lats, pos, None, ms, supercell=scs, forces_fn=ff, max_atoms_per_eval=50, **kw)
+    assert chunked.n_evals > both.n_evals
+    for s in range(len(sizes)):
+        one = phonons(None, lats[s:s + 1], pos[s:s + 1], None, ms[s:s + 1], supercell=scs[s], forces_fn=ff, **kw)
+        for r in (both, chunked):
+            assert torch.equal(one.force_constants[0], r.force_constants[s])
+            assert torch.equal(one.frequencies[0], r.frequencies[s]) and torch.equal(one.modes[0], r.modes[s])
+            assert torch.equal(one.dos_energies[0], r.dos_energies[s]) and torch.equal(one.dos_weights[0], r.dos_weights[s])
+
+
+# --- (6) the model path ------------------------------------------------------------------------------------------------------
+def _model():
+    torch.manual_seed(0)
+    cfg = ALIGNNAtomWiseConfig(name="alignn_atomwise", alignn_layers=2, gcn_layers=2, hidden_features=128, embedding_features=64,
+                               atom_input_features=92, calculate_gradient=True, stresswise_weight=0.05)
+    return ALIGNNAtomWise(cfg).to(DEV).eval()
+
+
+def test_model_path_matches_one_evaluation_per_supercell():
+    model = _model()
+    sizes, sc, delta = [2, 4, 5], (2, 2, 2), 0.05
+    lats, pos = [], []
+    for i, n in enumerate(sizes):
+        lat, frac, _ = make_crystal(n, 800 + i)
+        lats.append(np.asarray(lat, dtype=np.float64))
+        pos.append(np.asarray(frac, dtype=np.float64) @ lats[-1])
+    g = torch.Generator().manual_seed(3)
+    feats = [torch.randn(n, 92, generator=g) for n in sizes]
+    ms = [np.random.default_rng(i).uniform(5.0, 80.0, n) for i, n in enumerate(sizes)]
+    res = phonons(model, lats, pos, feats, ms, supercell=sc, delta=delta, dos_kpts=None)
+    small = phonons(model, lats, pos, feats, ms, supercell=sc, delta=delta, dos_kpts=None, max_atoms_per_eval=100)
+    assert small.n_evals > res.n_evals >= 1
+    worst = 0.0
+    for s, n in enumerate(sizes):
+        sl = lats[s] * np.array(sc, dtype=np.float64)[:, None]
+        sl_d = _t(sl)
+        inv_h = inv_supercell(lats[s], sc)  # (what phonons() uses)
+        f_sc = feats[s].repeat(8, 1)
+        forces = []
+        for f, _ in displaced_supercells(lats[s], pos[s], sc, delta, inv_h):  # the reference's shape: one call per supercell
+            batch = neighbors.crystal_batch([sl_d], [_t(f)], atom_features=[f_sc], device=DEV, line_graph=True)
+            with torch.enable_grad():
+                out = model(batch)
+            forces.append(out["grad"].detach().reshape(-1, 3).double().cpu().numpy())
+        want = force_constants(forces, n, sc, delta)
+        scale = np.abs(want).max()
+        for r in (res, small):
+            err = np.abs(r.force_constants[s].cpu().numpy() - want).max() / scale
+            worst = max(worst, err)
+            assert err <= 1e-5, (s, err)
+    print(f"model path vs one evaluation per supercell: worst |dC| / max |C| {worst:.2e}")
+
+
+# --- (7) the DOS ------------------------------------------------------------------------------------------------------------
+def test_dos_matches_the_restatement_on_the_kernels_frequencies():
+    sizes, scs = [1, 3], [(3, 3, 3), (2, 2, 2)]
+    lats, pos = _structures(sizes, 900)
+    ms = [np.array([40.0]), np.array([10.0, 20.0, 30.0])]
+    kpts = (6, 5, 4)
+    res = phonons(None, lats, pos, None, ms, supercell=scs, delta=0.02, dos_kpts=kpts, dos_npts=64, dos_width=2e-3,
+                  forces_fn=NumpyForces(pair_forces), device=DEV)
+    mesh = res.frequencies_at(monkhorst_pack(kpts))
+    for s in range(2):
+        x, w = dos(mesh[s].cpu().numpy(), 64, 2e-3)
+        assert _rel(res.dos_energies[s].cpu().numpy(), x) <= 1e-12
+        assert _rel(res.dos_weights[s].cpu().numpy(), w) <= 1e-12
