@@ -18,6 +18,60 @@ namespace {
 constexpr int FIRE_BLOCK = 256;
 constexpr int FIRE_WAVES = FIRE_BLOCK / ALIGNN_WAVE;
 
+// Record the evaluation (energy, max_i |F_i| from the reduced max |F_i|^2 in red[3]) and the outcome of Optimizer.run's
+// test: converged (max |F_i|^2 < fmax^2) or out of steps -> retire flag 1 / 2 in status[1 + k], else counted in status[0]
+__device__ __forceinline__ void fire_record(const double* red, int converged, int taken, int steps, int k, int s,
+                                            const double* energy, double* energy_out, double* fmax_out, int32_t* status) {
+    if (threadIdx.x == 0) {
+        energy_out[s] = energy[k];
+        fmax_out[s] = sqrt(red[3]);
+        const int flag = converged ? 1 : (taken >= steps ? 2 : 0);
+        status[1 + k] = flag;
+        if (!flag) atomicAdd(status, 1);  // (an integer count: order-independent)
+    }
+}
+
+// ASE FIRE.step's scalar part from the reduced F.v, |F|^2, |v|^2 (red[0..2]): the mixing weights (zero_v: v restarts from
+// zero) and the structure's new dt, a and Nsteps
+struct FireScalars {
+    double dt, a, mix_v, mix_f;
+    int nsteps;
+    bool zero_v;
+};
+
+__device__ __forceinline__ FireScalars fire_scalars(const double* red, const double* state, const int32_t* istate, int s,
+                                                    int taken, double dtmax, int nmin, double finc, double fdec, double astart,
+                                                    double fa) {
+    FireScalars f{state[2 * s], state[2 * s + 1], 1.0, 0.0, istate[2 * s], taken == 0};  // first step: v = 0, no mixing
+    if (!f.zero_v) {
+        if (red[0] > 0.0) {
+            f.mix_v = 1.0 - f.a;
+            f.mix_f = f.a / sqrt(red[1]) * sqrt(red[2]);
+            if (f.nsteps > nmin) {
+                f.dt = fmin(f.dt * finc, dtmax);
+                f.a *= fa;
+            }
+            f.nsteps += 1;
+        } else {
+            f.zero_v = true;
+            f.a = astart;
+            f.dt *= fdec;
+            f.nsteps = 0;
+        }
+    }
+    return f;
+}
+
+// the step's optimiser state back to the structure's slots
+__device__ __forceinline__ void fire_store(const FireScalars& f, int taken, int s, double* state, int32_t* istate) {
+    if (threadIdx.x == 0) {
+        state[2 * s] = f.dt;
+        state[2 * s + 1] = f.a;
+        istate[2 * s] = f.nsteps;
+        istate[2 * s + 1] = taken + 1;
+    }
+}
+
 __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(
     const double* __restrict__ forces, const double* __restrict__ energy, const int32_t* __restrict__ force_ptr,
     const int32_t* __restrict__ active, const int32_t* __restrict__ atom_ptr, const double* __restrict__ inv_lattice,
@@ -57,42 +111,18 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(
     }
     block_reduce<4, true>(red, sh);
     const int converged = red[3] < fmax_tol * fmax_tol;
-    if (threadIdx.x == 0) {
-        energy_out[s] = energy[k];
-        fmax_out[s] = sqrt(red[3]);
-        const int flag = converged ? 1 : (taken >= steps ? 2 : 0);
-        status[1 + k] = flag;
-        if (!flag) atomicAdd(status, 1);  // (an integer count: order-independent)
-    }
+    fire_record(red, converged, taken, steps, k, s, energy, energy_out, fmax_out, status);
     if (converged || taken >= steps) return;
 
     // pass 2: ASE FIRE.step
-    double dt = state[2 * s], a = state[2 * s + 1];
-    int nsteps = istate[2 * s];
-    bool zero_v = taken == 0;  // first step: v = 0, no mixing
-    double mix_v = 1.0, mix_f = 0.0;
-    if (!zero_v) {
-        if (red[0] > 0.0) {
-            mix_v = 1.0 - a;
-            mix_f = a / sqrt(red[1]) * sqrt(red[2]);
-            if (nsteps > nmin) {
-                dt = fmin(dt * finc, dtmax);
-                a *= fa;
-            }
-            nsteps += 1;
-        } else {
-            zero_v = true;
-            a = astart;
-            dt *= fdec;
-            nsteps = 0;
-        }
-    }
+    const FireScalars fire = fire_scalars(red, state, istate, s, taken, dtmax, nmin, finc, fdec, astart, fa);
+    const double dt = fire.dt;
     double dr2[1] = {0.0};
     for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const double f = F[3 * i + c];
-            double v = zero_v ? 0.0 : mix_v * V[3 * i + c] + mix_f * f;
+            double v = fire.zero_v ? 0.0 : fire.mix_v * V[3 * i + c] + fire.mix_f * f;
             v += dt * f;
             V[3 * i + c] = v;
             const double d = dt * v;
@@ -118,12 +148,7 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(
         for (int c = 0; c < 3; ++c)
             frac[3 * ((int64_t)beg + i) + c] = wrap01(r[0] * L[c] + r[1] * L[3 + c] + r[2] * L[6 + c]);
     }
-    if (threadIdx.x == 0) {
-        state[2 * s] = dt;
-        state[2 * s + 1] = a;
-        istate[2 * s] = nsteps;
-        istate[2 * s + 1] = taken + 1;
-    }
+    fire_store(fire, taken, s, state, istate);
 }
 
 // ---- FIRE with ASE's ExpCellFilter (optimize_lattice=True; ase/constraints.py, 3.22.1, default arguments) --------------------
@@ -336,36 +361,12 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_cell_step_kernel(
     }
     block_reduce<4, true>(red, sh);
     const int converged = red[3] < fmax_tol * fmax_tol;
-    if (threadIdx.x == 0) {
-        energy_out[s] = energy[k];
-        fmax_out[s] = sqrt(red[3]);
-        const int flag = converged ? 1 : (taken >= steps ? 2 : 0);
-        status[1 + k] = flag;
-        if (!flag) atomicAdd(status, 1);  // (an integer count: order-independent)
-    }
+    fire_record(red, converged, taken, steps, k, s, energy, energy_out, fmax_out, status);
     if (converged || taken >= steps) return;
 
     // stage 3: ASE FIRE.step over the n + 3 rows
-    double dt = state[2 * s], a = state[2 * s + 1];
-    int nsteps = istate[2 * s];
-    bool zero_v = taken == 0;
-    double mix_v = 1.0, mix_f = 0.0;
-    if (!zero_v) {
-        if (red[0] > 0.0) {
-            mix_v = 1.0 - a;
-            mix_f = a / sqrt(red[1]) * sqrt(red[2]);
-            if (nsteps > nmin) {
-                dt = fmin(dt * finc, dtmax);
-                a *= fa;
-            }
-            nsteps += 1;
-        } else {
-            zero_v = true;
-            a = astart;
-            dt *= fdec;
-            nsteps = 0;
-        }
-    }
+    const FireScalars fire = fire_scalars(red, state, istate, s, taken, dtmax, nmin, finc, fdec, astart, fa);
+    const double dt = fire.dt;
     double dr2[1] = {0.0};
     for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
         double f[3];
@@ -374,7 +375,7 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_cell_step_kernel(
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const double g = f[0] * D[j] + f[1] * D[3 + j] + f[2] * D[6 + j];
-            double v = zero_v ? 0.0 : mix_v * V[3 * i + j] + mix_f * g;
+            double v = fire.zero_v ? 0.0 : fire.mix_v * V[3 * i + j] + fire.mix_f * g;
             v += dt * g;
             V[3 * i + j] = v;
             const double d = dt * v;
@@ -384,7 +385,7 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_cell_step_kernel(
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
-            double v = zero_v ? 0.0 : mix_v * vc[i] + mix_f * G[i];
+            double v = fire.zero_v ? 0.0 : fire.mix_v * vc[i] + fire.mix_f * G[i];
             v += dt * G[i];
             vc[i] = v;
             const double d = dt * v;
@@ -441,12 +442,7 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_cell_step_kernel(
             frac[3 * ((int64_t)beg + i) + j] = wrap01(x[0] * Li[j] + x[1] * Li[3 + j] + x[2] * Li[6 + j]);
         }
     }
-    if (threadIdx.x == 0) {
-        state[2 * s] = dt;
-        state[2 * s + 1] = a;
-        istate[2 * s] = nsteps;
-        istate[2 * s + 1] = taken + 1;
-    }
+    fire_store(fire, taken, s, state, istate);
 }
 
 }  // namespace

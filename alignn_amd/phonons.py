@@ -25,7 +25,8 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, neighbors
+from . import _lib
+from ._structures import ForceEvaluator, check_inputs, gpu_device, pack
 
 __all__ = ["phonons", "PhononResult", "EV_TO_THZ", "EV_TO_CM1", "MAX_DIM", "monkhorst_pack", "lattice_points"]
 
@@ -79,10 +80,6 @@ class PhononResult:
         evaluation); with ``modes``, (frequencies, modes)."""
         freqs, vecs = _eigh(self._dyn, _qpoints(q), modes)
         return (freqs, vecs) if modes else freqs
-
-
-def _shape(x):
-    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
 
 
 def _qpoints(q) -> np.ndarray:
@@ -142,22 +139,18 @@ def phonons(model, lattices: Sequence, positions: Sequence, atom_features: Optio
     ``run()`` + ``read(method, symmetrize, acoustic)`` + ``band_structure(qpoints)`` + ``get_dos(kpts).sample_grid(npts,
     width)`` for each structure.
 
-    ``lattices``: B cells [3, 3] (rows a, b, c); ``positions``: B Cartesian [n_i, 3]; ``atom_features``: B [n_i, F];
-    ``masses``: B [n_i] in amu.  ``model``: an ``ALIGNNAtomWise`` with ``calculate_gradient=True`` in eval mode (forces
-    ``grad * force_multiplier``; ``intensive`` is accepted for symmetry with ``run_md`` - energies are not used).
-    ``forces_fn(lattices, positions) -> (energy [S], forces [sum atoms, 3])`` replaces the model: it gets the S displaced
-    supercells of one evaluation (lattices [3, 3], Cartesian positions unwrapped), device tensors it must not modify.
+    The structures, ``masses``, the model (or ``forces_fn``), ``force_multiplier``, ``cutoff`` ... ``neighbor_strategy`` and
+    the device: alignn_amd/_structures.py; energies are not used (``intensive`` is accepted for symmetry with ``run_md``).
+    ``forces_fn`` gets the S displaced supercells of one evaluation, their Cartesian positions unwrapped.
 
     ``supercell``: (N1, N2, N3) for all or one per structure; ``delta`` (A); ``drift``: "frederiksen" (ASE's default),
     "mean" (the mean force off every atom, ff.py:1175-1177) or None; ``symmetrize`` passes (0 / None: none, and no acoustic
     rule); ``acoustic``.  ``qpoints`` [K, 3] (fractional reciprocal coordinates): frequencies there (``modes``: eigenvectors
     too); ``dos_kpts`` (None: no DOS): the Monkhorst-Pack mesh of the DOS, sampled on ``dos_npts`` points with Gaussians of
     ``dos_width`` eV.  ``max_atoms_per_eval``: supercell atoms per evaluation (whole -/+ pairs; default
-    ``MAX_ATOMS_PER_EVAL``).  Runs on the GPU (the model's device, else ``device``, else the current one)."""
-    B = len(positions)
-    if B == 0 or len(lattices) != B or len(masses) != B:
-        raise ValueError(f"phonons: {len(lattices)} lattices, {B} position arrays, {len(masses)} mass arrays (need the same "
-                         "number, at least one)")
+    ``MAX_ATOMS_PER_EVAL``)."""
+    ns = check_inputs("phonons", model, lattices, positions, atom_features, masses, forces_fn=forces_fn)
+    B = len(ns)
     scs = _supercells(supercell, B)
     if not (isinstance(delta, numbers.Real) and np.isfinite(delta) and delta > 0):
         raise ValueError(f"phonons: delta must be a finite number > 0, got {delta!r}")
@@ -184,69 +177,33 @@ def phonons(model, lattices: Sequence, positions: Sequence, atom_features: Optio
         max_atoms_per_eval = MAX_ATOMS_PER_EVAL
     if not (isinstance(max_atoms_per_eval, numbers.Integral) and max_atoms_per_eval >= 1):
         raise ValueError("phonons: max_atoms_per_eval must be an int >= 1")
-    ns = []
-    for i, p in enumerate(positions):
-        sh = _shape(p)
-        if len(sh) != 2 or sh[1] != 3 or sh[0] < 1:
-            raise ValueError(f"phonons: positions[{i}] is {sh}, need [n_i, 3] with n_i >= 1")
-        ns.append(int(sh[0]))
-        if 3 * ns[-1] > MAX_DIM:
-            raise ValueError(f"phonons: structure {i} has {ns[-1]} atoms; the eigen launch takes 3n <= {MAX_DIM} "
+    for i, n in enumerate(ns):
+        if 3 * n > MAX_DIM:
+            raise ValueError(f"phonons: structure {i} has {n} atoms; the eigen launch takes 3n <= {MAX_DIM} "
                              f"(at most {MAX_DIM // 3} atoms per primitive cell)")
-    for i, m in enumerate(masses):
-        if _shape(m) != (ns[i],):
-            raise ValueError(f"phonons: masses[{i}] is {_shape(m)}, need [{ns[i]}]")
-    for i, lat in enumerate(lattices):
-        if _shape(lat) != (3, 3):
-            raise ValueError(f"phonons: lattices[{i}] is {_shape(lat)}, need [3, 3]")
-    if forces_fn is None:
-        from .alignn_atomwise import ALIGNNAtomWise
-
-        if not isinstance(model, ALIGNNAtomWise):
-            raise TypeError(f"phonons: the model must be an ALIGNNAtomWise, got {type(model).__name__} (or pass forces_fn)")
-        if not model.config.calculate_gradient:
-            raise ValueError("phonons: the model has calculate_gradient=False and predicts no forces")
-        if model.training:
-            raise ValueError("phonons: the model is in training mode; call model.eval() first")
-        if atom_features is None or len(atom_features) != B:
-            raise ValueError("phonons: the model needs atom_features, one [n_i, F] array per structure")
-        F_in = model.config.atom_input_features
-        for i, f in enumerate(atom_features):
-            if _shape(f) != (ns[i], F_in):
-                raise ValueError(f"phonons: atom_features[{i}] is {_shape(f)}, need [{ns[i]}, {F_in}]")
-        dev = model.fc.weight.device
-    else:
-        dev = torch.device(device) if device is not None else None
-    mass_h = torch.cat([torch.as_tensor(m).detach().to("cpu", torch.float64).reshape(-1) for m in masses])
-    if not bool(torch.isfinite(mass_h).all()) or not bool((mass_h > 0).all()):
-        raise ValueError("phonons: masses must be finite and > 0")
-    if dev is not None and dev.type != "cuda":
-        raise TypeError(f"phonons runs on the GPU (csrc/phonon.hip), got device {dev}")
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = gpu_device("phonons", model, forces_fn, device)
     lib = _lib.load()
 
     ncell = [int(np.prod(c)) for c in scs]
     ms = [3 * n for n in ns]
     n_sc = [n * c for n, c in zip(ns, ncell)]
     with _lib.device_guard(torch.empty(0, device=dev)):
-        lat = torch.stack([torch.as_tensor(x).to(dev, torch.float64) for x in lattices]).contiguous()
-        pos = torch.cat([torch.as_tensor(p).to(dev, torch.float64) for p in positions]).contiguous()
-        atom_ptr = torch.tensor(np.concatenate([[0], np.cumsum(ns)]), dtype=torch.int32, device=dev)
+        packed = pack(lattices, positions, ns, dev, masses, frac=False)
+        lat, pos, mass, atom_ptr = packed.lat, packed.pos, packed.mass, packed.atom_ptr
         dims = torch.tensor(scs, dtype=torch.int32, device=dev)
         super_lat = (lat * dims.to(torch.float64)[:, :, None]).contiguous()
         # (3 x 3 inverses on the host, one at a time: a structure's supercell coordinates do not depend on the batch)
         inv_super = torch.tensor(np.stack([np.linalg.inv(x) for x in super_lat.cpu().numpy()]), device=dev).contiguous()
-        mass = mass_h.to(dev)
         fc_off_h = np.concatenate([[0], np.cumsum([c * m * m for c, m in zip(ncell, ms)])]).astype(np.int64)
         fc_off = torch.tensor(fc_off_h, device=dev)
         fc = torch.zeros(int(fc_off_h[-1]), dtype=torch.float64, device=dev)
         # one lattice tensor per structure: every chunk hands neighbors the same objects, so its lattice tables stay cached
         lat_v = [super_lat[s] for s in range(B)]
-        if forces_fn is None:
-            line_graph = len(model.alignn_layers) > 0
-            feats = [torch.as_tensor(f).to(dev, torch.float32).repeat(ncell[s], 1).contiguous()
-                     for s, f in enumerate(atom_features)]
+        # (each structure's features once per supercell copy, in the order of the displaced supercells' rows)
+        feats = None if forces_fn is not None else [torch.as_tensor(f).repeat(c, 1) for f, c in zip(atom_features, ncell)]
+        evaluate = ForceEvaluator("phonons", model, forces_fn, feats, n_sc, dev, cutoff=cutoff, max_neighbors=max_neighbors,
+                                  neighbor_strategy=neighbor_strategy, intensive=intensive, force_multiplier=force_multiplier,
+                                  energies=False)
 
         # chunks of whole -/+ pairs, in (structure, row) order
         pairs = [(s, x) for s in range(B) for x in range(ms[s])]
@@ -276,21 +233,10 @@ def phonons(model, lattices: Sequence, positions: Sequence, atom_features: Optio
             _lib.check(lib.alignn_phonon_displace(
                 pos.data_ptr(), atom_ptr.data_ptr(), lat.data_ptr(), inv_super.data_ptr(), dims.data_ptr(), jobs_d.data_ptr(),
                 rows_d.data_ptr(), len(jobs), float(delta), frac.data_ptr(), _lib.ptr(cart), _lib.stream()), "phonon_displace")
-            lats_c = [lat_v[s] for s, _ in jobs]
-            if forces_fn is None:
-                fracs_c = [frac[o:o + n_sc[s]] for (s, _), o in zip(jobs, row_off)]
-                batch = neighbors.crystal_batch(lats_c, fracs_c, atom_features=[feats[s] for s, _ in jobs], device=dev,
-                                                cutoff=cutoff, max_neighbors=max_neighbors, line_graph=line_graph,
-                                                neighbor_strategy=neighbor_strategy)
-                with torch.enable_grad():  # (the force head differentiates the energy)
-                    res = model(batch)
-                forces = (res["grad"].detach().reshape(-1, 3) * force_multiplier).double()
-            else:
-                _, forces = forces_fn(lats_c, [cart[o:o + n_sc[s]] for (s, _), o in zip(jobs, row_off)])
-                forces = torch.as_tensor(forces).to(dev, torch.float64).reshape(-1, 3)
-            if forces.shape[0] != r:
-                raise ValueError(f"phonons: evaluation returned {forces.shape[0]} force rows for {r} supercell atoms")
-            forces = forces.contiguous()
+            which = [s for s, _ in jobs]
+            views = [(o, o + n_sc[s]) for s, o in zip(which, row_off)]
+            _, forces, _ = evaluate(which, [lat_v[s] for s in which], [frac[a:b] for a, b in views],
+                                    None if cart is None else [cart[a:b] for a, b in views])
             pairs_d = torch.tensor(ch, dtype=torch.int32, device=dev)
             prow_d = torch.tensor(pair_rows, dtype=torch.int64, device=dev)
             _lib.check(lib.alignn_phonon_fc_rows(

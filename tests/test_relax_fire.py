@@ -158,3 +158,24 @@ def test_relax_module_exists():
         relax(None, [np.eye(3)], [np.zeros((1, 3)), np.zeros((1, 3))], forces_fn=lambda lat, pos: None)
     with pytest.raises(TypeError):
         relax(object(), [np.eye(3)], [np.zeros((1, 3))])
+
+
+def test_relax_validates_before_touching_a_device():
+    lat, pos = [np.eye(3) * 5], [np.zeros((2, 3))]
+    ff = lambda lat, pos: None  # noqa: E731
+    bad = [
+        dict(lattices=lat, positions=pos + pos),
+        dict(positions=[np.zeros((2, 2))]),
+        dict(lattices=[np.eye(3)[:2]]),
+        dict(steps=-1),
+        dict(fmax=-1.0),
+        dict(maxstep=0.0),
+        dict(dt=0.0),
+    ]
+    for kw in bad:
+        args = dict(lattices=lat, positions=pos)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            relax(None, args.pop("lattices"), args.pop("positions"), forces_fn=ff, device="cpu", **args)
+    with pytest.raises(TypeError):  # a CPU device: the launches are HIP only
+        relax(None, lat, pos, forces_fn=ff, device="cpu")
