@@ -169,6 +169,8 @@ SIGNATURES = {
     # batched molecular dynamics (csrc/dynamics.hip)
     "alignn_md_step": (_i32, [_p, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32,
                               _i32, _f64, _f64, _f64, _i32, _f64, _p]),
+    "alignn_md_step_cell": (_i32, [_p, _p, _p, _i64, _p, _i32] + [_p] * 22 + [_i32, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _f64,
+                                   _p]),
     "alignn_md_init_momenta": (_i32, [_p, _i32, _p, _p, _p, _p, _f64, _p]),
     # batched finite-displacement phonons (csrc/phonon.hip)
     "alignn_phonon_displace": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _p]),

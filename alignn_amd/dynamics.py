@@ -1,17 +1,20 @@
-"""Batched molecular dynamics at fixed cell, integrator state on the device.
+"""Batched molecular dynamics at fixed cell or constant pressure, integrator state on the device.
 
 The reference runs MD one structure at a time: ``ForceField.run_nve_velocity_verlet`` / ``run_nvt_langevin`` /
-``run_nvt_berendsen`` (alignn/ff/ff.py:419-550) wrap ASE's ``VelocityVerlet`` / ``Langevin`` / ``NVTBerendsen`` around
-``AlignnAtomwiseCalculator``, one host round trip and one host-side graph build per step.  ``run_md`` integrates B independent
-crystals together:
+``run_nvt_berendsen`` / ``run_nvt_andersen`` / ``run_npt_berendsen`` (alignn/ff/ff.py:419-600) wrap ASE's ``VelocityVerlet`` /
+``Langevin`` / ``NVTBerendsen`` / ``Andersen`` / ``NPTBerendsen`` around ``AlignnAtomwiseCalculator``, one host round trip and
+one host-side graph build per step.  ``run_md`` integrates B independent crystals together:
 
 1. build the graph batch of all B structures on the device (``neighbors.crystal_batch``);
-2. evaluate energies and forces with ``model(batch)``, or replay that evaluation (``md.GraphedForceField``, ``replay=True``);
-3. one ``alignn_md_step`` launch (csrc/dynamics.hip): finish step t with the new forces, record frame t, begin step t + 1.
+2. evaluate energies and forces (NPT: and stresses) with ``model(batch)``, or replay that evaluation
+   (``md.GraphedForceField``, ``replay=True``);
+3. one ``alignn_md_step`` launch (csrc/dynamics.hip; ``alignn_md_step_cell`` for Andersen and NPT): finish step t with the new
+   forces, record frame t, begin step t + 1 - under NPT the pressure, the scaled cell, its inverse and the scaled positions too.
 
 No structure retires, so nothing is read back per step beyond what the neighbour search reads.  The semantics are ASE 3.22.1's
-(``environment.yml``), restated in numpy in tests/test_md_ref.py.  The random numbers are the project's own counter-based
-stream (Philox4x32-10 per structure, csrc/dynamics.hip): a structure's trajectory is the same bits alone or in a batch.
+(``environment.yml``), restated in numpy in tests/test_md_ref.py and tests/test_md_npt_ref.py.  The random numbers are the
+project's own counter-based stream (Philox4x32-10 per structure, csrc/dynamics.hip): a structure's trajectory is the same bits
+alone or in a batch.
 """
 
 from __future__ import annotations
@@ -26,13 +29,14 @@ import torch
 from . import _lib
 from ._structures import ForceEvaluator, check_inputs, gpu_device, pack, shape_of
 
-__all__ = ["run_md", "MDResult", "FS", "KB"]
+__all__ = ["run_md", "MDResult", "FS", "KB", "BAR"]
 
 # ASE's units (CODATA 2014, its default): the femtosecond in ASE time units (A sqrt(amu / eV)) and Boltzmann's constant (eV/K)
 FS = 0.09822694788464063
 KB = 8.617330337217213e-05
+BAR = 1e-4 / 160.21766208  # eV/A^3 (160.21766208 eV/A^3 per GPa, the constant of _structures.ForceEvaluator)
 
-ENSEMBLES = {"nve": 0, "nvt_langevin": 1, "nvt_berendsen": 2}
+ENSEMBLES = {"nve": 0, "nvt_langevin": 1, "nvt_berendsen": 2, "nvt_andersen": 3, "npt_berendsen": 4}
 
 
 @dataclass
@@ -41,7 +45,9 @@ class MDResult:
     (eV) and ``temperature`` (K, 3N degrees of freedom) are [n_frames, B]; ``traj_positions`` / ``traj_momenta`` [n_frames,
     sum n_i, 3] (``trajectory=True``, else None).  ``positions`` (Cartesian, unwrapped), ``momenta`` (amu A / ASE time) and
     ``forces`` (eV/A) are those of the final state, per structure in the input order.  ``n_evals`` counts batched force
-    evaluations (``steps + 1``)."""
+    evaluations (``steps + 1``).  ``npt_berendsen`` only (else None): ``lattices`` [B, 3, 3] the final cells (``positions`` are
+    Cartesian and unwrapped in them), ``pressure`` (eV/A^3, ``-tr(stress) / 3 + 2 KE / (3 V)``; divide by ``BAR`` for bar) and
+    ``volume`` (A^3) [n_frames, B], ``traj_lattices`` [n_frames, B, 3, 3] (``trajectory=True``)."""
 
     epot: torch.Tensor
     ekin: torch.Tensor
@@ -52,6 +58,10 @@ class MDResult:
     momenta: List[torch.Tensor]
     forces: List[torch.Tensor]
     n_evals: int
+    lattices: Optional[torch.Tensor] = None
+    pressure: Optional[torch.Tensor] = None
+    volume: Optional[torch.Tensor] = None
+    traj_lattices: Optional[torch.Tensor] = None
 
 
 def berendsen_taut(taut: Optional[float], timestep: float) -> float:
@@ -59,15 +69,20 @@ def berendsen_taut(taut: Optional[float], timestep: float) -> float:
     return (100.0 * timestep if taut is None else float(taut)) * FS
 
 
-def _per_structure(x, B: int, what: str) -> List[float]:
+def barostat_taup(taup: Optional[float]) -> float:
+    """NPTBerendsen's pressure time constant in ASE time units: ``taup`` fs, or ASE's default 1000 fs when None."""
+    return (1000.0 if taup is None else float(taup)) * FS
+
+
+def _per_structure(x, B: int, what: str, signed: bool = False) -> List[float]:
     if isinstance(x, numbers.Real):
         vals = [float(x)] * B
     else:
         vals = [float(v) for v in np.asarray(x, dtype=np.float64).reshape(-1)]
         if len(vals) != B:
             raise ValueError(f"run_md: {what} must be a number or one per structure ({B}), got {len(vals)}")
-    if not all(np.isfinite(v) and v >= 0.0 for v in vals):
-        raise ValueError(f"run_md: {what} must be finite and >= 0")
+    if not all(np.isfinite(v) and (signed or v >= 0.0) for v in vals):
+        raise ValueError(f"run_md: {what} must be finite" + ("" if signed else " and >= 0"))
     return vals
 
 
@@ -82,11 +97,12 @@ def _seeds(seed, B: int) -> List[int]:
 
 def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Optional[Sequence], masses: Sequence, *,
            ensemble: str = "nve", timestep: float = 0.01, steps: int = 1000, interval: int = 1, temperature_K=300.0,
-           friction: float = 1e-4, taut: Optional[float] = None, initial_temperature_K=None, momenta: Optional[Sequence] = None,
-           fixcm: bool = True, seed=0, trajectory: bool = True, replay: bool = False, cutoff: float = 8.0,
+           friction: float = 1e-4, taut: Optional[float] = None, andersen_prob: float = 0.1, taup: Optional[float] = None,
+           pressure=None, compressibility=None, stress_weight: float = 1.0, initial_temperature_K=None,
+           momenta: Optional[Sequence] = None, fixcm: bool = True, seed=0, trajectory: bool = True, replay: bool = False, cutoff: float = 8.0,
            max_neighbors: int = 12, neighbor_strategy: str = "k-nearest", intensive: bool = True, force_multiplier: float = 1.0,
            forces_fn: Optional[Callable] = None, device=None) -> MDResult:
-    """Run ``steps`` steps of MD on B crystals at fixed cell; ASE's ``Dynamics.run(steps)`` with observers every ``interval``
+    """Run ``steps`` steps of MD on B crystals; ASE's ``Dynamics.run(steps)`` with observers every ``interval``
     steps, for each structure.
 
     The structures, ``masses``, the model (or ``forces_fn``), ``cutoff`` ... ``force_multiplier`` and the device:
@@ -94,14 +110,21 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
 
     ``ensemble``: ``"nve"`` (VelocityVerlet), ``"nvt_langevin"`` (Langevin: ``temperature_K``, ``friction`` in ASE inverse
     time units), ``"nvt_berendsen"`` (NVTBerendsen: ``temperature_K``, ``taut`` in fs, ``100 * timestep`` when None, at least
-    ``timestep``).  ``timestep`` in fs.  ``temperature_K`` and ``initial_temperature_K`` are a number or one per structure.
+    ``timestep``), ``"nvt_andersen"`` (Andersen: ``temperature_K``, ``andersen_prob`` in [0, 1], the chance per step and
+    velocity component of a fresh Maxwell-Boltzmann draw; the uniform draws lie in (0, 1], so 0 never replaces and 1 always
+    does), ``"npt_berendsen"`` (NPTBerendsen, isotropic: ``temperature_K``, ``taut`` as above, ``taup`` in fs, 1000 when None,
+    at least ``timestep``; ``pressure`` in bar and ``compressibility`` in 1/bar, each a number or one per structure, both
+    required; the cell and the positions are scaled every step, ``MDResult.lattices`` are the final cells).  NPT needs
+    stresses: the model must predict per-crystal stresses, scaled by ``stress_weight`` as in ``relax``, and ``forces_fn`` must
+    return ``(energy, forces, stress)``; the cells it gets change from step to step.  ``timestep`` in fs.  ``temperature_K`` and ``initial_temperature_K`` are a number or one per structure.
     The start momenta: Maxwell-Boltzmann at ``initial_temperature_K`` when given, else ``momenta`` (B [n_i, 3]), else zero.
-    ``fixcm``: Langevin's and NVTBerendsen's centre-of-mass correction.  ``seed``: an int or B ints in [0, 2^64), the key of
+    ``fixcm``: the centre-of-mass correction of Langevin, NVTBerendsen / NPTBerendsen and Andersen.  ``seed``: an int or B ints in [0, 2^64), the key of
     each structure's random stream.  ``replay``: evaluate through ``md.GraphedForceField`` (the same bits)."""
-    ns = check_inputs("run_md", model, lattices, positions, atom_features, masses, forces_fn=forces_fn)
-    B = len(ns)
     if ensemble not in ENSEMBLES:
         raise ValueError(f"run_md: ensemble must be one of {sorted(ENSEMBLES)}, got {ensemble!r}")
+    npt, andersen = ensemble == "npt_berendsen", ensemble == "nvt_andersen"
+    ns = check_inputs("run_md", model, lattices, positions, atom_features, masses, forces_fn=forces_fn, stress=npt)
+    B = len(ns)
     if not (isinstance(steps, numbers.Integral) and isinstance(interval, numbers.Integral)) or steps < 0 or interval < 1:
         raise ValueError("run_md: need integer steps >= 0 and interval >= 1")
     if steps >= 2 ** 31 - 1:
@@ -112,8 +135,21 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
         raise ValueError("run_md: friction must be >= 0")
     t0 = _per_structure(temperature_K, B, "temperature_K")
     tau = berendsen_taut(taut, timestep)
-    if ensemble == "nvt_berendsen" and not (tau >= timestep * FS and np.isfinite(tau)):
+    if ensemble in ("nvt_berendsen", "npt_berendsen") and not (tau >= timestep * FS and np.isfinite(tau)):
         raise ValueError("run_md: taut must be at least the timestep")
+    if not (isinstance(andersen_prob, numbers.Real) and 0.0 <= andersen_prob <= 1.0):
+        raise ValueError("run_md: andersen_prob must lie in [0, 1]")
+    taup_ase = barostat_taup(taup)
+    p_target = comp = None
+    if npt:
+        if not (taup_ase >= timestep * FS and np.isfinite(taup_ase)):
+            raise ValueError("run_md: taup must be at least the timestep")
+        if pressure is None or compressibility is None:
+            raise ValueError("run_md: npt_berendsen needs pressure (bar) and compressibility (1/bar)")
+        p_target = [v * BAR for v in _per_structure(pressure, B, "pressure", signed=True)]
+        comp = [v / BAR for v in _per_structure(compressibility, B, "compressibility")]
+        if not (isinstance(stress_weight, numbers.Real) and np.isfinite(stress_weight)):
+            raise ValueError("run_md: stress_weight must be a finite number")
     t_init = None if initial_temperature_K is None else _per_structure(initial_temperature_K, B, "initial_temperature_K")
     if t_init is not None and momenta is not None:
         raise ValueError("run_md: give initial_temperature_K or momenta, not both")
@@ -142,23 +178,45 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
         else:
             mom = torch.zeros(N, 3, dtype=torch.float64, device=dev)
         vel = rnd_vel = None
-        if ensemble == "nvt_langevin":
+        if ensemble == "nvt_langevin" or andersen:  # (Andersen: v between the halves, the positions before the drift)
             vel, rnd_vel = torch.zeros(N, 3, dtype=torch.float64, device=dev), torch.zeros(N, 3, dtype=torch.float64, device=dev)
         n_frames = steps // interval + 1
         epot, ekin, temp = (torch.zeros(n_frames, B, dtype=torch.float64, device=dev) for _ in range(3))
         traj_p = torch.zeros(n_frames, N, 3, dtype=torch.float64, device=dev) if trajectory else None
         traj_m = torch.zeros(n_frames, N, 3, dtype=torch.float64, device=dev) if trajectory else None
         status = torch.zeros(1, dtype=torch.int32, device=dev)
+        lat_cur = p_out = v_out = traj_l = None
+        if npt:
+            lat_cur = packed.lat.clone()  # the kernel rewrites it and ``inv``
+            p_target_t = torch.tensor(p_target, dtype=torch.float64, device=dev)
+            comp_t = torch.tensor(comp, dtype=torch.float64, device=dev)
+            p_out, v_out = (torch.zeros(n_frames, B, dtype=torch.float64, device=dev) for _ in range(2))
+            traj_l = torch.zeros(n_frames, B, 3, 3, dtype=torch.float64, device=dev) if trajectory else None
         # fixed per-structure views: the same lattice tensors every step keep neighbors' lattice tables cached
         lat_v = [packed.lat[s] for s in range(B)]
         pos_v, frac_v = packed.rows(pos), packed.rows(frac)
         evaluate = ForceEvaluator("run_md", model, forces_fn, atom_features, ns, dev, cutoff=cutoff, max_neighbors=max_neighbors,
                                   neighbor_strategy=neighbor_strategy, intensive=intensive, force_multiplier=force_multiplier,
-                                  replay=replay)
+                                  stress_weight=float(stress_weight) if npt else None, replay=replay)
         every = list(range(B))
 
         for t in range(steps + 1):
-            energy, forces, _ = evaluate(every, lat_v, frac_v, pos_v)
+            if npt:
+                # fresh tensors every step: the kernel writes lat_cur through a raw pointer (no version bump), which the
+                # lattice-table cache of neighbors would not see
+                lat_now = lat_cur.clone()
+                lat_v = [lat_now[s] for s in range(B)]
+            energy, forces, stress = evaluate(every, lat_v, frac_v, pos_v)
+            if npt or andersen:
+                _lib.check(lib.alignn_md_step_cell(
+                    forces.data_ptr(), energy.data_ptr(), _lib.ptr(stress), forces.shape[0], atom_ptr.data_ptr(), B,
+                    mass.data_ptr(), (lat_cur if npt else packed.lat).data_ptr(), inv.data_ptr(), mom.data_ptr(), pos.data_ptr(),
+                    frac.data_ptr(), _lib.ptr(vel), _lib.ptr(rnd_vel), t0_t.data_ptr(), seed_t.data_ptr(),
+                    p_target_t.data_ptr() if npt else None, comp_t.data_ptr() if npt else None, epot.data_ptr(), ekin.data_ptr(),
+                    temp.data_ptr(), _lib.ptr(p_out), _lib.ptr(v_out), _lib.ptr(traj_p), _lib.ptr(traj_m), _lib.ptr(traj_l), None,
+                    status.data_ptr(), t, int(interval), int(steps), ens, dt, float(andersen_prob), tau, taup_ase,
+                    int(bool(fixcm)), KB, _lib.stream()), "md_step_cell")
+                continue
             _lib.check(lib.alignn_md_step(
                 forces.data_ptr(), energy.data_ptr(), forces.shape[0], atom_ptr.data_ptr(), B, mass.data_ptr(), inv.data_ptr(),
                 mom.data_ptr(), pos.data_ptr(), frac.data_ptr(), _lib.ptr(vel), _lib.ptr(rnd_vel), t0_t.data_ptr(),
@@ -170,4 +228,5 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
 
         return MDResult(epot=epot, ekin=ekin, temperature=temp, traj_positions=traj_p, traj_momenta=traj_m,
                         positions=[p.clone() for p in pos_v], momenta=[p.clone() for p in packed.rows(mom)],
-                        forces=[f.clone() for f in packed.rows(forces)], n_evals=steps + 1)
+                        forces=[f.clone() for f in packed.rows(forces)], n_evals=steps + 1, lattices=lat_cur, pressure=p_out,
+                        volume=v_out, traj_lattices=traj_l)

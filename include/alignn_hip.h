@@ -957,6 +957,29 @@ int alignn_md_step(const double* forces, const double* energy, int64_t n_rows, c
                    int interval, int steps, int ensemble, double dt, double friction, double taut, int fixcm, double kB,
                    alignn_stream_t stream);
 
+/* Andersen NVT (ensemble 3) and Berendsen NPT (ensemble 4; isotropic) of the same loop, same conventions and arguments as
+ * alignn_md_step, plus [B][3][3] row-major lattice / inv_lattice (read; NPT rewrites both) and stress (NPT: the evaluation's
+ * stress, eV/A^3, ASE's sign; may be NULL for Andersen), pressure / compressibility [B] (NPT: the target in eV/A^3 and the
+ * compressibility in A^3/eV).  Frames also record pressure_out (-tr(stress) / 3 + 2 KE / (3 V); needs stress) and volume_out
+ * (V = |det lattice|) [frames][B] and traj_lattice [frames][B][3][3], each unless NULL.  NPT begins a step with the Berendsen
+ * velocity scaling, then mu = 1 - dt / taup * compressibility / 3 * (pressure - P) with P from the scaled momenta, lattice and
+ * positions times mu, inv_lattice recomputed, then the half-kick, fixcm and the drift; frac wraps with the new inverse.
+ * Andersen begins a step with v = p / m, fixcm: + a random centre-of-mass velocity (Philox counter (0, t, block 0..1, 3),
+ * width sqrt(kB T0 / sum m)); the half-kick; every velocity component whose uniform draw is <= andersen_prob replaced by a
+ * normal of width sqrt(kB T0 / m) (counter (atom, t, block 0..3, 2): blocks 0, 1 the normals, 2, 3 the uniforms in (0, 1]);
+ * fixcm: the mass-weighted mean velocity removed and the centre of mass kept through the drift; v recomputed from the
+ * positions.  It keeps v in velocities and the positions before the drift in rnd_vel between the halves.  noise_out [N][36]
+ * (tests; NULL otherwise): per atom 4 normals, 4 uniforms, the 16 words, then the structure's 4 centre-of-mass normals and
+ * their 8 words (fixcm only). */
+int alignn_md_step_cell(const double* forces, const double* energy, const double* stress, int64_t n_rows,
+                        const int32_t* atom_ptr, int n_structures, const double* masses, double* lattice, double* inv_lattice,
+                        double* momenta, double* positions, double* frac, double* velocities, double* rnd_vel,
+                        const double* t0_kelvin, const uint64_t* seeds, const double* pressure, const double* compressibility,
+                        double* epot, double* ekin, double* temperature, double* pressure_out, double* volume_out,
+                        double* traj_positions, double* traj_momenta, double* traj_lattice, double* noise_out, int32_t* status,
+                        int t, int interval, int steps, int ensemble, double dt, double andersen_prob, double taut, double taup,
+                        int fixcm, double kB, alignn_stream_t stream);
+
 /* Maxwell-Boltzmann momenta (ASE's MaxwellBoltzmannDistribution, no Stationary): momenta[i] = xi sqrt(m_i kB t_kelvin[s]) with
  * xi three normals of the stream above (counter (atom, 0, block 0..1, 1)). */
 int alignn_md_init_momenta(const int32_t* atom_ptr, int n_structures, const double* masses, const double* t_kelvin,
