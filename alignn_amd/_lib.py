@@ -119,6 +119,8 @@ SIGNATURES = {
     "alignn_egc_conv_wgrad": (_i32, [_p, _p]),
     "alignn_egc_args_sizeof": (_sz, [_i32]),
     "alignn_fork_events_init": (_i32, []),
+    "alignn_knn_box": (_i32, [_p, _p, _p, _p, _i32, _i64, _p, _p]),
+    "alignn_knn_kth_cap": (_i32, []),
     "alignn_knn_levels": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _p]),
     "alignn_knn_kth": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _p, _p]),
     "alignn_knn_count": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p]),

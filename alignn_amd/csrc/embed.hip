@@ -228,7 +228,7 @@ __global__ void gather_rows_ld_kernel(const float* __restrict__ in, int64_t ld_i
 
 extern "C" {
 
-const char* alignn_version(void) { return "alignn_hip 0.1 gfx950"; }
+const char* alignn_version(void) { return "alignn_hip 0.2 gfx950"; }
 
 int alignn_rbf_fwd(const float* d, const float* centers, float gamma, float* out, int64_t rows, int bins,
                    alignn_stream_t stream) {

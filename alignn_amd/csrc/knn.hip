@@ -4,8 +4,10 @@
 // jarvis' get_all_neighbors - rebuilt at EVERY molecular-dynamics step by the ASE calculators
 // (alignn/ff/calculators.py:280-291).  Semantics restated (and pinned bit-exactly to the reference's own functions over
 // its 70 example structures, tests/test_graph_builder_golden.py):
-//   * candidates of site i: all (j, image I) with |I_k| <= reach_k = ceil(cutoff / plane spacing_k) and
-//     1e-8 < dist <= cutoff;
+//   * candidates of site i: all (j, image I) with lo_k <= I_k <= hi_k and kBondTol < dist <= cutoff.  The box comes from
+//     the caller (alignn_amd/neighbors.py: _image_box): |I_k| <= ceil(cutoff / plane spacing_k) for fractional coordinates
+//     inside [0, 1], the box jarvis lays out around the fractional extent for unwrapped ones - which is NOT symmetric and
+//     does not hold every image within the cutoff, so "b sees a at -I" is true only if -I is in the box too;
 //   * some site of the crystal has fewer than k candidates -> the WHOLE crystal is redone with a larger cutoff
 //     (longest lattice vector if the cutoff was below it, else twice the cutoff; :170-188) - a larger box can add
 //     near neighbours the smaller box did not scan, so the level is a property of the crystal, not of the site;
@@ -33,26 +35,42 @@ namespace {
 constexpr int kSitesPerBlock = 4;
 constexpr int kThreads = kSitesPerBlock * ALIGNN_WAVE;
 constexpr int kKthCap = 1024;  // distances inside the cutoff a site's wave keeps in LDS for the k-th smallest (more: the search by rounds)
+constexpr double kBondTol = 0.15;  // jarvis' get_all_neighbors(r, bond_tol=0.15): closer than this is no neighbour
 
 struct Cell {
     double lat[9];
-    int r0, r1, r2;      // image box half-widths
-    int n1, n2, nimg;    // 2*r1+1, 2*r2+1, images in the box
+    int lo[3], hi[3];    // image box scanned by the crystal's sites, inclusive
+    int s0, s1, s2;      // first image of the ENUMERATED box (the scanned box, or its hull with its mirror image)
+    int n1, n2, nimg;    // extents of the enumerated box along b and c, images in it
     double cutoff;
 };
 
+// HULL: enumerate the smallest box symmetric about 0 that holds the scanned one (the canonical image of a bond kept by
+// its larger end is the NEGATIVE of an image that end scanned); for a symmetric box - wrapped coordinates - the same box.
+template <bool HULL>
 __device__ __forceinline__ Cell load_cell(const double* __restrict__ lat, const double* __restrict__ cut,
-                                          const int32_t* __restrict__ reach, int b, int L, int level) {
+                                          const int32_t* __restrict__ box, int b, int L, int level) {
     Cell c;
 #pragma unroll
     for (int i = 0; i < 9; ++i) c.lat[i] = lat[(size_t)b * 9 + i];
-    const int32_t* r = reach + ((size_t)b * L + level) * 3;
-    c.r0 = r[0], c.r1 = r[1], c.r2 = r[2];
-    c.n1 = 2 * c.r1 + 1;
-    c.n2 = 2 * c.r2 + 1;
-    c.nimg = (2 * c.r0 + 1) * c.n1 * c.n2;
+    const int32_t* r = box + ((size_t)b * L + level) * 6;
+    int e[3][2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        c.lo[k] = r[k], c.hi[k] = r[3 + k];
+        e[k][0] = HULL ? min(c.lo[k], -c.hi[k]) : c.lo[k];
+        e[k][1] = HULL ? max(c.hi[k], -c.lo[k]) : c.hi[k];
+    }
+    c.s0 = e[0][0], c.s1 = e[1][0], c.s2 = e[2][0];
+    c.n1 = e[1][1] - e[1][0] + 1;
+    c.n2 = e[2][1] - e[2][0] + 1;
+    c.nimg = (e[0][1] - e[0][0] + 1) * c.n1 * c.n2;
     c.cutoff = cut[(size_t)b * L + level];
     return c;
+}
+
+__device__ __forceinline__ bool in_box(const Cell& c, int i0, int i1, int i2) {
+    return i0 >= c.lo[0] && i0 <= c.hi[0] && i1 >= c.lo[1] && i1 <= c.hi[1] && i2 >= c.lo[2] && i2 <= c.hi[2];
 }
 
 // distance of (cart_j + shift(image)) from cart_i, in the reference's operation order
@@ -68,7 +86,7 @@ __device__ __forceinline__ double image_distance(const Cell& c, const double ci[
     return __dsqrt_rn((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
 }
 
-// candidate index -> (j, image): candidates are ordered by (j, i0, i1, i2), images ascending from -r
+// candidate index -> (j, image): candidates are ordered by (j, i0, i1, i2), images ascending from the box's first
 __device__ __forceinline__ void split_candidate(const Cell& c, int cand, int& j, int& i0, int& i1, int& i2) {
     j = cand / c.nimg;
     int im = cand - j * c.nimg;
@@ -77,9 +95,9 @@ __device__ __forceinline__ void split_candidate(const Cell& c, int cand, int& j,
     im -= i0 * q;
     i1 = im / c.n2;
     i2 = im - i1 * c.n2;
-    i0 -= c.r0;
-    i1 -= c.r1;
-    i2 -= c.r2;
+    i0 += c.s0;
+    i1 += c.s1;
+    i2 += c.s2;
 }
 
 __device__ __forceinline__ int wave_sum_i(int v) {
@@ -104,9 +122,58 @@ __device__ __forceinline__ int count_candidates(const Cell& c, const double* __r
         split_candidate(c, cand, j, i0, i1, i2);
         const double cj[3] = {cart[3 * (size_t)(base + j)], cart[3 * (size_t)(base + j) + 1], cart[3 * (size_t)(base + j) + 2]};
         const double d = image_distance(c, ci, cj, i0, i1, i2);
-        cnt += (d <= c.cutoff && d > 1e-8) ? 1 : 0;
+        cnt += (d <= c.cutoff && d > kBondTol) ? 1 : 0;
     }
     return wave_sum_i(cnt);
+}
+
+// ---- pass 0: the image box of every crystal at every level, from the fractional extent of its sites (one wave per
+// crystal).  Axis with floor(min frac) == 0 and ceil(max frac) <= 1: [-reach, reach]; otherwise jarvis' box
+// [floor(min) - maxr, ceil(max) + maxr - 1] (the rule of alignn_amd/neighbors.py: _image_box).  A box whose candidate count
+// would not fit the kernels' 32-bit candidate index (absurd coordinates, NaN) is written EMPTY (lo 0, hi -1): the crystal
+// then finds no neighbour at any level and the caller raises.
+__global__ __launch_bounds__(ALIGNN_WAVE) void knn_box_kernel(const double* __restrict__ frac,
+                                                              const int32_t* __restrict__ graph_ptr,
+                                                              const int32_t* __restrict__ reach,
+                                                              const int32_t* __restrict__ maxr, int L,
+                                                              int32_t* __restrict__ box) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int base = graph_ptr[b], n = graph_ptr[b + 1] - base;
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    double mn0 = inf, mn1 = inf, mn2 = inf, mx0 = -inf, mx1 = -inf, mx2 = -inf;
+    bool bad = false;
+    for (int j = lane; j < n; j += ALIGNN_WAVE) {
+        const double* f = frac + 3 * (size_t)(base + j);
+        mn0 = fmin(mn0, f[0]), mn1 = fmin(mn1, f[1]), mn2 = fmin(mn2, f[2]);
+        mx0 = fmax(mx0, f[0]), mx1 = fmax(mx1, f[1]), mx2 = fmax(mx2, f[2]);
+        bad |= !(fabs(f[0]) < 1e6 && fabs(f[1]) < 1e6 && fabs(f[2]) < 1e6);  // (NaN included)
+    }
+    mn0 = wave_min_d(mn0), mn1 = wave_min_d(mn1), mn2 = wave_min_d(mn2);
+    mx0 = -wave_min_d(-mx0), mx1 = -wave_min_d(-mx1), mx2 = -wave_min_d(-mx2);
+    bad = __ballot(bad) != 0ull || n <= 0;
+    const int flo[3] = {bad ? 0 : (int)floor(mn0), bad ? 0 : (int)floor(mn1), bad ? 0 : (int)floor(mn2)};
+    const int fhi[3] = {bad ? 0 : (int)ceil(mx0), bad ? 0 : (int)ceil(mx1), bad ? 0 : (int)ceil(mx2)};
+    for (int level = lane; level < L; level += ALIGNN_WAVE) {
+        const int32_t* r = reach + ((size_t)b * L + level) * 3;
+        const int32_t* m = maxr + ((size_t)b * L + level) * 3;
+        int lo[3], hi[3];
+        long long images = 1;  // of the hull with the mirrored box: what the bond passes enumerate (>= the scanned box)
+        bool fits = !bad;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const bool wrapped = flo[k] == 0 && fhi[k] <= 1;
+            const long long l = wrapped ? -(long long)r[k] : (long long)flo[k] - m[k];
+            const long long h = wrapped ? (long long)r[k] : (long long)fhi[k] + m[k] - 1;
+            const long long a = l < -h ? l : -h, z = h > -l ? h : -l;
+            fits = fits && r[k] >= 0 && m[k] >= 0 && z - a + 1 <= (1 << 20);
+            images *= fits ? z - a + 1 : 1;
+            fits = fits && images * (long long)n <= (long long)INT32_MAX;
+            lo[k] = (int)l, hi[k] = (int)h;
+        }
+        int32_t* o = box + ((size_t)b * L + level) * 6;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = fits ? lo[k] : 0, o[3 + k] = fits ? hi[k] : -1;
+    }
 }
 
 // ---- pass 1: the crystal's level = the first cutoff of its sequence at which EVERY site has >= k candidates
@@ -114,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void knn_level_kernel(const double* __res
                                                              const int32_t* __restrict__ graph_ptr,
                                                              const int32_t* __restrict__ site_graph,
                                                              const double* __restrict__ cut,
-                                                             const int32_t* __restrict__ reach, int L, int k, int N,
+                                                             const int32_t* __restrict__ box, int L, int k, int N,
                                                              int32_t* __restrict__ crystal_level) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * kSitesPerBlock + (threadIdx.x >> 6);
@@ -122,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void knn_level_kernel(const double* __res
     const int b = site_graph[i], base = graph_ptr[b], n = graph_ptr[b + 1] - base;
     int level = 0;
     for (; level < L; ++level) {
-        const Cell c = load_cell(lat, cut, reach, b, L, level);
+        const Cell c = load_cell<false>(lat, cut, box, b, L, level);
         if (count_candidates(c, cart, base, n, i, lane) >= k) break;
     }
     // (level == L: not even the widest cutoff reaches k candidates - reported to the host through the level array)
@@ -133,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void knn_level_kernel(const double* __res
 __global__ __launch_bounds__(kThreads) void knn_kth_kernel(const double* __restrict__ lat, const double* __restrict__ cart,
                                                            const int32_t* __restrict__ graph_ptr,
                                                            const int32_t* __restrict__ site_graph,
-                                                           const double* __restrict__ cut, const int32_t* __restrict__ reach,
+                                                           const double* __restrict__ cut, const int32_t* __restrict__ box,
                                                            int L, int k, int N, const int32_t* __restrict__ crystal_level,
                                                            double* __restrict__ kth) {
     const int lane = threadIdx.x & 63;
@@ -145,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void knn_kth_kernel(const double* __restr
         if (lane == 0) kth[i] = -1.0;
         return;
     }
-    const Cell c = load_cell(lat, cut, reach, b, L, level);
+    const Cell c = load_cell<false>(lat, cut, box, b, L, level);
     const double ci[3] = {cart[3 * (size_t)i], cart[3 * (size_t)i + 1], cart[3 * (size_t)i + 2]};
     const int total = n * c.nimg;
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
@@ -165,19 +232,19 @@ __global__ __launch_bounds__(kThreads) void knn_kth_kernel(const double* __restr
             split_candidate(c, cand, j, i0, i1, i2);
             const double cj[3] = {cart[3 * (size_t)(base + j)], cart[3 * (size_t)(base + j) + 1], cart[3 * (size_t)(base + j) + 2]};
             d = image_distance(c, ci, cj, i0, i1, i2);
-            ok = d > 1e-8 && d <= c.cutoff;
+            ok = d > kBondTol && d <= c.cutoff;
         }
         const unsigned long long mask = __ballot(ok);
         const int pos = M + __popcll(mask & ((1ull << lane) - 1ull));
         if (ok && pos < kKthCap) buf[pos] = d;
         M += __popcll(mask);
     }
-    double last = 1e-8;
+    double last = kBondTol;
     if (M <= kKthCap) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        double best = inf, top = 1e-8;
+        double best = inf, top = kBondTol;
         for (int q = lane; q < M; q += ALIGNN_WAVE) {
             const double x = buf[q];
             int lt = 0, le = 0;
@@ -222,15 +289,18 @@ __global__ __launch_bounds__(kThreads) void knn_kth_kernel(const double* __restr
     if (lane == 0) kth[i] = last;
 }
 
-// Is the canonical bond (a, b, image of b seen from a), a <= b, in the graph?  Kept by a: a's own distance to (b, +im)
-// within a's shell; kept by b: b's distance to (a, -im) - evaluated the way b's wave evaluates it - within b's shell.
+// Is the canonical bond (a, b, image of b seen from a), a <= b, in the graph?  Kept by a: +im is an image a scanned and
+// a's own distance to (b, +im) is within a's shell; kept by b: -im is an image b scanned and b's distance to (a, -im) -
+// evaluated the way b's wave evaluates it - is within b's shell.
 __device__ __forceinline__ bool bond_exists(const Cell& c, const double ca[3], const double cb[3], bool same, int i0, int i1,
                                             int i2, double kth_a, double kth_b) {
-    const double da = image_distance(c, ca, cb, i0, i1, i2);
-    if (da > 1e-8 && da <= c.cutoff && da <= kth_a) return true;
-    if (same) return false;  // a == b: (a, a, im) and (a, a, -im) are separate keys, each kept on its own
+    if (in_box(c, i0, i1, i2)) {
+        const double da = image_distance(c, ca, cb, i0, i1, i2);
+        if (da > kBondTol && da <= c.cutoff && da <= kth_a) return true;
+    }
+    if (same || !in_box(c, -i0, -i1, -i2)) return false;  // a == b: (a, a, im) and (a, a, -im) are separate keys, each kept on its own
     const double db = image_distance(c, cb, ca, -i0, -i1, -i2);
-    return db > 1e-8 && db <= c.cutoff && db <= kth_b;
+    return db > kBondTol && db <= c.cutoff && db <= kth_b;
 }
 
 // ---- pass 3 (COUNT) / pass 4 (EMIT): canonical bonds owned by site a = those to sites b >= a
@@ -238,7 +308,7 @@ template <bool EMIT>
 __global__ __launch_bounds__(kThreads) void knn_bonds_kernel(const double* __restrict__ lat, const double* __restrict__ cart,
                                                              const int32_t* __restrict__ graph_ptr,
                                                              const int32_t* __restrict__ site_graph,
-                                                             const double* __restrict__ cut, const int32_t* __restrict__ reach,
+                                                             const double* __restrict__ cut, const int32_t* __restrict__ box,
                                                              int L, int N, const int32_t* __restrict__ crystal_level,
                                                              const double* __restrict__ kth, int64_t* __restrict__ count,
                                                              const int64_t* __restrict__ offset, int64_t* __restrict__ U,
@@ -253,7 +323,7 @@ __global__ __launch_bounds__(kThreads) void knn_bonds_kernel(const double* __res
         if (!EMIT && lane == 0) count[a] = 0;
         return;
     }
-    const Cell c = load_cell(lat, cut, reach, b_, L, level);
+    const Cell c = load_cell<true>(lat, cut, box, b_, L, level);
     const double ca[3] = {cart[3 * (size_t)a], cart[3 * (size_t)a + 1], cart[3 * (size_t)a + 2]};
     const double kth_a = kth[a];
     const int la = a - base;
@@ -307,51 +377,63 @@ __global__ __launch_bounds__(kThreads) void knn_bonds_kernel(const double* __res
 
 extern "C" {
 
+int alignn_knn_box(const double* frac, const int32_t* graph_ptr, const int32_t* reach, const int32_t* maxr, int levels,
+                   int64_t n_crystals, int32_t* box, alignn_stream_t stream) {
+    if (levels <= 0 || n_crystals < 0 || n_crystals > INT32_MAX || !box) return (int)hipErrorInvalidValue;
+    if (n_crystals == 0) return 0;
+    hipLaunchKernelGGL(knn_box_kernel, dim3((unsigned)n_crystals), dim3(ALIGNN_WAVE), 0, (hipStream_t)stream, frac, graph_ptr,
+                       reach, maxr, levels, box);
+    ALIGNN_CHECK_LAUNCH();
+    return 0;
+}
+
 int alignn_knn_levels(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                      const double* cut, const int32_t* reach, int levels, int k, int64_t n_sites, int32_t* crystal_level,
+                      const double* cut, const int32_t* box, int levels, int k, int64_t n_sites, int32_t* crystal_level,
                       alignn_stream_t stream) {
     if (levels <= 0 || k <= 0 || n_sites < 0 || n_sites > INT32_MAX) return (int)hipErrorInvalidValue;
     if (n_sites == 0) return 0;
     hipLaunchKernelGGL(knn_level_kernel, dim3(alignn_ceil_div(n_sites, kSitesPerBlock)), dim3(kThreads), 0, (hipStream_t)stream,
-                       lat, cart, graph_ptr, site_graph, cut, reach, levels, k, (int)n_sites, crystal_level);
+                       lat, cart, graph_ptr, site_graph, cut, box, levels, k, (int)n_sites, crystal_level);
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
 
 int alignn_knn_kth(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                   const double* cut, const int32_t* reach, int levels, int k, int64_t n_sites, const int32_t* crystal_level,
+                   const double* cut, const int32_t* box, int levels, int k, int64_t n_sites, const int32_t* crystal_level,
                    double* kth, alignn_stream_t stream) {
     if (levels <= 0 || k <= 0 || n_sites < 0 || n_sites > INT32_MAX) return (int)hipErrorInvalidValue;
     if (n_sites == 0) return 0;
     hipLaunchKernelGGL(knn_kth_kernel, dim3(alignn_ceil_div(n_sites, kSitesPerBlock)), dim3(kThreads), 0, (hipStream_t)stream, lat,
-                       cart, graph_ptr, site_graph, cut, reach, levels, k, (int)n_sites, crystal_level, kth);
+                       cart, graph_ptr, site_graph, cut, box, levels, k, (int)n_sites, crystal_level, kth);
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
 
 int alignn_knn_count(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                     const double* cut, const int32_t* reach, int levels, int64_t n_sites, const int32_t* crystal_level,
+                     const double* cut, const int32_t* box, int levels, int64_t n_sites, const int32_t* crystal_level,
                      const double* kth, int64_t* count, alignn_stream_t stream) {
     if (levels <= 0 || n_sites < 0 || n_sites > INT32_MAX) return (int)hipErrorInvalidValue;
     if (n_sites == 0) return 0;
     hipLaunchKernelGGL(knn_bonds_kernel<false>, dim3(alignn_ceil_div(n_sites, kSitesPerBlock)), dim3(kThreads), 0,
-                       (hipStream_t)stream, lat, cart, graph_ptr, site_graph, cut, reach, levels, (int)n_sites, crystal_level, kth,
+                       (hipStream_t)stream, lat, cart, graph_ptr, site_graph, cut, box, levels, (int)n_sites, crystal_level, kth,
                        count, nullptr, nullptr, nullptr, nullptr, nullptr);
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
 
 int alignn_knn_emit(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                    const double* cut, const int32_t* reach, int levels, int64_t n_sites, const int32_t* crystal_level,
+                    const double* cut, const int32_t* box, int levels, int64_t n_sites, const int32_t* crystal_level,
                     const double* kth, const int64_t* offset, int64_t* u, int64_t* v, float* r, int32_t* image,
                     alignn_stream_t stream) {
     if (levels <= 0 || n_sites < 0 || n_sites > INT32_MAX || !u || !v || !r) return (int)hipErrorInvalidValue;
     if (n_sites == 0) return 0;
     hipLaunchKernelGGL(knn_bonds_kernel<true>, dim3(alignn_ceil_div(n_sites, kSitesPerBlock)), dim3(kThreads), 0,
-                       (hipStream_t)stream, lat, cart, graph_ptr, site_graph, cut, reach, levels, (int)n_sites, crystal_level, kth,
+                       (hipStream_t)stream, lat, cart, graph_ptr, site_graph, cut, box, levels, (int)n_sites, crystal_level, kth,
                        nullptr, offset, u, v, r, image);
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
+
+int alignn_knn_kth_cap(void) { return kKthCap; }
 
 }  // extern "C"

@@ -6,7 +6,10 @@ rebuild it at EVERY molecular-dynamics step (``alignn/ff/calculators.py:280-291`
 at 14 ms for 3 200 atoms (fused eval path) that host-side build is what bounds MD.  This module restates the same
 construction as device tensor operations, so positions never leave the GPU:
 
-* all periodic images within ``cutoff`` (enough images along each lattice vector: cutoff / plane spacing);
+* all periodic images within ``cutoff`` and farther than jarvis' ``bond_tol`` = 0.15 A (enough images along each lattice
+  vector: cutoff / plane spacing - for fractional coordinates in [0, 1]; for UNWRAPPED coordinates the box jarvis lays out
+  around the fractional extent, ``_image_box``: once the fractions span more than a cell that box misses images inside
+  the cutoff, and the reference's bond list - reproduced here - is defined by what it scans, not by the geometry);
 * too few neighbours somewhere -> widen the search sphere (``graphs.py:170-188``);
 * per site keep everything out to the shell of the ``max_neighbors``-th neighbour (ties with it included);
 * canonise to an undirected multigraph keyed (smaller id, larger id, image) and emit both directions as a consecutive
@@ -37,11 +40,28 @@ __all__ = ["knn_multigraph", "knn_multigraph_batch", "knn_multigraph_batch_hip",
 PAD_BUDGET = 2 << 30  # bytes of padded distance tensor above which knn_multigraph_batch goes crystal by crystal
 
 
+BOND_TOL = 0.15  # jarvis' get_all_neighbors(r, bond_tol=0.15): anything closer than this is not a neighbour
+
+
+def _image_box(spacing: torch.Tensor, fmin: torch.Tensor, fmax: torch.Tensor, cut: torch.Tensor):
+    """Inclusive image range ``(lo, hi)`` (float64, integer valued) a crystal scans at cutoff ``cut`` - the rule of
+    ``alignn_amd.synthetic.image_box``.  Axis with all fractions inside [0, 1]: ``|I| <= ceil(cut / plane spacing)``,
+    every image within the cutoff.  Otherwise the box jarvis lays out: ``floor(min frac) - maxr .. ceil(max frac) + maxr
+    - 1``, ``maxr = ceil((cut + BOND_TOL) / spacing)``.  ``spacing``, ``fmin``, ``fmax`` [..., 3]; ``cut`` broadcastable to
+    them."""
+    reach = torch.ceil(cut / spacing)
+    maxr = torch.ceil((cut + BOND_TOL) / spacing)
+    flo, fhi = torch.floor(fmin), torch.ceil(fmax)
+    wrapped = (flo == 0) & (fhi <= 1)
+    return torch.where(wrapped, -reach, flo - maxr), torch.where(wrapped, reach, fhi + maxr - 1)
+
+
 def _all_neighbors(lat: torch.Tensor, frac: torch.Tensor, cutoff: float):
     inv = torch.linalg.inv(lat)
     spacing = 1.0 / torch.linalg.norm(inv, dim=0)
-    reach = torch.ceil(cutoff / spacing).to(torch.int64).tolist()  # 3 small integers (host)
-    rng = [torch.arange(-k, k + 1, device=lat.device) for k in reach]
+    lo, hi = _image_box(spacing, frac.min(dim=0).values, frac.max(dim=0).values, torch.as_tensor(cutoff, dtype=lat.dtype, device=lat.device))
+    box = torch.stack([lo, hi]).to(torch.int64).tolist()  # 6 small integers (host)
+    rng = [torch.arange(a, b + 1, device=lat.device) for a, b in zip(*box)]
     images = torch.stack(torch.meshgrid(*rng, indexing="ij"), -1).reshape(-1, 3)
     # explicit elementwise float64 operations in the same fixed order as alignn_amd.synthetic._all_neighbors (separate
     # multiply / add kernels, no matmul, no fused multiply-add): identical distance bits, identical tie decisions
@@ -51,7 +71,7 @@ def _all_neighbors(lat: torch.Tensor, frac: torch.Tensor, cutoff: float):
     d = (cart[None, :, None, :] + shift[None, None, :, :]) - cart[:, None, None, :]  # d[i, j, I] = cart[j] + shift[I] - cart[i]
     dx, dy, dz = d[..., 0], d[..., 1], d[..., 2]
     dist = torch.sqrt(dx * dx + dy * dy + dz * dz)
-    src, dst, img = torch.nonzero((dist <= cutoff) & (dist > 1e-8), as_tuple=True)
+    src, dst, img = torch.nonzero((dist <= cutoff) & (dist > BOND_TOL), as_tuple=True)
     return src, dst, images[img], dist[src, dst, img]
 
 
@@ -135,18 +155,21 @@ def knn_multigraph_batch(lattices: Sequence, fracs: Sequence, cutoff: float = 8.
     spacing = 1.0 / torch.linalg.norm(torch.linalg.inv(lat), dim=1)  # [B,3]: plane spacings (column norms of the inverse)
     # same fixed-order float64 arithmetic as knn_multigraph / synthetic._all_neighbors
     cart = frac[..., 0:1] * lat[:, None, 0, :] + frac[..., 1:2] * lat[:, None, 1, :] + frac[..., 2:3] * lat[:, None, 2, :]
+    pad = ~real[:, :, None]
+    fmin = frac.masked_fill(pad, float("inf")).min(dim=1).values  # [B,3] fractional extent of the real sites
+    fmax = frac.masked_fill(pad, float("-inf")).max(dim=1).values
     while True:
-        reach = torch.ceil(cut[:, None] / spacing).to(torch.int64)  # [B,3]
-        rmax = reach.max(dim=0).values.tolist()  # host: three integers per batch
-        rng = [torch.arange(-q, q + 1, device=dev) for q in rmax]
+        lo, hi = (x.to(torch.int64) for x in _image_box(spacing, fmin, fmax, cut[:, None]))  # [B,3] each
+        box = torch.stack([lo.min(dim=0).values, hi.max(dim=0).values]).tolist()  # host: six integers per batch
+        rng = [torch.arange(a, b + 1, device=dev) for a, b in zip(*box)]
         images = torch.stack(torch.meshgrid(*rng, indexing="ij"), -1).reshape(-1, 3)  # [I,3]
-        inside = (images.abs()[None, :, :] <= reach[:, None, :]).all(-1)  # [B,I]: the images crystal b itself would scan
+        inside = ((images[None, :, :] >= lo[:, None, :]) & (images[None, :, :] <= hi[:, None, :])).all(-1)  # [B,I]: the images crystal b itself would scan
         imf = images.to(torch.float64)
         shift = imf[None, :, 0:1] * lat[:, None, 0, :] + imf[None, :, 1:2] * lat[:, None, 1, :] + imf[None, :, 2:3] * lat[:, None, 2, :]
         d = (cart[:, None, :, None, :] + shift[:, None, None, :, :]) - cart[:, :, None, None, :]  # [B,i,j,I,3]
         dx, dy, dz = d[..., 0], d[..., 1], d[..., 2]
         dist = torch.sqrt(dx * dx + dy * dy + dz * dz)
-        ok = ((dist <= cut[:, None, None, None]) & (dist > 1e-8) & real[:, :, None, None] & real[:, None, :, None]
+        ok = ((dist <= cut[:, None, None, None]) & (dist > BOND_TOL) & real[:, :, None, None] & real[:, None, :, None]
               & inside[:, None, None, :])
         counts = ok.sum(dim=(2, 3))  # [B,nmax] neighbours per site
         short = ((counts < k) & real).any(dim=1)  # [B]
@@ -315,7 +338,7 @@ KNN_LEVELS = 5  # cutoffs tried per crystal: the given one, then longest lattice
 
 
 # What knn_multigraph_batch_hip derives from the LATTICES alone (cell matrices, per-site crystal index, the ladder of cutoffs
-# and image-box reaches: ~20 small torch operations incl. a batched 3 x 3 inverse).  MD at constant cell (alignn/ff/
+# and image-box half-widths: ~20 small torch operations incl. a batched 3 x 3 inverse).  MD at constant cell (alignn/ff/
 # calculators.py rebuilds the graph of the same atoms every step) passes the same lattice tensors again and again: the last
 # result is kept, keyed on the tensors' identity and version counters.
 # The key covers identity, version counter, storage address, device and dtype of every lattice tensor: an edit through a
@@ -352,9 +375,11 @@ def _lattice_tables(lattices, ns, dev, cutoff):
         c = cuts[-1]
         cuts.append(torch.where(c < longest, longest, 2.0 * c))
     cut = torch.stack(cuts, 1).contiguous()  # [B,L]
+    # the two half-widths _image_box chooses between, per level; the box itself needs the coordinates (alignn_knn_box)
     reach = torch.ceil(cut[:, :, None] / spacing[:, None, :]).to(torch.int32).contiguous()  # [B,L,3]
+    maxr = torch.ceil((cut[:, :, None] + BOND_TOL) / spacing[:, None, :]).to(torch.int32).contiguous()
     # (the cell volumes - crystal_batch's GraphBatch.volume - travel WITH the tables: same key, same lifetime)
-    val = (lat, gptr, site_graph, lg, cut, reach, torch.linalg.det(lat).abs().float())
+    val = (lat, gptr, site_graph, lg, cut, reach, maxr, torch.linalg.det(lat).abs().float())
     if key is not None:
         import weakref
 
@@ -366,7 +391,10 @@ def knn_multigraph_batch_hip(lattices: Sequence, fracs: Sequence, cutoff: float 
                              return_images: bool = False, return_volume: bool = False):
     """``knn_multigraph_batch`` on the hand-written kernels of csrc/knn.hip (one wavefront per site): the same bond
     list in the same order - bit-identical index arrays, bond vectors equal to rounding - with no padded [B,n,n,I]
-    tensors and ONE host read per batch (the total bond count, to size the output).  CUDA(HIP) device only."""
+    tensors and ONE host read per batch (the total bond count, to size the output).  The image box of every crystal is
+    formed on the device from its fractional extent (``alignn_knn_box``); what depends on the lattices alone stays cached
+    (``_lattice_tables``).  Raises ``RuntimeError`` when a site lacks ``max_neighbors`` neighbours at the widest of the
+    ``KNN_LEVELS`` cutoffs (the reference would go on doubling).  CUDA(HIP) device only."""
     from . import _lib
     from ._lib import check, ptr, stream
 
@@ -379,7 +407,7 @@ def knn_multigraph_batch_hip(lattices: Sequence, fracs: Sequence, cutoff: float 
     N = sum(ns)
     with _lib.device_guard(torch.empty(0, device=dev)):
         frac = torch.cat([torch.as_tensor(f).to(dev, torch.float64) for f in fracs]).contiguous()  # [N,3]
-        lat, gptr, site_graph, lg, cut, reach, volume = _lattice_tables(lattices, ns, dev, float(cutoff))
+        lat, gptr, site_graph, lg, cut, reach, maxr, volume = _lattice_tables(lattices, ns, dev, float(cutoff))
         # the fixed-order float64 product of knn_multigraph / synthetic._all_neighbors (separate multiplies and adds)
         cart = (frac[:, 0:1] * lg[:, 0, :] + frac[:, 1:2] * lg[:, 1, :] + frac[:, 2:3] * lg[:, 2, :]).contiguous()
         level = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -387,11 +415,13 @@ def knn_multigraph_batch_hip(lattices: Sequence, fracs: Sequence, cutoff: float 
         count = torch.empty(N, dtype=torch.int64, device=dev)
         st = stream()
         L, k = KNN_LEVELS, int(max_neighbors)
-        check(lib.alignn_knn_levels(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(reach), L, k, N, ptr(level),
+        box = torch.empty(B, L, 6, dtype=torch.int32, device=dev)  # image range per crystal and level (_image_box), on the device
+        check(lib.alignn_knn_box(ptr(frac), ptr(gptr), ptr(reach), ptr(maxr), L, B, ptr(box), st), "knn_box")
+        check(lib.alignn_knn_levels(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(box), L, k, N, ptr(level),
                                     st), "knn_levels")
-        check(lib.alignn_knn_kth(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(reach), L, k, N, ptr(level),
+        check(lib.alignn_knn_kth(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(box), L, k, N, ptr(level),
                                  ptr(kth), st), "knn_kth")
-        check(lib.alignn_knn_count(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(reach), L, N, ptr(level),
+        check(lib.alignn_knn_count(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(box), L, N, ptr(level),
                                    ptr(kth), ptr(count), st), "knn_count")
         csum = torch.cumsum(count, 0)
         offset = (csum - count).contiguous()
@@ -405,7 +435,7 @@ def knn_multigraph_batch_hip(lattices: Sequence, fracs: Sequence, cutoff: float 
         r = torch.empty(E, 3, dtype=torch.float32, device=dev)
         img = torch.empty(E, 3, dtype=torch.int32, device=dev) if return_images else None
         if E:
-            check(lib.alignn_knn_emit(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(reach), L, N, ptr(level),
+            check(lib.alignn_knn_emit(ptr(lat), ptr(cart), ptr(gptr), ptr(site_graph), ptr(cut), ptr(box), L, N, ptr(level),
                                       ptr(kth), ptr(offset), ptr(u), ptr(v), ptr(r), ptr(img), st), "knn_emit")
     out = (u, v, r, ns) + ((img,) if return_images else ()) + ((volume,) if return_volume else ())
     return out

@@ -120,14 +120,32 @@ def make_molecule(n_atoms: int, seed: int, box: float = 500.0, spread: float = 1
 # --------------------------------------------------------------------------
 # bond graph
 # --------------------------------------------------------------------------
+BOND_TOL = 0.15  # jarvis' get_all_neighbors(r, bond_tol=0.15): anything closer than this is not a neighbour
+
+
+def image_box(spacing, fmin, fmax, cutoff):
+    """Inclusive image range (lo[3], hi[3]) scanned for neighbours within ``cutoff``.  Fractions inside [0, 1] on an axis:
+    ``|I| <= ceil(cutoff / plane spacing)``, which holds every image within the cutoff.  Anything else (unwrapped input):
+    the box jarvis lays out, ``floor(min frac) - maxr .. ceil(max frac) + maxr - 1`` with ``maxr = ceil((cutoff + BOND_TOL)
+    / spacing)`` - that box does NOT hold every image within the cutoff once the fractions span more than one cell, and
+    the reference's bond list is defined by what it scans."""
+    reach = np.ceil(cutoff / spacing)
+    maxr = np.ceil((cutoff + BOND_TOL) / spacing)
+    flo, fhi = np.floor(fmin), np.ceil(fmax)
+    wrapped = (flo == 0) & (fhi <= 1)
+    lo = np.where(wrapped, -reach, flo - maxr)
+    hi = np.where(wrapped, reach, fhi + maxr - 1)
+    return lo.astype(np.int64), hi.astype(np.int64)
+
+
 def _all_neighbors(lat, frac, cutoff):
     """(src, dst, image[3], dist) of every periodic neighbour within ``cutoff``."""
     n = frac.shape[0]
     # number of images needed along each lattice vector: cutoff / plane spacing
     inv = np.linalg.inv(lat)
     spacing = 1.0 / np.linalg.norm(inv, axis=0)
-    reach = np.ceil(cutoff / spacing).astype(int)
-    rng_ = [np.arange(-k, k + 1) for k in reach]
+    lo, hi = image_box(spacing, frac.min(axis=0), frac.max(axis=0), cutoff)
+    rng_ = [np.arange(a, b + 1) for a, b in zip(lo, hi)]
     images = np.stack(np.meshgrid(*rng_, indexing="ij"), -1).reshape(-1, 3)
     # distances as explicit elementwise float64 operations in a FIXED order (no BLAS, no fused multiply-add): the tie
     # decisions at the shell of the 12th neighbour then agree bit for bit with the oracle's neighbour list
@@ -138,7 +156,7 @@ def _all_neighbors(lat, frac, cutoff):
     # d[i, j, I] = (cart[j] + shift[I]) - cart[i]
     d = (cart[None, :, None, :] + shift[None, None, :, :]) - cart[:, None, None, :]
     dist = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2])
-    mask = (dist <= cutoff) & (dist > 1e-8)
+    mask = (dist <= cutoff) & (dist > BOND_TOL)
     src, dst, img = np.nonzero(mask)
     return src, dst, images[img], dist[src, dst, img], n
 

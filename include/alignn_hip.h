@@ -35,7 +35,7 @@ extern "C" {
 
 typedef void* alignn_stream_t; /* hipStream_t */
 
-/* Library / build identification: returns a static string such as "alignn_hip 0.1 gfx950". */
+/* Library / build identification: returns a static string such as "alignn_hip 0.2 gfx950". */
 const char* alignn_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -541,8 +541,14 @@ int alignn_egc_dual_bwd_lg_dense_ln(const float* GY, const float* GYt, const flo
  * no atomics on the output, no host synchronisation.  Inputs shared by the four passes:
  *   lat[B][9] float64 (rows a, b, c), cart[N][3] float64 Cartesian positions (frac . lat, the caller's fixed-order
  *   product), graph_ptr[B+1] site offsets, site_graph[N] crystal of each site, cut[B][levels] the crystal's cutoff
- *   sequence (cutoff, then "longest lattice vector if below it, else twice", graphs.py:170-188), reach[B][levels][3]
- *   image-box half-widths ceil(cut / plane spacing).
+ *   sequence (cutoff, then "longest lattice vector if below it, else twice", graphs.py:170-188), box[B][levels][6]
+ *   the inclusive image range (lo[3], hi[3]) the crystal's sites scan.  Candidates are the pairs with
+ *   0.15 (jarvis' bond_tol) < distance <= cutoff.
+ *   knn_box:    box from frac[N][3] float64 and the lattice-only tables reach / maxr [B][levels][3] =
+ *               ceil(cut / plane spacing) / ceil((cut + 0.15) / plane spacing): per axis [-reach, reach] when every
+ *               fraction of the crystal lies in [0, 1], else jarvis' [floor(min) - maxr, ceil(max) + maxr - 1] (unwrapped
+ *               input; not symmetric, and a bond is kept by an end only at an image that end scans).  A box too large for
+ *               32-bit candidate indices is written empty (lo 0, hi -1): the crystal then ends on level == levels.
  *   knn_levels: crystal_level[B] (zeroed by the caller) = first level at which EVERY site of the crystal has >= k
  *               candidates (== levels: not reachable - the caller raises)
  *   knn_kth:    kth[N] = distance of the k-th nearest candidate (ties share it)
@@ -550,17 +556,21 @@ int alignn_egc_dual_bwd_lg_dense_ln(const float* GY, const float* GYt, const flo
  *   knn_emit:   offset[N] = exclusive prefix sum of count; writes both directions of bond e at rows 2e, 2e+1 of
  *               u, v (int64), r[.][3] float32 = src -> dst displacement, image[.][3] int32 (optional; forward image for
  *               both directions, like the reference's `images`); a site's bonds leave sorted by (b, image). */
+int alignn_knn_box(const double* frac, const int32_t* graph_ptr, const int32_t* reach, const int32_t* maxr, int levels,
+                   int64_t n_crystals, int32_t* box, alignn_stream_t stream);
+/* distances inside the cutoff a site's wave keeps in LDS for the k-th smallest; above it knn_kth searches by rounds */
+int alignn_knn_kth_cap(void);
 int alignn_knn_levels(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                      const double* cut, const int32_t* reach, int levels, int k, int64_t n_sites, int32_t* crystal_level,
+                      const double* cut, const int32_t* box, int levels, int k, int64_t n_sites, int32_t* crystal_level,
                       alignn_stream_t stream);
 int alignn_knn_kth(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                   const double* cut, const int32_t* reach, int levels, int k, int64_t n_sites, const int32_t* crystal_level,
+                   const double* cut, const int32_t* box, int levels, int k, int64_t n_sites, const int32_t* crystal_level,
                    double* kth, alignn_stream_t stream);
 int alignn_knn_count(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                     const double* cut, const int32_t* reach, int levels, int64_t n_sites, const int32_t* crystal_level,
+                     const double* cut, const int32_t* box, int levels, int64_t n_sites, const int32_t* crystal_level,
                      const double* kth, int64_t* count, alignn_stream_t stream);
 int alignn_knn_emit(const double* lat, const double* cart, const int32_t* graph_ptr, const int32_t* site_graph,
-                    const double* cut, const int32_t* reach, int levels, int64_t n_sites, const int32_t* crystal_level,
+                    const double* cut, const int32_t* box, int levels, int64_t n_sites, const int32_t* crystal_level,
                     const double* kth, const int64_t* offset, int64_t* u, int64_t* v, float* r, int32_t* image,
                     alignn_stream_t stream);
 
