@@ -164,15 +164,11 @@ SIGNATURES = {
     "alignn_add_inplace": (_i32, [_p, _p, _i64, _p]),
     "alignn_add3": (_i32, [_p, _p, _p, _p, _i64, _p]),
     # batched FIRE relaxation (csrc/relax.hip)
-    "alignn_fire_step": (_i32, [_p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f64, _i32, _f64, _f64, _i32, _f64,
-                                _f64, _f64, _f64, _p]),
-    "alignn_fire_cell_step": (_i32, [_p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                                     _p, _f64, _i32, _f64, _f64, _i32, _f64, _f64, _f64, _f64, _p]),
+    "alignn_fire_step": (_i32, [_p, _p]),
+    "alignn_fire_args_sizeof": (_sz, []),
     # batched molecular dynamics (csrc/dynamics.hip)
-    "alignn_md_step": (_i32, [_p, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32,
-                              _i32, _f64, _f64, _f64, _i32, _f64, _p]),
-    "alignn_md_step_cell": (_i32, [_p, _p, _p, _i64, _p, _i32] + [_p] * 22 + [_i32, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _f64,
-                                   _p]),
+    "alignn_md_step": (_i32, [_p, _p]),
+    "alignn_md_args_sizeof": (_sz, []),
     "alignn_md_init_momenta": (_i32, [_p, _i32, _p, _p, _p, _p, _f64, _p]),
     # batched finite-displacement phonons (csrc/phonon.hip)
     "alignn_phonon_displace": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _p]),
@@ -192,6 +188,30 @@ import struct as _struct
 EGC_FWD_ARGS = _struct.Struct("@5P2q6i2f32PN")
 EGC_BWD_ARGS = _struct.Struct("@8P3q8i22Pq14PN")
 EGC_WGRAD_ARGS = _struct.Struct("@2q4i14PN")
+
+
+
+# argument blocks of alignn_fire_step / alignn_md_step (include/alignn_hip.h: alignn_fire_args / alignn_md_args, field for
+# field, where each one is described).  Filled by name, a field left out is NULL / 0; passed with ``ctypes.byref``.  load()
+# checks the sizes against the library's.
+class FireArgs(C.Structure):
+    _fields_ = [(n, _p) for n in (
+        "forces", "energy", "stress", "force_ptr", "active", "atom_ptr", "inv_lattice", "lattice0",  # inputs of the step
+        "positions", "velocities", "frac", "state", "istate", "xa", "xc", "cell_velocities", "defgrad", "lattice",  # state
+        "forces_out", "energy_out", "fmax_out", "stress_out", "status")] + [  # outputs
+        (n, _i32) for n in ("n_active", "steps", "nmin")] + [
+        (n, _f64) for n in ("fmax", "maxstep", "dtmax", "finc", "fdec", "astart", "fa")]
+
+
+class MdArgs(C.Structure):
+    _fields_ = [("forces", _p), ("energy", _p), ("stress", _p), ("n_rows", _i64)] + [(n, _p) for n in (  # inputs of the step
+        "atom_ptr", "masses", "t0_kelvin", "seeds", "pressure", "compressibility",
+        "lattice", "inv_lattice", "momenta", "positions", "frac", "velocities", "scratch", "status",  # state
+        "epot", "ekin", "temperature", "pressure_out", "volume_out", "traj_positions", "traj_momenta", "traj_lattice",
+        "noise_out")] + [  # outputs
+        (n, _i32) for n in ("n_structures", "t", "interval", "steps", "ensemble", "fixcm")] + [
+        (n, _f64) for n in ("dt", "friction", "andersen_prob", "taut", "taup", "kB")]
+
 
 _lib = None
 
@@ -214,6 +234,10 @@ def load() -> C.CDLL:
             if lib.alignn_egc_args_sizeof(which) != st.size:
                 raise RuntimeError(f"argument block {which} of the composite entry points: library says "
                                    f"{lib.alignn_egc_args_sizeof(which)} bytes, the binding packs {st.size}")
+        for query, block in ((lib.alignn_fire_args_sizeof, FireArgs), (lib.alignn_md_args_sizeof, MdArgs)):
+            if query() != C.sizeof(block):
+                raise RuntimeError(f"argument block {block.__name__}: library says {query()} bytes, the binding packs "
+                                   f"{C.sizeof(block)}")
         _lib = lib
     return _lib
 

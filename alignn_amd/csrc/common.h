@@ -145,3 +145,32 @@ __device__ __forceinline__ double wrap01(double f) {
     f -= floor(f);
     return f < 1.0 ? f : 0.0;  // (-tiny - floor(-tiny) rounds to 1.0)
 }
+
+// row-major 3 x 3: c = a b
+__device__ __forceinline__ void mm3(const double* a, const double* b, double* c) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+}
+
+// det of a row-major 3 x 3 matrix, along its first row
+__device__ __forceinline__ double det3(const double* a) {
+    return a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
+}
+
+// det and inverse of a row-major 3 x 3 matrix by cofactors
+__device__ __forceinline__ double inverse3(const double (&a)[9], double (&inv)[9]) {
+    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[3] * a[8] - a[5] * a[6], c02 = a[3] * a[7] - a[4] * a[6];
+    const double det = a[0] * c00 - a[1] * c01 + a[2] * c02;
+    inv[0] = c00 / det;
+    inv[1] = (a[2] * a[7] - a[1] * a[8]) / det;
+    inv[2] = (a[1] * a[5] - a[2] * a[4]) / det;
+    inv[3] = -c01 / det;
+    inv[4] = (a[0] * a[8] - a[2] * a[6]) / det;
+    inv[5] = (a[2] * a[3] - a[0] * a[5]) / det;
+    inv[6] = c02 / det;
+    inv[7] = (a[1] * a[6] - a[0] * a[7]) / det;
+    inv[8] = (a[0] * a[4] - a[1] * a[3]) / det;
+    return det;
+}

@@ -1,15 +1,24 @@
-// One FIRE step (fixed cell) for a batch of crystals: ASE's ase/optimize/fire.py as the reference's
-// ForceField.optimize_atoms drives it (alignn/ff/ff.py:373-415: FIRE, downhill_check=False) with the convergence test of
-// Optimizer.run in front of it, every structure's optimiser state on the device (alignn_amd/relax.py is the host loop).
+// One FIRE step for a batch of crystals: ASE's ase/optimize/fire.py as the reference's ForceField.optimize_atoms drives it
+// (alignn/ff/ff.py:373-415: FIRE, downhill_check=False) with the convergence test of Optimizer.run in front of it, every
+// structure's optimiser state on the device (alignn_amd/relax.py is the host loop).  One kernel, fire_step_kernel<CELL>, on
+// the argument block alignn_fire_args (include/alignn_hip.h names every field): at fixed cell over the atoms' rows, with
+// ASE's ExpCellFilter (CELL) over the filter's n + 3 generalised rows; what the filter adds sits under if constexpr (CELL).
 //
 // One workgroup per ACTIVE structure, threads grid-strided over its atoms, float64 throughout.  Three passes over the
-// structure's atoms, each followed by a fixed-order workgroup reduction (shuffle-down within a wave, then the four wave
+// structure's rows, each followed by a fixed-order workgroup reduction (shuffle-down within a wave, then the four wave
 // partials added in wave order by every thread alike): no float atomics, so a structure's step is bit-identical from run to
 // run and does not depend on which other structures share the launch.
-//   pass 1  record F (and E) in the full-batch result arrays; F.v, |F|^2, |v|^2, max_i |F_i|^2
-//           converged (max |F_i|^2 < fmax^2) or out of steps -> retire flag, no step
-//   pass 2  v <- mix / reset (ASE's branch on P = F.v), v += dt F; |dr|^2 with dr = dt v
-//   pass 3  dr clipped to maxstep over the whole structure, r += dr, frac = r inv(L) wrapped into [0, 1)
+//   reduce  record F (and E) in the full-batch result arrays; F.v, |F|^2, |v|^2, max_i |F_i|^2 over the rows
+//   test    converged (max |F_i|^2 < fmax^2) or out of steps -> retire flag, no step
+//   mix     v <- mix / reset (ASE's branch on P = F.v), v += dt F; |dr|^2 with dr = dt v
+//   move    dr clipped to maxstep over the whole structure, rows += dr, frac = atom rows inv(L) wrapped into [0, 1)
+//
+// The filter (ase/constraints.py, 3.22.1, default arguments).  Generalised positions of a structure of n atoms: n atom rows
+// X_a = positions F^-T and three cell rows X_c = c logm(F), c = n, F the deformation gradient of the current cell C = C0 F^T.
+// Generalised forces: atom rows f F; cell rows the virial W = -V sym(stress) (the "naive" force) or, when it points too far
+// from it, the exact gradient -d E / d logm(F), the Frechet derivative of expm at L = X_c / c applied to W expm(-L); either
+// one / c.  X_c is kept as state instead of recomputing logm(F) from the cell every step (the round trip is the identity to
+// rounding: tests/test_relax_cell.py).  The cell rows are thread 0's.
 #include "../../include/alignn_hip.h"
 #include "common.h"
 
@@ -70,101 +79,6 @@ __device__ __forceinline__ void fire_store(const FireScalars& f, int taken, int 
         istate[2 * s] = f.nsteps;
         istate[2 * s + 1] = taken + 1;
     }
-}
-
-__global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(
-    const double* __restrict__ forces, const double* __restrict__ energy, const int32_t* __restrict__ force_ptr,
-    const int32_t* __restrict__ active, const int32_t* __restrict__ atom_ptr, const double* __restrict__ inv_lattice,
-    double* __restrict__ pos, double* __restrict__ vel, double* __restrict__ frac, double* __restrict__ forces_out,
-    double* __restrict__ energy_out, double* __restrict__ state, int32_t* __restrict__ istate, double* __restrict__ fmax_out,
-    int32_t* __restrict__ status, double fmax_tol, int steps, double maxstep, double dtmax, int nmin, double finc, double fdec,
-    double astart, double fa) {
-    __shared__ double sh[4][FIRE_WAVES];
-    const int k = blockIdx.x;
-    const int s = active[k];
-    const int beg = atom_ptr[s], n = atom_ptr[s + 1] - beg;
-    const int fbeg = force_ptr[k];
-    if (force_ptr[k + 1] - fbeg != n) {  // forces of another shape than the structure: touch nothing
-        if (threadIdx.x == 0) status[1 + k] = -1;
-        return;
-    }
-    const double* F = forces + 3 * (int64_t)fbeg;
-    double* R = pos + 3 * (int64_t)beg;
-    double* V = vel + 3 * (int64_t)beg;
-    const int taken = istate[2 * s + 1];
-
-    // pass 1
-    double red[4] = {0.0, 0.0, 0.0, 0.0};  // F.v, |F|^2, |v|^2, max |F_i|^2
-    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
-        double f[3], v[3], fi2 = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            f[c] = F[3 * i + c];
-            v[c] = V[3 * i + c];
-            forces_out[3 * ((int64_t)beg + i) + c] = f[c];
-            red[0] += f[c] * v[c];
-            fi2 += f[c] * f[c];
-            red[2] += v[c] * v[c];
-        }
-        red[1] += fi2;
-        red[3] = fmax(red[3], fi2);
-    }
-    block_reduce<4, true>(red, sh);
-    const int converged = red[3] < fmax_tol * fmax_tol;
-    fire_record(red, converged, taken, steps, k, s, energy, energy_out, fmax_out, status);
-    if (converged || taken >= steps) return;
-
-    // pass 2: ASE FIRE.step
-    const FireScalars fire = fire_scalars(red, state, istate, s, taken, dtmax, nmin, finc, fdec, astart, fa);
-    const double dt = fire.dt;
-    double dr2[1] = {0.0};
-    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double f = F[3 * i + c];
-            double v = fire.zero_v ? 0.0 : fire.mix_v * V[3 * i + c] + fire.mix_f * f;
-            v += dt * f;
-            V[3 * i + c] = v;
-            const double d = dt * v;
-            dr2[0] += d * d;
-        }
-    }
-    block_reduce<1, false>(dr2, sh);
-
-    // pass 3
-    const double normdr = sqrt(dr2[0]);
-    const bool clip = normdr > maxstep;
-    const double* L = inv_lattice + 9 * (int64_t)s;
-    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
-        double r[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double d = dt * V[3 * i + c];
-            if (clip) d = maxstep * d / normdr;
-            r[c] = R[3 * i + c] + d;
-            R[3 * i + c] = r[c];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            frac[3 * ((int64_t)beg + i) + c] = wrap01(r[0] * L[c] + r[1] * L[3 + c] + r[2] * L[6 + c]);
-    }
-    fire_store(fire, taken, s, state, istate);
-}
-
-// ---- FIRE with ASE's ExpCellFilter (optimize_lattice=True; ase/constraints.py, 3.22.1, default arguments) --------------------
-// Generalised positions of a structure of n atoms: n atom rows X_a = positions F^-T and three cell rows X_c = c logm(F),
-// c = n, F the deformation gradient of the current cell C = C0 F^T.  Generalised forces: atom rows f F; cell rows the
-// virial W = -V sym(stress) (the "naive" force) or, when it points too far from it, the exact gradient -d E / d logm(F), the
-// Frechet derivative of expm at L = X_c / c applied to W expm(-L); either one / c.  FIRE and the convergence test then run
-// over all n + 3 rows.  X_c is kept as state instead of recomputing logm(F) from the cell every step (the round trip is the
-// identity to rounding: tests/test_relax_cell.py).
-
-// row-major 3x3: c = a b
-__device__ __forceinline__ void mm3(const double* a, const double* b, double* c) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
 }
 
 constexpr int EXPM_TAYLOR = 18;  // with |X| <= 1/2 after scaling the remainder is below 1e-22 of |expm|
@@ -229,8 +143,7 @@ __device__ __forceinline__ void expm3(const double* L, double* E) {
 // the filter's cell rows (before the division by c) from the current cell C, the stress S (eV/A^3, ASE sign) and L = X_c / c;
 // Ssym (the symmetrised stress) is returned as well
 __device__ void cell_force(const double* C, const double* S, const double* L, double* G, double* Ssym) {
-    const double det = C[0] * (C[4] * C[8] - C[5] * C[7]) - C[1] * (C[3] * C[8] - C[5] * C[6]) + C[2] * (C[3] * C[7] - C[4] * C[6]);
-    const double V = fabs(det);
+    const double V = fabs(det3(C));
     double W[9];  // the virial; naive force
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -280,207 +193,195 @@ __device__ void cell_force(const double* C, const double* S, const double* L, do
     for (int i = 0; i < 9; ++i) G[i] = naive ? W[i] : E[i];
 }
 
-__global__ __launch_bounds__(FIRE_BLOCK) void fire_cell_step_kernel(
-    const double* __restrict__ forces, const double* __restrict__ energy, const double* __restrict__ stress,
-    const int32_t* __restrict__ force_ptr, const int32_t* __restrict__ active, const int32_t* __restrict__ atom_ptr,
-    const double* __restrict__ lattice0, const double* __restrict__ inv_lattice0, double* __restrict__ xa,
-    double* __restrict__ pos, double* __restrict__ vel, double* __restrict__ frac, double* __restrict__ xc,
-    double* __restrict__ cell_vel, double* __restrict__ defgrad, double* __restrict__ lattice, double* __restrict__ forces_out,
-    double* __restrict__ energy_out, double* __restrict__ stress_out, double* __restrict__ state, int32_t* __restrict__ istate,
-    double* __restrict__ fmax_out, int32_t* __restrict__ status, double fmax_tol, int steps, double maxstep, double dtmax,
-    int nmin, double finc, double fdec, double astart, double fa) {
+using FireArgs = alignn_fire_args;
+
+template <bool CELL>
+__global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(const FireArgs a) {
     __shared__ double sh[4][FIRE_WAVES];
-    __shared__ double Fsh[9];
     const int k = blockIdx.x;
-    const int s = active[k];
-    const int beg = atom_ptr[s], n = atom_ptr[s + 1] - beg;
-    const int fbeg = force_ptr[k];
-    if (force_ptr[k + 1] - fbeg != n) {  // forces of another shape than the structure: touch nothing
-        if (threadIdx.x == 0) status[1 + k] = -1;
+    const int s = a.active[k];
+    const int beg = a.atom_ptr[s], n = a.atom_ptr[s + 1] - beg;
+    const int fbeg = a.force_ptr[k];
+    if (a.force_ptr[k + 1] - fbeg != n) {  // forces of another shape than the structure: touch nothing
+        if (threadIdx.x == 0) a.status[1 + k] = -1;
         return;
     }
-    const double c = (double)n;  // ExpCellFilter's cell_factor
-    const double* Fo = forces + 3 * (int64_t)fbeg;
-    double* XA = xa + 3 * (int64_t)beg;
-    double* V = vel + 3 * (int64_t)beg;
-    double* XC = xc + 9 * (int64_t)s;
-    double* VC = cell_vel + 9 * (int64_t)s;
-    const int taken = istate[2 * s + 1];
-    double D[9];  // deformation gradient of the evaluated cell
-#pragma unroll
-    for (int i = 0; i < 9; ++i) D[i] = defgrad[9 * (int64_t)s + i];
+    const double* Fo = a.forces + 3 * (int64_t)fbeg;
+    double* X = (CELL ? a.xa : a.positions) + 3 * (int64_t)beg;  // the atom rows
+    double* V = a.velocities + 3 * (int64_t)beg;
+    double* FOUT = a.forces_out + 3 * (int64_t)beg;
+    const int taken = a.istate[2 * s + 1];
+    const double maxstep = a.maxstep;
 
-    // stage 1 (thread 0): the cell rows of the filter forces
-    double G[9], vc[9];
-    if (threadIdx.x == 0) {
-        double L[9], Ssym[9];
+    // the filter's part of the rows: the deformation gradient of the evaluated cell and, on thread 0, the cell rows' forces
+    // (ExpCellFilter's cell_factor is n) and velocities
+    double D[9], G[9], vc[9];
+    [[maybe_unused]] double* XC = nullptr;
+    [[maybe_unused]] double* VC = nullptr;
+    if constexpr (CELL) {
+        const double c = (double)n;
+        XC = a.xc + 9 * (int64_t)s;
+        VC = a.cell_velocities + 9 * (int64_t)s;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) L[i] = XC[i] / c;
-        cell_force(lattice + 9 * (int64_t)s, stress + 9 * (int64_t)k, L, G, Ssym);
+        for (int i = 0; i < 9; ++i) D[i] = a.defgrad[9 * (int64_t)s + i];
+        if (threadIdx.x == 0) {
+            double L[9], Ssym[9];
 #pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            G[i] /= c;
-            vc[i] = VC[i];
-            stress_out[9 * (int64_t)s + i] = Ssym[i];
-        }
-    }
-
-    // stage 2: record, reduce over the n + 3 rows (the cell rows are thread 0's last), test convergence
-    double red[4] = {0.0, 0.0, 0.0, 0.0};  // G.v, |G|^2, |v|^2, max |G_i|^2
-    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
-        double f[3], fi2 = 0.0;
+            for (int i = 0; i < 9; ++i) L[i] = XC[i] / c;
+            cell_force(a.lattice + 9 * (int64_t)s, a.stress + 9 * (int64_t)k, L, G, Ssym);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            f[j] = Fo[3 * i + j];
-            forces_out[3 * ((int64_t)beg + i) + j] = f[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double g = f[0] * D[j] + f[1] * D[3 + j] + f[2] * D[6 + j];  // (f F)_j
-            const double v = V[3 * i + j];
-            red[0] += g * v;
-            fi2 += g * g;
-            red[2] += v * v;
-        }
-        red[1] += fi2;
-        red[3] = fmax(red[3], fi2);
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            double fi2 = 0.0;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                red[0] += G[3 * r + j] * vc[3 * r + j];
-                fi2 += G[3 * r + j] * G[3 * r + j];
-                red[2] += vc[3 * r + j] * vc[3 * r + j];
+            for (int i = 0; i < 9; ++i) {
+                G[i] /= c;
+                vc[i] = VC[i];
+                a.stress_out[9 * (int64_t)s + i] = Ssym[i];
             }
-            red[1] += fi2;
-            red[3] = fmax(red[3], fi2);
         }
     }
-    block_reduce<4, true>(red, sh);
-    const int converged = red[3] < fmax_tol * fmax_tol;
-    fire_record(red, converged, taken, steps, k, s, energy, energy_out, fmax_out, status);
-    if (converged || taken >= steps) return;
-
-    // stage 3: ASE FIRE.step over the n + 3 rows
-    const FireScalars fire = fire_scalars(red, state, istate, s, taken, dtmax, nmin, finc, fdec, astart, fa);
-    const double dt = fire.dt;
-    double dr2[1] = {0.0};
-    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
-        double f[3];
+    // the generalised force of atom row i: f F under the filter, else f
+    auto atom_force = [&](int i, double (&f)[3], double (&g)[3]) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) f[j] = Fo[3 * i + j];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const double g = f[0] * D[j] + f[1] * D[3 + j] + f[2] * D[6 + j];
-            double v = fire.zero_v ? 0.0 : fire.mix_v * V[3 * i + j] + fire.mix_f * g;
-            v += dt * g;
-            V[3 * i + j] = v;
-            const double d = dt * v;
-            dr2[0] += d * d;
+            if constexpr (CELL)
+                g[j] = f[0] * D[j] + f[1] * D[3 + j] + f[2] * D[6 + j];
+            else
+                g[j] = f[j];
+        }
+    };
+
+    // reduce over the rows (the cell rows are thread 0's last), record, test convergence
+    double red[4] = {0.0, 0.0, 0.0, 0.0};  // G.v, |G|^2, |v|^2, max |G_i|^2
+    auto reduce_row = [&](const double* g, const double* v) {
+        double fi2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            red[0] += g[j] * v[j];
+            fi2 += g[j] * g[j];
+            red[2] += v[j] * v[j];
+        }
+        red[1] += fi2;
+        red[3] = fmax(red[3], fi2);
+    };
+    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
+        double f[3], g[3], v[3];
+        atom_force(i, f, g);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            FOUT[3 * i + j] = f[j];
+            v[j] = V[3 * i + j];
+        }
+        reduce_row(g, v);
+    }
+    if constexpr (CELL) {
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) reduce_row(G + 3 * r, vc + 3 * r);
         }
     }
-    if (threadIdx.x == 0) {
+    block_reduce<4, true>(red, sh);
+    const int converged = red[3] < a.fmax * a.fmax;
+    fire_record(red, converged, taken, a.steps, k, s, a.energy, a.energy_out, a.fmax_out, a.status);
+    if (converged || taken >= a.steps) return;
+
+    // ASE FIRE.step: mix and kick
+    const FireScalars fire = fire_scalars(red, a.state, a.istate, s, taken, a.dtmax, a.nmin, a.finc, a.fdec, a.astart, a.fa);
+    const double dt = fire.dt;
+    double dr2[1] = {0.0};
+    auto kick = [&](double v, double g) {
+        v = fire.zero_v ? 0.0 : fire.mix_v * v + fire.mix_f * g;
+        v += dt * g;
+        const double d = dt * v;
+        dr2[0] += d * d;
+        return v;
+    };
+    for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
+        double f[3], g[3];
+        atom_force(i, f, g);
 #pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            double v = fire.zero_v ? 0.0 : fire.mix_v * vc[i] + fire.mix_f * G[i];
-            v += dt * G[i];
-            vc[i] = v;
-            const double d = dt * v;
-            dr2[0] += d * d;
+        for (int j = 0; j < 3; ++j) V[3 * i + j] = kick(V[3 * i + j], g[j]);
+    }
+    if constexpr (CELL) {
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) vc[i] = kick(vc[i], G[i]);
         }
     }
     block_reduce<1, false>(dr2, sh);
 
-    // stage 4: clipped move; F = expm(X_c / c), C = C0 F^T (thread 0), then positions X_a F^T and frac = X_a inv(C0) wrapped
+    // the clipped move; under the filter F = expm(X_c / c), C = C0 F^T (thread 0), positions X_a F^T
     const double normdr = sqrt(dr2[0]);
     const bool clip = normdr > maxstep;
-    if (threadIdx.x == 0) {
-        double L[9], Fn[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            double d = dt * vc[i];
-            if (clip) d = maxstep * d / normdr;
-            const double x = XC[i] + d;
-            XC[i] = x;
-            VC[i] = vc[i];
-            L[i] = x / c;
-        }
-        expm3(L, Fn);
-        const double* C0 = lattice0 + 9 * (int64_t)s;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                lattice[9 * (int64_t)s + 3 * i + j] = C0[3 * i] * Fn[3 * j] + C0[3 * i + 1] * Fn[3 * j + 1] + C0[3 * i + 2] * Fn[3 * j + 2];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            defgrad[9 * (int64_t)s + i] = Fn[i];
-            Fsh[i] = Fn[i];
-        }
-    }
-    __syncthreads();
+    auto step_of = [&](double v) {
+        double d = dt * v;
+        if (clip) d = maxstep * d / normdr;
+        return d;
+    };
     double Fn[9];
+    if constexpr (CELL) {
+        __shared__ double Fsh[9];
+        if (threadIdx.x == 0) {
+            const double c = (double)n;
+            double L[9];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) Fn[i] = Fsh[i];
-    const double* Li = inv_lattice0 + 9 * (int64_t)s;
-    double* R = pos + 3 * (int64_t)beg;
+            for (int i = 0; i < 9; ++i) {
+                const double x = XC[i] + step_of(vc[i]);
+                XC[i] = x;
+                VC[i] = vc[i];
+                L[i] = x / c;
+            }
+            expm3(L, Fn);
+            const double* C0 = a.lattice0 + 9 * (int64_t)s;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    a.lattice[9 * (int64_t)s + 3 * i + j] = C0[3 * i] * Fn[3 * j] + C0[3 * i + 1] * Fn[3 * j + 1] + C0[3 * i + 2] * Fn[3 * j + 2];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                a.defgrad[9 * (int64_t)s + i] = Fn[i];
+                Fsh[i] = Fn[i];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Fn[i] = Fsh[i];
+    }
+    const double* Li = a.inv_lattice + 9 * (int64_t)s;
     for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
         double x[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            double d = dt * V[3 * i + j];
-            if (clip) d = maxstep * d / normdr;
-            x[j] = XA[3 * i + j] + d;
-            XA[3 * i + j] = x[j];
+            x[j] = X[3 * i + j] + step_of(V[3 * i + j]);
+            X[3 * i + j] = x[j];
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            R[3 * i + j] = x[0] * Fn[3 * j] + x[1] * Fn[3 * j + 1] + x[2] * Fn[3 * j + 2];
-            frac[3 * ((int64_t)beg + i) + j] = wrap01(x[0] * Li[j] + x[1] * Li[3 + j] + x[2] * Li[6 + j]);
+            if constexpr (CELL) a.positions[3 * ((int64_t)beg + i) + j] = x[0] * Fn[3 * j] + x[1] * Fn[3 * j + 1] + x[2] * Fn[3 * j + 2];
+            a.frac[3 * ((int64_t)beg + i) + j] = wrap01(x[0] * Li[j] + x[1] * Li[3 + j] + x[2] * Li[6 + j]);
         }
     }
-    fire_store(fire, taken, s, state, istate);
+    fire_store(fire, taken, s, a.state, a.istate);
 }
 
 }  // namespace
 
-extern "C" int alignn_fire_step(const double* forces, const double* energy, const int32_t* force_ptr, const int32_t* active,
-                                int n_active, const int32_t* atom_ptr, const double* inv_lattice, double* positions,
-                                double* velocities, double* frac, double* forces_out, double* energy_out, double* state,
-                                int32_t* istate, double* fmax_out, int32_t* status, double fmax_tol, int steps, double maxstep,
-                                double dtmax, int nmin, double finc, double fdec, double astart, double fa,
-                                alignn_stream_t stream) {
-    if (n_active < 0 || !status) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
-    if (e != hipSuccess) return (int)e;
-    if (n_active == 0) return 0;
-    fire_step_kernel<<<n_active, FIRE_BLOCK, 0, st>>>(forces, energy, force_ptr, active, atom_ptr, inv_lattice, positions,
-                                                      velocities, frac, forces_out, energy_out, state, istate, fmax_out, status,
-                                                      fmax_tol, steps, maxstep, dtmax, nmin, finc, fdec, astart, fa);
-    ALIGNN_CHECK_LAUNCH();
-    return 0;
-}
+extern "C" size_t alignn_fire_args_sizeof(void) { return sizeof(alignn_fire_args); }
 
-extern "C" int alignn_fire_cell_step(const double* forces, const double* energy, const double* stress, const int32_t* force_ptr,
-                                     const int32_t* active, int n_active, const int32_t* atom_ptr, const double* lattice0,
-                                     const double* inv_lattice0, double* xa, double* positions, double* velocities, double* frac,
-                                     double* xc, double* cell_velocities, double* defgrad, double* lattice, double* forces_out,
-                                     double* energy_out, double* stress_out, double* state, int32_t* istate, double* fmax_out,
-                                     int32_t* status, double fmax, int steps, double maxstep, double dtmax, int nmin, double finc,
-                                     double fdec, double astart, double fa, alignn_stream_t stream) {
-    if (n_active < 0 || !status) return (int)hipErrorInvalidValue;
+extern "C" int alignn_fire_step(const alignn_fire_args* args, alignn_stream_t stream) {
+    if (!args || args->n_active < 0 || !args->status) return (int)hipErrorInvalidValue;
+    const FireArgs& a = *args;
+    const bool cell = a.xc != nullptr;  // a cell-filter state: every field of the filter is then needed
+    if (cell && (!a.stress || !a.lattice0 || !a.xa || !a.cell_velocities || !a.defgrad || !a.lattice || !a.stress_out))
+        return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    hipError_t e = hipMemsetAsync(a.status, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;
-    if (n_active == 0) return 0;
-    fire_cell_step_kernel<<<n_active, FIRE_BLOCK, 0, st>>>(
-        forces, energy, stress, force_ptr, active, atom_ptr, lattice0, inv_lattice0, xa, positions, velocities, frac, xc,
-        cell_velocities, defgrad, lattice, forces_out, energy_out, stress_out, state, istate, fmax_out, status, fmax, steps, maxstep,
-        dtmax, nmin, finc, fdec, astart, fa);
+    if (a.n_active == 0) return 0;
+    if (cell)
+        fire_step_kernel<true><<<a.n_active, FIRE_BLOCK, 0, st>>>(a);
+    else
+        fire_step_kernel<false><<<a.n_active, FIRE_BLOCK, 0, st>>>(a);
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }

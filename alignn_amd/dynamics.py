@@ -8,8 +8,9 @@ one host-side graph build per step.  ``run_md`` integrates B independent crystal
 1. build the graph batch of all B structures on the device (``neighbors.crystal_batch``);
 2. evaluate energies and forces (NPT: and stresses) with ``model(batch)``, or replay that evaluation
    (``md.GraphedForceField``, ``replay=True``);
-3. one ``alignn_md_step`` launch (csrc/dynamics.hip; ``alignn_md_step_cell`` for Andersen and NPT): finish step t with the new
-   forces, record frame t, begin step t + 1 - under NPT the pressure, the scaled cell, its inverse and the scaled positions too.
+3. one ``alignn_md_step`` launch (csrc/dynamics.hip; its argument block ``alignn_md_args`` is filled once, a step sets the
+   evaluation's pointers and ``t``): finish step t with the new forces, record frame t, begin step t + 1 - under NPT the
+   pressure, the scaled cell, its inverse and the scaled positions too.
 
 No structure retires, so nothing is read back per step beyond what the neighbour search reads.  The semantics are ASE 3.22.1's
 (``environment.yml``), restated in numpy in tests/test_md_ref.py and tests/test_md_npt_ref.py.  The random numbers are the
@@ -19,6 +20,7 @@ alone or in a batch.
 
 from __future__ import annotations
 
+import ctypes as C
 import numbers
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
@@ -177,9 +179,9 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
             mom = torch.cat([torch.as_tensor(p).to(dev, torch.float64) for p in momenta]).contiguous()
         else:
             mom = torch.zeros(N, 3, dtype=torch.float64, device=dev)
-        vel = rnd_vel = None
-        if ensemble == "nvt_langevin" or andersen:  # (Andersen: v between the halves, the positions before the drift)
-            vel, rnd_vel = torch.zeros(N, 3, dtype=torch.float64, device=dev), torch.zeros(N, 3, dtype=torch.float64, device=dev)
+        vel = scratch = None
+        if ensemble == "nvt_langevin" or andersen:  # v between the halves; Langevin's noise, Andersen's positions before the drift
+            vel, scratch = torch.zeros(N, 3, dtype=torch.float64, device=dev), torch.zeros(N, 3, dtype=torch.float64, device=dev)
         n_frames = steps // interval + 1
         epot, ekin, temp = (torch.zeros(n_frames, B, dtype=torch.float64, device=dev) for _ in range(3))
         traj_p = torch.zeros(n_frames, N, 3, dtype=torch.float64, device=dev) if trajectory else None
@@ -199,6 +201,16 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
                                   neighbor_strategy=neighbor_strategy, intensive=intensive, force_multiplier=force_multiplier,
                                   stress_weight=float(stress_weight) if npt else None, replay=replay)
         every = list(range(B))
+        args = _lib.MdArgs(
+            atom_ptr=atom_ptr.data_ptr(), masses=mass.data_ptr(), t0_kelvin=t0_t.data_ptr(), seeds=seed_t.data_ptr(),
+            pressure=p_target_t.data_ptr() if npt else None, compressibility=comp_t.data_ptr() if npt else None,
+            lattice=(lat_cur if npt else packed.lat).data_ptr() if npt or andersen else None, inv_lattice=inv.data_ptr(),
+            momenta=mom.data_ptr(), positions=pos.data_ptr(), frac=frac.data_ptr(), velocities=_lib.ptr(vel),
+            scratch=_lib.ptr(scratch), status=status.data_ptr(), epot=epot.data_ptr(), ekin=ekin.data_ptr(),
+            temperature=temp.data_ptr(), pressure_out=_lib.ptr(p_out), volume_out=_lib.ptr(v_out),
+            traj_positions=_lib.ptr(traj_p), traj_momenta=_lib.ptr(traj_m), traj_lattice=_lib.ptr(traj_l),
+            n_structures=B, interval=int(interval), steps=int(steps), ensemble=ens, fixcm=int(bool(fixcm)), dt=dt,
+            friction=float(friction), andersen_prob=float(andersen_prob), taut=tau, taup=taup_ase, kB=KB)
 
         for t in range(steps + 1):
             if npt:
@@ -207,22 +219,9 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
                 lat_now = lat_cur.clone()
                 lat_v = [lat_now[s] for s in range(B)]
             energy, forces, stress = evaluate(every, lat_v, frac_v, pos_v)
-            if npt or andersen:
-                _lib.check(lib.alignn_md_step_cell(
-                    forces.data_ptr(), energy.data_ptr(), _lib.ptr(stress), forces.shape[0], atom_ptr.data_ptr(), B,
-                    mass.data_ptr(), (lat_cur if npt else packed.lat).data_ptr(), inv.data_ptr(), mom.data_ptr(), pos.data_ptr(),
-                    frac.data_ptr(), _lib.ptr(vel), _lib.ptr(rnd_vel), t0_t.data_ptr(), seed_t.data_ptr(),
-                    p_target_t.data_ptr() if npt else None, comp_t.data_ptr() if npt else None, epot.data_ptr(), ekin.data_ptr(),
-                    temp.data_ptr(), _lib.ptr(p_out), _lib.ptr(v_out), _lib.ptr(traj_p), _lib.ptr(traj_m), _lib.ptr(traj_l), None,
-                    status.data_ptr(), t, int(interval), int(steps), ens, dt, float(andersen_prob), tau, taup_ase,
-                    int(bool(fixcm)), KB, _lib.stream()), "md_step_cell")
-                continue
-            _lib.check(lib.alignn_md_step(
-                forces.data_ptr(), energy.data_ptr(), forces.shape[0], atom_ptr.data_ptr(), B, mass.data_ptr(), inv.data_ptr(),
-                mom.data_ptr(), pos.data_ptr(), frac.data_ptr(), _lib.ptr(vel), _lib.ptr(rnd_vel), t0_t.data_ptr(),
-                seed_t.data_ptr(), epot.data_ptr(), ekin.data_ptr(), temp.data_ptr(), _lib.ptr(traj_p), _lib.ptr(traj_m), None,
-                status.data_ptr(), t, int(interval), int(steps), ens, dt, float(friction), tau, int(bool(fixcm)), KB,
-                _lib.stream()), "md_step")
+            args.forces, args.energy, args.stress = forces.data_ptr(), energy.data_ptr(), _lib.ptr(stress)
+            args.n_rows, args.t = forces.shape[0], t
+            _lib.check(lib.alignn_md_step(C.byref(args), _lib.stream()), "md_step")
         if status.item() != 0:
             raise RuntimeError("run_md: md_step found force rows that do not match the batch's atom count")
 

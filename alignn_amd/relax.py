@@ -8,7 +8,8 @@ around ``AlignnAtomwiseCalculator`` (alignn/ff/calculators.py:280-370), one host
 1. build the graph batch of the ACTIVE structures on the device (``neighbors.crystal_batch``, the line graph only when the
    model has ALIGNN layers);
 2. evaluate energies and forces with ``model(batch)`` (the fused ``alignn_ff_eval`` path wherever it applies);
-3. one ``alignn_fire_step`` launch (csrc/relax.hip): convergence test of ``Optimizer.run`` (max_i |F_i|^2 < fmax^2), then
+3. one ``alignn_fire_step`` launch (csrc/relax.hip; its argument block ``alignn_fire_args`` is filled once, a step sets the
+   evaluation's pointers and, when structures have retired, the active list): convergence test of ``Optimizer.run`` (max_i |F_i|^2 < fmax^2), then
    the FIRE update of every unconverged structure, wrapped fractional coordinates for the next neighbour search;
 4. read the number of structures still active and their retire flags (one small host read), drop the retired ones.
 
@@ -18,12 +19,13 @@ alone or beside others.
 
 ``optimize_lattice=True`` relaxes the cells too, as ``optimize_atoms``' default does: ASE's ``ExpCellFilter`` around the atoms,
 its n + 3 generalised rows per structure (atom rows in the starting cell, cell rows ``n logm(F)`` of the deformation gradient
-``F``) driven by the same FIRE in ``alignn_fire_cell_step``.  The model's per-crystal stresses enter as the calculator gives
-them (``stress * stress_weight / 160.21766208``, eV/A^3).
+``F``) driven by the same FIRE in the same ``alignn_fire_step`` (the filter's state in its argument block selects it).  The
+model's per-crystal stresses enter as the calculator gives them (``stress * stress_weight / 160.21766208``, eV/A^3).
 """
 
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
@@ -100,6 +102,16 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
         lat_v = [lat[s] for s in range(B)]
         pos_v, frac_v = packed.rows(pos), packed.rows(frac)
 
+        args = _lib.FireArgs(
+            atom_ptr=atom_ptr.data_ptr(), inv_lattice=inv.data_ptr(), positions=pos.data_ptr(), velocities=vel.data_ptr(),
+            frac=frac.data_ptr(), state=state.data_ptr(), istate=istate.data_ptr(), forces_out=forces_all.data_ptr(),
+            energy_out=energy_all.data_ptr(), fmax_out=fmax_all.data_ptr(), status=status.data_ptr(), steps=int(steps),
+            nmin=int(Nmin), fmax=float(fmax), maxstep=float(maxstep), dtmax=float(dtmax), finc=float(finc), fdec=float(fdec),
+            astart=float(astart), fa=float(fa))
+        if optimize_lattice:
+            args.lattice0, args.xa, args.xc, args.cell_velocities = lat.data_ptr(), xa.data_ptr(), xc.data_ptr(), cvel.data_ptr()
+            args.defgrad, args.lattice, args.stress_out = defgrad.data_ptr(), lat_cur.data_ptr(), stress_all.data_ptr()
+
         flag = [0] * B
         active = list(range(B))
         n_evals = 0
@@ -112,6 +124,7 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
                 for s in active:
                     fp.append(fp[-1] + ns[s])
                 force_ptr = torch.tensor(fp, dtype=torch.int32, device=dev)
+                args.active, args.n_active, args.force_ptr = act_t.data_ptr(), Ba, force_ptr.data_ptr()
                 changed = False
             if optimize_lattice:
                 # fresh tensors every step: the kernel writes lat_cur through a raw pointer (no version bump), which the
@@ -122,21 +135,8 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
                 lat_act = [lat_v[s] for s in active]
             energy, forces, stress = evaluate(active, lat_act, [frac_v[s] for s in active], [pos_v[s] for s in active])
             n_evals += 1
-            if optimize_lattice:
-                _lib.check(lib.alignn_fire_cell_step(
-                    forces.data_ptr(), energy.data_ptr(), stress.data_ptr(), force_ptr.data_ptr(), act_t.data_ptr(), Ba,
-                    atom_ptr.data_ptr(), lat.data_ptr(), inv.data_ptr(), xa.data_ptr(), pos.data_ptr(), vel.data_ptr(),
-                    frac.data_ptr(), xc.data_ptr(), cvel.data_ptr(), defgrad.data_ptr(), lat_cur.data_ptr(), forces_all.data_ptr(),
-                    energy_all.data_ptr(), stress_all.data_ptr(), state.data_ptr(), istate.data_ptr(), fmax_all.data_ptr(),
-                    status.data_ptr(), float(fmax), int(steps), float(maxstep), float(dtmax), int(Nmin), float(finc), float(fdec),
-                    float(astart), float(fa), _lib.stream()), "fire_cell_step")
-            else:
-                _lib.check(lib.alignn_fire_step(forces.data_ptr(), energy.data_ptr(), force_ptr.data_ptr(), act_t.data_ptr(), Ba,
-                                                atom_ptr.data_ptr(), inv.data_ptr(), pos.data_ptr(), vel.data_ptr(), frac.data_ptr(),
-                                                forces_all.data_ptr(), energy_all.data_ptr(), state.data_ptr(), istate.data_ptr(),
-                                                fmax_all.data_ptr(), status.data_ptr(), float(fmax), int(steps), float(maxstep),
-                                                float(dtmax), int(Nmin), float(finc), float(fdec), float(astart), float(fa),
-                                                _lib.stream()), "fire_step")
+            args.forces, args.energy, args.stress = forces.data_ptr(), energy.data_ptr(), _lib.ptr(stress)
+            _lib.check(lib.alignn_fire_step(C.byref(args), _lib.stream()), "fire_step")
             st = status[:1 + Ba].tolist()  # the one host read of a step
             if st[0] == Ba:
                 continue

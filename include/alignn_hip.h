@@ -909,86 +909,113 @@ int alignn_radius_emit(const float* lat, const float* cart, const int32_t* graph
                        alignn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Batched structure relaxation (csrc/relax.hip; alignn_amd/relax.py is the host loop): one FIRE step at fixed cell, ASE's
- * ase/optimize/fire.py as alignn/ff/ff.py:373-415 runs it (optimize_lattice=False, downhill_check=False), preceded by the
- * convergence test of Optimizer.run (max_i |F_i|^2 < fmax^2) on the forces of the current positions.  float64.  One
- * workgroup per ACTIVE structure k < n_active; structure s = active[k] owns atoms [atom_ptr[s], atom_ptr[s+1]) of the
- * full-batch arrays positions / velocities / frac / forces_out [N][3], and forces [.][3] rows [force_ptr[k], force_ptr[k+1])
- * of the evaluation of the active batch (energy[k] its energy).  Per structure: state[s] = {dt, a}, istate[s] = {Nsteps,
- * steps taken}.  A structure is recorded (forces_out, energy_out[s], fmax_out[s] = max_i |F_i|), then either retired
- * (status[1+k] = 1: converged, 2: `steps` steps taken; -1: force rows of another count than its atoms, nothing written) or
- * stepped (status[1+k] = 0): positions += dr (|dr| over the structure clipped to maxstep), frac = positions inv_lattice[s]
- * wrapped into [0, 1).  status[0] = number of structures stepped.  Fixed-order reductions: a structure's step is
- * bit-identical whatever else shares the launch.
+ * Batched structure relaxation (csrc/relax.hip; alignn_amd/relax.py is the host loop): one FIRE step, ASE's
+ * ase/optimize/fire.py as alignn/ff/ff.py:373-415 runs it (downhill_check=False), preceded by the convergence test of
+ * Optimizer.run (max_i |F_i|^2 < fmax^2) on the forces of the current positions.  float64.  One workgroup per ACTIVE structure
+ * k < n_active; structure s = active[k] owns atoms [atom_ptr[s], atom_ptr[s+1]) of the full-batch [N][3] arrays and row s of
+ * the [B] / [B][3][3] (row-major) ones; the evaluation is that of the active batch.  A structure is recorded (forces_out,
+ * energy_out, fmax_out, stress_out), then either retired (status[1+k] = 1: converged, 2: `steps` steps taken; -1: force rows
+ * of another count than its atoms, nothing written) or stepped (status[1+k] = 0): |dr| over the structure clipped to maxstep.
+ * Fixed-order reductions: a structure's step is bit-identical whatever else shares the launch.
+ *
+ * At fixed cell (xc == NULL; optimize_lattice=False) the rows are the atoms'.  With a cell-filter state (xc != NULL: every
+ * field marked "filter" is then required, and ignored otherwise) the step is that of ASE's ExpCellFilter (ase/constraints.py,
+ * default arguments; optimize_lattice=True) over n + 3 generalised rows per structure of n atoms: atom rows X_a = positions
+ * F^-T with forces f F, cell rows X_c = n logm(F) of the deformation gradient F with the forces: the virial W = -|det C|
+ * sym(stress), or the exact gradient -expm([[L, -W expm(-L)], [0, L]])[0:3, 3:6] (symmetrised, L = X_c / n) where the two
+ * point apart (cosine <= 0.8 and not numpy-isclose), divided by n.  Convergence and fmax_out run over all n + 3 rows.
+ * Initial filter state: xa = positions, xc = cell_velocities = 0, defgrad = I, lattice = lattice0.
  * ------------------------------------------------------------------------------------------ */
-int alignn_fire_step(const double* forces, const double* energy, const int32_t* force_ptr, const int32_t* active, int n_active,
-                     const int32_t* atom_ptr, const double* inv_lattice, double* positions, double* velocities, double* frac,
-                     double* forces_out, double* energy_out, double* state, int32_t* istate, double* fmax_out, int32_t* status,
-                     double fmax, int steps, double maxstep, double dtmax, int nmin, double finc, double fdec, double astart,
-                     double fa, alignn_stream_t stream);
-
-/* One FIRE step with ASE's ExpCellFilter (ase/constraints.py, default arguments: optimize_lattice=True of ff.py:373-415):
- * alignn_fire_step over n + 3 generalised rows per structure of n atoms.  Besides the per-atom arrays above, structure s
- * owns xa [N][3] (atom rows X_a = positions F^-T; positions [N][3] are written as X_a F^T), and [B][3][3] row-major:
- * xc (X_c = n logm(F)), cell_velocities, defgrad (F), lattice (C = lattice0 F^T), lattice0 (the starting cell C0),
- * inv_lattice0 (its inverse), stress_out.  stress [n_active][3][3] is the evaluation's stress (eV/A^3, ASE's sign), row k
- * for active[k]; it is symmetrised (stress_out[s]) and turned into the cell rows: the virial W = -|det C| stress, or the
- * exact gradient -expm([[L, -W expm(-L)], [0, L]])[0:3, 3:6] (symmetrised, L = X_c / n) where the two point apart
- * (cosine <= 0.8 and not numpy-isclose), divided by n.  Atom rows: forces F.  Convergence and fmax_out over all n + 3
- * rows; frac = xa inv_lattice0 wrapped into [0, 1).  Initial state: xa = positions, xc = cell_velocities = 0, defgrad = I,
- * lattice = lattice0. */
-int alignn_fire_cell_step(const double* forces, const double* energy, const double* stress, const int32_t* force_ptr,
-                          const int32_t* active, int n_active, const int32_t* atom_ptr, const double* lattice0,
-                          const double* inv_lattice0, double* xa, double* positions, double* velocities, double* frac, double* xc,
-                          double* cell_velocities, double* defgrad, double* lattice, double* forces_out, double* energy_out,
-                          double* stress_out, double* state, int32_t* istate, double* fmax_out, int32_t* status, double fmax,
-                          int steps, double maxstep, double dtmax, int nmin, double finc, double fdec, double astart, double fa,
-                          alignn_stream_t stream);
+typedef struct alignn_fire_args {
+    /* inputs of the step: the evaluation of the active batch */
+    const double* forces;      /* [.][3]: rows [force_ptr[k], force_ptr[k+1]) are active[k]'s */
+    const double* energy;      /* [n_active] */
+    const double* stress;      /* filter: [n_active][3][3], eV/A^3, ASE's sign */
+    const int32_t* force_ptr;  /* [n_active + 1] */
+    const int32_t* active;     /* [n_active] structure indices */
+    const int32_t* atom_ptr;   /* [B + 1] */
+    const double* inv_lattice; /* [B][3][3] inverse of the cell (filter: of lattice0): frac = rows times it, wrapped into [0, 1) */
+    const double* lattice0;    /* filter: [B][3][3] the starting cells C0 */
+    /* state */
+    double* positions;       /* [N][3] Cartesian, unwrapped (filter: written as X_a F^T) */
+    double* velocities;      /* [N][3] of the atom rows */
+    double* frac;            /* [N][3] for the next neighbour search */
+    double* state;           /* [B][2] = {dt, a} */
+    int32_t* istate;         /* [B][2] = {Nsteps, steps taken} */
+    double* xa;              /* filter: [N][3] atom rows X_a */
+    double* xc;              /* filter: [B][3][3] cell rows X_c; non-NULL selects the filter */
+    double* cell_velocities; /* filter: [B][3][3] */
+    double* defgrad;         /* filter: [B][3][3] F of the evaluated cell */
+    double* lattice;         /* filter: [B][3][3] the current cells C = C0 F^T */
+    /* outputs */
+    double* forces_out;  /* [N][3] */
+    double* energy_out;  /* [B] */
+    double* fmax_out;    /* [B] max over the rows of |F_i| */
+    double* stress_out;  /* filter: [B][3][3] symmetrised */
+    int32_t* status;     /* [1 + n_active]: [0] the number of structures stepped, [1+k] as above */
+    /* scalars */
+    int n_active, steps, nmin; /* `steps`: the cap per structure; nmin: FIRE's Nmin */
+    double fmax, maxstep, dtmax, finc, fdec, astart, fa; /* the tolerance and FIRE's parameters */
+} alignn_fire_args;
+int alignn_fire_step(const alignn_fire_args* args, alignn_stream_t stream);
+size_t alignn_fire_args_sizeof(void); /* a binding checks its own packing against this */
 
 /* ------------------------------------------------------------------------------------------
- * Batched molecular dynamics at fixed cell (csrc/dynamics.hip; alignn_amd/dynamics.py is the host loop): ASE 3.22.1's
- * VelocityVerlet (ensemble 0), Langevin (1) and NVTBerendsen (2) as alignn/ff/ff.py:419-550 runs them, float64, ASE units
- * (eV, A, amu, A sqrt(amu / eV)).  One workgroup per structure s < n_structures; it owns atoms [atom_ptr[s], atom_ptr[s+1]) of
- * masses [N], momenta / positions (Cartesian, unwrapped) / frac / velocities / rnd_vel [N][3], and forces [n_rows][3] rows of
- * the same range (the evaluation at the current positions, energy[s] its energy).  n_rows must equal atom_ptr[n_structures],
- * else status[0] = -1 and nothing is written.  One launch per evaluation t = 0 .. steps: finish step t (t > 0: the second
- * half-kick with these forces), record frame t / interval when t % interval == 0 (epot / ekin / temperature [frames][B], KE =
- * 0.5 sum p^2 / m, T = 2 KE / (3 n kB); traj_positions / traj_momenta [frames][N][3] unless NULL), then, unless t == steps,
- * begin step t + 1 (Berendsen velocity scaling toward t0_kelvin[s] with time constant taut; the first half-kick; fixcm's
- * momentum / noise corrections; the drift; frac = positions inv_lattice[s] wrapped into [0, 1)).  Langevin draws 6 normals
- * per atom from Philox4x32-10 (key = seeds[s], counter (atom, t, block 0..2, 0)) and keeps velocities and rnd_vel between the
- * two halves; noise_out [N][18] (tests; NULL otherwise) receives per atom xi[3], eta[3] and the 12 Philox words as doubles.
- * Fixed-order reductions: a structure's trajectory is bit-identical whatever else shares the launch.
+ * Batched molecular dynamics (csrc/dynamics.hip; alignn_amd/dynamics.py is the host loop): ASE 3.22.1's VelocityVerlet
+ * (ensemble 0), Langevin (1), NVTBerendsen (2), Andersen (3) and NPTBerendsen (4; isotropic) as alignn/ff/ff.py:419-600 runs
+ * them, float64, ASE units (eV, A, amu, A sqrt(amu / eV)).  One workgroup per structure s < n_structures; it owns atoms
+ * [atom_ptr[s], atom_ptr[s+1]) of the [N] / [N][3] arrays and row s of the [B] / [B][3][3] (row-major) ones.  One launch per
+ * evaluation t = 0 .. steps: finish step t (t > 0: the second half-kick with these forces), record frame t / interval when
+ * t % interval == 0, then, unless t == steps, begin step t + 1 (Berendsen's velocity scaling; the first half-kick; fixcm's
+ * corrections; the drift; frac).  NPT begins a step with the Berendsen velocity scaling, then mu = 1 - dt / taup *
+ * compressibility / 3 * (pressure - P) with P from the scaled momenta, lattice and positions times mu, inv_lattice
+ * recomputed, then the half-kick, fixcm and the drift.  Andersen begins a step with v = p / m, fixcm: + a random
+ * centre-of-mass velocity of width sqrt(kB T0 / sum m); the half-kick; every velocity component whose uniform draw is <=
+ * andersen_prob replaced by a normal of width sqrt(kB T0 / m); fixcm: the mass-weighted mean velocity removed and the centre
+ * of mass kept through the drift; v recomputed from the positions.  Random numbers: Philox4x32-10, key seeds[s], counter (atom,
+ * t, block, purpose): Langevin blocks 0..2 of purpose 0 (6 normals); Andersen blocks 0..3 of purpose 2 (0, 1: normals; 2, 3:
+ * uniforms in (0, 1]) and, for the centre of mass, blocks 0..1 of (0, t, ., 3).  Fixed-order reductions: a structure's
+ * trajectory is bit-identical whatever else shares the launch.  "Required" below: NULL is hipErrorInvalidValue.
  * ------------------------------------------------------------------------------------------ */
-int alignn_md_step(const double* forces, const double* energy, int64_t n_rows, const int32_t* atom_ptr, int n_structures,
-                   const double* masses, const double* inv_lattice, double* momenta, double* positions, double* frac,
-                   double* velocities, double* rnd_vel, const double* t0_kelvin, const uint64_t* seeds, double* epot, double* ekin,
-                   double* temperature, double* traj_positions, double* traj_momenta, double* noise_out, int32_t* status, int t,
-                   int interval, int steps, int ensemble, double dt, double friction, double taut, int fixcm, double kB,
-                   alignn_stream_t stream);
-
-/* Andersen NVT (ensemble 3) and Berendsen NPT (ensemble 4; isotropic) of the same loop, same conventions and arguments as
- * alignn_md_step, plus [B][3][3] row-major lattice / inv_lattice (read; NPT rewrites both) and stress (NPT: the evaluation's
- * stress, eV/A^3, ASE's sign; may be NULL for Andersen), pressure / compressibility [B] (NPT: the target in eV/A^3 and the
- * compressibility in A^3/eV).  Frames also record pressure_out (-tr(stress) / 3 + 2 KE / (3 V); needs stress) and volume_out
- * (V = |det lattice|) [frames][B] and traj_lattice [frames][B][3][3], each unless NULL.  NPT begins a step with the Berendsen
- * velocity scaling, then mu = 1 - dt / taup * compressibility / 3 * (pressure - P) with P from the scaled momenta, lattice and
- * positions times mu, inv_lattice recomputed, then the half-kick, fixcm and the drift; frac wraps with the new inverse.
- * Andersen begins a step with v = p / m, fixcm: + a random centre-of-mass velocity (Philox counter (0, t, block 0..1, 3),
- * width sqrt(kB T0 / sum m)); the half-kick; every velocity component whose uniform draw is <= andersen_prob replaced by a
- * normal of width sqrt(kB T0 / m) (counter (atom, t, block 0..3, 2): blocks 0, 1 the normals, 2, 3 the uniforms in (0, 1]);
- * fixcm: the mass-weighted mean velocity removed and the centre of mass kept through the drift; v recomputed from the
- * positions.  It keeps v in velocities and the positions before the drift in rnd_vel between the halves.  noise_out [N][36]
- * (tests; NULL otherwise): per atom 4 normals, 4 uniforms, the 16 words, then the structure's 4 centre-of-mass normals and
- * their 8 words (fixcm only). */
-int alignn_md_step_cell(const double* forces, const double* energy, const double* stress, int64_t n_rows,
-                        const int32_t* atom_ptr, int n_structures, const double* masses, double* lattice, double* inv_lattice,
-                        double* momenta, double* positions, double* frac, double* velocities, double* rnd_vel,
-                        const double* t0_kelvin, const uint64_t* seeds, const double* pressure, const double* compressibility,
-                        double* epot, double* ekin, double* temperature, double* pressure_out, double* volume_out,
-                        double* traj_positions, double* traj_momenta, double* traj_lattice, double* noise_out, int32_t* status,
-                        int t, int interval, int steps, int ensemble, double dt, double andersen_prob, double taut, double taup,
-                        int fixcm, double kB, alignn_stream_t stream);
+typedef struct alignn_md_args {
+    /* inputs of the step: the evaluation at the current positions */
+    const double* forces;  /* [n_rows][3] */
+    const double* energy;  /* [B] */
+    const double* stress;  /* [B][3][3], eV/A^3, ASE's sign: required by 4; 3: NULL records no pressure; 0-2: ignored */
+    int64_t n_rows;        /* must equal atom_ptr[n_structures], else status[0] = -1 and nothing is written */
+    const int32_t* atom_ptr;       /* [B + 1] */
+    const double* masses;          /* [N] */
+    const double* t0_kelvin;       /* [B] thermostat targets: required by 1-4 */
+    const uint64_t* seeds;         /* [B]: required by 1 and 3 */
+    const double* pressure;        /* [B] barostat targets, eV/A^3: required by 4 */
+    const double* compressibility; /* [B] A^3/eV: required by 4 */
+    /* state */
+    double* lattice;     /* [B][3][3]: required by 3 (read) and 4 (rewritten); 0-2: ignored */
+    double* inv_lattice; /* [B][3][3]: frac = positions times it, wrapped into [0, 1); 4 rewrites it */
+    double* momenta;     /* [N][3] */
+    double* positions;   /* [N][3] Cartesian, unwrapped */
+    double* frac;        /* [N][3] for the next neighbour search */
+    double* velocities;  /* [N][3] v between the halves: required by 1 and 3 */
+    double* scratch;     /* [N][3] between the halves, 1: the velocity noise of the step, 3: the positions before the drift; required by both */
+    int32_t* status;     /* [1]; required */
+    /* outputs: frames [steps / interval + 1]; epot, ekin, temperature required, the others written unless NULL */
+    double* epot;           /* [frames][B] = energy */
+    double* ekin;           /* [frames][B] KE = 0.5 sum p^2 / m */
+    double* temperature;    /* [frames][B] 2 KE / (3 n kB) */
+    double* pressure_out;   /* 3, 4: [frames][B] -tr(stress) / 3 + 2 KE / (3 V); needs stress */
+    double* volume_out;     /* 3, 4: [frames][B] V = |det lattice| */
+    double* traj_positions; /* [frames][N][3] */
+    double* traj_momenta;   /* [frames][N][3] */
+    double* traj_lattice;   /* 3, 4: [frames][B][3][3] */
+    double* noise_out;      /* tests: 1: [N][18] per atom xi[3], eta[3], the 12 Philox words as doubles; 3: [N][36] per atom 4
+                               normals, 4 uniforms, 16 words, then the structure's 4 centre-of-mass normals and their 8 words
+                               (fixcm only) */
+    /* scalars */
+    int n_structures, t, interval, steps, ensemble, fixcm;
+    double dt, friction, andersen_prob, taut, taup, kB; /* friction: 1; andersen_prob: 3; taut: 2, 4; taup: 4 */
+} alignn_md_args;
+int alignn_md_step(const alignn_md_args* args, alignn_stream_t stream);
+size_t alignn_md_args_sizeof(void); /* a binding checks its own packing against this */
 
 /* Maxwell-Boltzmann momenta (ASE's MaxwellBoltzmannDistribution, no Stationary): momenta[i] = xi sqrt(m_i kB t_kelvin[s]) with
  * xi three normals of the stream above (counter (atom, 0, block 0..1, 1)). */

@@ -4,6 +4,8 @@ stream; (2) NVE on periodic spring crystals: second-order energy error, time rev
 thermostats and the Maxwell-Boltzmann start; (4) a structure alone vs. in a batch, bit for bit; (5) run_md with an
 ALIGNNAtomWise against a host loop over the same model; (6) replay and run-to-run bit identity."""
 
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -61,17 +63,20 @@ def test_kernel_matches_the_restatement_step_by_step(ensemble):
         refs = [BerendsenRef(r0[s], p0[s], ms[s], dt, t0[s], taut, fixcm) for s in range(B)]
     else:
         refs = [LangevinRef(r0[s], p0[s], ms[s], dt, t0[s], fr, fixcm, seeds[s]) for s in range(B)]
+    args = _lib.MdArgs(
+        atom_ptr=S["ptr"].data_ptr(), masses=S["m"].data_ptr(), t0_kelvin=S["t0"].data_ptr(), seeds=S["seed"].data_ptr(),
+        inv_lattice=S["inv"].data_ptr(), momenta=S["p"].data_ptr(), positions=S["r"].data_ptr(), frac=S["frac"].data_ptr(),
+        velocities=S["v"].data_ptr(), scratch=S["rv"].data_ptr(), status=S["status"].data_ptr(), epot=S["epot"].data_ptr(),
+        ekin=S["ekin"].data_ptr(), temperature=S["temp"].data_ptr(), traj_positions=S["tp"].data_ptr(),
+        traj_momenta=S["tm"].data_ptr(), noise_out=noise.data_ptr(), n_structures=B, interval=interval, steps=steps,
+        ensemble=ens, fixcm=int(fixcm), dt=dt, friction=fr, taut=taut, kB=KB)
     scales = set()
     for t in range(steps + 1):
         fs = [rng.normal(0.0, 1.0, (n, 3)) for n in ns]
         es = rng.normal(size=B)
         f_d, e_d = _t(np.concatenate(fs)), _t(es)
-        _lib.check(lib.alignn_md_step(
-            f_d.data_ptr(), e_d.data_ptr(), N, S["ptr"].data_ptr(), B, S["m"].data_ptr(),
-            S["inv"].data_ptr(), S["p"].data_ptr(), S["r"].data_ptr(), S["frac"].data_ptr(), S["v"].data_ptr(),
-            S["rv"].data_ptr(), S["t0"].data_ptr(), S["seed"].data_ptr(), S["epot"].data_ptr(), S["ekin"].data_ptr(),
-            S["temp"].data_ptr(), S["tp"].data_ptr(), S["tm"].data_ptr(), noise.data_ptr(), S["status"].data_ptr(), t, interval,
-            steps, ens, dt, fr, taut, int(fixcm), KB, _lib.stream()), "md_step")
+        args.forces, args.energy, args.n_rows, args.t = f_d.data_ptr(), e_d.data_ptr(), N, t
+        _lib.check(lib.alignn_md_step(ctypes.byref(args), _lib.stream()), "md_step")
         nz = noise.cpu().numpy()
         for s, o in enumerate(refs):
             a, b = ptr[s], ptr[s + 1]
@@ -113,12 +118,10 @@ def test_kernel_matches_the_restatement_step_by_step(ensemble):
     # a force array of another row count than the batch: status -1, nothing written
     before = S["p"].clone()
     f_d, e_d = torch.zeros(N - 1, 3, dtype=torch.float64, device=DEV), _t(np.zeros(B))
-    _lib.check(lib.alignn_md_step(
-        f_d.data_ptr(), e_d.data_ptr(), N - 1, S["ptr"].data_ptr(),
-        B, S["m"].data_ptr(), S["inv"].data_ptr(), S["p"].data_ptr(), S["r"].data_ptr(), S["frac"].data_ptr(), S["v"].data_ptr(),
-        S["rv"].data_ptr(), S["t0"].data_ptr(), S["seed"].data_ptr(), S["epot"].data_ptr(), S["ekin"].data_ptr(),
-        S["temp"].data_ptr(), None, None, None, S["status"].data_ptr(), 1, 1, 3, ens, dt, fr, taut, 1, KB, _lib.stream()),
-        "md_step")
+    args.forces, args.energy, args.n_rows = f_d.data_ptr(), e_d.data_ptr(), N - 1
+    args.traj_positions = args.traj_momenta = args.noise_out = None
+    args.t, args.interval, args.steps, args.fixcm = 1, 1, 3, 1
+    _lib.check(lib.alignn_md_step(ctypes.byref(args), _lib.stream()), "md_step")
     assert S["status"].item() == -1 and torch.equal(S["p"], before)
 
 

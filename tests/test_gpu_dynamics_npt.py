@@ -1,9 +1,11 @@
-"""Andersen NVT and Berendsen NPT on the device (csrc/dynamics.hip ``alignn_md_step_cell``, alignn_amd/dynamics.py) against the
+"""Andersen NVT and Berendsen NPT on the device (csrc/dynamics.hip ``alignn_md_step``, ensembles 3 and 4, alignn_amd/dynamics.py) against the
 float64 restatement in test_md_npt_ref.py: (1) the kernel alone, step by step, both ensembles, the exported random numbers
 against the numpy stream; (2) NPT at zero compressibility is NVT Berendsen; (3) the barostat reaches a ladder of pressures on
 spring crystals, as the restatement does; (4) Andersen reaches its temperature ladder; (5) a structure alone vs. in a batch,
 bit for bit; (6) run_md with an ALIGNNAtomWise against a host loop over the same model; (7) replay and run-to-run bit
 identity."""
+
+import ctypes
 
 import numpy as np
 import pytest
@@ -35,15 +37,17 @@ def _relmax(got, want):
 
 
 def _step_cell(lib, S, f_d, e_d, st_d, n_rows, noise, traj, t, interval, steps, ens, dt, prob, taut, taup, fixcm):
-    B = S["t0"].numel()
-    _lib.check(lib.alignn_md_step_cell(
-        f_d.data_ptr(), e_d.data_ptr(), _lib.ptr(st_d), n_rows, S["ptr"].data_ptr(), B, S["m"].data_ptr(), S["lat"].data_ptr(),
-        S["inv"].data_ptr(), S["p"].data_ptr(), S["r"].data_ptr(), S["frac"].data_ptr(), S["v"].data_ptr(), S["x"].data_ptr(),
-        S["t0"].data_ptr(), S["seed"].data_ptr(), S["ptarget"].data_ptr(), S["comp"].data_ptr(), S["epot"].data_ptr(),
-        S["ekin"].data_ptr(), S["temp"].data_ptr(), S["pout"].data_ptr(), S["vout"].data_ptr(),
-        S["tp"].data_ptr() if traj else None, S["tm"].data_ptr() if traj else None, S["tl"].data_ptr() if traj else None,
-        _lib.ptr(noise), S["status"].data_ptr(), t, interval, steps, ens, dt, prob, taut, taup, int(fixcm), KB, _lib.stream()),
-        "md_step_cell")
+    args = _lib.MdArgs(
+        forces=f_d.data_ptr(), energy=e_d.data_ptr(), stress=_lib.ptr(st_d), n_rows=n_rows, atom_ptr=S["ptr"].data_ptr(),
+        masses=S["m"].data_ptr(), t0_kelvin=S["t0"].data_ptr(), seeds=S["seed"].data_ptr(), pressure=S["ptarget"].data_ptr(),
+        compressibility=S["comp"].data_ptr(), lattice=S["lat"].data_ptr(), inv_lattice=S["inv"].data_ptr(),
+        momenta=S["p"].data_ptr(), positions=S["r"].data_ptr(), frac=S["frac"].data_ptr(), velocities=S["v"].data_ptr(),
+        scratch=S["x"].data_ptr(), status=S["status"].data_ptr(), epot=S["epot"].data_ptr(), ekin=S["ekin"].data_ptr(),
+        temperature=S["temp"].data_ptr(), pressure_out=S["pout"].data_ptr(), volume_out=S["vout"].data_ptr(),
+        traj_positions=S["tp"].data_ptr() if traj else None, traj_momenta=S["tm"].data_ptr() if traj else None,
+        traj_lattice=S["tl"].data_ptr() if traj else None, noise_out=_lib.ptr(noise), n_structures=S["t0"].numel(), t=t,
+        interval=interval, steps=steps, ensemble=ens, fixcm=int(fixcm), dt=dt, andersen_prob=prob, taut=taut, taup=taup, kB=KB)
+    _lib.check(lib.alignn_md_step(ctypes.byref(args), _lib.stream()), "md_step")
 
 
 # --- (1) the kernel against the restatement, step by step -----------------------------------------------------------------

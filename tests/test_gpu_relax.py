@@ -3,6 +3,8 @@ Optimizer.run in test_relax_fire.py: (a) the kernel alone, step by step; (b) the
 counts, and bit-identical trajectories alone vs. in a batch whose other members retire earlier); (c) the relaxer with an
 ALIGNNAtomWise against a host loop over the same model; (d) run-to-run bit identity."""
 
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -17,12 +19,14 @@ DEV = "cuda"
 
 
 def _fire_step(lib, forces, energy, force_ptr, active, atom_ptr, inv, S, fmax, steps, p=DEFAULTS):
-    _lib.check(lib.alignn_fire_step(forces.data_ptr(), energy.data_ptr(), force_ptr.data_ptr(), active.data_ptr(), active.numel(),
-                                    atom_ptr.data_ptr(), inv.data_ptr(), S["pos"].data_ptr(), S["vel"].data_ptr(),
-                                    S["frac"].data_ptr(), S["F"].data_ptr(), S["E"].data_ptr(), S["state"].data_ptr(),
-                                    S["istate"].data_ptr(), S["fmax"].data_ptr(), S["status"].data_ptr(), fmax, steps,
-                                    p["maxstep"], p["dtmax"], p["Nmin"], p["finc"], p["fdec"], p["astart"], p["fa"],
-                                    _lib.stream()), "fire_step")
+    args = _lib.FireArgs(
+        forces=forces.data_ptr(), energy=energy.data_ptr(), force_ptr=force_ptr.data_ptr(), active=active.data_ptr(),
+        atom_ptr=atom_ptr.data_ptr(), inv_lattice=inv.data_ptr(), positions=S["pos"].data_ptr(), velocities=S["vel"].data_ptr(),
+        frac=S["frac"].data_ptr(), state=S["state"].data_ptr(), istate=S["istate"].data_ptr(), forces_out=S["F"].data_ptr(),
+        energy_out=S["E"].data_ptr(), fmax_out=S["fmax"].data_ptr(), status=S["status"].data_ptr(), n_active=active.numel(),
+        steps=steps, nmin=p["Nmin"], fmax=fmax, maxstep=p["maxstep"], dtmax=p["dtmax"], finc=p["finc"], fdec=p["fdec"],
+        astart=p["astart"], fa=p["fa"])
+    _lib.check(lib.alignn_fire_step(ctypes.byref(args), _lib.stream()), "fire_step")
 
 
 def test_kernel_matches_the_restatement_step_by_step():

@@ -1,8 +1,10 @@
-"""Batched FIRE with ASE's ExpCellFilter on the device (csrc/relax.hip ``alignn_fire_cell_step``, ``relax(optimize_lattice=True)``)
-against the float64 restatement in test_relax_cell.py: (a) the kernel alone, step by step, with injected forces and stresses,
+"""Batched FIRE with ASE's ExpCellFilter on the device (csrc/relax.hip ``alignn_fire_step`` with the filter's state,
+``relax(optimize_lattice=True)``) against the float64 restatement in test_relax_cell.py: (a) the kernel alone, step by step, with injected forces and stresses,
 naive and exact cell-force branches; (b) the relaxer on harmonic spring crystals (agreement with the restatement, cells at the
 analytic minimum, bit-identical trajectories alone vs. in a shrinking batch); (c) the relaxer with an ALIGNNAtomWise against a
 host loop over the same model; (d) run-to-run bit identity; (e) invalid input."""
+
+import ctypes
 
 import numpy as np
 import pytest
@@ -25,13 +27,16 @@ def _t(x, dtype=torch.float64):
 
 
 def _cell_step(lib, forces, energy, stress, force_ptr, active, atom_ptr, S, fmax, steps, p=DEFAULTS):
-    _lib.check(lib.alignn_fire_cell_step(
-        forces.data_ptr(), energy.data_ptr(), stress.data_ptr(), force_ptr.data_ptr(), active.data_ptr(), active.numel(),
-        atom_ptr.data_ptr(), S["lat0"].data_ptr(), S["inv0"].data_ptr(), S["xa"].data_ptr(), S["pos"].data_ptr(),
-        S["vel"].data_ptr(), S["frac"].data_ptr(), S["xc"].data_ptr(), S["cvel"].data_ptr(), S["defgrad"].data_ptr(),
-        S["lat"].data_ptr(), S["F"].data_ptr(), S["E"].data_ptr(), S["stress"].data_ptr(), S["state"].data_ptr(),
-        S["istate"].data_ptr(), S["fmax"].data_ptr(), S["status"].data_ptr(), fmax, steps, p["maxstep"], p["dtmax"], p["Nmin"],
-        p["finc"], p["fdec"], p["astart"], p["fa"], _lib.stream()), "fire_cell_step")
+    args = _lib.FireArgs(
+        forces=forces.data_ptr(), energy=energy.data_ptr(), stress=stress.data_ptr(), force_ptr=force_ptr.data_ptr(),
+        active=active.data_ptr(), atom_ptr=atom_ptr.data_ptr(), inv_lattice=S["inv0"].data_ptr(), lattice0=S["lat0"].data_ptr(),
+        positions=S["pos"].data_ptr(), velocities=S["vel"].data_ptr(), frac=S["frac"].data_ptr(), state=S["state"].data_ptr(),
+        istate=S["istate"].data_ptr(), xa=S["xa"].data_ptr(), xc=S["xc"].data_ptr(), cell_velocities=S["cvel"].data_ptr(),
+        defgrad=S["defgrad"].data_ptr(), lattice=S["lat"].data_ptr(), forces_out=S["F"].data_ptr(), energy_out=S["E"].data_ptr(),
+        fmax_out=S["fmax"].data_ptr(), stress_out=S["stress"].data_ptr(), status=S["status"].data_ptr(),
+        n_active=active.numel(), steps=steps, nmin=p["Nmin"], fmax=fmax, maxstep=p["maxstep"], dtmax=p["dtmax"], finc=p["finc"],
+        fdec=p["fdec"], astart=p["astart"], fa=p["fa"])
+    _lib.check(lib.alignn_fire_step(ctypes.byref(args), _lib.stream()), "fire_step")
 
 
 def _close(got, want, rel=1e-12):

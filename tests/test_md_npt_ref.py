@@ -1,6 +1,6 @@
 """The executable specification of the ``nvt_andersen`` and ``npt_berendsen`` ensembles of ``alignn_amd.run_md``
-(csrc/dynamics.hip, ``alignn_md_step_cell``): a float64 numpy restatement of ASE 3.22.1's ``Andersen`` and ``NPTBerendsen``
-as the reference's ``ForceField.run_nvt_andersen`` / ``run_npt_berendsen`` drive them (alignn/ff/ff.py:477-600), on top of
+(csrc/dynamics.hip, ``alignn_md_step`` with ensembles 3 and 4): a float64 numpy restatement of ASE 3.22.1's ``Andersen`` and
+``NPTBerendsen`` as the reference's ``ForceField.run_nvt_andersen`` / ``run_npt_berendsen`` drive them (alignn/ff/ff.py:477-600), on top of
 the base classes and the random stream of test_md_ref.py.  ASE is not a dependency of this project; the restatement follows
 the published ase/md/andersen.py and ase/md/nptberendsen.py, and the checks below pin it to steps computed by hand.  Where a
 detail of ASE was in doubt when this was written, the project's own statement rules:
@@ -25,6 +25,7 @@ normals g0..g3 (replacement velocity ``(g0, g1, g2) sqrt(kB T0 / m)``), blocks j
 (0, t, j, 3), j = 0, 1, the three centre-of-mass normals of the structure.  ``unit_interval`` lies in (0, 1]: probability 0
 never replaces, 1 always.  The GPU tests (test_gpu_dynamics_npt.py) hold the kernel and ``run_md`` to this file."""
 
+import ctypes
 import os
 
 import numpy as np
@@ -343,9 +344,16 @@ def test_run_md_validates_the_new_arguments_before_touching_a_device():
     res = MDResult(1, 2, 3, 4, 5, 6, 7, 8, 9)  # (the nine fields of the fixed-cell ensembles, positionally)
     assert res.n_evals == 9 and res.lattices is None and res.pressure is None and res.volume is None
     assert res.traj_lattices is None
-    assert "alignn_md_step_cell" in _lib.SIGNATURES
+    assert "alignn_md_step" in _lib.SIGNATURES and "alignn_md_args_sizeof" in _lib.SIGNATURES
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    assert "alignn_md_step_cell(" in open(os.path.join(root, "include", "alignn_hip.h")).read()
+    header = open(os.path.join(root, "include", "alignn_hip.h")).read()
+    assert "alignn_md_step(" in header and "alignn_md_args_sizeof(" in header
+    from alignn_amd.build import build
+
+    build()
+    lib = _lib.load()  # (host-only queries: the binding's two argument blocks are the library's)
+    assert lib.alignn_md_args_sizeof() == ctypes.sizeof(_lib.MdArgs)
+    assert lib.alignn_fire_args_sizeof() == ctypes.sizeof(_lib.FireArgs)
     lat, pos, m = [np.eye(3) * 5, np.eye(3) * 6], [np.zeros((2, 3)), np.ones((3, 3))], [np.ones(2), np.ones(3)]
     ff = lambda lat, pos: None  # noqa: E731
     npt = dict(ensemble="npt_berendsen", pressure=1.0, compressibility=1e-6)

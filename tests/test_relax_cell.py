@@ -1,4 +1,4 @@
-"""The executable specification of ``alignn_amd.relax(..., optimize_lattice=True)`` (csrc/relax.hip, ``alignn_fire_cell_step``):
+"""The executable specification of ``alignn_amd.relax(..., optimize_lattice=True)`` (csrc/relax.hip, ``alignn_fire_step`` with the filter's state):
 a float64 numpy / scipy restatement of ASE's ``ExpCellFilter`` (ase/constraints.py, 3.22.1, default arguments) as the
 reference's ``ForceField.optimize_atoms`` applies it (alignn/ff/ff.py:373-415, ``optimize_lattice=True``), and the run loop of
 ``Optimizer.run`` over its n + 3 generalised rows with ``FireRef`` / ``converged`` of test_relax_fire.py.  ASE is not a

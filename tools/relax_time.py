@@ -1,7 +1,8 @@
 """Batched FIRE relaxation (alignn_amd.relax) timed per step: B in {1, 16, 64} crystals of 60 atoms (synthetic.make_crystal),
 the tools/md_step.py model, fmax = 0 so every structure takes exactly --steps steps.  Beside each batch, the same structures
 relaxed one at a time through the same function - what the reference's per-structure optimize_atoms loop amounts to.
---cell relaxes the cells too (optimize_lattice=True: ExpCellFilter, alignn_fire_cell_step).  Prints one JSON line per B."""
+--cell relaxes the cells too (optimize_lattice=True: ExpCellFilter, alignn_fire_step with the filter's state).  Prints one JSON
+line per B."""
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
