@@ -275,7 +275,7 @@ __global__ __launch_bounds__(kT) void egc_bwd_lg_dense_ln_kernel(
                 float* out = GP + (int64_t)i * ldp + H + f;
                 if (qb > 0) a = f4_add(f4_ld(out), a);  // written by this very thread in the previous pass
                 f4_st(out, a);
-                gp_am = fmaxf(gp_am, f4_absmax(a));
+                if (qb + kW * KS >= n_src) gp_am = fmaxf(gp_am, f4_absmax(a));  // (the sum is complete in the last pass only)
             }
         }
         if (active) {
@@ -560,8 +560,10 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_ln_kernel(
                 }
                 f4_st(out, sa);
                 f4_st(outt, sat);
-                pam = fmaxf(pam, f4_absmax(sa));
-                pamt = fmaxf(pamt, f4_absmax(sat));
+                if (qb + kW * KS >= n_src) {  // (the sums are complete in the last pass only)
+                    pam = fmaxf(pam, f4_absmax(sa));
+                    pamt = fmaxf(pamt, f4_absmax(sat));
+                }
             }
         }
         if (active) {

@@ -1,0 +1,431 @@
+"""csrc/convln.hip - the line-graph and bond-graph convolutions of ALIGNNAtomWise with the edge LayerNorm formed inside the
+gate passes - against float64 torch restatements of alignn/models/alignn_atomwise.py:151-208, entry point by entry point and
+output by output.  tests/test_gpu_dual.py compares these kernels with the separate HIP kernels they replace (which pins the
+summation order, but lets a formula shared by both pass); here the other side is ``index_add`` / ``layer_norm`` / ``silu`` /
+``sigmoid`` in float64, explicit value + tangent expressions for the dual passes (validated by central differences), and
+float64 autograd of those expressions for the reverse passes.
+
+Tolerances.  On N(0,1) operands: the bounds tests/test_gpu_dual.py asserts for the separate kernels against float64 - 2e-6
+for what a LayerNorm forward writes, 2e-5 for what a gate forward writes and for the LayerNorm parameter gradients, 5e-5 (with
+its floor of 1e-2 of the largest node gradient) for what a gate reverse writes.  On every other data distribution the SAME
+restatement is evaluated in float32 on the identical float32 operands; the kernel may be 4x as far from float64 as that
+(the margin tests/test_gpu_kernels.py::test_gemm_x6_accuracy gives a reordered fp32 sum), plus the N(0,1) bound as a floor.
+Errors are max |a - b| / max |b| over the whole tensor (tests/helpers.rel_err); no element, row or case is left out.
+
+An ``amax`` output (zeroed before the launch) must EQUAL the largest magnitude among the elements the launch wrote: the next
+f16x3 product takes its power-of-two scale from it, and a value too small overflows the fp16 slices silently."""
+
+import functools
+import os
+import zlib
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+from alignn_amd import GraphBatch, _lib  # noqa: E402
+from alignn_amd._lib import ptr, stream  # noqa: E402
+from alignn_amd.graph import build_csr  # noqa: E402
+from alignn_amd.synthetic import make_batch  # noqa: E402
+
+DEV = "cuda"
+EPS, EPS_GATE = 1e-5, 1e-6  # nn.LayerNorm's default; ALIGNN_EPS_GATE (csrc/common.h)
+INVALID = 1  # hipErrorInvalidValue
+HS = (4, 36, 64, 100, 128, 252, 256)
+DATA = ("normal", "mean_over_spread", "constant_rows", "rows_1e-4_1e4", "gamma_zero_negative")
+# bounds on N(0,1) operands (see the module docstring) and floors of everything else
+B_LN_FWD, B_GATE_FWD, B_LN_PARAM, B_REVERSE = 2e-6, 2e-5, 2e-5, 5e-5
+SEG_LENGTHS = (0, 1, 2, 3, 4, 5, 0, 7, 8, 9, 0, 0, 331, 1, 11, 12, 13, 15, 16, 17, 0, 64, 3)  # around multiples of the row unroll 4
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# graphs
+# ----------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _graph(name):
+    if name == "synthetic":  # empty segments next to a long one, a one-row segment, lengths on and around multiples of 4
+        n = len(SEG_LENGTHS)
+        g = torch.Generator().manual_seed(3)
+        v = torch.repeat_interleave(torch.arange(n), torch.tensor(SEG_LENGTHS))
+        u = torch.randint(0, n, (int(v.numel()),), generator=g)
+        return build_csr(u.to(DEV), v.to(DEV), n)
+    raw = {"lg_small": lambda: make_batch(3, 14, seed0=31), "bond": lambda: make_batch(3, 14, seed0=31),
+           "lg_deg17": lambda: make_batch(4, 3, seed0=11),  # atoms with more than 16 in-edges: several dense passes
+           "lg_4096seg": lambda: make_batch(8, 60, seed0=5),  # more than 4 x 1024 segments: a wave owns several
+           "lg_stream": lambda: make_batch(16, 60, seed0=3)}[name]()  # >= 128 MiB per [rows, 256] tensor: STREAM = true
+    batch = GraphBatch.from_raw(raw, device=DEV)
+    if name == "bond":
+        return batch.g
+    lg = batch.lg
+    assert lg.dense_max_src > 0 and lg.grp_seg_ptr is not None
+    if name == "lg_deg17":
+        assert lg.dense_max_src > 16
+    if name == "lg_4096seg":
+        assert lg.n_nodes > 4096
+    if name == "lg_stream":
+        assert lg.n_edges * 256 * 4 >= 128 << 20
+    return lg
+
+
+def _is_line_graph(g):
+    return g.grp_seg_ptr is not None and g.dense_max_src > 0
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# operands (float32, on the device: what the kernels and both restatements read)
+# ----------------------------------------------------------------------------------------------------------------------
+def _operands(H, gname, data):
+    g = _graph(gname)
+    n, m = g.n_nodes, g.n_edges
+    gen = torch.Generator(device=DEV).manual_seed(zlib.crc32(f"{H} {gname} {data}".encode()))
+    R = lambda *s: torch.randn(*s, device=DEV, generator=gen)  # noqa: E731
+    o = {k: R(n, 4 * H) for k in ("P", "Pt")}
+    o.update({k: R(m, H) for k in ("M", "Mt", "Ct", "Y", "Rt", "GY", "GYt")})
+    o.update({k: R(n, H) for k in ("Q1", "Q0", "Q1t", "Q0t")})
+    o["gamma"], o["beta"] = 1 + 0.2 * R(H), 0.2 * R(H)
+    row = torch.arange(m, device=DEV)
+    if data == "mean_over_spread":  # row means up to 1e2 spreads
+        o["M"] = o["M"] + 100.0 * (2 * torch.rand(m, 1, device=DEV, generator=gen) - 1)
+    elif data == "constant_rows":  # variance exactly 0 in every third row
+        c = R(m, 1).expand(m, H)
+        o["M"] = torch.where((row % 3 == 0)[:, None], c, o["M"]).contiguous()
+    elif data == "rows_1e-4_1e4":
+        s = torch.where(row % 3 == 0, 1e-4, 1.0) * torch.where(row % 3 == 1, 1e4, 1.0)
+        o["M"] = o["M"] * s[:, None].float()
+    elif data == "gamma_zero_negative":
+        o["gamma"] = torch.where(torch.arange(H, device=DEV) % 3 == 0, 0.0, 1.0) * R(H)
+    return g, o
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# restatements (any dtype; alignn/models/alignn_atomwise.py:151-208 with m = A[u] + Bd[v] + C already formed)
+# ----------------------------------------------------------------------------------------------------------------------
+def _blocks(P, H):
+    return P[:, :H], P[:, H:2 * H], P[:, 2 * H:3 * H], P[:, 3 * H:]
+
+
+def _values(P, M, gamma, beta, u, v, n, H):
+    """what the forward pass writes: the LayerNorm branch y = silu(LN(m)), the row statistics, the two segment sums of
+    sigma(m) and the node pre-activation Ux + s1 / (s0 + eps)"""
+    _, _, Bh, Ux = _blocks(P, H)
+    y = F.silu(F.layer_norm(M, (H,), gamma, beta, EPS))
+    mean = M.mean(1)
+    rstd = (((M - mean[:, None]) ** 2).mean(1) + EPS).rsqrt()
+    sg = torch.sigmoid(M)
+    z = lambda: torch.zeros(n, H, dtype=M.dtype, device=M.device)  # noqa: E731
+    s1, s0 = z().index_add(0, v, sg * Bh[u]), z().index_add(0, v, sg)
+    hh = s1 / (s0 + EPS_GATE)
+    return dict(y=y, mean=mean, rstd=rstd, s1=s1, s0=s0, hh=hh, xpre=Ux + hh)
+
+
+def _duals(P, Pt, M, Mt, gamma, beta, u, v, n, H):
+    """value and tangent of the same, written out with differentiable torch operations (the explicit style of
+    tests/test_gpu_dual.py: torch's jvp tangents do not differentiate correctly w.r.t. the primal)"""
+    _, _, Bh, Ux = _blocks(P, H)
+    _, _, Bht, Uxt = _blocks(Pt, H)
+    mean = M.mean(1, keepdim=True)
+    rho = (((M - mean) ** 2).mean(1, keepdim=True) + EPS).rsqrt()
+    xh = (M - mean) * rho
+    th = rho * (Mt - Mt.mean(1, keepdim=True) - xh * (xh * Mt).mean(1, keepdim=True))
+    zz, zt = gamma * xh + beta, gamma * th
+    sz = torch.sigmoid(zz)
+    y, yt = zz * sz, (sz + zz * sz * (1 - sz)) * zt
+    sg = torch.sigmoid(M)
+    sgt = sg * (1 - sg) * Mt
+    z = lambda: torch.zeros(n, H, dtype=M.dtype, device=M.device)  # noqa: E731
+    s1, s0 = z().index_add(0, v, sg * Bh[u]), z().index_add(0, v, sg)
+    s1t, s0t = z().index_add(0, v, sgt * Bh[u] + sg * Bht[u]), z().index_add(0, v, sgt)
+    hh = s1 / (s0 + EPS_GATE)
+    hht = (s1t - hh * s0t) / (s0 + EPS_GATE)
+    return dict(y=y, yt=yt, s1=s1, s0=s0, s1t=s1t, s0t=s0t, hh=hh, hht=hht, xpre=Ux + hh, xpre_t=Uxt + hht)
+
+
+def _forward_ref(dt, g, o, H):
+    u, v, n = g.src.long(), g.dst.long(), g.n_nodes
+    c = {k: t.to(dt) for k, t in o.items()}
+    f = _values(c["P"], c["M"], c["gamma"], c["beta"], u, v, n, H)
+    At, Bdt, _, _ = _blocks(c["Pt"], H)
+    mt = At[u] + Bdt[v] + c["Ct"]
+    d = _duals(c["P"], c["Pt"], c["M"], mt, c["gamma"], c["beta"], u, v, n, H)
+    return dict(y=f["y"], y_res=f["y"] + c["Y"], mean=f["mean"], rstd=f["rstd"], xpre=f["xpre"], s0=f["s0"], hh=f["hh"], mt=mt,
+                xpre_t=d["xpre_t"], s0t=d["s0t"], hht=d["hht"], yt=d["yt"], yt_res=d["yt"] + c["Rt"])
+
+
+def _reverse_ref(dt, g, o, H, dual):
+    """float-``dt`` autograd of the restatements: adjoints of m (and mt), of the node projections' A / Bd / Bh blocks, of the
+    edge bias (column sums of the adjoint of m) and of the LayerNorm parameters, for the adjoints GY (GYt) of the LayerNorm
+    branch and Q1, Q0 (Q1t, Q0t) of the segment sums.  m = A[u] + Bd[v] + C enters as the given tensor M plus terms that are
+    zero in value and carry the gradient to A and Bd."""
+    u, v, n = g.src.long(), g.dst.long(), g.n_nodes
+    c = {k: t.to(dt) for k, t in o.items()}
+    leaves = {k: c[k].clone().requires_grad_(True) for k in ("M", "Mt", "P", "Pt", "gamma", "beta")}
+    A, Bd, _, _ = _blocks(leaves["P"], H)
+    At, Bdt, _, _ = _blocks(leaves["Pt"], H)
+    m = leaves["M"] + (A[u] - A[u].detach()) + (Bd[v] - Bd[v].detach())
+    if dual:
+        mt = leaves["Mt"] + (At[u] - At[u].detach()) + (Bdt[v] - Bdt[v].detach())
+        d = _duals(leaves["P"], leaves["Pt"], m, mt, leaves["gamma"], leaves["beta"], u, v, n, H)
+        loss = ((c["GY"] * d["y"]).sum() + (c["GYt"] * d["yt"]).sum() + (c["Q1"] * d["s1"]).sum() + (c["Q0"] * d["s0"]).sum()
+                + (c["Q1t"] * d["s1t"]).sum() + (c["Q0t"] * d["s0t"]).sum())
+        names = ("M", "Mt", "P", "Pt", "gamma", "beta")
+    else:
+        f = _values(leaves["P"], m, leaves["gamma"], leaves["beta"], u, v, n, H)
+        loss = (c["GY"] * f["y"]).sum() + (c["Q1"] * f["s1"]).sum() + (c["Q0"] * f["s0"]).sum()
+        names = ("M", "P", "gamma", "beta")
+    gr = dict(zip(names, torch.autograd.grad(loss, [leaves[k] for k in names])))
+    out = dict(GM=gr["M"], GP=gr["P"][:, :3 * H], GP_bd=gr["P"][:, H:2 * H], gb=gr["M"].sum(0), dbeta=gr["beta"], dgamma=gr["gamma"])
+    if dual:
+        out.update(GMt=gr["Mt"], GPt=gr["Pt"][:, :3 * H], GPt_bd=gr["Pt"][:, H:2 * H])
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# comparison
+# ----------------------------------------------------------------------------------------------------------------------
+def _err(a, b, floor=1e-30):
+    """tests/helpers.rel_err on the device"""
+    return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(floor))
+
+
+class _Report:
+    def __init__(self, case):
+        self.case, self.failed, self.worst = case, [], {}
+
+    def close(self, entry, name, got, ref64, ref32, bound, floor=1e-30):
+        e = _err(got, ref64, floor)
+        e32 = None if ref32 is None else _err(ref32, ref64, floor)
+        allowed = bound if e32 is None else 4 * e32 + bound
+        key = (entry.split(" ")[0], name)
+        if key not in self.worst or e / allowed > self.worst[key][0] / self.worst[key][2]:
+            self.worst[key] = (e, e32, allowed, entry)
+        if not e < allowed:
+            self.failed.append((entry, name, e, e32, allowed))
+
+    def amax(self, entry, name, slot, written):
+        got, want = float(slot), float(written.abs().max()) if written.numel() else 0.0
+        if got != want:
+            self.failed.append((entry, name, got, "amax: largest magnitude written", want))
+
+    def finish(self):
+        for (entry, name), (e, e32, allowed, where) in sorted(self.worst.items()):
+            f32 = "       -" if e32 is None else f"{e32:8.2e}"
+            print(f"convln-parity {self.case:<38s} {entry:<32s} {name:<8s} err {e:8.2e}  float32 {f32}  allowed {allowed:8.2e}  [{where}]")
+        assert not self.failed, self.failed
+
+
+def _run_case(H, gname, data):
+    lib = _lib.load()
+    g, o = _operands(H, gname, data)
+    n, m = g.n_nodes, g.n_edges
+    st = stream()
+    rep = _Report(f"H={H} {gname} {data}")
+    other = data != "normal"
+    E = lambda *s: torch.empty(*s, device=DEV)  # noqa: E731
+    Z = lambda *s: torch.zeros(*s, device=DEV)  # noqa: E731
+    P, Pt, M, gamma, beta = o["P"], o["Pt"], o["M"], o["gamma"], o["beta"]
+
+    # ---- forward values and tangents
+    r64 = _forward_ref(torch.float64, g, o, H)
+    r32 = _forward_ref(torch.float32, g, o, H) if other else {}
+    f32 = lambda k: r32.get(k)  # noqa: E731
+    for res in (False, True):
+        xpre, s0, hh, yout, stat, am = E(n, H), E(n, H), E(n, H), E(m, H), E(m, 2), Z(1)
+        assert lib.alignn_egc_gate_fwd_pre_ln(ptr(P), ptr(M), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H, ptr(xpre), ptr(s0),
+                                              ptr(hh), ptr(gamma), ptr(beta), EPS, ptr(o["Y"]) if res else None, ptr(yout), ptr(stat),
+                                              ptr(am), st) == 0
+        torch.cuda.synchronize()
+        ent = "gate_fwd_pre_ln" + (" +Y" if res else "")
+        k = "y_res" if res else "y"
+        rep.close(ent, "YOUT", yout, r64[k], f32(k), B_LN_FWD)
+        rep.close(ent, "mean", stat[:, 0], r64["mean"], f32("mean"), B_LN_FWD)
+        rep.close(ent, "rstd", stat[:, 1], r64["rstd"], f32("rstd"), B_LN_FWD)
+        rep.close(ent, "XPRE", xpre, r64["xpre"], f32("xpre"), B_GATE_FWD)
+        rep.close(ent, "S0", s0, r64["s0"], f32("s0"), B_GATE_FWD)
+        rep.close(ent, "HH", hh, r64["hh"], f32("hh"), B_GATE_FWD)
+        rep.amax(ent, "y_amax", am[0], yout)
+    # (what the later passes are handed: the float64 statistics and node sums, rounded once)
+    e_stat = torch.stack([r64["mean"], r64["rstd"]], 1).float().contiguous()
+    s0_in, hh_in = r64["s0"].float().contiguous(), r64["hh"].float().contiguous()
+    for res in (False, True):
+        mt, xpre_t, s0t, hht, yt, am2 = o["Ct"].clone(), E(n, H), E(n, H), E(n, H), E(m, H), Z(2)
+        assert lib.alignn_egc_gate_dual_tan_ln(ptr(P), ptr(Pt), ptr(M), ptr(mt), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H,
+                                               ptr(xpre_t), ptr(s0_in), ptr(hh_in), ptr(s0t), ptr(hht), ptr(gamma), ptr(beta), ptr(e_stat),
+                                               ptr(o["Rt"]) if res else None, ptr(yt), ptr(am2), st) == 0
+        torch.cuda.synchronize()
+        ent = "gate_dual_tan_ln" + (" +Rt" if res else "")
+        k = "yt_res" if res else "yt"
+        rep.close(ent, "Mt", mt, r64["mt"], f32("mt"), B_LN_FWD)
+        rep.close(ent, "xpre_t", xpre_t, r64["xpre_t"], f32("xpre_t"), B_GATE_FWD)
+        rep.close(ent, "s0t", s0t, r64["s0t"], f32("s0t"), B_GATE_FWD)
+        rep.close(ent, "hht", hht, r64["hht"], f32("hht"), B_GATE_FWD)
+        rep.close(ent, "Yt", yt, r64[k], f32(k), B_LN_FWD)
+        rep.amax(ent, "amax2[0]", am2[0], torch.zeros(0))  # (a tangent-only pass writes no values)
+        rep.amax(ent, "amax2[1]", am2[1], yt)
+    del r64, r32
+
+    # ---- reverse passes
+    v64 = _reverse_ref(torch.float64, g, o, H, dual=False)
+    v32 = _reverse_ref(torch.float32, g, o, H, dual=False) if other else {}
+    d64 = _reverse_ref(torch.float64, g, o, H, dual=True)
+    d32 = _reverse_ref(torch.float32, g, o, H, dual=True) if other else {}
+    Mt, GY, GYt, Q1, Q0, Q1t, Q0t = (o[k] for k in ("Mt", "GY", "GYt", "Q1", "Q0", "Q1t", "Q0t"))
+
+    def reverse_asserts(ent, ref, r32_, GM, GP, gb, red, gp_key, GMt=None, GPt=None):
+        fl = 1e-2 * float(ref["GP"].abs().max())
+        rep.close(ent, "GM", GM, ref["GM"], r32_.get("GM"), B_REVERSE, fl)
+        rep.close(ent, gp_key, GP, ref[gp_key], r32_.get(gp_key), B_REVERSE, fl)
+        rep.close(ent, "gb", gb.sum(0), ref["gb"], r32_.get("gb"), B_REVERSE, fl)
+        rep.close(ent, "dbeta", red[0], ref["dbeta"], r32_.get("dbeta"), B_LN_PARAM)
+        rep.close(ent, "dgamma", red[1], ref["dgamma"], r32_.get("dgamma"), B_LN_PARAM)
+        if GMt is not None:
+            flt = 1e-2 * float(ref["GPt"].abs().max())
+            kt = gp_key.replace("GP", "GPt")
+            rep.close(ent, "GMt", GMt, ref["GMt"], r32_.get("GMt"), B_REVERSE, flt)
+            rep.close(ent, kt, GPt, ref[kt], r32_.get(kt), B_REVERSE, flt)
+
+    # destination-ordered halves (any CSR), then the unchanged source-ordered halves
+    slabs = lib.alignn_egc_ln_dst_slabs(n)
+    GM, GP, gb, lnp, red, gma, gpa = E(m, H), Z(n, 4 * H), E(slabs, H), E(slabs, 2, H), E(2, H), Z(1), Z(1)
+    assert lib.alignn_egc_bwd_dst_ln(ptr(GY), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(gamma), ptr(beta), ptr(e_stat), ptr(g.seg_ptr),
+                                     ptr(g.seg_node), ptr(g.src), n, H, ptr(GM), ptr(GP), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
+    assert lib.alignn_bn_bwd_finalize(ptr(lnp), slabs, H, ptr(red), st) == 0
+    torch.cuda.synchronize()
+    assert float(GP[:, :H].abs().max()) == 0.0 and float(GP[:, 2 * H:].abs().max()) == 0.0  # (this half writes the Bd block only)
+    reverse_asserts("bwd_dst_ln", v64, v32, GM, GP[:, H:2 * H], gb, red, "GP_bd")
+    rep.amax("bwd_dst_ln", "gm_amax", gma[0], GM)
+    rep.amax("bwd_dst_ln", "gp_amax", gpa[0], GP[:, H:2 * H])
+    assert lib.alignn_egc_bwd_src(ptr(GM), ptr(M), ptr(Q1), ptr(g.out_ptr), ptr(g.out_slot), ptr(g.dst), n, H, ptr(GP), None, st) == 0
+    torch.cuda.synchronize()
+    fl = 1e-2 * float(v64["GP"].abs().max())
+    rep.close("bwd_dst_ln + bwd_src", "GP", GP[:, :3 * H], v64["GP"], v32.get("GP"), B_REVERSE, fl)
+
+    GM, GMt, GP, GPt, gma, gpa = E(m, H), E(m, H), Z(n, 4 * H), Z(n, 4 * H), Z(2), Z(2)
+    assert lib.alignn_egc_dual_bwd_dst_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(Q1), ptr(Q0), ptr(Q1t), ptr(Q0t),
+                                          ptr(gamma), ptr(beta), ptr(e_stat), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, H, ptr(GM),
+                                          ptr(GMt), ptr(GP), ptr(GPt), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
+    assert lib.alignn_bn_bwd_finalize(ptr(lnp), slabs, H, ptr(red), st) == 0
+    torch.cuda.synchronize()
+    reverse_asserts("dual_bwd_dst_ln", d64, d32, GM, GP[:, H:2 * H], gb, red, "GP_bd", GMt, GPt[:, H:2 * H])
+    for w, (a, b) in enumerate(((GM, GP), (GMt, GPt))):
+        rep.amax("dual_bwd_dst_ln", f"gm_amax2[{w}]", gma[w], a)
+        rep.amax("dual_bwd_dst_ln", f"gp_amax2[{w}]", gpa[w], b[:, H:2 * H])
+    assert lib.alignn_egc_dual_bwd_src(ptr(GM), ptr(GMt), ptr(M), ptr(Mt), ptr(Q1), ptr(Q1t), ptr(g.out_ptr), ptr(g.out_slot), ptr(g.dst),
+                                       n, H, ptr(GP), ptr(GPt), None, st) == 0
+    torch.cuda.synchronize()
+    rep.close("dual_bwd_dst_ln + dual_bwd_src", "GP", GP[:, :3 * H], d64["GP"], d32.get("GP"), B_REVERSE, fl)
+    rep.close("dual_bwd_dst_ln + dual_bwd_src", "GPt", GPt[:, :3 * H], d64["GPt"], d32.get("GPt"), B_REVERSE,
+              1e-2 * float(d64["GPt"].abs().max()))
+
+    # dense-block kernels (line graphs), every launch variant of both
+    if _is_line_graph(g):
+        groups = g.grp_seg_ptr.numel() - 1
+        prev = os.environ.get("ALIGNN_AMD_LN_REV")
+        try:
+            for var in (a + b for a in "012" for b in "012"):
+                os.environ["ALIGNN_AMD_LN_REV"] = var
+                GM, GP, gb, lnp, gma, gpa = E(m, H), Z(n, 4 * H), E(groups, H), E(groups, 2, H), Z(1), Z(1)
+                assert lib.alignn_egc_bwd_lg_dense_ln(ptr(GY), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(gamma), ptr(beta), ptr(e_stat), m,
+                                                      ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, g.dense_max_src, ptr(g.seg_ptr),
+                                                      ptr(g.seg_node), H, ptr(GM), ptr(GP), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
+                assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
+                torch.cuda.synchronize()
+                ent = "bwd_lg_dense_ln " + var
+                reverse_asserts(ent, v64, v32, GM, GP[:, :3 * H], gb, red, "GP")
+                assert float(GP[:, 3 * H:].abs().max()) == 0.0
+                rep.amax(ent, "gm_amax", gma[0], GM)
+                rep.amax(ent, "gp_amax", gpa[0], GP)
+                GM, GMt, GP, GPt, gma, gpa = E(m, H), E(m, H), Z(n, 4 * H), Z(n, 4 * H), Z(2), Z(2)
+                assert lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(Q1), ptr(Q0), ptr(Q1t),
+                                                           ptr(Q0t), ptr(gamma), ptr(beta), ptr(e_stat), m, ptr(g.grp_seg_ptr),
+                                                           ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr), ptr(g.seg_node), H, ptr(GM), ptr(GMt),
+                                                           ptr(GP), ptr(GPt), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
+                assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
+                torch.cuda.synchronize()
+                ent = "dual_bwd_lg_dense_ln " + var
+                reverse_asserts(ent, d64, d32, GM, GP[:, :3 * H], gb, red, "GP", GMt, GPt[:, :3 * H])
+                for w, (a, b) in enumerate(((GM, GP), (GMt, GPt))):
+                    rep.amax(ent, f"gm_amax2[{w}]", gma[w], a)
+                    rep.amax(ent, f"gp_amax2[{w}]", gpa[w], b)
+        finally:
+            if prev is None:
+                os.environ.pop("ALIGNN_AMD_LN_REV", None)
+            else:
+                os.environ["ALIGNN_AMD_LN_REV"] = prev
+    rep.finish()
+
+
+SMALL = ("lg_small", "lg_deg17", "bond", "synthetic")
+CASES = ([(H, gname, "normal") for H in HS for gname in SMALL]
+         + [(H, gname, data) for H in (100, 256) for gname in ("lg_small", "synthetic") for data in DATA[1:]]
+         + [(64, "lg_4096seg", "normal"), (252, "lg_4096seg", "mean_over_spread"),
+            (256, "lg_stream", "normal"), (256, "lg_stream", "rows_1e-4_1e4")])
+
+
+@pytest.mark.parametrize("H,gname,data", CASES)
+def test_entry_points_against_float64(H, gname, data):
+    """Every output of the six entry points of csrc/convln.hip against the float64 restatements: on line graphs all six (every
+    ALIGNN_AMD_LN_REV variant of the two dense-block reverse kernels), on other graphs the forward, the dual forward and the
+    two destination-ordered reverse passes (completed by the source-ordered halves).  See the module docstring for the
+    bounds; the worst error per entry point and output is printed."""
+    _run_case(H, gname, data)
+
+
+@pytest.mark.parametrize("H,gname", [(36, "lg_small"), (64, "synthetic")])
+def test_the_restatements_are_consistent(H, gname):
+    """The explicit value + tangent expressions: same values as the layer_norm / silu / index_add restatement, and tangents
+    that ARE the directional derivative (central differences, the tolerances of tests/test_gpu_dual.py)."""
+    g, o = _operands(H, gname, "normal")
+    u, v, n = g.src.long(), g.dst.long(), g.n_nodes
+    c = {k: t.double() for k, t in o.items()}
+    args = (c["gamma"], c["beta"], u, v, n, H)
+    d = _duals(c["P"], c["Pt"], c["M"], c["Mt"], *args)
+    f = _values(c["P"], c["M"], *args)
+    for k in ("y", "s1", "s0", "hh", "xpre"):
+        assert _err(d[k], f[k]) < 1e-12, k
+    h = 1e-6
+    fp, fm = (_values(c["P"] + s * h * c["Pt"], c["M"] + s * h * c["Mt"], *args) for s in (1, -1))
+    for k, kt, tol in (("y", "yt", 1e-7), ("s1", "s1t", 1e-7), ("s0", "s0t", 1e-7), ("hh", "hht", 1e-6), ("xpre", "xpre_t", 1e-6)):
+        assert _err(d[kt], (fp[k] - fm[k]) / (2 * h)) < tol, kt
+
+
+@pytest.mark.parametrize("H", [0, 2, 6, 260])
+def test_unsupported_widths_are_refused(H):
+    """hipErrorInvalidValue and no launch (every output buffer keeps its fill) at widths outside H % 4 == 0, 4 <= H <= 256."""
+    lib = _lib.load()
+    g = _graph("lg_small")
+    n, m, W = g.n_nodes, g.n_edges, 264
+    groups = g.grp_seg_ptr.numel() - 1
+    st = stream()
+    I = lambda *s: torch.randn(*s, device=DEV)  # noqa: E731, E741
+    P, Pt, M, Mt, Y = I(n, 4 * W), I(n, 4 * W), I(m, W), I(m, W), I(m, W)
+    q = [I(n, W) for _ in range(4)]
+    gamma, beta, e_stat = I(W), I(W), I(m, 2)
+    mt_before = Mt.clone()
+    outs = [torch.full(s, 7.0, device=DEV) for s in ((m, W), (m, W), (n, 4 * W), (n, 4 * W), (n, W), (n, W), (n, W), (1024, W),
+                                                       (1024, 2, W), (m, 2), (2,), (2,))]
+    em, emt, gp, gpt, na, nb, nc, gb, lnp, stat, am, am_b = outs
+    rc = [
+        lib.alignn_egc_gate_fwd_pre_ln(ptr(P), ptr(M), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H, ptr(na), ptr(nb), ptr(nc),
+                                       ptr(gamma), ptr(beta), EPS, ptr(Y), ptr(em), ptr(stat), ptr(am), st),
+        lib.alignn_egc_gate_dual_tan_ln(ptr(P), ptr(Pt), ptr(M), ptr(Mt), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H, ptr(na),
+                                        ptr(q[0]), ptr(q[1]), ptr(nb), ptr(nc), ptr(gamma), ptr(beta), ptr(e_stat), ptr(Y), ptr(em),
+                                        ptr(am), st),
+        lib.alignn_egc_bwd_lg_dense_ln(ptr(Y), ptr(M), ptr(P), ptr(q[0]), ptr(q[1]), ptr(gamma), ptr(beta), ptr(e_stat), m,
+                                       ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, g.dense_max_src, ptr(g.seg_ptr), ptr(g.seg_node), H,
+                                       ptr(em), ptr(gp), ptr(gb), ptr(lnp), ptr(am), ptr(am_b), st),
+        lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(Y), ptr(Y), ptr(M), ptr(Mt), ptr(P), ptr(Pt), *(ptr(t) for t in q), ptr(gamma),
+                                            ptr(beta), ptr(e_stat), m, ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr),
+                                            ptr(g.seg_node), H, ptr(em), ptr(emt), ptr(gp), ptr(gpt), ptr(gb), ptr(lnp), ptr(am),
+                                            ptr(am_b), st),
+        lib.alignn_egc_bwd_dst_ln(ptr(Y), ptr(M), ptr(P), ptr(q[0]), ptr(q[1]), ptr(gamma), ptr(beta), ptr(e_stat), ptr(g.seg_ptr),
+                                  ptr(g.seg_node), ptr(g.src), n, H, ptr(em), ptr(gp), ptr(gb), ptr(lnp), ptr(am), ptr(am_b), st),
+        lib.alignn_egc_dual_bwd_dst_ln(ptr(Y), ptr(Y), ptr(M), ptr(Mt), ptr(P), ptr(Pt), *(ptr(t) for t in q), ptr(gamma), ptr(beta),
+                                       ptr(e_stat), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, H, ptr(em), ptr(emt), ptr(gp),
+                                       ptr(gpt), ptr(gb), ptr(lnp), ptr(am), ptr(am_b), st),
+    ]
+    torch.cuda.synchronize()
+    assert rc == [INVALID] * 6, rc
+    assert all(bool((t == 7.0).all()) for t in outs) and torch.equal(Mt, mt_before)
+    assert lib.alignn_egc_ln_fused_supported(H, 1 << 30) == 0 and lib.alignn_egc_ln_dst_supported(H) == 0
