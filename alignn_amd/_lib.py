@@ -200,7 +200,9 @@ class FireArgs(C.Structure):
         "positions", "velocities", "frac", "state", "istate", "xa", "xc", "cell_velocities", "defgrad", "lattice",  # state
         "forces_out", "energy_out", "fmax_out", "stress_out", "status")] + [  # outputs
         (n, _i32) for n in ("n_active", "steps", "nmin")] + [
-        (n, _f64) for n in ("fmax", "maxstep", "dtmax", "finc", "fdec", "astart", "fa")]
+        (n, _f64) for n in ("fmax", "maxstep", "dtmax", "finc", "fdec", "astart", "fa")] + [
+        ("fixed", _p), ("cell_mask", _p), ("scalar_pressure", _p),  # constraints: NULL / 0 is off
+        ("hydrostatic_strain", _i32), ("constant_volume", _i32), ("enthalpy_out", _p)]
 
 
 class MdArgs(C.Structure):

@@ -19,6 +19,12 @@
 // from it, the exact gradient -d E / d logm(F), the Frechet derivative of expm at L = X_c / c applied to W expm(-L); either
 // one / c.  X_c is kept as state instead of recomputing logm(F) from the cell every step (the round trip is the identity to
 // rounding: tests/test_relax_cell.py).  The cell rows are thread 0's.
+//
+// Constraints (the last fields of the block, NULL / 0 = off and then the same instructions on the same values as without
+// them; tests/test_relax_constraints.py restates them).  FixAtoms: a fixed atom's force row reads as zero everywhere but in
+// forces_out, so its velocity stays zero and its row in place; the move leaves its row and its frac unwritten.  ExpCellFilter's
+// scalar_pressure, hydrostatic_strain and mask shape the virial W before the naive / exact choice, constant_volume takes the
+// trace off the chosen force after it.  The flags are the same for a whole workgroup: scalar branches.
 #include "../../include/alignn_hip.h"
 #include "common.h"
 
@@ -30,9 +36,11 @@ constexpr int FIRE_WAVES = FIRE_BLOCK / ALIGNN_WAVE;
 // Record the evaluation (energy, max_i |F_i| from the reduced max |F_i|^2 in red[3]) and the outcome of Optimizer.run's
 // test: converged (max |F_i|^2 < fmax^2) or out of steps -> retire flag 1 / 2 in status[1 + k], else counted in status[0]
 __device__ __forceinline__ void fire_record(const double* red, int converged, int taken, int steps, int k, int s,
-                                            const double* energy, double* energy_out, double* fmax_out, int32_t* status) {
+                                            const double* energy, double* energy_out, double* fmax_out, int32_t* status,
+                                            double* enthalpy_out, double pv) {
     if (threadIdx.x == 0) {
         energy_out[s] = energy[k];
+        if (enthalpy_out) enthalpy_out[s] = energy[k] + pv;
         fmax_out[s] = sqrt(red[3]);
         const int flag = converged ? 1 : (taken >= steps ? 2 : 0);
         status[1 + k] = flag;
@@ -140,9 +148,16 @@ __device__ __forceinline__ void expm3(const double* L, double* E) {
     expm_block(L, Z, E, unused);
 }
 
+// ExpCellFilter's arguments for one structure (all off: pressure and mask NULL, the flags 0)
+struct CellOptions {
+    const double* pressure;  // the structure's scalar_pressure
+    const double* mask;      // its 3 x 3 mask
+    int hydrostatic_strain, constant_volume;
+};
+
 // the filter's cell rows (before the division by c) from the current cell C, the stress S (eV/A^3, ASE sign) and L = X_c / c;
-// Ssym (the symmetrised stress) is returned as well
-__device__ void cell_force(const double* C, const double* S, const double* L, double* G, double* Ssym) {
+// Ssym (the symmetrised stress) is returned as well, and the cell's volume
+__device__ double cell_force(const double* C, const double* S, const double* L, const CellOptions& o, double* G, double* Ssym) {
     const double V = fabs(det3(C));
     double W[9];  // the virial; naive force
 #pragma unroll
@@ -152,6 +167,20 @@ __device__ void cell_force(const double* C, const double* S, const double* L, do
             Ssym[3 * i + j] = i == j ? S[3 * i + j] : (S[3 * i + j] + S[3 * j + i]) / 2;
             W[3 * i + j] = -V * Ssym[3 * i + j];
         }
+    if (o.pressure) {
+        const double p = *o.pressure;
+#pragma unroll
+        for (int i = 0; i < 9; i += 4) W[i] = -V * (Ssym[i] + p);
+    }
+    if (o.hydrostatic_strain) {
+        const double t = (W[0] + W[4] + W[8]) / 3.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) W[i] = (i % 4 == 0) ? t : 0.0;
+    }
+    if (o.mask) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) W[i] *= o.mask[i];
+    }
     // exact force: -expm([[L, -W expm(-L)], [0, L]])[0:3, 3:6], symmetrised; the upper-right block is linear in W, so it is
     // computed for W scaled by a power of two to below one
     double mL[9], Em[9], Bm[9], E11[9], E12[9];
@@ -191,6 +220,12 @@ __device__ void cell_force(const double* C, const double* S, const double* L, do
     const bool naive = close || en / sqrt(ee * nn) > 0.8;
 #pragma unroll
     for (int i = 0; i < 9; ++i) G[i] = naive ? W[i] : E[i];
+    if (o.constant_volume) {
+        const double t = (G[0] + G[4] + G[8]) / 3.0;
+#pragma unroll
+        for (int i = 0; i < 9; i += 4) G[i] -= t;
+    }
+    return V;
 }
 
 using FireArgs = alignn_fire_args;
@@ -210,8 +245,10 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(const FireArgs a)
     double* X = (CELL ? a.xa : a.positions) + 3 * (int64_t)beg;  // the atom rows
     double* V = a.velocities + 3 * (int64_t)beg;
     double* FOUT = a.forces_out + 3 * (int64_t)beg;
+    const uint8_t* FIX = a.fixed ? a.fixed + beg : nullptr;  // FixAtoms: the structure's flags
     const int taken = a.istate[2 * s + 1];
     const double maxstep = a.maxstep;
+    double pv = 0.0;  // scalar_pressure * volume (thread 0)
 
     // the filter's part of the rows: the deformation gradient of the evaluated cell and, on thread 0, the cell rows' forces
     // (ExpCellFilter's cell_factor is n) and velocities
@@ -228,7 +265,10 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(const FireArgs a)
             double L[9], Ssym[9];
 #pragma unroll
             for (int i = 0; i < 9; ++i) L[i] = XC[i] / c;
-            cell_force(a.lattice + 9 * (int64_t)s, a.stress + 9 * (int64_t)k, L, G, Ssym);
+            const CellOptions opt{a.scalar_pressure ? a.scalar_pressure + s : nullptr,
+                                  a.cell_mask ? a.cell_mask + 9 * (int64_t)s : nullptr, a.hydrostatic_strain, a.constant_volume};
+            const double vol = cell_force(a.lattice + 9 * (int64_t)s, a.stress + 9 * (int64_t)k, L, opt, G, Ssym);
+            if (opt.pressure) pv = *opt.pressure * vol;
 #pragma unroll
             for (int i = 0; i < 9; ++i) {
                 G[i] /= c;
@@ -237,7 +277,7 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(const FireArgs a)
             }
         }
     }
-    // the generalised force of atom row i: f F under the filter, else f
+    // the generalised force of atom row i: f F under the filter, else f (f: as evaluated); a fixed atom's is zero
     auto atom_force = [&](int i, double (&f)[3], double (&g)[3]) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) f[j] = Fo[3 * i + j];
@@ -248,6 +288,7 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(const FireArgs a)
             else
                 g[j] = f[j];
         }
+        if (FIX && FIX[i]) g[0] = g[1] = g[2] = 0.0;
     };
 
     // reduce over the rows (the cell rows are thread 0's last), record, test convergence
@@ -281,7 +322,8 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(const FireArgs a)
     }
     block_reduce<4, true>(red, sh);
     const int converged = red[3] < a.fmax * a.fmax;
-    fire_record(red, converged, taken, a.steps, k, s, a.energy, a.energy_out, a.fmax_out, a.status);
+    fire_record(red, converged, taken, a.steps, k, s, a.energy, a.energy_out, a.fmax_out, a.status,
+                CELL ? a.enthalpy_out : nullptr, pv);
     if (converged || taken >= a.steps) return;
 
     // ASE FIRE.step: mix and kick
@@ -349,16 +391,21 @@ __global__ __launch_bounds__(FIRE_BLOCK) void fire_step_kernel(const FireArgs a)
     }
     const double* Li = a.inv_lattice + 9 * (int64_t)s;
     for (int i = threadIdx.x; i < n; i += FIRE_BLOCK) {
+        const bool held = FIX && FIX[i];  // its row and its frac stay as they are; under the filter it rides with the cell
         double x[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            x[j] = X[3 * i + j] + step_of(V[3 * i + j]);
-            X[3 * i + j] = x[j];
+            if (held) {
+                x[j] = X[3 * i + j];
+            } else {
+                x[j] = X[3 * i + j] + step_of(V[3 * i + j]);
+                X[3 * i + j] = x[j];
+            }
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             if constexpr (CELL) a.positions[3 * ((int64_t)beg + i) + j] = x[0] * Fn[3 * j] + x[1] * Fn[3 * j + 1] + x[2] * Fn[3 * j + 2];
-            a.frac[3 * ((int64_t)beg + i) + j] = wrap01(x[0] * Li[j] + x[1] * Li[3 + j] + x[2] * Li[6 + j]);
+            if (!held) a.frac[3 * ((int64_t)beg + i) + j] = wrap01(x[0] * Li[j] + x[1] * Li[3 + j] + x[2] * Li[6 + j]);
         }
     }
     fire_store(fire, taken, s, a.state, a.istate);
@@ -374,6 +421,8 @@ extern "C" int alignn_fire_step(const alignn_fire_args* args, alignn_stream_t st
     const bool cell = a.xc != nullptr;  // a cell-filter state: every field of the filter is then needed
     if (cell && (!a.stress || !a.lattice0 || !a.xa || !a.cell_velocities || !a.defgrad || !a.lattice || !a.stress_out))
         return (int)hipErrorInvalidValue;
+    if (!cell && (a.cell_mask || a.scalar_pressure || a.hydrostatic_strain || a.constant_volume || a.enthalpy_out))
+        return (int)hipErrorInvalidValue;  // the filter's options without the filter
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(a.status, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;

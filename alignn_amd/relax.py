@@ -21,6 +21,11 @@ alone or beside others.
 its n + 3 generalised rows per structure (atom rows in the starting cell, cell rows ``n logm(F)`` of the deformation gradient
 ``F``) driven by the same FIRE in the same ``alignn_fire_step`` (the filter's state in its argument block selects it).  The
 model's per-crystal stresses enter as the calculator gives them (``stress * stress_weight / 160.21766208``, eV/A^3).
+
+Constraints, as ASE states them: ``fixed`` is ``FixAtoms`` (those atoms' force rows are zero to the optimiser and to the
+convergence test; at fixed cell they stay where they are, under the filter they ride with the cell), and ``cell_mask``,
+``hydrostatic_strain``, ``constant_volume`` and ``scalar_pressure`` are ``ExpCellFilter``'s arguments.  They are fields of the
+same argument block, passed only when they are on: the same kernel, and without them the same bits as before.
 """
 
 from __future__ import annotations
@@ -29,6 +34,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -53,6 +59,69 @@ class RelaxResult:
     n_evals: int
     lattices: Optional[torch.Tensor] = None  # [B, 3, 3] float64: the final cells (optimize_lattice only)
     stresses: Optional[torch.Tensor] = None  # [B, 3, 3] float64, eV/A^3, ASE's sign, symmetrised (optimize_lattice only)
+    enthalpies: Optional[torch.Tensor] = None  # [B] float64: energy + scalar_pressure * volume (optimize_lattice only)
+
+
+def _host(x) -> np.ndarray:
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _full_mask(m, what: str) -> np.ndarray:
+    """One cell mask, six Voigt flags (xx, yy, zz, yz, xz, xy) or [3, 3], as the full 3 x 3 of 0.0 / 1.0 (ASE's
+    voigt_6_to_full_3x3_stress for the Voigt form)."""
+    m = _host(m)
+    if m.shape == (6,):
+        xx, yy, zz, yz, xz, xy = m
+        m = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+    elif m.shape != (3, 3):
+        raise ValueError(f"relax: {what} is {m.shape}, need six Voigt flags or [3, 3]")
+    if m.dtype == object or not np.isin(m, (0, 1)).all():
+        raise ValueError(f"relax: {what} must hold 0 / 1 only")
+    return m.astype(np.float64)
+
+
+def _constraints(ns: List[int], fixed, cell_mask, hydrostatic_strain, constant_volume, scalar_pressure, optimize_lattice):
+    """The host-side checks of the constraint arguments -> (fixed [N] bool or None, masks [B, 3, 3] or None, pressures [B] or
+    None), None where the option is off (no atom fixed, every mask all ones, every pressure zero)."""
+    B = len(ns)
+    for name, v in (("hydrostatic_strain", hydrostatic_strain), ("constant_volume", constant_volume)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"relax: {name} is one bool for the whole call, got {type(v).__name__}")
+    fix = None
+    if fixed is not None:
+        if isinstance(fixed, (torch.Tensor, np.ndarray)) and fixed.ndim != 2 or len(fixed) != B:
+            raise ValueError(f"relax: fixed needs one boolean [n_i] array (or None) per structure, {B} of them")
+        rows = []
+        for i, f in enumerate(fixed):
+            f = np.zeros(ns[i], dtype=bool) if f is None else _host(f)
+            if f.shape != (ns[i],) or f.dtype != np.bool_:
+                raise ValueError(f"relax: fixed[{i}] is {f.dtype} {f.shape}, need bool [{ns[i]}]")
+            rows.append(f)
+        fix = np.concatenate(rows)
+        fix = fix if fix.any() else None
+    masks = None
+    if cell_mask is not None:
+        shape = None
+        try:
+            shape = _host(cell_mask).shape
+        except (ValueError, TypeError):  # a ragged list: Voigt and [3, 3] masks mixed
+            pass
+        if shape in ((6,), (3, 3)):  # one mask for every structure
+            masks = np.stack([_full_mask(cell_mask, "cell_mask")] * B)
+        elif shape is not None and len(shape) < 2 or len(cell_mask) != B:
+            raise ValueError(f"relax: cell_mask needs one mask (six Voigt flags or [3, 3]) or {B} of them")
+        else:
+            masks = np.stack([_full_mask(m, f"cell_mask[{i}]") for i, m in enumerate(cell_mask)])
+    press = _host(scalar_pressure)
+    if press.dtype.kind not in "iuf" or press.shape not in ((), (B,)):
+        raise ValueError(f"relax: scalar_pressure needs one number or {B} of them (eV/A^3)")
+    press = np.broadcast_to(press.astype(np.float64), (B,)).copy()
+    if not np.isfinite(press).all():
+        raise ValueError("relax: scalar_pressure must be finite")
+    if not optimize_lattice and (masks is not None or hydrostatic_strain or constant_volume or press.any()):
+        raise ValueError("relax: cell_mask, hydrostatic_strain, constant_volume and a non-zero scalar_pressure need "
+                         "optimize_lattice=True")
+    return fix, None if masks is None or (masks == 1.0).all() else masks, press if press.any() else None
 
 
 def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optional[Sequence] = None, *, fmax: float = 0.1,
@@ -60,7 +129,8 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
           fdec: float = 0.5, astart: float = 0.1, fa: float = 0.99, a: float = 0.1, cutoff: float = 8.0, max_neighbors: int = 12,
           neighbor_strategy: str = "k-nearest", intensive: bool = True, force_multiplier: float = 1.0,
           forces_fn: Optional[Callable] = None, device=None, optimize_lattice: bool = False,
-          stress_weight: float = 1.0) -> RelaxResult:
+          stress_weight: float = 1.0, fixed: Optional[Sequence] = None, cell_mask=None, hydrostatic_strain: bool = False,
+          constant_volume: bool = False, scalar_pressure=0.0) -> RelaxResult:
     """Relax the atomic positions of B crystals with FIRE until max_i |F_i| < ``fmax`` or ``steps`` steps; at fixed cell, or
     with the cells too when ``optimize_lattice``.
 
@@ -70,10 +140,23 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
     ``optimize_lattice``: relax the cells as well, through ASE's ``ExpCellFilter`` (default arguments).  The reference's
     ``optimize_atoms`` defaults to ``optimize_lattice=True``; here the default stays ``False``.  The model must then predict
     per-crystal stresses, scaled by ``stress_weight``; ``forces_fn`` must return ``(energy, forces, stress)``.  The cells and
-    positions it gets change from step to step."""
+    positions it gets change from step to step.
+
+    ``fixed``: ASE's ``FixAtoms``, B boolean arrays [n_i] (``None`` for a structure: none of its atoms), with or without
+    ``optimize_lattice``.  The optimiser and the convergence test see zero force rows for these atoms (``fmax`` of the result
+    too; ``forces`` stay the forces as evaluated).  At fixed cell a fixed atom does not move; under the filter it keeps its
+    place in the cell and moves with it.
+
+    ``cell_mask``, ``hydrostatic_strain``, ``constant_volume``, ``scalar_pressure``: ``ExpCellFilter``'s arguments of these
+    names (``cell_mask`` its ``mask``); they need ``optimize_lattice``.  ``cell_mask``: which cell components may relax, six
+    Voigt flags (xx, yy, zz, yz, xz, xy) or a [3, 3] array of 0 / 1, one for all structures or B of them (a [3, 3] array is
+    always one mask).  ``scalar_pressure``: the target pressure in eV/A^3, ASE's unit (``dynamics.BAR`` converts from bar),
+    one number or B; the run then minimises the enthalpy ``E + scalar_pressure * V``, returned as ``enthalpies``."""
     ns = check_inputs("relax", model, lattices, positions, atom_features, forces_fn=forces_fn, stress=optimize_lattice)
     if steps < 0 or fmax < 0 or maxstep <= 0 or dt <= 0:
         raise ValueError("relax: need steps >= 0, fmax >= 0, maxstep > 0, dt > 0")
+    fix, masks, press = _constraints(ns, fixed, cell_mask, hydrostatic_strain, constant_volume, scalar_pressure,
+                                     optimize_lattice)
     dev = gpu_device("relax", model, forces_fn, device)
     lib = _lib.load()
     B = len(ns)
@@ -98,6 +181,11 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
             defgrad = torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous()
             lat_cur = lat.clone()
             stress_all = torch.zeros_like(xc)
+            enthalpy_all = torch.zeros(B, dtype=torch.float64, device=dev)
+        # the constraints that are on (None: a NULL field)
+        fix_t = None if fix is None else torch.tensor(fix.astype(np.uint8), device=dev)
+        mask_t = None if masks is None else torch.tensor(masks, dtype=torch.float64, device=dev)
+        press_t = None if press is None else torch.tensor(press, dtype=torch.float64, device=dev)
         # fixed per-structure views: the same lattice tensors every step keep neighbors' lattice tables cached
         lat_v = [lat[s] for s in range(B)]
         pos_v, frac_v = packed.rows(pos), packed.rows(frac)
@@ -107,8 +195,10 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
             frac=frac.data_ptr(), state=state.data_ptr(), istate=istate.data_ptr(), forces_out=forces_all.data_ptr(),
             energy_out=energy_all.data_ptr(), fmax_out=fmax_all.data_ptr(), status=status.data_ptr(), steps=int(steps),
             nmin=int(Nmin), fmax=float(fmax), maxstep=float(maxstep), dtmax=float(dtmax), finc=float(finc), fdec=float(fdec),
-            astart=float(astart), fa=float(fa))
+            astart=float(astart), fa=float(fa), fixed=_lib.ptr(fix_t), cell_mask=_lib.ptr(mask_t),
+            scalar_pressure=_lib.ptr(press_t), hydrostatic_strain=int(hydrostatic_strain), constant_volume=int(constant_volume))
         if optimize_lattice:
+            args.enthalpy_out = enthalpy_all.data_ptr()
             args.lattice0, args.xa, args.xc, args.cell_velocities = lat.data_ptr(), xa.data_ptr(), xc.data_ptr(), cvel.data_ptr()
             args.defgrad, args.lattice, args.stress_out = defgrad.data_ptr(), lat_cur.data_ptr(), stress_all.data_ptr()
 
@@ -151,4 +241,5 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
                            forces=[f.clone() for f in packed.rows(forces_all)], fmax=fmax_all,
                            converged=torch.tensor([f == 1 for f in flag], device=dev), n_steps=istate[:, 1].long(),
                            n_evals=n_evals, lattices=lat_cur.clone() if optimize_lattice else None,
-                           stresses=stress_all if optimize_lattice else None)
+                           stresses=stress_all if optimize_lattice else None,
+                           enthalpies=enthalpy_all if optimize_lattice else None)

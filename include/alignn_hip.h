@@ -925,6 +925,14 @@ int alignn_radius_emit(const float* lat, const float* cart, const int32_t* graph
  * sym(stress), or the exact gradient -expm([[L, -W expm(-L)], [0, L]])[0:3, 3:6] (symmetrised, L = X_c / n) where the two
  * point apart (cosine <= 0.8 and not numpy-isclose), divided by n.  Convergence and fmax_out run over all n + 3 rows.
  * Initial filter state: xa = positions, xc = cell_velocities = 0, defgrad = I, lattice = lattice0.
+ *
+ * Constraints (the last fields of the block; NULL / 0 is off, and the step is then the same bits as without them).
+ * `fixed` is ASE's FixAtoms: a fixed atom's force row is zero wherever the step reduces or integrates it (forces_out keeps
+ * the force as evaluated), so its row X_a and its velocity never change; its frac is not rewritten, and at fixed cell neither
+ * is its position.  The others are ExpCellFilter's arguments, in ASE's order: W = -|det C| (sym(stress) + scalar_pressure I);
+ * hydrostatic_strain: W <- (tr W / 3) I; W <- W * cell_mask elementwise; the naive / exact choice on this W; constant_volume:
+ * tr / 3 taken off the diagonal of the chosen force; then / n.  enthalpy_out[s] = energy + scalar_pressure |det C| of the
+ * evaluated cell.
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_fire_args {
     /* inputs of the step: the evaluation of the active batch */
@@ -956,6 +964,12 @@ typedef struct alignn_fire_args {
     /* scalars */
     int n_active, steps, nmin; /* `steps`: the cap per structure; nmin: FIRE's Nmin */
     double fmax, maxstep, dtmax, finc, fdec, astart, fa; /* the tolerance and FIRE's parameters */
+    /* constraints: NULL / 0 is off */
+    const uint8_t* fixed;          /* [N] non-zero: the atom is held (FixAtoms) */
+    const double* cell_mask;       /* filter: [B][3][3] of 0 / 1, ExpCellFilter's mask as the full 3x3 */
+    const double* scalar_pressure; /* filter: [B] eV/A^3 */
+    int hydrostatic_strain, constant_volume; /* filter: ExpCellFilter's flags, the same for every structure */
+    double* enthalpy_out;          /* filter: [B] energy + scalar_pressure * volume */
 } alignn_fire_args;
 int alignn_fire_step(const alignn_fire_args* args, alignn_stream_t stream);
 size_t alignn_fire_args_sizeof(void); /* a binding checks its own packing against this */
