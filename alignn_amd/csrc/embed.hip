@@ -120,12 +120,13 @@ __global__ void rbf_bwd_kernel(const float* __restrict__ d, const float* __restr
     }
 }
 
-// gv[r,:] = g[r] * v[r,:] / |v[r]|
+// gv[r,:] = g[r] * v[r,:] / |v[r]|; 0 for a zero vector, the subgradient torch.norm's backward takes (not 0 * inf = NaN)
 __global__ void norm3_bwd_kernel(const float* __restrict__ v, const float* __restrict__ g, float* __restrict__ gv,
                                  int64_t rows) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
         const float x = v[3 * r], y = v[3 * r + 1], z = v[3 * r + 2];
-        const float s = g[r] / sqrtf(x * x + y * y + z * z);
+        const float n = sqrtf(x * x + y * y + z * z);
+        const float s = n > 0.0f ? g[r] / n : 0.0f;
         gv[3 * r] = s * x, gv[3 * r + 1] = s * y, gv[3 * r + 2] = s * z;
     }
 }
