@@ -212,7 +212,9 @@ class MdArgs(C.Structure):
         "epot", "ekin", "temperature", "pressure_out", "volume_out", "traj_positions", "traj_momenta", "traj_lattice",
         "noise_out")] + [  # outputs
         (n, _i32) for n in ("n_structures", "t", "interval", "steps", "ensemble", "fixcm")] + [
-        (n, _f64) for n in ("dt", "friction", "andersen_prob", "taut", "taup", "kB")]
+        (n, _f64) for n in ("dt", "friction", "andersen_prob", "taut", "taup", "kB")] + [
+        ("nhc_state", _p), ("conserved_out", _p), ("chain", _i32), ("nhc_loops", _i32), ("nhc_order", _i32),  # ensembles 5, 6
+        ("ttime", _f64), ("ptime", _f64)]
 
 
 _lib = None

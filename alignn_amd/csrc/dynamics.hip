@@ -2,7 +2,7 @@
 // the reference's ForceField.run_nve_velocity_verlet / run_nvt_langevin / run_nvt_berendsen / run_nvt_andersen /
 // run_npt_berendsen drive them (alignn/ff/ff.py:419-600), every structure's integrator state on the device
 // (alignn_amd/dynamics.py is the host loop; tests/test_md_ref.py and tests/test_md_npt_ref.py the numpy restatements this file
-// follows).  One kernel, md_step_kernel<ENS>, instantiated per ensemble 0-4 on the argument block alignn_md_args
+// follows).  One kernel, md_step_kernel<ENS>, instantiated per ensemble 0-6 on the argument block alignn_md_args
 // (include/alignn_hip.h names every field); what the ensembles share is written once, what differs sits under if constexpr.
 //
 // Iteration t of the host loop evaluates the forces F_t at r_t; one md_step_kernel launch then
@@ -31,6 +31,17 @@
 // (every thread computes mu, the new cell and its inverse by cofactors alike; thread 0 writes them), then NVTBerendsen's
 // half-kick, fixcm and drift; frac uses the new inverse.  Andersen keeps v between the halves (velocities) and the positions
 // before the drift (scratch).
+//
+// Ensembles 5 and 6 are not ASE's: Nose-Hoover chain NVT and the isotropic MTK NPT in the explicit reversible form of Martyna,
+// Tuckerman, Tobias and Klein (Mol. Phys. 87, 1117, 1996), the barostat measure-preserving (Tuckerman et al., J. Phys. A 39,
+// 5629, 2006); tests/test_md_nose_hoover_ref.py is the restatement.  Per structure kT = kB T0, g = 3N, Q_0 = g kT ttime^2,
+// Q_k = kT ttime^2, W = (g + 3) kT ptime^2, the barostat's own chain Q'_k = kT ptime^2 (one degree of freedom), alpha = 1 + 3 / g.
+// A step is: chains dt/2 (barostat's, then the particles'), v_eps += dt/2 G_eps, half-kick, drift (cell and positions times
+// exp(v_eps dt)) | evaluate | half-kick, v_eps += dt/2 G_eps, chains dt/2 (particles', then barostat's); G_eps = (alpha sum
+// p^2/m + 3 V (P_vir - P_ext)) / W.  The 34 doubles of a structure's chain state (nhc_state) are read by every thread before the
+// first reduction's barrier; every lane runs the scalar chain from the reduced sum p^2/m (the same instructions, the same
+// bits) and thread 0 writes the state back at the end.  ttime <= 0 / ptime <= 0 switch a part off; both off is velocity Verlet
+// in the expressions of ensemble 0.  fixcm takes the centre-of-mass velocity out once, at t = 0.
 #include "../../include/alignn_hip.h"
 #include "common.h"
 
@@ -38,7 +49,16 @@ namespace {
 
 constexpr int MD_BLOCK = 256;
 constexpr int MD_WAVES = MD_BLOCK / ALIGNN_WAVE;
-enum { MD_NVE = 0, MD_LANGEVIN = 1, MD_BERENDSEN = 2, MD_ANDERSEN = 3, MD_NPT_BERENDSEN = 4 };
+constexpr int NHC_MAX = 8, NHC_STATE = 4 * NHC_MAX + 2;  // eta[8], v[8], eta'[8], v'[8], eps, v_eps
+enum {
+    MD_NVE = 0,
+    MD_LANGEVIN = 1,
+    MD_BERENDSEN = 2,
+    MD_ANDERSEN = 3,
+    MD_NPT_BERENDSEN = 4,
+    MD_NVT_NOSE_HOOVER = 5,
+    MD_NPT_NOSE_HOOVER = 6
+};
 enum { PURPOSE_LANGEVIN = 0, PURPOSE_MOMENTA = 1, PURPOSE_ANDERSEN = 2, PURPOSE_ANDERSEN_COM = 3 };
 
 // Philox4x32-10 (Salmon et al., SC'11), the counter c overwritten by the output block
@@ -95,7 +115,8 @@ using MdArgs = alignn_md_args;
 using MdShared = double (*)[MD_WAVES];
 
 // the ensembles that read the cell and record pressure, volume and cell; those that keep velocities and scratch between the halves
-constexpr bool md_has_cell(int ens) { return ens == MD_ANDERSEN || ens == MD_NPT_BERENDSEN; }
+constexpr bool md_has_cell(int ens) { return ens == MD_ANDERSEN || ens == MD_NPT_BERENDSEN || ens == MD_NPT_NOSE_HOOVER; }
+constexpr bool md_is_nose_hoover(int ens) { return ens == MD_NVT_NOSE_HOOVER || ens == MD_NPT_NOSE_HOOVER; }
 constexpr bool md_keeps_velocity(int ens) { return ens == MD_LANGEVIN || ens == MD_ANDERSEN; }
 
 // What structure s owns: its rows of the per-atom arrays (V, W: velocities and scratch, for the ensembles that keep them) and
@@ -448,6 +469,256 @@ __device__ __forceinline__ void md_begin_andersen(const MdArgs& a, const MdView&
     }
 }
 
+// sinh(x) / x; the series below |x| = 1e-2 (its next term is x^10 / 39916800 < 3e-28)
+__device__ __forceinline__ double sinhc(double x) {
+    const double x2 = x * x;
+    if (fabs(x) < 1e-2) return 1.0 + x2 / 6.0 + x2 * x2 / 120.0 + x2 * x2 * x2 / 5040.0 + x2 * x2 * x2 * x2 / 362880.0;
+    return sinh(x) / x;
+}
+
+// A Nose-Hoover chain by dt / 2 (MTK 1996, eqs. 25-29): a.nhc_loops loops over the a.nhc_order Suzuki-Yoshida weights.  K2 is
+// sum p^2 / m of what the chain thermostats, dof its degrees of freedom, Q0 / Qk the masses of link 0 / the others.  Returns the
+// factor s on the thermostatted momenta.  The loops over the links are unrolled to NHC_MAX and predicated on a.chain, so v and
+// eta stay in registers.
+__device__ __forceinline__ double nhc_half(const MdArgs& a, double K2, double dof, double kT, double Q0, double Qk,
+                                           double (&v)[NHC_MAX], double (&eta)[NHC_MAX]) {
+    const int M = a.chain, order = a.nhc_order, loops = a.nhc_loops;
+    // 1 / (2 - 2^(1/3)) and 1 / (4 - 4^(1/3)) with the cube roots as float64 literals
+    const double wside = order == 3 ? 1.0 / (2.0 - 1.2599210498948732) : order == 5 ? 1.0 / (4.0 - 1.5874010519681994) : 1.0;
+    const double wmid = 1.0 - (order - 1) * wside;
+    double s = 1.0;
+    auto G = [&](int k) {
+        if (k == 0) return (K2 * s * s - dof * kT) / Q0;
+        return ((k == 1 ? Q0 : Qk) * v[k - 1] * v[k - 1] - kT) / Qk;
+    };
+    for (int l = 0; l < loops; ++l) {
+        for (int j = 0; j < order; ++j) {
+            const double h = (2 * j + 1 == order ? wmid : wside) * (0.5 * a.dt) / loops;
+#pragma unroll
+            for (int k = 0; k < NHC_MAX; ++k)
+                if (k == M - 1) v[k] += 0.5 * h * G(k);
+#pragma unroll
+            for (int k = NHC_MAX - 2; k >= 0; --k)
+                if (k <= M - 2) {
+                    const double e = exp(-0.25 * h * v[k + 1]);
+                    v[k] *= e;
+                    v[k] += 0.5 * h * G(k);
+                    v[k] *= e;
+                }
+            s *= exp(-h * v[0]);
+#pragma unroll
+            for (int k = 0; k < NHC_MAX; ++k)
+                if (k < M) eta[k] += h * v[k];
+#pragma unroll
+            for (int k = 0; k < NHC_MAX - 1; ++k)
+                if (k <= M - 2) {
+                    const double e = exp(-0.25 * h * v[k + 1]);
+                    v[k] *= e;
+                    v[k] += 0.5 * h * G(k);
+                    v[k] *= e;
+                }
+#pragma unroll
+            for (int k = 0; k < NHC_MAX; ++k)
+                if (k == M - 1) v[k] += 0.5 * h * G(k);
+        }
+    }
+    return s;
+}
+
+// Ensembles 5 and 6, the whole launch: 1. - 3. of the header comment.  thermo / baro: the thermostat / the barostat is on.
+template <int ENS>
+__device__ __forceinline__ void md_step_nose_hoover(const MdArgs& a, const MdView& w, bool record, int64_t frame, MdShared sh) {
+    const int s = w.s, n = w.n, t = a.t;
+    const bool thermo = a.ttime > 0.0, baro = ENS == MD_NPT_NOSE_HOOVER && a.ptime > 0.0;
+    const double dt = a.dt, half_dt = 0.5 * dt;
+    const double kT = a.kB * a.t0_kelvin[s], g = 3.0 * n, alpha = 1.0 + 3.0 / g;
+    const double Q0 = g * kT * a.ttime * a.ttime, Qk = kT * a.ttime * a.ttime;
+    const double Qb = kT * a.ptime * a.ptime, Wm = (g + 3.0) * kT * a.ptime * a.ptime;
+    const double p_ext = baro ? a.pressure[s] : 0.0;
+    double* st = a.nhc_state + NHC_STATE * (int64_t)s;
+    double eta[NHC_MAX], v[NHC_MAX], etab[NHC_MAX], vb[NHC_MAX];
+#pragma unroll
+    for (int k = 0; k < NHC_MAX; ++k) {
+        eta[k] = st[k];
+        v[k] = st[NHC_MAX + k];
+        etab[k] = st[2 * NHC_MAX + k];
+        vb[k] = st[3 * NHC_MAX + k];
+    }
+    double eps = st[4 * NHC_MAX], veps = st[4 * NHC_MAX + 1];
+    double volume = 0.0, virial = 0.0;
+    if constexpr (md_has_cell(ENS)) {
+        volume = fabs(det3(w.C));
+        const double* S = a.stress ? a.stress + 9 * (int64_t)s : nullptr;
+        virial = S ? -(S[0] + S[4] + S[8]) / 3.0 : 0.0;
+    }
+    auto g_eps = [&](double K2) { return (alpha * K2 + 3.0 * volume * (virial - p_ext)) / Wm; };
+
+    if (t == 0 && a.fixcm) {  // once: p_i -= m_i sum p / sum m
+        double sums[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int i = threadIdx.x; i < n; i += MD_BLOCK) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sums[c] += w.P[3 * i + c];
+            sums[3] += w.M[i];
+        }
+        block_reduce<4, false>(sums, sh);
+        for (int i = threadIdx.x; i < n; i += MD_BLOCK) {
+            const double m = w.M[i];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) w.P[3 * i + c] -= m * sums[c] / sums[3];
+        }
+    }
+
+    // 1. the second half-kick, v_eps += dt/2 G_eps, the chains
+    double ke[1] = {0.0};
+    {
+        double ea = 1.0, eb = 1.0;
+        if (baro) {
+            const double x = alpha * veps * 0.25 * dt;
+            ea = exp(-alpha * veps * half_dt);
+            eb = exp(-x) * sinhc(x);
+        }
+        for (int i = threadIdx.x; i < n; i += MD_BLOCK) {
+            const double m = w.M[i];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int k = 3 * i + c;
+                double p = w.P[k];
+                if (t > 0) {
+                    if (baro)
+                        p = p * ea + half_dt * w.F[k] * eb;
+                    else
+                        p += half_dt * w.F[k];
+                    w.P[k] = p;
+                }
+                ke[0] += p * p / m;
+            }
+        }
+        block_reduce<1, false>(ke, sh);
+    }
+    if (t > 0) {
+        if (baro) veps += half_dt * g_eps(ke[0]);
+        if (thermo) {
+            const double sc = nhc_half(a, ke[0], g, kT, Q0, Qk, v, eta);
+            if (baro) veps *= nhc_half(a, Wm * veps * veps, 1.0, kT, Qb, Qb, vb, etab);
+            ke[0] = 0.0;
+            for (int i = threadIdx.x; i < n; i += MD_BLOCK) {
+                const double m = w.M[i];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double p = sc * w.P[3 * i + c];
+                    w.P[3 * i + c] = p;
+                    ke[0] += p * p / m;
+                }
+            }
+            block_reduce<1, false>(ke, sh);
+        }
+    }
+    const double KE = 0.5 * ke[0];
+
+    // 2.
+    if (record) {
+        double* TP = a.traj_positions ? a.traj_positions + 3 * (frame * a.n_rows + w.beg) : nullptr;
+        double* TM = a.traj_momenta ? a.traj_momenta + 3 * (frame * a.n_rows + w.beg) : nullptr;
+        // (per atom, the mapping of every loop that writes P and R: a thread records what it alone rewrites in 3., no barrier)
+        for (int i = threadIdx.x; i < n; i += MD_BLOCK) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (TM) TM[3 * i + c] = w.P[3 * i + c];
+                if (TP) TP[3 * i + c] = w.R[3 * i + c];
+            }
+        }
+        if (threadIdx.x == 0) {
+            md_record<ENS>(a, w, frame, KE, 2.0 * KE / (3.0 * n * a.kB), virial, volume);
+            if (a.conserved_out) {
+                double H = KE + a.energy[s];
+                if (thermo) {
+                    double q = 0.0, e = 0.0;
+#pragma unroll
+                    for (int k = 0; k < NHC_MAX; ++k)
+                        if (k < a.chain) {
+                            q += (k == 0 ? Q0 : Qk) * v[k] * v[k];
+                            if (k > 0) e += eta[k];
+                        }
+                    H += 0.5 * q + g * kT * eta[0] + kT * e;
+                }
+                if (baro) H += p_ext * volume + 0.5 * Wm * veps * veps;
+                if (baro && thermo) {
+                    double q = 0.0, e = 0.0;
+#pragma unroll
+                    for (int k = 0; k < NHC_MAX; ++k)
+                        if (k < a.chain) {
+                            q += Qb * vb[k] * vb[k];
+                            e += etab[k];
+                        }
+                    H += 0.5 * q + kT * e;
+                }
+                a.conserved_out[frame * gridDim.x + s] = H;
+            }
+        }
+    }
+
+    // 3. the chains, v_eps += dt/2 G_eps, the first half-kick, the drift
+    if (t < a.steps) {
+        if (thermo) {
+            if (baro) veps *= nhc_half(a, Wm * veps * veps, 1.0, kT, Qb, Qb, vb, etab);
+            const double sc = nhc_half(a, ke[0], g, kT, Q0, Qk, v, eta);
+            ke[0] = 0.0;
+            for (int i = threadIdx.x; i < n; i += MD_BLOCK) {
+                const double m = w.M[i];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double p = sc * w.P[3 * i + c];
+                    w.P[3 * i + c] = p;
+                    ke[0] += p * p / m;
+                }
+            }
+            if (baro) block_reduce<1, false>(ke, sh);
+        }
+        if (baro) {
+            veps += half_dt * g_eps(ke[0]);
+            const double x = alpha * veps * 0.25 * dt, y = veps * half_dt;
+            const double ea = exp(-alpha * veps * half_dt), eb = exp(-x) * sinhc(x);
+            const double er = exp(veps * dt), ed = exp(y) * sinhc(y);
+            eps += veps * dt;
+            double C[9], Ci[9];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) C[c] = er * w.C[c];
+            inverse3(C, Ci);
+            if (threadIdx.x == 0) {
+#pragma unroll
+                for (int c = 0; c < 9; ++c) {
+                    a.lattice[9 * (int64_t)s + c] = C[c];
+                    a.inv_lattice[9 * (int64_t)s + c] = Ci[c];
+                }
+            }
+            for (int i = threadIdx.x; i < n; i += MD_BLOCK) {
+                const double m = w.M[i];
+                double r[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double p = w.P[3 * i + c] * ea + half_dt * w.F[3 * i + c] * eb;
+                    w.P[3 * i + c] = p;
+                    r[c] = w.R[3 * i + c] * er + dt * (p / m) * ed;
+                }
+                md_drift_to(w, Ci, i, r);
+            }
+        } else {
+            md_begin_verlet(a, w);
+        }
+    }
+    if (threadIdx.x == 0) {  // (every thread read st before the first reduction's barrier)
+#pragma unroll
+        for (int k = 0; k < NHC_MAX; ++k) {
+            st[k] = eta[k];
+            st[NHC_MAX + k] = v[k];
+            st[2 * NHC_MAX + k] = etab[k];
+            st[3 * NHC_MAX + k] = vb[k];
+        }
+        st[4 * NHC_MAX] = eps;
+        st[4 * NHC_MAX + 1] = veps;
+    }
+}
+
 template <int ENS>
 __global__ __launch_bounds__(MD_BLOCK) void md_step_kernel(const MdArgs a) {
     __shared__ double sh[6][MD_WAVES];
@@ -461,6 +732,10 @@ __global__ __launch_bounds__(MD_BLOCK) void md_step_kernel(const MdArgs a) {
     // 1. + 2.
     const bool record = a.t % a.interval == 0;
     const int64_t frame = a.t / a.interval;
+    if constexpr (md_is_nose_hoover(ENS)) {
+        md_step_nose_hoover<ENS>(a, w, record, frame, sh);
+        return;
+    }
     const double KE = md_finish<ENS>(a, w, record, frame, sh);
     const double T = 2.0 * KE / (3.0 * w.n * a.kB);
     double volume = 0.0, virial = 0.0;
@@ -518,19 +793,28 @@ extern "C" int alignn_md_step(const alignn_md_args* args, alignn_stream_t stream
     const MdArgs& a = *args;
     const int ens = a.ensemble;
     if (a.n_structures < 1 || !a.status || !a.epot || !a.ekin || !a.temperature || a.interval < 1 || a.t < 0 || a.t > a.steps ||
-        ens < MD_NVE || ens > MD_NPT_BERENDSEN)
+        ens < MD_NVE || ens > MD_NPT_NOSE_HOOVER)
         return (int)hipErrorInvalidValue;
     if (ens != MD_NVE && !a.t0_kelvin) return (int)hipErrorInvalidValue;
     if (md_keeps_velocity(ens) && (!a.velocities || !a.scratch || !a.seeds)) return (int)hipErrorInvalidValue;
     if (md_has_cell(ens) && (!a.lattice || !a.inv_lattice)) return (int)hipErrorInvalidValue;
     if (ens == MD_NPT_BERENDSEN && (!a.stress || !a.pressure || !a.compressibility)) return (int)hipErrorInvalidValue;
+    if (md_is_nose_hoover(ens)) {
+        if (!a.nhc_state || a.chain < 1 || a.chain > NHC_MAX || a.nhc_loops < 1 || a.nhc_loops > 16 ||
+            !(a.nhc_order == 1 || a.nhc_order == 3 || a.nhc_order == 5))
+            return (int)hipErrorInvalidValue;
+        if (ens == MD_NPT_NOSE_HOOVER && a.ptime > 0.0 && (!a.stress || !a.pressure || !a.lattice || !a.inv_lattice))
+            return (int)hipErrorInvalidValue;
+    }
     hipStream_t st = (hipStream_t)stream;
     switch (ens) {
         case MD_NVE: md_launch<MD_NVE>(a, st); break;
         case MD_LANGEVIN: md_launch<MD_LANGEVIN>(a, st); break;
         case MD_BERENDSEN: md_launch<MD_BERENDSEN>(a, st); break;
         case MD_ANDERSEN: md_launch<MD_ANDERSEN>(a, st); break;
-        default: md_launch<MD_NPT_BERENDSEN>(a, st); break;
+        case MD_NPT_BERENDSEN: md_launch<MD_NPT_BERENDSEN>(a, st); break;
+        case MD_NVT_NOSE_HOOVER: md_launch<MD_NVT_NOSE_HOOVER>(a, st); break;
+        default: md_launch<MD_NPT_NOSE_HOOVER>(a, st); break;
     }
     ALIGNN_CHECK_LAUNCH();
     return 0;

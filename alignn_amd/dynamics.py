@@ -38,7 +38,9 @@ FS = 0.09822694788464063
 KB = 8.617330337217213e-05
 BAR = 1e-4 / 160.21766208  # eV/A^3 (160.21766208 eV/A^3 per GPa, the constant of _structures.ForceEvaluator)
 
-ENSEMBLES = {"nve": 0, "nvt_langevin": 1, "nvt_berendsen": 2, "nvt_andersen": 3, "npt_berendsen": 4}
+ENSEMBLES = {"nve": 0, "nvt_langevin": 1, "nvt_berendsen": 2, "nvt_andersen": 3, "npt_berendsen": 4, "nvt_nose_hoover": 5,
+             "npt_nose_hoover": 6}
+NHC_MAX, NHC_STATE = 8, 34  # links per chain at the most; the doubles of a structure's chain state (alignn_md_args.nhc_state)
 
 
 @dataclass
@@ -49,7 +51,9 @@ class MDResult:
     ``forces`` (eV/A) are those of the final state, per structure in the input order.  ``n_evals`` counts batched force
     evaluations (``steps + 1``).  ``npt_berendsen`` only (else None): ``lattices`` [B, 3, 3] the final cells (``positions`` are
     Cartesian and unwrapped in them), ``pressure`` (eV/A^3, ``-tr(stress) / 3 + 2 KE / (3 V)``; divide by ``BAR`` for bar) and
-    ``volume`` (A^3) [n_frames, B], ``traj_lattices`` [n_frames, B, 3, 3] (``trajectory=True``)."""
+    ``volume`` (A^3) [n_frames, B], ``traj_lattices`` [n_frames, B, 3, 3] (``trajectory=True``).  ``npt_nose_hoover`` fills them
+    too (``pressure`` only with the barostat on: without it no stress is evaluated).  ``conserved`` [n_frames, B] (eV;
+    ``nvt_nose_hoover`` / ``npt_nose_hoover`` only): the extended system's conserved energy H'."""
 
     epot: torch.Tensor
     ekin: torch.Tensor
@@ -64,6 +68,7 @@ class MDResult:
     pressure: Optional[torch.Tensor] = None
     volume: Optional[torch.Tensor] = None
     traj_lattices: Optional[torch.Tensor] = None
+    conserved: Optional[torch.Tensor] = None
 
 
 def berendsen_taut(taut: Optional[float], timestep: float) -> float:
@@ -100,7 +105,8 @@ def _seeds(seed, B: int) -> List[int]:
 def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Optional[Sequence], masses: Sequence, *,
            ensemble: str = "nve", timestep: float = 0.01, steps: int = 1000, interval: int = 1, temperature_K=300.0,
            friction: float = 1e-4, taut: Optional[float] = None, andersen_prob: float = 0.1, taup: Optional[float] = None,
-           pressure=None, compressibility=None, stress_weight: float = 1.0, initial_temperature_K=None,
+           pressure=None, compressibility=None, ttime: Optional[float] = None, ptime: Optional[float] = None, chain: int = 3,
+           nhc_loops: int = 1, nhc_order: int = 3, stress_weight: float = 1.0, initial_temperature_K=None,
            momenta: Optional[Sequence] = None, fixcm: bool = True, seed=0, trajectory: bool = True, replay: bool = False, cutoff: float = 8.0,
            max_neighbors: int = 12, neighbor_strategy: str = "k-nearest", intensive: bool = True, force_multiplier: float = 1.0,
            forces_fn: Optional[Callable] = None, device=None) -> MDResult:
@@ -118,13 +124,37 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
     at least ``timestep``; ``pressure`` in bar and ``compressibility`` in 1/bar, each a number or one per structure, both
     required; the cell and the positions are scaled every step, ``MDResult.lattices`` are the final cells).  NPT needs
     stresses: the model must predict per-crystal stresses, scaled by ``stress_weight`` as in ``relax``, and ``forces_fn`` must
-    return ``(energy, forces, stress)``; the cells it gets change from step to step.  ``timestep`` in fs.  ``temperature_K`` and ``initial_temperature_K`` are a number or one per structure.
+    return ``(energy, forces, stress)``; the cells it gets change from step to step.  ``"nvt_nose_hoover"`` / ``"npt_nose_hoover"``
+    are not ASE's: Nose-Hoover chains and the isotropic MTK barostat in the explicit reversible form of Martyna, Tuckerman,
+    Tobias and Klein (Mol. Phys. 87, 1117, 1996; tests/test_md_nose_hoover_ref.py restates it): ``temperature_K`` (> 0),
+    ``ttime`` / ``ptime`` the thermostat's / barostat's time constants in fs, at least ``timestep`` (chain masses
+    ``Q_0 = 3N kT ttime^2``, ``Q_k = kT ttime^2``, barostat mass ``(3N + 3) kT ptime^2``), ``chain`` links (1..8), ``nhc_loops``
+    (1..16) loops of the Suzuki-Yoshida weights of ``nhc_order`` (1, 3 or 5), ``pressure`` in bar.  ``nvt_nose_hoover`` needs
+    ``ttime``; ``npt_nose_hoover`` takes None for either: ``ttime=None`` is no thermostat, ``ptime=None`` no barostat (then no
+    ``pressure`` and no stresses are needed), both None constant cell and energy - what the reference's
+    ``run_npt_nose_hoover`` runs.  ``MDResult.conserved`` is their conserved energy.  ``timestep`` in fs.  ``temperature_K`` and ``initial_temperature_K`` are a number or one per structure.
     The start momenta: Maxwell-Boltzmann at ``initial_temperature_K`` when given, else ``momenta`` (B [n_i, 3]), else zero.
-    ``fixcm``: the centre-of-mass correction of Langevin, NVTBerendsen / NPTBerendsen and Andersen.  ``seed``: an int or B ints in [0, 2^64), the key of
+    ``fixcm``: the centre-of-mass correction of Langevin, NVTBerendsen / NPTBerendsen and Andersen; for the Nose-Hoover
+    ensembles the centre-of-mass velocity is removed from the start momenta, once.  ``seed``: an int or B ints in [0, 2^64), the key of
     each structure's random stream.  ``replay``: evaluate through ``md.GraphedForceField`` (the same bits)."""
     if ensemble not in ENSEMBLES:
         raise ValueError(f"run_md: ensemble must be one of {sorted(ENSEMBLES)}, got {ensemble!r}")
-    npt, andersen = ensemble == "npt_berendsen", ensemble == "nvt_andersen"
+    andersen, nose = ensemble == "nvt_andersen", ensemble in ("nvt_nose_hoover", "npt_nose_hoover")
+    if nose:
+        if ensemble == "nvt_nose_hoover" and ttime is None:
+            raise ValueError("run_md: nvt_nose_hoover needs ttime (fs)")
+        for name, val in (("ttime", ttime),) + ((("ptime", ptime),) if ensemble == "npt_nose_hoover" else ()):
+            if val is not None and not (isinstance(val, numbers.Real) and np.isfinite(val) and val >= timestep):
+                raise ValueError(f"run_md: {name} must be finite and at least the timestep")
+        if not (isinstance(chain, numbers.Integral) and 1 <= chain <= NHC_MAX):
+            raise ValueError(f"run_md: chain must be an integer in 1..{NHC_MAX}")
+        if not (isinstance(nhc_loops, numbers.Integral) and 1 <= nhc_loops <= 16):
+            raise ValueError("run_md: nhc_loops must be an integer in 1..16")
+        if nhc_order not in (1, 3, 5):
+            raise ValueError("run_md: nhc_order must be 1, 3 or 5")
+    baro = ensemble == "npt_nose_hoover" and ptime is not None  # the MTK barostat is on
+    cell = ensemble in ("npt_berendsen", "npt_nose_hoover")  # the NPT outputs are filled
+    npt = ensemble == "npt_berendsen" or baro  # stresses are needed
     ns = check_inputs("run_md", model, lattices, positions, atom_features, masses, forces_fn=forces_fn, stress=npt)
     B = len(ns)
     if not (isinstance(steps, numbers.Integral) and isinstance(interval, numbers.Integral)) or steps < 0 or interval < 1:
@@ -143,13 +173,20 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
         raise ValueError("run_md: andersen_prob must lie in [0, 1]")
     taup_ase = barostat_taup(taup)
     p_target = comp = None
-    if npt:
+    if nose and (ttime is not None or baro) and not all(v > 0.0 for v in t0):
+        raise ValueError("run_md: a Nose-Hoover thermostat or barostat needs temperature_K > 0")
+    if baro:
+        if pressure is None:
+            raise ValueError("run_md: npt_nose_hoover with ptime needs pressure (bar)")
+        p_target = [v * BAR for v in _per_structure(pressure, B, "pressure", signed=True)]
+    elif npt:
         if not (taup_ase >= timestep * FS and np.isfinite(taup_ase)):
             raise ValueError("run_md: taup must be at least the timestep")
         if pressure is None or compressibility is None:
             raise ValueError("run_md: npt_berendsen needs pressure (bar) and compressibility (1/bar)")
         p_target = [v * BAR for v in _per_structure(pressure, B, "pressure", signed=True)]
         comp = [v / BAR for v in _per_structure(compressibility, B, "compressibility")]
+    if npt:
         if not (isinstance(stress_weight, numbers.Real) and np.isfinite(stress_weight)):
             raise ValueError("run_md: stress_weight must be a finite number")
     t_init = None if initial_temperature_K is None else _per_structure(initial_temperature_K, B, "initial_temperature_K")
@@ -187,13 +224,18 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
         traj_p = torch.zeros(n_frames, N, 3, dtype=torch.float64, device=dev) if trajectory else None
         traj_m = torch.zeros(n_frames, N, 3, dtype=torch.float64, device=dev) if trajectory else None
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        lat_cur = p_out = v_out = traj_l = None
-        if npt:
+        lat_cur = p_out = v_out = traj_l = p_target_t = comp_t = nhc = conserved = None
+        if cell:
             lat_cur = packed.lat.clone()  # the kernel rewrites it and ``inv``
-            p_target_t = torch.tensor(p_target, dtype=torch.float64, device=dev)
-            comp_t = torch.tensor(comp, dtype=torch.float64, device=dev)
-            p_out, v_out = (torch.zeros(n_frames, B, dtype=torch.float64, device=dev) for _ in range(2))
+            v_out = torch.zeros(n_frames, B, dtype=torch.float64, device=dev)
             traj_l = torch.zeros(n_frames, B, 3, 3, dtype=torch.float64, device=dev) if trajectory else None
+        if npt:
+            p_target_t = torch.tensor(p_target, dtype=torch.float64, device=dev)
+            comp_t = None if comp is None else torch.tensor(comp, dtype=torch.float64, device=dev)
+            p_out = torch.zeros(n_frames, B, dtype=torch.float64, device=dev)
+        if nose:
+            nhc = torch.zeros(B, NHC_STATE, dtype=torch.float64, device=dev)
+            conserved = torch.zeros(n_frames, B, dtype=torch.float64, device=dev)
         # fixed per-structure views: the same lattice tensors every step keep neighbors' lattice tables cached
         lat_v = [packed.lat[s] for s in range(B)]
         pos_v, frac_v = packed.rows(pos), packed.rows(frac)
@@ -203,14 +245,17 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
         every = list(range(B))
         args = _lib.MdArgs(
             atom_ptr=atom_ptr.data_ptr(), masses=mass.data_ptr(), t0_kelvin=t0_t.data_ptr(), seeds=seed_t.data_ptr(),
-            pressure=p_target_t.data_ptr() if npt else None, compressibility=comp_t.data_ptr() if npt else None,
-            lattice=(lat_cur if npt else packed.lat).data_ptr() if npt or andersen else None, inv_lattice=inv.data_ptr(),
+            pressure=_lib.ptr(p_target_t), compressibility=_lib.ptr(comp_t),
+            lattice=(lat_cur if cell else packed.lat).data_ptr() if cell or andersen else None, inv_lattice=inv.data_ptr(),
             momenta=mom.data_ptr(), positions=pos.data_ptr(), frac=frac.data_ptr(), velocities=_lib.ptr(vel),
             scratch=_lib.ptr(scratch), status=status.data_ptr(), epot=epot.data_ptr(), ekin=ekin.data_ptr(),
             temperature=temp.data_ptr(), pressure_out=_lib.ptr(p_out), volume_out=_lib.ptr(v_out),
             traj_positions=_lib.ptr(traj_p), traj_momenta=_lib.ptr(traj_m), traj_lattice=_lib.ptr(traj_l),
             n_structures=B, interval=int(interval), steps=int(steps), ensemble=ens, fixcm=int(bool(fixcm)), dt=dt,
-            friction=float(friction), andersen_prob=float(andersen_prob), taut=tau, taup=taup_ase, kB=KB)
+            friction=float(friction), andersen_prob=float(andersen_prob), taut=tau, taup=taup_ase, kB=KB,
+            nhc_state=_lib.ptr(nhc), conserved_out=_lib.ptr(conserved), chain=int(chain) if nose else 0,
+            nhc_loops=int(nhc_loops) if nose else 0, nhc_order=int(nhc_order) if nose else 0,
+            ttime=float(ttime) * FS if nose and ttime is not None else 0.0, ptime=float(ptime) * FS if baro else 0.0)
 
         for t in range(steps + 1):
             if npt:
@@ -228,4 +273,4 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
         return MDResult(epot=epot, ekin=ekin, temperature=temp, traj_positions=traj_p, traj_momenta=traj_m,
                         positions=[p.clone() for p in pos_v], momenta=[p.clone() for p in packed.rows(mom)],
                         forces=[f.clone() for f in packed.rows(forces)], n_evals=steps + 1, lattices=lat_cur, pressure=p_out,
-                        volume=v_out, traj_lattices=traj_l)
+                        volume=v_out, traj_lattices=traj_l, conserved=conserved)

@@ -977,7 +977,7 @@ size_t alignn_fire_args_sizeof(void); /* a binding checks its own packing agains
 /* ------------------------------------------------------------------------------------------
  * Batched molecular dynamics (csrc/dynamics.hip; alignn_amd/dynamics.py is the host loop): ASE 3.22.1's VelocityVerlet
  * (ensemble 0), Langevin (1), NVTBerendsen (2), Andersen (3) and NPTBerendsen (4; isotropic) as alignn/ff/ff.py:419-600 runs
- * them, float64, ASE units (eV, A, amu, A sqrt(amu / eV)).  One workgroup per structure s < n_structures; it owns atoms
+ * them, and Nose-Hoover chain NVT (5) and isotropic MTK NPT (6), float64, ASE units (eV, A, amu, A sqrt(amu / eV)).  One workgroup per structure s < n_structures; it owns atoms
  * [atom_ptr[s], atom_ptr[s+1]) of the [N] / [N][3] arrays and row s of the [B] / [B][3][3] (row-major) ones.  One launch per
  * evaluation t = 0 .. steps: finish step t (t > 0: the second half-kick with these forces), record frame t / interval when
  * t % interval == 0, then, unless t == steps, begin step t + 1 (Berendsen's velocity scaling; the first half-kick; fixcm's
@@ -990,22 +990,32 @@ size_t alignn_fire_args_sizeof(void); /* a binding checks its own packing agains
  * t, block, purpose): Langevin blocks 0..2 of purpose 0 (6 normals); Andersen blocks 0..3 of purpose 2 (0, 1: normals; 2, 3:
  * uniforms in (0, 1]) and, for the centre of mass, blocks 0..1 of (0, t, ., 3).  Fixed-order reductions: a structure's
  * trajectory is bit-identical whatever else shares the launch.  "Required" below: NULL is hipErrorInvalidValue.
+ * Ensembles 5 (nvt_nose_hoover) and 6 (npt_nose_hoover; isotropic) are not ASE's: Nose-Hoover chains and the MTK barostat in
+ * the explicit reversible form of Martyna, Tuckerman, Tobias and Klein (Mol. Phys. 87, 1117, 1996; the barostat as in Tuckerman
+ * et al., J. Phys. A 39, 5629, 2006).  With kT = kB t0_kelvin[s], g = 3 n: chain masses Q_0 = g kT ttime^2, Q_k = kT ttime^2,
+ * barostat mass W = (g + 3) kT ptime^2, its own chain Q'_k = kT ptime^2.  A launch finishes step t (half-kick, v_eps += dt/2
+ * G_eps, the particles' chain dt/2, the barostat's chain dt/2), records, and begins step t + 1 in the mirrored order (chains,
+ * v_eps, half-kick, drift with cell and positions times exp(v_eps dt)); G_eps = ((1 + 3/g) sum p^2/m - V tr(stress) - 3 V
+ * pressure) / W.  conserved_out: H' = KE + energy + sum_k Q_k v_k^2 / 2 + g kT eta_0 + kT sum_{k>=1} eta_k + pressure V + W
+ * v_eps^2 / 2 + sum_k Q'_k v'_k^2 / 2 + kT sum_k eta'_k (the parts that are on).  fixcm (5, 6): at t = 0 only, momenta -= m sum
+ * p / sum m.  Out-of-range chain / nhc_loops / nhc_order are hipErrorInvalidValue.
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_md_args {
     /* inputs of the step: the evaluation at the current positions */
     const double* forces;  /* [n_rows][3] */
     const double* energy;  /* [B] */
-    const double* stress;  /* [B][3][3], eV/A^3, ASE's sign: required by 4; 3: NULL records no pressure; 0-2: ignored */
+    const double* stress;  /* [B][3][3], eV/A^3, ASE's sign: required by 4 and by 6 with ptime > 0; 3, 6: NULL records no
+                              pressure; 0-2, 5: ignored */
     int64_t n_rows;        /* must equal atom_ptr[n_structures], else status[0] = -1 and nothing is written */
     const int32_t* atom_ptr;       /* [B + 1] */
     const double* masses;          /* [N] */
-    const double* t0_kelvin;       /* [B] thermostat targets: required by 1-4 */
+    const double* t0_kelvin;       /* [B] thermostat targets: required by 1-6 */
     const uint64_t* seeds;         /* [B]: required by 1 and 3 */
-    const double* pressure;        /* [B] barostat targets, eV/A^3: required by 4 */
+    const double* pressure;        /* [B] barostat targets, eV/A^3: required by 4 and by 6 with ptime > 0 */
     const double* compressibility; /* [B] A^3/eV: required by 4 */
     /* state */
-    double* lattice;     /* [B][3][3]: required by 3 (read) and 4 (rewritten); 0-2: ignored */
-    double* inv_lattice; /* [B][3][3]: frac = positions times it, wrapped into [0, 1); 4 rewrites it */
+    double* lattice;     /* [B][3][3]: required by 3 (read), 4 and 6 (rewritten; 6: while ptime > 0); 0-2, 5: ignored */
+    double* inv_lattice; /* [B][3][3]: frac = positions times it, wrapped into [0, 1); 4 and 6 rewrite it */
     double* momenta;     /* [N][3] */
     double* positions;   /* [N][3] Cartesian, unwrapped */
     double* frac;        /* [N][3] for the next neighbour search */
@@ -1016,17 +1026,24 @@ typedef struct alignn_md_args {
     double* epot;           /* [frames][B] = energy */
     double* ekin;           /* [frames][B] KE = 0.5 sum p^2 / m */
     double* temperature;    /* [frames][B] 2 KE / (3 n kB) */
-    double* pressure_out;   /* 3, 4: [frames][B] -tr(stress) / 3 + 2 KE / (3 V); needs stress */
-    double* volume_out;     /* 3, 4: [frames][B] V = |det lattice| */
+    double* pressure_out;   /* 3, 4, 6: [frames][B] -tr(stress) / 3 + 2 KE / (3 V); needs stress */
+    double* volume_out;     /* 3, 4, 6: [frames][B] V = |det lattice| */
     double* traj_positions; /* [frames][N][3] */
     double* traj_momenta;   /* [frames][N][3] */
-    double* traj_lattice;   /* 3, 4: [frames][B][3][3] */
+    double* traj_lattice;   /* 3, 4, 6: [frames][B][3][3] */
     double* noise_out;      /* tests: 1: [N][18] per atom xi[3], eta[3], the 12 Philox words as doubles; 3: [N][36] per atom 4
                                normals, 4 uniforms, 16 words, then the structure's 4 centre-of-mass normals and their 8 words
                                (fixcm only) */
     /* scalars */
     int n_structures, t, interval, steps, ensemble, fixcm;
     double dt, friction, andersen_prob, taut, taup, kB; /* friction: 1; andersen_prob: 3; taut: 2, 4; taup: 4 */
+    /* Nose-Hoover chains (5) and isotropic MTK (6): NULL / 0 is off, and 0-4 ignore them */
+    double* nhc_state;     /* [B][34] per structure eta[8], v[8] (the particles' chain: positions and velocities of its links),
+                              eta'[8], v'[8] (the barostat's chain), eps = ln(V / V0) / 3, v_eps; zero at the start; required by
+                              5 and 6, rewritten every launch */
+    double* conserved_out; /* 5, 6: [frames][B] the conserved energy H' (eV), see above */
+    int chain, nhc_loops, nhc_order; /* 5, 6: links per chain 1..8, n_c 1..16, the Suzuki-Yoshida order 1, 3 or 5 */
+    double ttime, ptime;   /* 5, 6: the thermostat's / (6) the barostat's time constant, ASE time units; <= 0: that part is off */
 } alignn_md_args;
 int alignn_md_step(const alignn_md_args* args, alignn_stream_t stream);
 size_t alignn_md_args_sizeof(void); /* a binding checks its own packing against this */

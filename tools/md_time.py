@@ -1,6 +1,6 @@
 """Batched MD (alignn_amd.run_md) timed per step: B in {1, 16, 64} crystals of 60 atoms (synthetic.make_crystal), the
 tools/md_step.py model, at 300 K from a Maxwell-Boltzmann start (--ensemble: any of run_md's; npt_berendsen at 1 bar with a
-compressibility of 1e-6 / bar).  Beside each batch, the same structures run one at a
+compressibility of 1e-6 / bar; nvt_nose_hoover with ttime 25 fs, npt_nose_hoover with that, ptime 250 fs and 1 bar).  Beside each batch, the same structures run one at a
 time through the same function - what the reference's per-structure ForceField MD amounts to - and both with and without
 replay (md.GraphedForceField).  Prints one JSON line per B."""
 import argparse, json, os, sys, time
@@ -34,6 +34,10 @@ kw = dict(ensemble=args.ensemble, timestep=1.0, steps=args.steps, temperature_K=
           initial_temperature_K=300.0, trajectory=False)
 if args.ensemble == "npt_berendsen":
     kw.update(pressure=1.0, compressibility=1e-6)
+if args.ensemble == "nvt_nose_hoover":
+    kw.update(ttime=25.0)
+if args.ensemble == "npt_nose_hoover":
+    kw.update(ttime=25.0, ptime=250.0, pressure=1.0)
 
 
 def timed(B, one_at_a_time, replay):
