@@ -1,7 +1,7 @@
 // Batched molecular dynamics: ASE 3.22.1's VelocityVerlet, Langevin, NVTBerendsen, Andersen and NPTBerendsen (ase/md/*.py) as
 // the reference's ForceField.run_nve_velocity_verlet / run_nvt_langevin / run_nvt_berendsen / run_nvt_andersen /
 // run_npt_berendsen drive them (alignn/ff/ff.py:419-600), every structure's integrator state on the device
-// (alignn_amd/dynamics.py is the host loop; tests/test_md_ref.py and tests/test_md_npt_ref.py the numpy restatements this file
+// (alignn_amd/dynamics.py is the host loop; tests/md_ref.py and tests/md_npt_ref.py the numpy restatements this file
 // follows).  One kernel, md_step_kernel<ENS>, instantiated per ensemble 0-6 on the argument block alignn_md_args
 // (include/alignn_hip.h names every field); what the ensembles share is written once, what differs sits under if constexpr.
 //
@@ -34,7 +34,7 @@
 //
 // Ensembles 5 and 6 are not ASE's: Nose-Hoover chain NVT and the isotropic MTK NPT in the explicit reversible form of Martyna,
 // Tuckerman, Tobias and Klein (Mol. Phys. 87, 1117, 1996), the barostat measure-preserving (Tuckerman et al., J. Phys. A 39,
-// 5629, 2006); tests/test_md_nose_hoover_ref.py is the restatement.  Per structure kT = kB T0, g = 3N, Q_0 = g kT ttime^2,
+// 5629, 2006); tests/md_nose_hoover_ref.py is the restatement.  Per structure kT = kB T0, g = 3N, Q_0 = g kT ttime^2,
 // Q_k = kT ttime^2, W = (g + 3) kT ptime^2, the barostat's own chain Q'_k = kT ptime^2 (one degree of freedom), alpha = 1 + 3 / g.
 // A step is: chains dt/2 (barostat's, then the particles'), v_eps += dt/2 G_eps, half-kick, drift (cell and positions times
 // exp(v_eps dt)) | evaluate | half-kick, v_eps += dt/2 G_eps, chains dt/2 (particles', then barostat's); G_eps = (alpha sum

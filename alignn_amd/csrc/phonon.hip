@@ -1,6 +1,6 @@
 // Batched finite-displacement phonons: ASE 3.22.1's Phonons (ase/phonons.py: run, read, band_structure, get_dos) as the
 // reference's ase_phonon drives it (alignn/ff/ff.py:1337), every structure's arrays on the device (alignn_amd/phonons.py is
-// the host loop; tests/test_phonons_ref.py the numpy restatement this file follows).  float64 throughout.
+// the host loop; tests/phonons_ref.py the numpy restatement this file follows).  float64 throughout.
 //
 //   phonon_displace_kernel   the wrapped fractional (and unwrapped Cartesian) coordinates of the displaced supercells of a
 //                            chunk of model evaluations, one workgroup per supercell;

@@ -18,10 +18,10 @@
 // Generalised forces: atom rows f F; cell rows the virial W = -V sym(stress) (the "naive" force) or, when it points too far
 // from it, the exact gradient -d E / d logm(F), the Frechet derivative of expm at L = X_c / c applied to W expm(-L); either
 // one / c.  X_c is kept as state instead of recomputing logm(F) from the cell every step (the round trip is the identity to
-// rounding: tests/test_relax_cell.py).  The cell rows are thread 0's.
+// rounding: tests/relax_ref.py).  The cell rows are thread 0's.
 //
 // Constraints (the last fields of the block, NULL / 0 = off and then the same instructions on the same values as without
-// them; tests/test_relax_constraints.py restates them).  FixAtoms: a fixed atom's force row reads as zero everywhere but in
+// them; tests/relax_ref.py restates them).  FixAtoms: a fixed atom's force row reads as zero everywhere but in
 // forces_out, so its velocity stays zero and its row in place; the move leaves its row and its frac unwritten.  ExpCellFilter's
 // scalar_pressure, hydrostatic_strain and mask shape the virial W before the naive / exact choice, constant_volume takes the
 // trace off the chosen force after it.  The flags are the same for a whole workgroup: scalar branches.

@@ -13,7 +13,7 @@ one host-side graph build per step.  ``run_md`` integrates B independent crystal
    pressure, the scaled cell, its inverse and the scaled positions too.
 
 No structure retires, so nothing is read back per step beyond what the neighbour search reads.  The semantics are ASE 3.22.1's
-(``environment.yml``), restated in numpy in tests/test_md_ref.py and tests/test_md_npt_ref.py.  The random numbers are the
+(``environment.yml``), restated in numpy in tests/md_ref.py and tests/md_npt_ref.py.  The random numbers are the
 project's own counter-based stream (Philox4x32-10 per structure, csrc/dynamics.hip): a structure's trajectory is the same bits
 alone or in a batch.
 """
@@ -126,7 +126,7 @@ def run_md(model, lattices: Sequence, positions: Sequence, atom_features: Option
     stresses: the model must predict per-crystal stresses, scaled by ``stress_weight`` as in ``relax``, and ``forces_fn`` must
     return ``(energy, forces, stress)``; the cells it gets change from step to step.  ``"nvt_nose_hoover"`` / ``"npt_nose_hoover"``
     are not ASE's: Nose-Hoover chains and the isotropic MTK barostat in the explicit reversible form of Martyna, Tuckerman,
-    Tobias and Klein (Mol. Phys. 87, 1117, 1996; tests/test_md_nose_hoover_ref.py restates it): ``temperature_K`` (> 0),
+    Tobias and Klein (Mol. Phys. 87, 1117, 1996; tests/md_nose_hoover_ref.py restates it): ``temperature_K`` (> 0),
     ``ttime`` / ``ptime`` the thermostat's / barostat's time constants in fs, at least ``timestep`` (chain masses
     ``Q_0 = 3N kT ttime^2``, ``Q_k = kT ttime^2``, barostat mass ``(3N + 3) kT ptime^2``), ``chain`` links (1..8), ``nhc_loops``
     (1..16) loops of the Suzuki-Yoshida weights of ``nhc_order`` (1, 3 or 5), ``pressure`` in bar.  ``nvt_nose_hoover`` needs

@@ -13,7 +13,7 @@ q-point, for a band path and a 20 x 20 x 20 DOS mesh.  ``phonons`` does this for
 4. ``alignn_phonon_eigh``: D(q) and its eigenvalues (and eigenvectors) in one workgroup per (structure, q), parallel cyclic
    Jacobi in LDS; ``alignn_phonon_dos``: the Gaussian-smeared DOS over a Monkhorst-Pack mesh.
 
-The semantics are ASE 3.22.1's ``Phonons`` (``environment.yml``), restated in numpy in tests/test_phonons_ref.py.
+The semantics are ASE 3.22.1's ``Phonons`` (``environment.yml``), restated in numpy in tests/phonons_ref.py.
 """
 
 from __future__ import annotations

@@ -23,6 +23,13 @@ def state_dict_from_golden(z, prefix="sd."):
     return {k[len(prefix):]: torch.from_numpy(v) for k, v in z.items() if k.startswith(prefix)}
 
 
+def ref_keys(u, v, r, lat, frac):
+    """The (u, v, periodic image) key of every bond of an edge list."""
+    cart = frac @ lat
+    img = np.rint((np.asarray(r, np.float64) - (cart[v] - cart[u])) @ np.linalg.inv(lat)).astype(np.int64)
+    return list(zip(u.tolist(), v.tolist(), map(tuple, img.tolist())))
+
+
 def rel_err(a, b, floor=1e-30):
     """max |a-b| / max(|b|_inf, floor): the 'within 1e-4 rel' of BASELINE.json's north_star,
     measured against the tensor's scale (elementwise relative error is meaningless at zero crossings).

@@ -1,5 +1,5 @@
 """Batched MD on the device (csrc/dynamics.hip, alignn_amd/dynamics.py) against the float64 restatement of ASE's integrators in
-test_md_ref.py: (1) the kernel alone, step by step, for the three ensembles, the exported random numbers against the numpy
+md_ref.py: (1) the kernel alone, step by step, for the three ensembles, the exported random numbers against the numpy
 stream; (2) NVE on periodic spring crystals: second-order energy error, time reversal; (3) the Langevin and Berendsen
 thermostats and the Maxwell-Boltzmann start; (4) a structure alone vs. in a batch, bit for bit; (5) run_md with an
 ALIGNNAtomWise against a host loop over the same model; (6) replay and run-to-run bit identity."""
@@ -10,23 +10,14 @@ import numpy as np
 import pytest
 import torch
 
-from alignn_amd import ALIGNNAtomWise, ALIGNNAtomWiseConfig, _lib, neighbors
+from alignn_amd import _lib
 from alignn_amd.dynamics import ENSEMBLES, FS, KB, berendsen_taut, run_md
 from alignn_amd.synthetic import make_crystal
-from tests.test_md_ref import (BerendsenRef, LangevinRef, VerletRef, kinetic_energy, maxwell_boltzmann, normals,
-                               stream_words, temperature)
-from tests.test_relax_cell import spring_list
+from tests.md_ref import (BerendsenRef, LangevinRef, VerletRef, kinetic_energy, maxwell_boltzmann, normals, stream_words,
+                          temperature)
+from tests.sim_gpu import DEV, _md_crystals as _crystals, _model, _rel, _second_half_mean, _spring_crystals, _t, host_md_loop
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _t(x, dtype=torch.float64):
-    return torch.tensor(np.asarray(x), dtype=dtype, device=DEV)
-
-
-def _rel(got, want):
-    return np.abs(got - want).max() / max(1.0, np.abs(want).max())
 
 
 # --- (1) the kernel against the restatement, step by step -----------------------------------------------------------------
@@ -137,54 +128,7 @@ def test_initial_momenta_match_the_restatement():
         assert _rel(res.momenta[s].cpu().numpy(), want) <= 1e-14
 
 
-# --- periodic spring crystals (forces_fn) -----------------------------------------------------------------------------------
-class Springs:
-    """Each atom tied to its 8 nearest neighbours of the start structure (test_relax_cell.spring_list), at rest there.  The
-    forces gather every atom's springs through a fixed table and sum them in a fixed order (no atomics): the same bits for a
-    structure whatever else is evaluated beside it."""
-
-    def __init__(self, lats, fracs):
-        self.tabs = []
-        for lat, frac in zip(lats, fracs):
-            I, J, img, d0, k = spring_list(lat, frac, nnb=8)
-            n = len(frac)
-            rows = [[] for _ in range(n)]
-            for e, (i, j) in enumerate(zip(I, J)):
-                rows[i].append((e, 1.0))
-                rows[j].append((e, -1.0))
-            deg = max(len(r) for r in rows)
-            idx, sgn = np.zeros((n, deg), dtype=np.int64), np.zeros((n, deg))
-            for i, r in enumerate(rows):
-                for c, (e, sg) in enumerate(r):
-                    idx[i, c], sgn[i, c] = e, sg
-            shift = img[:, 0:1] * lat[0] + img[:, 1:2] * lat[1] + img[:, 2:3] * lat[2]
-            self.tabs.append(tuple(_t(x) if x.dtype != np.int64 else _t(x, torch.int64) for x in (I, J, shift, d0, k, idx, sgn)))
-
-    def __call__(self, lats, poss):
-        es, fs = [], []
-        for (I, J, shift, d0, k, idx, sgn), pos in zip(self.tabs, poss):
-            d = pos[J] - pos[I] + shift
-            r = torch.sqrt((d * d).sum(1))
-            fv = (k * (r - d0) / r)[:, None] * d
-            fs.append((fv[idx] * sgn[..., None]).sum(1))
-            es.append(0.5 * (k * (r - d0) ** 2).sum())
-        return torch.stack(es), torch.cat(fs)
-
-    def subset(self, which):
-        out = Springs.__new__(Springs)
-        out.tabs = [self.tabs[s] for s in which]
-        return out
-
-
-def _spring_crystals(sizes, seed0):
-    lats, fracs = [], []
-    for i, n in enumerate(sizes):
-        lat, frac, _ = make_crystal(n, seed0 + i)
-        lats.append(lat)
-        fracs.append(frac)
-    return lats, [f @ l for f, l in zip(fracs, lats)], Springs(lats, fracs)
-
-
+# --- periodic spring crystals (forces_fn: sim_gpu.Springs) -------------------------------------------------------------------
 def test_nve_springs_second_order_energy_and_time_reversal():
     sizes = [16, 24, 32, 20]
     lats, pos, ff = _spring_crystals(sizes, 300)
@@ -212,11 +156,6 @@ def test_nve_springs_second_order_energy_and_time_reversal():
         err_p = np.abs(back.momenta[s].cpu().numpy() + p_start[s].cpu().numpy()).max()
         print(f"time reversal {s}: moved {moved:.3e} A, back to {err_r:.3e} A, momenta {err_p:.3e}")
         assert moved > 0.05 and err_r < 1e-9 and err_p < 1e-9 * np.abs(p_start[s].cpu().numpy()).max()
-
-
-def _second_half_mean(res):
-    T = res.temperature.cpu().numpy()
-    return T[T.shape[0] // 2:].mean(0)
 
 
 def test_thermostats_reach_their_temperature_ladder():
@@ -283,59 +222,16 @@ def test_langevin_structure_alone_equals_its_slice_of_the_batch():
 
 
 # --- (5), (6) a random-initialised ALIGNNAtomWise -------------------------------------------------------------------------
-def _model():
-    torch.manual_seed(0)
-    cfg = ALIGNNAtomWiseConfig(name="alignn_atomwise", alignn_layers=2, gcn_layers=2, hidden_features=128, embedding_features=64,
-                               atom_input_features=92, calculate_gradient=True, stresswise_weight=0.05)
-    return ALIGNNAtomWise(cfg).to(DEV).eval()
-
-
-def _crystals(B=6, n=24):
-    lats, pos, feats, ms = [], [], [], []
-    g = torch.Generator().manual_seed(3)
-    for i in range(B):
-        lat, frac, _ = make_crystal(n + 2 * i, 900 + i)
-        lats.append(lat)
-        pos.append(frac @ lat)
-        feats.append(torch.randn(n + 2 * i, 92, generator=g))
-        ms.append(np.random.default_rng(i).uniform(1.0, 100.0, n + 2 * i))
-    return lats, pos, feats, ms
-
-
 def _host_loop(model, lats, pos, feats, ms, ensemble, steps, dt, t0, fr, seeds, t_init):
-    """The reference's loop, batched by hand: model(crystal_batch(...)) on the device, the integrators as the restatement."""
+    """The reference's loop, batched by hand (sim_gpu.host_md_loop): model(crystal_batch(...)) on the device, the integrators as
+    the restatement."""
     B = len(pos)
     p0 = [maxwell_boltzmann(seeds[s], ms[s], t_init) for s in range(B)]
     if ensemble == "nve":
         refs = [VerletRef(pos[s], p0[s], ms[s], dt) for s in range(B)]
     else:
         refs = [LangevinRef(pos[s], p0[s], ms[s], dt, t0, fr, True, seeds[s]) for s in range(B)]
-    lat_t = [torch.tensor(l, device=DEV) for l in lats]
-    n_t = torch.tensor([len(p) for p in pos], dtype=torch.float32, device=DEV)
-
-    def evaluate():
-        fr_ = []
-        for s, o in enumerate(refs):
-            f = o.r @ np.linalg.inv(lats[s])
-            f = f - np.floor(f)
-            fr_.append(torch.tensor(np.where(f < 1.0, f, 0.0), device=DEV))
-        out = model(neighbors.crystal_batch(lat_t, fr_, atom_features=feats, device=DEV))
-        e = (out["out"].detach().reshape(-1).float() * n_t).double().cpu().numpy()
-        F = out["grad"].detach().reshape(-1, 3).double().cpu().numpy()
-        ptr = np.concatenate([[0], np.cumsum([len(p) for p in pos])])
-        return e, [F[ptr[s]:ptr[s + 1]] for s in range(B)]
-
-    e, F = evaluate()
-    epot = [e]
-    for _ in range(steps):
-        for s, o in enumerate(refs):
-            o.begin(F[s])
-        e, F = evaluate()
-        for s, o in enumerate(refs):
-            o.finish(F[s])
-            o.nsteps += 1
-        epot.append(e)
-    return refs, np.array(epot)
+    return refs, host_md_loop(model, refs, lats, feats, steps)[0]
 
 
 @pytest.mark.parametrize("ensemble", ["nve", "nvt_langevin"])

@@ -1,5 +1,5 @@
 """Nose-Hoover chain NVT and isotropic MTK NPT on the device (csrc/dynamics.hip ``alignn_md_step``, ensembles 5 and 6,
-alignn_amd/dynamics.py) against the float64 restatement in test_md_nose_hoover_ref.py: (1) the kernel alone, step by step;
+alignn_amd/dynamics.py) against the float64 restatement in md_nose_hoover_ref.py: (1) the kernel alone, step by step;
 (2) the limits, bit for bit; (3) the conserved quantity at second order and the drift; (4) the temperature and the pressure
 ladder; (5) a structure alone vs. in a batch; (6) run_md with an ALIGNNAtomWise against a host loop; (7) replay and run-to-run
 bit identity; (8) what the entry point refuses."""
@@ -10,31 +10,18 @@ import numpy as np
 import pytest
 import torch
 
-from alignn_amd import _lib, neighbors
+from alignn_amd import _lib
 from alignn_amd.dynamics import BAR, ENSEMBLES, FS, KB, run_md
 from alignn_amd.synthetic import make_crystal
-from tests.test_gpu_dynamics import _crystals, _model, _second_half_mean, _spring_crystals
-from tests.test_gpu_dynamics_npt import _no_stress, _stress_springs
-from tests.test_md_nose_hoover_ref import (BARO, BARO_SEED, BARO_SIZES, LADDER_BAR, MTKRef, NoseHooverChainRef, barostat_ref,
-                                            barostat_residuals)
-from tests.test_md_npt_ref import pressure_of
-from tests.test_md_ref import kinetic_energy, maxwell_boltzmann, temperature
+from tests.md_nose_hoover_ref import (BARO, BARO_SEED, BARO_SIZES, LADDER_BAR, MTKRef, NoseHooverChainRef, barostat_ref,
+                                      barostat_residuals)
+from tests.md_npt_ref import pressure_of
+from tests.md_ref import kinetic_energy, maxwell_boltzmann, temperature
+from tests.sim_gpu import (DEV, _md_crystals as _crystals, _model, _no_stress, _rel, _relmax, _second_half_mean, _spring_crystals,
+                           _stress_springs, _t, host_md_loop)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 INVALID = 1  # hipErrorInvalidValue
-
-
-def _t(x, dtype=torch.float64):
-    return torch.tensor(np.asarray(x), dtype=dtype, device=DEV)
-
-
-def _rel(got, want):
-    return np.abs(got - want).max() / max(1.0, np.abs(want).max())
-
-
-def _relmax(got, want):
-    return np.abs(got - want).max() / np.abs(want).max()
 
 
 def _args(S, f_d, e_d, st_d, n_rows, t, interval, steps, ens, dt, **kw):
@@ -324,35 +311,8 @@ def _host_loop(model, lats, pos, feats, ms, ensemble, steps, dt, t0, seeds, t_in
                        fixcm=True) for s in range(B)]
     else:
         refs = [NoseHooverChainRef(pos[s], p0[s], ms[s], dt, t0, NH_KW["ttime"] * FS, fixcm=True) for s in range(B)]
-    n_t = torch.tensor([len(p) for p in pos], dtype=torch.float32, device=DEV)
-    ptr = np.concatenate([[0], np.cumsum([len(p) for p in pos])])
-
-    def evaluate():
-        fr_, lat_t = [], []
-        for s, o in enumerate(refs):
-            cell = o.cell if npt else lats[s]
-            f = o.r @ np.linalg.inv(cell)
-            f = f - np.floor(f)
-            fr_.append(torch.tensor(np.where(f < 1.0, f, 0.0), device=DEV))
-            lat_t.append(torch.tensor(cell, device=DEV))
-        out = model(neighbors.crystal_batch(lat_t, fr_, atom_features=feats, device=DEV))
-        e = (out["out"].detach().reshape(-1).float() * n_t).double().cpu().numpy()
-        F = out["grad"].detach().reshape(-1, 3).double().cpu().numpy()
-        st = out["stresses"].detach().reshape(-1, 3, 3).float()
-        st = ((st + st.transpose(1, 2)) / 2 * 1.0 / 160.21766208).double().cpu().numpy()
-        return e, [F[ptr[s]:ptr[s + 1]] for s in range(B)], st
-
-    e, F, st = evaluate()
-    epot, cons = [e], [[o.conserved(e[s]) for s, o in enumerate(refs)]]
-    for _ in range(steps):
-        for s, o in enumerate(refs):
-            o.begin(F[s], st[s])
-        e, F, st = evaluate()
-        for s, o in enumerate(refs):
-            o.finish(F[s], st[s])
-        epot.append(e)
-        cons.append([o.conserved(e[s]) for s, o in enumerate(refs)])
-    return refs, np.array(epot), np.array(cons)
+    epot, cons = host_md_loop(model, refs, lats, feats, steps, "both", lambda o, e, st: o.conserved(e))
+    return refs, epot, cons
 
 
 @pytest.mark.parametrize("ensemble", ["nvt_nose_hoover", "npt_nose_hoover"])

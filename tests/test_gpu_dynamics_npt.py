@@ -1,5 +1,5 @@
 """Andersen NVT and Berendsen NPT on the device (csrc/dynamics.hip ``alignn_md_step``, ensembles 3 and 4, alignn_amd/dynamics.py) against the
-float64 restatement in test_md_npt_ref.py: (1) the kernel alone, step by step, both ensembles, the exported random numbers
+float64 restatement in md_npt_ref.py: (1) the kernel alone, step by step, both ensembles, the exported random numbers
 against the numpy stream; (2) NPT at zero compressibility is NVT Berendsen; (3) the barostat reaches a ladder of pressures on
 spring crystals, as the restatement does; (4) Andersen reaches its temperature ladder; (5) a structure alone vs. in a batch,
 bit for bit; (6) run_md with an ALIGNNAtomWise against a host loop over the same model; (7) replay and run-to-run bit
@@ -11,29 +11,16 @@ import numpy as np
 import pytest
 import torch
 
-from alignn_amd import _lib, neighbors
+from alignn_amd import _lib
 from alignn_amd.dynamics import BAR, ENSEMBLES, FS, KB, run_md
 from alignn_amd.synthetic import make_crystal
-from tests.test_gpu_dynamics import Springs, _crystals, _model, _second_half_mean, _spring_crystals
-from tests.test_gpu_relax_cell import springs_torch
-from tests.test_md_npt_ref import AndersenRef, NPTBerendsenRef, pressure_of, run_npt_ref
-from tests.test_md_ref import kinetic_energy, maxwell_boltzmann, normals, stream_words, temperature, unit_interval
-from tests.test_relax_cell import spring_list, springs_efs
+from tests.md_npt_ref import AndersenRef, NPTBerendsenRef, pressure_of, run_npt_ref
+from tests.md_ref import kinetic_energy, maxwell_boltzmann, normals, stream_words, temperature, unit_interval
+from tests.sim_gpu import (DEV, _md_crystals as _crystals, _model, _no_stress, _rel, _relmax, _second_half_mean, _spring_crystals,
+                           _stress_springs, _t, host_md_loop)
+from tests.springs_ref import springs_efs
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _t(x, dtype=torch.float64):
-    return torch.tensor(np.asarray(x), dtype=dtype, device=DEV)
-
-
-def _rel(got, want):
-    return np.abs(got - want).max() / max(1.0, np.abs(want).max())
-
-
-def _relmax(got, want):
-    return np.abs(got - want).max() / np.abs(want).max()
 
 
 def _step_cell(lib, S, f_d, e_d, st_d, n_rows, noise, traj, t, interval, steps, ens, dt, prob, taut, taup, fixcm):
@@ -162,26 +149,6 @@ def test_cell_kernel_matches_the_restatement_step_by_step(ensemble):
     assert S["status"].item() == -1 and all(torch.equal(S[k], v) for k, v in before.items())
 
 
-# --- periodic spring crystals with stresses --------------------------------------------------------------------------------
-def _stress_springs(sizes, seed0, nnb=14):
-    """Crystals of distinct sizes at rest in their springs (test_relax_cell.spring_list) -> lattices, positions, the numpy
-    spring lists and the device ``forces_fn`` with stresses (test_gpu_relax_cell.springs_torch, fixed-order sums)."""
-    assert len(set(sizes)) == len(sizes)  # (springs_torch finds a structure's table by its atom count)
-    lats, pos, sls, cases = [], [], [], []
-    for i, n in enumerate(sizes):
-        lat, frac, _ = make_crystal(n, seed0 + i)
-        sl = spring_list(lat, frac, nnb=nnb)
-        lats.append(lat)
-        pos.append(frac @ lat)
-        sls.append(sl)
-        cases.append((lat, frac, lat, frac @ lat, sl))
-    return lats, pos, sls, springs_torch(cases)
-
-
-def _no_stress(fn):
-    return lambda lats, poss: fn(lats, poss)[:2]
-
-
 # --- (2) zero compressibility -----------------------------------------------------------------------------------------------
 def test_npt_at_zero_compressibility_is_nvt_berendsen():
     sizes = [16, 24, 32, 20]
@@ -301,8 +268,8 @@ NPT_KW = dict(taut=20.0, taup=10.0, pressure=0.0, compressibility=1e-7)
 
 
 def _host_loop(model, lats, pos, feats, ms, ensemble, steps, dt, t0, seeds, t_init, prob):
-    """The reference's loop, batched by hand: model(crystal_batch(...)) on the device with the calculator's rules for energy,
-    forces and stress (alignn_amd/_structures.py), the integrators as the restatement."""
+    """The reference's loop, batched by hand (sim_gpu.host_md_loop): model(crystal_batch(...)) on the device with the calculator's
+    rules for energy, forces and stress, the integrators as the restatement."""
     B = len(pos)
     npt = ensemble == "npt_berendsen"
     p0 = [maxwell_boltzmann(seeds[s], ms[s], t_init) for s in range(B)]
@@ -311,37 +278,9 @@ def _host_loop(model, lats, pos, feats, ms, ensemble, steps, dt, t0, seeds, t_in
                                 NPT_KW["pressure"] * BAR, NPT_KW["compressibility"] / BAR, True) for s in range(B)]
     else:
         refs = [AndersenRef(pos[s], p0[s], ms[s], dt, t0, prob, True, seeds[s]) for s in range(B)]
-    n_t = torch.tensor([len(p) for p in pos], dtype=torch.float32, device=DEV)
-    ptr = np.concatenate([[0], np.cumsum([len(p) for p in pos])])
-
-    def evaluate():
-        fr_, lat_t = [], []
-        for s, o in enumerate(refs):
-            cell = o.cell if npt else lats[s]
-            f = o.r @ np.linalg.inv(cell)
-            f = f - np.floor(f)
-            fr_.append(torch.tensor(np.where(f < 1.0, f, 0.0), device=DEV))
-            lat_t.append(torch.tensor(cell, device=DEV))
-        out = model(neighbors.crystal_batch(lat_t, fr_, atom_features=feats, device=DEV))
-        e = (out["out"].detach().reshape(-1).float() * n_t).double().cpu().numpy()
-        F = out["grad"].detach().reshape(-1, 3).double().cpu().numpy()
-        st = out["stresses"].detach().reshape(-1, 3, 3).float()
-        st = ((st + st.transpose(1, 2)) / 2 * 1.0 / 160.21766208).double().cpu().numpy()
-        return e, [F[ptr[s]:ptr[s + 1]] for s in range(B)], st
-
-    e, F, st = evaluate()
-    epot, press = [e], []
-    for _ in range(steps):
-        press.append([pressure_of(o.p, o.m, st[s], o.cell) if npt else 0.0 for s, o in enumerate(refs)])
-        for s, o in enumerate(refs):
-            o.begin(F[s], st[s]) if npt else o.begin(F[s])
-        e, F, st = evaluate()
-        for s, o in enumerate(refs):
-            o.finish(F[s])
-            o.nsteps += 1
-        epot.append(e)
-    press.append([pressure_of(o.p, o.m, st[s], o.cell) if npt else 0.0 for s, o in enumerate(refs)])
-    return refs, np.array(epot), np.array(press)
+    epot, press = host_md_loop(model, refs, lats, feats, steps, "begin" if npt else "",
+                               lambda o, e, st: pressure_of(o.p, o.m, st, o.cell) if npt else 0.0)
+    return refs, epot, press
 
 
 @pytest.mark.parametrize("ensemble", ["nvt_andersen", "npt_berendsen"])

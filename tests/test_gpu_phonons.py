@@ -1,5 +1,5 @@
 """Batched phonons on the device (csrc/phonon.hip, alignn_amd/phonons.py) against the numpy restatement of ASE's Phonons in
-test_phonons_ref.py: (1) the displaced supercells bit for bit; (2) force constants from forces_fn forces for every drift,
+phonons_ref.py: (1) the displaced supercells bit for bit; (2) force constants from forces_fn forces for every drift,
 symmetrize and acoustic setting; (3) the Jacobi eigen launch against numpy.linalg.eigvalsh (random Hermitian, degenerate,
 diagonal and zero matrices; eigenvector residuals and orthonormality; D(q) from the upper triangle); (4) the analytic
 dispersion of spring crystals end to end; (5) a structure alone vs. in a batch, bit for bit; (6) the model path against one
@@ -9,18 +9,14 @@ import numpy as np
 import pytest
 import torch
 
-from alignn_amd import ALIGNNAtomWise, ALIGNNAtomWiseConfig, _lib, neighbors, phonons
-from alignn_amd.phonons import FREQ_SCALE, monkhorst_pack
+from alignn_amd import _lib, neighbors, phonons
+from alignn_amd.phonons import FREQ_SCALE, lattice_points, monkhorst_pack
 from alignn_amd.synthetic import make_crystal
-from tests.test_phonons_ref import (displaced_supercells, dos, dq, dynamical_matrices, force_constants, frequencies,
-                                    inv_supercell, lattice_points, sc_analytic, simple_cubic, spring_forces_of)
+from tests.phonons_ref import (displaced_supercells, dos, dq, dynamical_matrices, force_constants, frequencies, inv_supercell,
+                               sc_analytic, simple_cubic, spring_forces_of)
+from tests.sim_gpu import DEV, _model, _t
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _t(x, dtype=torch.float64):
-    return torch.tensor(np.asarray(x), dtype=dtype, device=DEV)
 
 
 def _rel(got, want):
@@ -256,13 +252,6 @@ def test_structure_alone_equals_its_slice_of_the_batch():
 
 
 # --- (6) the model path ------------------------------------------------------------------------------------------------------
-def _model():
-    torch.manual_seed(0)
-    cfg = ALIGNNAtomWiseConfig(name="alignn_atomwise", alignn_layers=2, gcn_layers=2, hidden_features=128, embedding_features=64,
-                               atom_input_features=92, calculate_gradient=True, stresswise_weight=0.05)
-    return ALIGNNAtomWise(cfg).to(DEV).eval()
-
-
 def test_model_path_matches_one_evaluation_per_supercell():
     model = _model()
     sizes, sc, delta = [2, 4, 5], (2, 2, 2), 0.05

@@ -1,5 +1,5 @@
 """Batched FIRE relaxation on the device (csrc/relax.hip, alignn_amd/relax.py) against the float64 restatement of ASE's FIRE and
-Optimizer.run in test_relax_fire.py: (a) the kernel alone, step by step; (b) the relaxer on harmonic springs (convergence, step
+Optimizer.run in relax_ref.py: (a) the kernel alone, step by step; (b) the relaxer on harmonic springs (convergence, step
 counts, and bit-identical trajectories alone vs. in a batch whose other members retire earlier); (c) the relaxer with an
 ALIGNNAtomWise against a host loop over the same model; (d) run-to-run bit identity."""
 
@@ -9,13 +9,13 @@ import numpy as np
 import pytest
 import torch
 
-from alignn_amd import ALIGNNAtomWise, ALIGNNAtomWiseConfig, _lib, neighbors
+from alignn_amd import _lib
 from alignn_amd.relax import relax
 from alignn_amd.synthetic import make_crystal
-from tests.test_relax_fire import DEFAULTS, FireRef, converged, run_ref
+from tests.relax_ref import DEFAULTS, FireRef, converged, run_ref
+from tests.sim_gpu import DEV, _crystals, _model, host_relax_loop
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 
 
 def _fire_step(lib, forces, energy, force_ptr, active, atom_ptr, inv, S, fmax, steps, p=DEFAULTS):
@@ -189,54 +189,11 @@ def test_relax_springs_converge_like_the_restatement_alone_or_batched():
 
 
 # --- (c), (d) a random-initialised ALIGNNAtomWise --------------------------------------------------------------------------
-def _model():
-    torch.manual_seed(0)
-    cfg = ALIGNNAtomWiseConfig(name="alignn_atomwise", alignn_layers=2, gcn_layers=2, hidden_features=128, embedding_features=64,
-                               atom_input_features=92, calculate_gradient=True, stresswise_weight=0.05)
-    return ALIGNNAtomWise(cfg).to(DEV).eval()
-
-
-def _crystals(B=8, n=24):
-    lats, pos, feats = [], [], []
-    g = torch.Generator().manual_seed(3)
-    for i in range(B):
-        lat, frac, _ = make_crystal(n + 2 * i, 900 + i)
-        lats.append(lat)
-        pos.append(frac @ lat)
-        feats.append(torch.randn(n + 2 * i, 92, generator=g))
-    return lats, pos, feats
-
-
 def _host_loop(model, lats, pos, feats, fmax, steps):
-    """The reference's loop, batched by hand: model(crystal_batch(active)) on the device, FIRE as the numpy restatement."""
-    opts = [FireRef(p, **DEFAULTS) for p in pos]
-    taken = [0] * len(pos)
-    energies = [None] * len(pos)
-    active = list(range(len(pos)))
-    lat_t = [torch.tensor(l, device=DEV) for l in lats]
-    while active:
-        fr = []
-        for s in active:
-            f = opts[s].r @ np.linalg.inv(lats[s])
-            f = f - np.floor(f)
-            fr.append(torch.tensor(np.where(f < 1.0, f, 0.0), device=DEV))
-        b = neighbors.crystal_batch([lat_t[s] for s in active], fr, atom_features=[feats[s] for s in active], device=DEV)
-        out = model(b)
-        n_act = torch.tensor([len(pos[s]) for s in active], dtype=torch.float32, device=DEV)
-        e = (out["out"].detach().reshape(-1).float() * n_act).double().cpu().numpy()
-        F = out["grad"].detach().reshape(-1, 3).double().cpu().numpy()
-        nxt, off = [], 0
-        for k, s in enumerate(active):
-            f = F[off:off + len(pos[s])]
-            off += len(pos[s])
-            energies[s] = e[k]
-            if converged(f, fmax) or taken[s] >= steps:
-                continue
-            opts[s].step(f)
-            taken[s] += 1
-            nxt.append(s)
-        active = nxt
-    return [o.r for o in opts], np.array(energies), taken
+    """The reference's loop, batched by hand (sim_gpu.host_relax_loop): model(crystal_batch(active)) on the device, FIRE as the
+    numpy restatement."""
+    opts, energies, taken, _ = host_relax_loop(model, lats, pos, feats, fmax, steps)
+    return [o.r for o in opts], energies, taken
 
 
 def test_relax_model_matches_a_host_loop():

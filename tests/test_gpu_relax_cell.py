@@ -1,5 +1,5 @@
 """Batched FIRE with ASE's ExpCellFilter on the device (csrc/relax.hip ``alignn_fire_step`` with the filter's state,
-``relax(optimize_lattice=True)``) against the float64 restatement in test_relax_cell.py: (a) the kernel alone, step by step, with injected forces and stresses,
+``relax(optimize_lattice=True)``) against the float64 restatement in relax_ref.py: (a) the kernel alone, step by step, with injected forces and stresses,
 naive and exact cell-force branches; (b) the relaxer on harmonic spring crystals (agreement with the restatement, cells at the
 analytic minimum, bit-identical trajectories alone vs. in a shrinking batch); (c) the relaxer with an ALIGNNAtomWise against a
 host loop over the same model; (d) run-to-run bit identity; (e) invalid input."""
@@ -9,21 +9,16 @@ import ctypes
 import numpy as np
 import pytest
 import torch
-from scipy.linalg import expm, logm
+from scipy.linalg import logm
 
-from alignn_amd import ALIGNNAtomWise, ALIGNNAtomWiseConfig, _lib, neighbors
+from alignn_amd import _lib
 from alignn_amd.relax import relax
 from alignn_amd.synthetic import make_crystal
-from tests.test_relax_cell import (ExpCellFilterRef, _case, exact_branch_state, run_cell_ref, spring_list, springs_efs,
-                                   sym_strain)
-from tests.test_relax_fire import DEFAULTS, FireRef, converged
+from tests.relax_ref import DEFAULTS, ExpCellFilterRef, FireRef, _case, exact_branch_state, run_cell_ref, sym_strain
+from tests.sim_gpu import DEV, _close, _crystals, _model, _t, host_relax_loop, springs_torch
+from tests.springs_ref import spring_list, springs_efs
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _t(x, dtype=torch.float64):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
 
 
 def _cell_step(lib, forces, energy, stress, force_ptr, active, atom_ptr, S, fmax, steps, p=DEFAULTS):
@@ -37,10 +32,6 @@ def _cell_step(lib, forces, energy, stress, force_ptr, active, atom_ptr, S, fmax
         n_active=active.numel(), steps=steps, nmin=p["Nmin"], fmax=fmax, maxstep=p["maxstep"], dtmax=p["dtmax"], finc=p["finc"],
         fdec=p["fdec"], astart=p["astart"], fa=p["fa"])
     _lib.check(lib.alignn_fire_step(ctypes.byref(args), _lib.stream()), "fire_step")
-
-
-def _close(got, want, rel=1e-12):
-    return np.abs(got - want).max() <= rel * max(1.0, np.abs(want).max())
 
 
 def test_kernel_matches_the_restatement_step_by_step():
@@ -153,42 +144,6 @@ def _spring_cases():
     return cases
 
 
-def _det3(m):
-    return (m[0, 0] * (m[1, 1] * m[2, 2] - m[1, 2] * m[2, 1]) - m[0, 1] * (m[1, 0] * m[2, 2] - m[1, 2] * m[2, 0])
-            + m[0, 2] * (m[1, 0] * m[2, 1] - m[1, 1] * m[2, 0]))
-
-
-def springs_torch(cases, record=None):
-    """springs_efs on the device with reductions of a fixed order only (no atomics, no BLAS): the same bits for a structure
-    whatever else is evaluated beside it."""
-    tabs = {}
-    for c in cases:
-        I, J, img, d0, k = c[4]
-        n = len(c[3])
-        inc = np.zeros((n, len(I)))  # +1 at the spring's first atom, -1 at its second (0 for a spring to an own image)
-        np.add.at(inc, (I, np.arange(len(I))), 1.0)
-        np.add.at(inc, (J, np.arange(len(I))), -1.0)
-        tabs[n] = tuple(torch.tensor(x, device=DEV) for x in (I, J, img, d0, k, inc))
-
-    def fn(lats, poss):
-        es, fs, ss = [], [], []
-        for lat, pos in zip(lats, poss):
-            n = pos.shape[0]
-            I, J, img, d0, k, inc = tabs[n]
-            d = pos[J] - pos[I] + (img[:, 0:1] * lat[0] + img[:, 1:2] * lat[1] + img[:, 2:3] * lat[2])
-            r = torch.sqrt((d * d).sum(1))
-            dphi = k * (r - d0)
-            fv = (dphi / r)[:, None] * d
-            fs.append((inc[:, :, None] * fv[None, :, :]).sum(1))
-            ss.append((fv[:, :, None] * d[:, None, :]).sum(0) / _det3(lat).abs())
-            es.append(0.5 * (k * (r - d0) ** 2).sum())
-            if record is not None:
-                record.setdefault(n, []).append((lat.clone(), pos.clone()))
-        return torch.stack(es), torch.cat(fs), torch.stack(ss)
-
-    return fn
-
-
 def test_relax_cell_springs_match_the_restatement_alone_or_batched():
     cases = _spring_cases()
     fmax, steps = 1e-6, 4000
@@ -228,58 +183,11 @@ def test_relax_cell_springs_match_the_restatement_alone_or_batched():
 
 
 # --- (c), (d), (e) a random-initialised ALIGNNAtomWise ---------------------------------------------------------------------
-def _model(**kw):
-    torch.manual_seed(0)
-    cfg = dict(name="alignn_atomwise", alignn_layers=2, gcn_layers=2, hidden_features=128, embedding_features=64,
-               atom_input_features=92, calculate_gradient=True, stresswise_weight=0.05)
-    cfg.update(kw)
-    return ALIGNNAtomWise(ALIGNNAtomWiseConfig(**cfg)).to(DEV).eval()
-
-
-def _crystals(B=8, n=24):
-    lats, pos, feats = [], [], []
-    g = torch.Generator().manual_seed(3)
-    for i in range(B):
-        lat, frac, _ = make_crystal(n + 2 * i, 900 + i)
-        lats.append(lat)
-        pos.append(frac @ lat)
-        feats.append(torch.randn(n + 2 * i, 92, generator=g))
-    return lats, pos, feats
-
-
 def _host_loop(model, lats, pos, feats, fmax, steps, stress_weight=1.0):
-    """The reference's loop, batched by hand: model(crystal_batch(active)) on the device with fresh lattice tensors every step,
-    the calculator's rules, ExpCellFilter and FIRE as the numpy restatement."""
+    """The reference's loop, batched by hand (sim_gpu.host_relax_loop): model(crystal_batch(active)) on the device with fresh
+    lattice tensors every step, the calculator's rules, ExpCellFilter and FIRE as the numpy restatement."""
     filts = [ExpCellFilterRef(l, len(p)) for l, p in zip(lats, pos)]
-    opts = [FireRef(f.initial(p), **DEFAULTS) for f, p in zip(filts, pos)]
-    taken = [0] * len(pos)
-    branches = set()
-    active = list(range(len(pos)))
-    while active:
-        lat_t, fr = [], []
-        for s in active:
-            C, _, _ = filts[s].atoms(opts[s].r)
-            lat_t.append(torch.tensor(C, device=DEV))
-            f = opts[s].r[:len(pos[s])] @ np.linalg.inv(lats[s])
-            f = f - np.floor(f)
-            fr.append(torch.tensor(np.where(f < 1.0, f, 0.0), device=DEV))
-        b = neighbors.crystal_batch(lat_t, fr, atom_features=[feats[s] for s in active], device=DEV)
-        out = model(b)
-        F = out["grad"].detach().reshape(-1, 3).double().cpu().numpy()
-        st = out["stresses"].detach().reshape(-1, 3, 3).float()
-        st = ((st + st.transpose(1, 2)) / 2 * stress_weight / 160.21766208).double().cpu().numpy()
-        nxt, off = [], 0
-        for k, s in enumerate(active):
-            f = F[off:off + len(pos[s])]
-            off += len(pos[s])
-            g = filts[s].forces(opts[s].r, f, st[k])
-            branches.add(filts[s].branch)
-            if converged(g, fmax) or taken[s] >= steps:
-                continue
-            opts[s].step(g)
-            taken[s] += 1
-            nxt.append(s)
-        active = nxt
+    opts, _, taken, branches = host_relax_loop(model, lats, pos, feats, fmax, steps, filts, stress_weight)
     res = [f.atoms(o.r) for f, o in zip(filts, opts)]
     return [r[1] for r in res], [r[0] for r in res], taken, branches
 

@@ -1,6 +1,6 @@
 """The constraints of the batched FIRE relaxer on the device (csrc/relax.hip: ``fixed``, ``cell_mask``, ``scalar_pressure``,
 ``hydrostatic_strain``, ``constant_volume`` and ``enthalpy_out`` of ``alignn_fire_args``; ``relax(fixed=, cell_mask=, ...)``)
-against the float64 restatement in test_relax_constraints.py.  Three structures of 1, 2 and 7 atoms in one launch: one atom
+against the float64 restatement in relax_ref.py.  Three structures of 1, 2 and 7 atoms in one launch: one atom
 per workgroup, fewer atoms than lanes, a ragged batch.  (1) the kernel alone, step by step, forces and stresses of the spring
 potential from the host, each option alone and all together; (2) the relaxer on spring crystals, alone and batched; (3) the
 options passed but off give the bits of a call without them; (4) a fixed atom at fixed cell; (5) the relaxer with an
@@ -13,28 +13,19 @@ import pytest
 import torch
 from scipy.linalg import expm
 
-from alignn_amd import _lib, neighbors
+from alignn_amd import _lib
 from alignn_amd.relax import relax
 from alignn_amd.synthetic import make_crystal
-from tests.test_gpu_relax_cell import _crystals, _model, springs_torch
-from tests.test_relax_cell import _case, spring_list, springs_efs, sym_strain
-from tests.test_relax_constraints import SLAB, ConstrainedFilterRef, run_constrained_ref, run_fixed_ref, voigt_mask
-from tests.test_relax_fire import DEFAULTS, FireRef, converged
+from tests.relax_ref import (DEFAULTS, SLAB, ConstrainedFilterRef, FireRef, _case, run_constrained_ref, run_fixed_ref, sym_strain,
+                             voigt_mask)
+from tests.sim_gpu import DEV, _close, _crystals, _model, _t, host_relax_loop, springs_torch
+from tests.springs_ref import spring_list, springs_efs
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 NS = [1, 2, 7]
 FIXED = [np.array([False]), np.array([False, True]), np.array([False, False, False, True, False, False, False])]
 TWO_FIXED = np.array([False, False, False, True, False, True, False])
 DIAG = [1, 1, 1, 0, 0, 0]
-
-
-def _t(x, dtype=torch.float64):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def _close(got, want, rel=1e-12):
-    return np.abs(got - want).max() <= rel * max(1.0, np.abs(want).max())
 
 
 # --- (1) the kernel, step by step --------------------------------------------------------------------------------------------
@@ -360,38 +351,9 @@ def test_fixed_atoms_at_fixed_cell_stay_where_they_are():
 # --- (5) with the model ------------------------------------------------------------------------------------------------------
 def _host_loop(model, lats, pos, feats, fmax, steps, options):
     """test_gpu_relax_cell._host_loop with the constrained filter: model(crystal_batch) on the device, the calculator's rules,
-    the filter and FIRE as the numpy restatement."""
+    the filter and FIRE as the numpy restatement (sim_gpu.host_relax_loop)."""
     filts = [ConstrainedFilterRef(l, len(p), **o) for l, p, o in zip(lats, pos, options)]
-    opts = [FireRef(f.initial(p), **DEFAULTS) for f, p in zip(filts, pos)]
-    taken = [0] * len(pos)
-    active = list(range(len(pos)))
-    energy = [0.0] * len(pos)
-    while active:
-        lat_t, fr = [], []
-        for s in active:
-            C, _, _ = filts[s].atoms(opts[s].r)
-            lat_t.append(torch.tensor(C, device=DEV))
-            f = opts[s].r[:len(pos[s])] @ np.linalg.inv(lats[s])
-            f = f - np.floor(f)
-            fr.append(torch.tensor(np.where(f < 1.0, f, 0.0), device=DEV))
-        b = neighbors.crystal_batch(lat_t, fr, atom_features=[feats[s] for s in active], device=DEV)
-        out = model(b)
-        F = out["grad"].detach().reshape(-1, 3).double().cpu().numpy()
-        E = (out["out"].detach().reshape(-1).float() * torch.tensor([float(len(pos[s])) for s in active], device=DEV)).double()
-        st = out["stresses"].detach().reshape(-1, 3, 3).float()
-        st = ((st + st.transpose(1, 2)) / 2 / 160.21766208).double().cpu().numpy()
-        nxt, off = [], 0
-        for k, s in enumerate(active):
-            f = F[off:off + len(pos[s])]
-            off += len(pos[s])
-            energy[s] = E[k].item()
-            g = filts[s].forces(opts[s].r, f, st[k])
-            if converged(g, fmax) or taken[s] >= steps:
-                continue
-            opts[s].step(g)
-            taken[s] += 1
-            nxt.append(s)
-        active = nxt
+    opts, energy, taken, _ = host_relax_loop(model, lats, pos, feats, fmax, steps, filts)
     res = [f.atoms(o.r) for f, o in zip(filts, opts)]
     return [r[1] for r in res], [r[0] for r in res], taken, [f.enthalpy(o.r, e) for f, o, e in zip(filts, opts, energy)]
 

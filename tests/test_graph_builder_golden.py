@@ -13,7 +13,7 @@ import torch
 
 from alignn_amd import neighbors
 from alignn_amd.synthetic import knn_multigraph
-from tests.helpers import load_golden
+from tests.helpers import load_golden, ref_keys
 
 
 def _multiset(u, v, r, lat, frac):
@@ -46,12 +46,6 @@ def _check(build, tol=2e-5):
             assert np.abs(mine[k] - gr[i]).max() < tol * max(1.0, np.abs(gr[i]).max()), (name, k)
         n += 1
     assert n == 70
-
-
-def ref_keys(u, v, r, lat, frac):
-    cart = frac @ lat
-    img = np.rint((np.asarray(r, np.float64) - (cart[v] - cart[u])) @ np.linalg.inv(lat)).astype(np.int64)
-    return list(zip(u.tolist(), v.tolist(), map(tuple, img.tolist())))
 
 
 def test_numpy_builder_reproduces_the_reference_edge_sets():

@@ -15,8 +15,7 @@ import pytest
 import torch
 
 from alignn_amd import neighbors, synthetic
-from tests.helpers import load_golden
-from tests.test_graph_builder_golden import ref_keys
+from tests.helpers import load_golden, ref_keys
 
 RADIUS_CUTOFF = 4.0
 FIELDS = "seg_ptr seg_node src dst out_ptr out_slot perm inv grp_seg_ptr grp_src_ptr seg_rank".split()  # every index array of a CSRGraph

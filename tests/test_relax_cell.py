@@ -1,163 +1,18 @@
-"""The executable specification of ``alignn_amd.relax(..., optimize_lattice=True)`` (csrc/relax.hip, ``alignn_fire_step`` with the filter's state):
-a float64 numpy / scipy restatement of ASE's ``ExpCellFilter`` (ase/constraints.py, 3.22.1, default arguments) as the
-reference's ``ForceField.optimize_atoms`` applies it (alignn/ff/ff.py:373-415, ``optimize_lattice=True``), and the run loop of
-``Optimizer.run`` over its n + 3 generalised rows with ``FireRef`` / ``converged`` of test_relax_fire.py.  ASE is not a
-dependency: the restatement is pinned by gradient checks against an analytic periodic potential (harmonic springs over a
-fixed list of periodic images) instead.  The GPU tests (test_gpu_relax_cell.py) hold the kernel and the relaxer to it."""
+"""Checks of ``ExpCellFilterRef`` and ``run_cell_ref`` of tests/relax_ref.py, the float64 numpy / scipy restatement of ASE's
+``ExpCellFilter`` that specifies ``alignn_amd.relax(..., optimize_lattice=True)`` (csrc/relax.hip, ``alignn_fire_step`` with the
+filter's state).  ASE is not a dependency: the restatement is pinned by gradient checks against an analytic periodic potential
+(the harmonic springs of tests/springs_ref.py) instead.  The GPU tests (test_gpu_relax_cell.py) hold the kernel and the relaxer
+to it."""
 
 import inspect
-import itertools
 
 import numpy as np
 import pytest
-from scipy.linalg import expm, logm
+from scipy.linalg import expm
 
 from alignn_amd.relax import RelaxResult, relax
-from tests.test_relax_fire import DEFAULTS, FireRef, converged
-
-
-def sym3(s):
-    """full_3x3_to_voigt_6_stress followed by voigt_6_to_full_3x3_stress: the off-diagonal pairs averaged."""
-    s = np.asarray(s, dtype=np.float64)
-    out = s.copy()
-    for i, j in ((0, 1), (0, 2), (1, 2)):
-        out[i, j] = out[j, i] = (s[i, j] + s[j, i]) / 2
-    return out
-
-
-class ExpCellFilterRef:
-    """ExpCellFilter(atoms) of one structure with original cell ``C0`` (rows a, b, c): generalised positions X [n + 3, 3]."""
-
-    def __init__(self, C0, n):
-        self.C0 = np.array(C0, dtype=np.float64)
-        self.n = n
-        self.c = float(n)  # cell_factor = exp_cell_factor = len(atoms)
-        self.branch = None  # "naive" / "exact": which cell force the last forces() call used
-
-    def initial(self, pos):
-        return np.vstack([np.asarray(pos, dtype=np.float64), np.zeros((3, 3))])  # F = I: X_c = c logm(I) = 0
-
-    def atoms(self, X):
-        """set_positions: -> (cell C, Cartesian positions, deformation gradient F)."""
-        F = expm(X[self.n:] / self.c)
-        return self.C0 @ F.T, X[:self.n] @ F.T, F
-
-    def from_atoms(self, C, pos):
-        """get_positions: X from the cell and the Cartesian positions (ASE recomputes this every step)."""
-        F = np.linalg.solve(self.C0, C).T
-        return np.vstack([pos @ np.linalg.inv(F).T, self.c * np.real(logm(F))])
-
-    def cell_forces(self, X, stress):
-        """-> (naive, exact) cell forces before the division by c."""
-        C, _, _ = self.atoms(X)
-        W = -abs(np.linalg.det(C)) * sym3(stress)
-        L = X[self.n:] / self.c
-        Y = np.zeros((6, 6))
-        Y[0:3, 0:3] = L
-        Y[3:6, 3:6] = L
-        Y[0:3, 3:6] = -W @ expm(-L)
-        E = -expm(Y)[0:3, 3:6]
-        for i, j in ((0, 1), (0, 2), (1, 2)):
-            E[i, j] = E[j, i] = 0.5 * (E[i, j] + E[j, i])
-        return W.copy(), E
-
-    def forces(self, X, f, stress):
-        """get_forces from the atoms' Cartesian forces f [n, 3] and the calculator's stress (eV/A^3, ASE's sign)."""
-        _, _, F = self.atoms(X)
-        N, E = self.cell_forces(X, stress)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            cos = np.sum(E * N) / np.sqrt(np.sum(E ** 2) * np.sum(N ** 2))
-        naive = bool(np.all(np.isclose(E, N))) or bool(cos > 0.8)
-        self.branch = "naive" if naive else "exact"
-        return np.vstack([np.asarray(f, dtype=np.float64) @ F, (N if naive else E) / self.c])
-
-
-def run_cell_ref(C0, pos0, efs, fmax=0.1, steps=100, **fire):
-    """Optimizer.run(fmax, steps) of FIRE(ExpCellFilter(atoms)); ``efs(C, pos) -> (e, f [n, 3], stress [3, 3])``.
-    -> dict(X, C, pos, e, f, s, g (the n + 3 rows), n_steps, converged, n_evals, traj (C, pos after each step), branches)."""
-    filt = ExpCellFilterRef(C0, len(pos0))
-    opt = FireRef(filt.initial(pos0), **{**DEFAULTS, **fire})
-
-    def evaluate():
-        C, pos, _ = filt.atoms(opt.r)
-        e, f, s = efs(C, pos)
-        return e, f, s, filt.forces(opt.r, f, s)
-
-    e, f, s, g = evaluate()
-    n_evals, n_steps, branches = 1, 0, [filt.branch]
-    traj = [filt.atoms(opt.r)[:2]]
-    conv = converged(g, fmax)
-    while not conv and n_steps < steps:
-        opt.step(g)
-        n_steps += 1
-        traj.append(filt.atoms(opt.r)[:2])
-        e, f, s, g = evaluate()
-        branches.append(filt.branch)
-        n_evals += 1
-        conv = converged(g, fmax)
-    C, pos, _ = filt.atoms(opt.r)
-    return dict(X=opt.r, C=C, pos=pos, e=e, f=f, s=s, g=g, n_steps=n_steps, converged=conv, n_evals=n_evals, traj=traj,
-                branches=branches, opt=opt)
-
-
-# --- an analytic periodic potential: harmonic springs over a fixed image list, at rest in a target structure ----------------
-def spring_list(lat, frac, nnb=8):
-    """Each atom tied to its ``nnb`` nearest neighbours (images within one cell) of the target (lat, frac), rest length the
-    target distance.  -> (i, j, image [m, 3], d0, k)."""
-    lat, frac = np.asarray(lat, dtype=np.float64), np.asarray(frac, dtype=np.float64)
-    pos = frac @ lat
-    n = len(pos)
-    rows = []
-    for i in range(n):
-        cand = []
-        for j in range(n):
-            for img in itertools.product((-1, 0, 1), repeat=3):
-                if i == j and img == (0, 0, 0):
-                    continue
-                d = pos[j] + np.array(img) @ lat - pos[i]
-                cand.append((float(np.linalg.norm(d)), j, img))
-        cand.sort(key=lambda t: t[0])
-        rows += [(i, j, img, d0) for d0, j, img in cand[:nnb]]
-    I = np.array([r[0] for r in rows])
-    J = np.array([r[1] for r in rows])
-    img = np.array([r[2] for r in rows], dtype=np.float64)
-    d0 = np.array([r[3] for r in rows])
-    k = 1.0 + 0.5 * (np.arange(len(rows)) % 3)
-    return I, J, img, d0, k
-
-
-def springs_efs(I, J, img, d0, k):
-    """-> efs(C, pos) = (E, forces, stress = (1/V) dE/d strain): ASE's sign (positive under tension)."""
-
-    def efs(C, pos):
-        d = pos[J] - pos[I] + img @ C
-        r = np.sqrt((d * d).sum(1))
-        dphi = k * (r - d0)
-        fv = (dphi / r)[:, None] * d  # dE / dd
-        f = np.zeros_like(pos)
-        np.add.at(f, I, fv)
-        np.add.at(f, J, -fv)
-        s = fv.T @ d / abs(np.linalg.det(C))
-        return 0.5 * float((k * (r - d0) ** 2).sum()), f, s
-
-    return efs
-
-
-def sym_strain(rng, eps):
-    A = rng.normal(0.0, eps, (3, 3))
-    return np.eye(3) + (A + A.T) / 2
-
-
-def _case(seed, n, eps=0.05):
-    """target (lat*, frac*), a start cell lat* S (S symmetric, ~eps) and start positions near the strained target."""
-    from alignn_amd.synthetic import make_crystal
-
-    lat_t, frac_t, _ = make_crystal(max(n, 2), 700 + seed)
-    frac_t = frac_t[:n]
-    rng = np.random.default_rng(seed)
-    C0 = lat_t @ sym_strain(rng, eps)
-    pos0 = frac_t @ C0 + rng.normal(0.0, 0.05, (n, 3))
-    return lat_t, frac_t, C0, pos0
+from tests.relax_ref import ExpCellFilterRef, _case, _strained_state, exact_branch_state, run_cell_ref, sym3
+from tests.springs_ref import simple_cubic, spring_list, springs_efs
 
 
 def _energy_of_X(filt, efs):
@@ -180,15 +35,6 @@ def test_cell_rows_at_identity_are_the_virial_over_n():
     W = -abs(np.linalg.det(C0)) * sym3(s)
     assert filt.branch == "naive" and np.abs(W).max() > 1e-2
     assert np.array_equal(g[5:], W / 5) and np.array_equal(g[:5], f @ np.eye(3))
-
-
-def _strained_state(seed, n, eps):
-    lat_t, frac_t, C0, pos0 = _case(seed, n)
-    filt = ExpCellFilterRef(C0, n)
-    rng = np.random.default_rng(100 + seed)
-    F = sym_strain(rng, eps)  # ~eps strain / shear on top of C0
-    X = np.vstack([pos0 + rng.normal(0.0, 0.05, (n, 3)), n * np.real(logm(F))])
-    return filt, X, springs_efs(*spring_list(lat_t, frac_t))
 
 
 @pytest.mark.parametrize("seed,n,eps", [(2, 3, 0.05), (3, 6, 0.08), (4, 1, 0.05)])
@@ -223,24 +69,6 @@ def test_exact_cell_rows_and_atom_rows_are_minus_the_gradient(seed, n, eps):
     assert np.abs(N / filt.c - cell).max() > 1e-9 * scale
     filt.forces(X, f, s)
     assert filt.branch == "naive"
-
-
-def exact_branch_state(seed):
-    """A large symmetric log-strain L and a skewed virial for which cos(exact, naive) < 0.8: (L, stress) with the stress
-    in eV/A^3 for a cell of volume ``V``."""
-    rng = np.random.default_rng(seed)
-    while True:
-        A = rng.normal(size=(3, 3))
-        L = 0.6 * (A + A.T)
-        B = rng.normal(size=(3, 3))
-        W = 50.0 * (B + B.T)
-        Y = np.zeros((6, 6))
-        Y[:3, :3] = Y[3:, 3:] = L
-        Y[:3, 3:] = -W @ expm(-L)
-        E = -expm(Y)[:3, 3:]
-        E = (E + E.T) / 2
-        if np.sum(E * W) / np.sqrt(np.sum(E * E) * np.sum(W * W)) < 0.6:
-            return L, W
 
 
 def test_switch_takes_the_exact_force_when_the_two_point_apart():
@@ -279,15 +107,6 @@ def test_expm_logm_round_trip():
     filt = ExpCellFilterRef(np.eye(3) * 4.0, 4)
     X = np.vstack([np.ones((4, 3)), 4 * L])
     assert np.abs(filt.from_atoms(*filt.atoms(X)[:2]) - X).max() <= 1e-12 * np.abs(X).max()
-
-
-def simple_cubic(a0, k=2.0):
-    """One atom, springs of rest length a0 (faces) and a0 sqrt(2) (edges) to its periodic images."""
-    imgs = [v for v in itertools.product((-1, 0, 1), repeat=3) if 0 < sum(abs(x) for x in v) <= 2]
-    img = np.array(imgs, dtype=np.float64)
-    d0 = a0 * np.sqrt((img ** 2).sum(1))
-    z = np.zeros(len(imgs), dtype=int)
-    return springs_efs(z, z, img, d0, np.full(len(imgs), k))
 
 
 def test_one_atom_cubic_crystal_relaxes_to_its_lattice_constant():

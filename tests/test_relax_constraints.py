@@ -1,151 +1,21 @@
-"""The executable specification of the constraints of ``alignn_amd.relax`` (csrc/relax.hip, the last fields of
-``alignn_fire_args``): ASE 3.22.1's ``FixAtoms`` and the arguments ``mask``, ``hydrostatic_strain``, ``constant_volume`` and
-``scalar_pressure`` of ``ExpCellFilter`` (ase/constraints.py), restated in float64 numpy / scipy on top of ``ExpCellFilterRef``
-and ``FireRef``.  ASE is not a dependency: the restatement is pinned by a case worked out by hand, by gradient checks of the
-enthalpy of the analytic spring potential of test_relax_cell.py, and by the physics of converged runs.  The GPU tests
-(test_gpu_relax_constraints.py) hold the kernel and the relaxer to it.
-
-``ExpCellFilter.get_forces`` with its arguments, in ASE's order (V = |det C|, S the symmetrised stress, L = X_c / c):
-  1. FixAtoms: the fixed atoms' rows of the forces are zero (``atoms.get_forces(apply_constraint=True)``); atom rows f F
-  2. virial W = -V (S + scalar_pressure I)
-  3. hydrostatic_strain: W <- (tr W / 3) I
-  4. W <- W * mask
-  5. naive force W, exact force -expm([[L, -W expm(-L)], [0, L]])[0:3, 3:6] symmetrised, ASE's switch between them
-  6. constant_volume: tr / 3 off the diagonal of the chosen one
-  7. / c
-"""
+"""Checks of ``ConstrainedFilterRef``, ``run_constrained_ref`` and ``run_fixed_ref`` of tests/relax_ref.py, the restatement of
+ASE 3.22.1's ``FixAtoms`` and of the arguments ``mask``, ``hydrostatic_strain``, ``constant_volume`` and ``scalar_pressure`` of
+``ExpCellFilter`` that specifies the constraints of ``alignn_amd.relax`` (csrc/relax.hip, the last fields of
+``alignn_fire_args``); the order of ``ExpCellFilter.get_forces`` is written out there.  ASE is not a dependency: the restatement
+is pinned by a case worked out by hand, by gradient checks of the enthalpy of the analytic spring potential of
+tests/springs_ref.py, and by the physics of converged runs.  The GPU tests (test_gpu_relax_constraints.py) hold the kernel and
+the relaxer to it."""
 
 import inspect
 
 import numpy as np
 import pytest
-from scipy.linalg import expm
 
 from alignn_amd import _lib
 from alignn_amd.relax import RelaxResult, relax
-from tests.test_relax_cell import (ExpCellFilterRef, _case, _strained_state, run_cell_ref, simple_cubic, spring_list,
-                                   springs_efs, sym3)
-from tests.test_relax_fire import DEFAULTS, FireRef, converged
-
-
-def voigt_mask(m):
-    """A mask of six Voigt flags (xx, yy, zz, yz, xz, xy) as the full 3 x 3 (voigt_6_to_full_3x3_stress); a [3, 3] as it is."""
-    m = np.asarray(m, dtype=np.float64)
-    if m.shape == (3, 3):
-        return m.copy()
-    xx, yy, zz, yz, xz, xy = m
-    return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
-
-
-class ConstrainedFilterRef(ExpCellFilterRef):
-    """ExpCellFilter(atoms, mask, hydrostatic_strain, constant_volume, scalar_pressure) around atoms with FixAtoms(fixed)."""
-
-    def __init__(self, C0, n, mask=None, hydrostatic_strain=False, constant_volume=False, scalar_pressure=0.0, fixed=None):
-        super().__init__(C0, n)
-        self.mask = np.ones((3, 3)) if mask is None else voigt_mask(mask)
-        self.hydrostatic_strain, self.constant_volume = hydrostatic_strain, constant_volume
-        self.pressure = float(scalar_pressure)
-        self.fixed = np.zeros(n, dtype=bool) if fixed is None else np.asarray(fixed, dtype=bool)
-
-    def virial(self, X, stress):
-        C, _, _ = self.atoms(X)
-        W = -abs(np.linalg.det(C)) * (sym3(stress) + np.diag([self.pressure] * 3))
-        if self.hydrostatic_strain:
-            vtr = W.trace()
-            W = np.diag([vtr / 3.0, vtr / 3.0, vtr / 3.0])
-        if (self.mask != 1.0).any():
-            W = W * self.mask
-        return W
-
-    def cell_forces(self, X, stress):
-        W = self.virial(X, stress)
-        L = X[self.n:] / self.c
-        Y = np.zeros((6, 6))
-        Y[0:3, 0:3] = L
-        Y[3:6, 3:6] = L
-        Y[0:3, 3:6] = -W @ expm(-L)
-        E = -expm(Y)[0:3, 3:6]
-        for i, j in ((0, 1), (0, 2), (1, 2)):
-            E[i, j] = E[j, i] = 0.5 * (E[i, j] + E[j, i])
-        return W.copy(), E
-
-    def constrain(self, G):
-        """The constant-volume step on a cell force (after the choice between naive and exact)."""
-        G = G.copy()
-        if self.constant_volume:
-            np.fill_diagonal(G, np.diag(G) - G.trace() / 3.0)
-        return G
-
-    def forces(self, X, f, stress):
-        f = np.array(f, dtype=np.float64)
-        f[self.fixed] = 0.0
-        _, _, F = self.atoms(X)
-        N, E = self.cell_forces(X, stress)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            cos = np.sum(E * N) / np.sqrt(np.sum(E ** 2) * np.sum(N ** 2))
-        naive = bool(np.all(np.isclose(E, N))) or bool(cos > 0.8)
-        self.branch = "naive" if naive else "exact"
-        return np.vstack([f @ F, self.constrain(N if naive else E) / self.c])
-
-    def enthalpy(self, X, e):
-        return e + self.pressure * abs(np.linalg.det(self.atoms(X)[0]))
-
-
-def run_constrained_ref(C0, pos0, efs, fmax=0.1, steps=100, fire=None, **options):
-    """run_cell_ref with the constrained filter: Optimizer.run(fmax, steps) of FIRE(ExpCellFilter(atoms, **options)).
-    Beside run_cell_ref's fields: h (the enthalpy), h0 (that of the start), Xs (X at the start and after each step)."""
-    filt = ConstrainedFilterRef(C0, len(pos0), **options)
-    opt = FireRef(filt.initial(pos0), **{**DEFAULTS, **(fire or {})})
-
-    def evaluate():
-        C, pos, _ = filt.atoms(opt.r)
-        e, f, s = efs(C, pos)
-        return e, f, s, filt.forces(opt.r, f, s)
-
-    e, f, s, g = evaluate()
-    h0 = filt.enthalpy(opt.r, e)
-    n_evals, n_steps, branches, Xs = 1, 0, [filt.branch], [opt.r.copy()]
-    traj = [filt.atoms(opt.r)[:2]]
-    conv = converged(g, fmax)
-    while not conv and n_steps < steps:
-        opt.step(g)
-        n_steps += 1
-        Xs.append(opt.r.copy())
-        traj.append(filt.atoms(opt.r)[:2])
-        e, f, s, g = evaluate()
-        branches.append(filt.branch)
-        n_evals += 1
-        conv = converged(g, fmax)
-    C, pos, _ = filt.atoms(opt.r)
-    return dict(X=opt.r, C=C, pos=pos, e=e, f=f, s=s, g=g, n_steps=n_steps, converged=conv, n_evals=n_evals, traj=traj,
-                branches=branches, opt=opt, h=filt.enthalpy(opt.r, e), h0=h0, Xs=Xs, filt=filt)
-
-
-def run_fixed_ref(pos0, ef, fixed, fmax=0.1, steps=100, fire=None):
-    """Optimizer.run(fmax, steps) of FIRE(atoms) at fixed cell with FixAtoms(fixed); ``ef(pos) -> (e, f)``.  ``f`` of the result
-    is the force as evaluated, ``g`` the constrained one."""
-    fixed = np.asarray(fixed, dtype=bool)
-    opt = FireRef(pos0, **{**DEFAULTS, **(fire or {})})
-
-    def evaluate():
-        e, f = ef(opt.r)
-        g = np.array(f, dtype=np.float64)
-        g[fixed] = 0.0
-        return e, np.asarray(f, dtype=np.float64), g
-
-    e, f, g = evaluate()
-    n_steps, Xs = 0, [opt.r.copy()]
-    conv = converged(g, fmax)
-    while not conv and n_steps < steps:
-        opt.step(g)
-        n_steps += 1
-        Xs.append(opt.r.copy())
-        e, f, g = evaluate()
-        conv = converged(g, fmax)
-    return dict(r=opt.r, e=e, f=f, g=g, n_steps=n_steps, converged=conv, n_evals=n_steps + 1, Xs=Xs)
-
-
-SLAB = [1, 1, 0, 0, 0, 1]  # the in-plane cell free, the vacuum axis frozen
+from tests.relax_ref import (SLAB, ConstrainedFilterRef, _case, _strained_state, run_cell_ref, run_constrained_ref, run_fixed_ref,
+                             sym3, voigt_mask)
+from tests.springs_ref import simple_cubic, spring_list, springs_efs
 
 
 # --- the restatement with everything off is ExpCellFilterRef ----------------------------------------------------------------
@@ -214,7 +84,7 @@ def test_cell_rows_by_hand():
 
 # --- the cell rows are minus the gradient of the enthalpy over the free components -------------------------------------------
 def _state_in(seed, n, eps, basis):
-    """A strained state (test_relax_cell._strained_state) whose log-strain L lies in the span of ``basis`` (symmetric 3 x 3
+    """A strained state (relax_ref._strained_state) whose log-strain L lies in the span of ``basis`` (symmetric 3 x 3
     matrices, orthogonal to each other): its projection onto it."""
     filt, X, efs = _strained_state(seed, n, eps)
     L = X[n:] / n

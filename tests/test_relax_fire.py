@@ -1,87 +1,13 @@
-"""The executable specification of ``alignn_amd.relax`` (csrc/relax.hip): a float64 numpy restatement of the FIRE optimiser and
-of the run loop the reference drives it with (``ForceField.optimize_atoms``, alignn/ff/ff.py:373-415: ``FIRE(atoms).run(fmax,
-steps)`` with ``optimize_lattice=False``, ``downhill_check=False``).  ASE is not a dependency of this project, so ``FireRef``
-and ``run_ref`` follow ASE's published ``ase/optimize/fire.py`` (``FIRE.step``) and ``ase/optimize/optimize.py``
-(``Optimizer.run`` / ``Dynamics.irun`` / ``Optimizer.converged``) line by line; the checks below pin them to steps computed by
-hand on a 1-D harmonic well.  The GPU tests (test_gpu_relax.py) hold the kernel and the batched relaxer to this restatement."""
+"""Checks of ``FireRef`` and ``run_ref`` of tests/relax_ref.py, the float64 numpy restatement of ASE's FIRE and ``Optimizer.run``
+that specifies ``alignn_amd.relax`` (csrc/relax.hip): steps computed by hand on a 1-D harmonic well, and what the entry point
+refuses before it touches a device.  The GPU tests (test_gpu_relax.py) hold the kernel and the batched relaxer to the
+restatement."""
 
 import numpy as np
 import pytest
 
-from alignn_amd.relax import RelaxResult, relax  # the batched relaxer this file specifies
-
-# ASE's FIRE defaults
-DEFAULTS = dict(dt=0.1, maxstep=0.2, dtmax=1.0, Nmin=5, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, a=0.1)
-
-
-class FireRef:
-    """ase/optimize/fire.py FIRE.step, downhill_check=False, one structure; ``r`` [n, 3] Cartesian positions."""
-
-    def __init__(self, r, dt=0.1, maxstep=0.2, dtmax=1.0, Nmin=5, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, a=0.1):
-        self.r = np.array(r, dtype=np.float64)
-        self.v = None  # FIRE.initialize
-        self.dt, self.maxstep, self.dtmax, self.Nmin = dt, maxstep, dtmax, Nmin
-        self.finc, self.fdec, self.astart, self.fa, self.a = finc, fdec, astart, fa, a
-        self.Nsteps = 0
-
-    def step(self, f):
-        f = np.asarray(f, dtype=np.float64)
-        if self.v is None:
-            self.v = np.zeros((len(self.r), 3))
-        else:
-            vf = np.vdot(f, self.v)
-            if vf > 0.0:
-                self.v = (1.0 - self.a) * self.v + self.a * f / np.sqrt(np.vdot(f, f)) * np.sqrt(np.vdot(self.v, self.v))
-                if self.Nsteps > self.Nmin:
-                    self.dt = min(self.dt * self.finc, self.dtmax)
-                    self.a *= self.fa
-                self.Nsteps += 1
-            else:
-                self.v[:] *= 0.0
-                self.a = self.astart
-                self.dt *= self.fdec
-                self.Nsteps = 0
-        self.v += self.dt * f
-        dr = self.dt * self.v
-        normdr = np.sqrt(np.vdot(dr, dr))
-        if normdr > self.maxstep:
-            dr = self.maxstep * dr / normdr
-        self.r = self.r + dr
-
-
-def converged(f, fmax):
-    """Optimizer.converged: max over atoms of |F_i|^2 below fmax^2."""
-    return bool((np.asarray(f) ** 2).sum(axis=1).max() < fmax ** 2)
-
-
-def run_ref(r0, energy_forces, fmax=0.1, steps=100, **fire):
-    """Optimizer.run(fmax, steps): evaluate, then step while not converged and fewer than ``steps`` steps were taken.
-    ``energy_forces(r) -> (e, f)``.  -> dict(r, e, f, n_steps, converged, n_evals, traj: positions after each step)."""
-    opt = FireRef(r0, **{**DEFAULTS, **fire})
-    e, f = energy_forces(opt.r)
-    n_evals, n_steps, traj = 1, 0, [opt.r.copy()]
-    conv = converged(f, fmax)
-    while not conv and n_steps < steps:
-        opt.step(f)
-        n_steps += 1
-        traj.append(opt.r.copy())
-        e, f = energy_forces(opt.r)
-        n_evals += 1
-        conv = converged(f, fmax)
-    return dict(r=opt.r, e=e, f=np.asarray(f, dtype=np.float64), n_steps=n_steps, converged=conv, n_evals=n_evals, traj=traj,
-                opt=opt)
-
-
-def well(k, x0=0.0):
-    """1-D harmonic well along x for one atom: E = k (x - x0)^2 / 2, F = -k (x - x0)."""
-
-    def ef(r):
-        d = r[:, 0] - x0
-        f = np.zeros_like(r)
-        f[:, 0] = -k * d
-        return 0.5 * k * float(d @ d), f
-
-    return ef
+from alignn_amd.relax import RelaxResult, relax  # the batched relaxer the restatement specifies
+from tests.relax_ref import FireRef, run_ref, well
 
 
 def test_first_step_has_no_mixing():

@@ -61,7 +61,7 @@ def host_dispersion(C, m, qs):
 
 def reference_loop(model, lats, pos, feats, masses, delta=0.01):
     """One displaced supercell per model call, force constants in numpy, then the host dispersion."""
-    from tests.test_phonons_ref import displaced_supercells, force_constants, inv_supercell
+    from tests.phonons_ref import displaced_supercells, force_constants, inv_supercell
 
     for lat, p, f, m in zip(lats, pos, feats, masses):
         n = len(p)
