@@ -179,6 +179,9 @@ SIGNATURES = {
     "alignn_phonon_eigh_max_dim": (_i32, []),
     "alignn_phonon_eigh": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _p, _i32, _f64, _p, _p, _p, _p, _p, _p, _p]),
     "alignn_phonon_dos": (_i32, [_p, _p, _i32, _i32, _f64, _p, _p, _p]),
+    # builders of the defect tasks' supercells and slabs (csrc/defects.hip)
+    "alignn_defect_supercells": (_i32, [_p, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
+    "alignn_slab_build": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

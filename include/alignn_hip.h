@@ -1099,6 +1099,30 @@ int alignn_phonon_eigh(const double* dyn, const int64_t* dyn_off, const int32_t*
 int alignn_phonon_dos(const double* freqs, const int64_t* freq_off, int n_structures, int npts, double width, double* energies,
                       double* weights, alignn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Builders of the defect tasks' derived structures (csrc/defects.hip; alignn_amd/defects.py is the driver, tests/defects_ref.py
+ * the numpy restatement).  positions [atoms][3] Cartesian, atom_ptr [n_structures + 1] and lattice [n_structures][3][3] (rows
+ * a, b, c) are the packed parents.  Job k writes its cell to cells [k][3][3] and its rows [row_off[k], row_off[k+1]) of cart
+ * [.][3] (Cartesian), frac [.][3] (wrapped into [0, 1) of its cell) and src [.] (the row of positions an atom came from).  One
+ * workgroup per job, float64 without contraction, fixed-order sums: a job's bits do not depend on the launch it is in.  A job
+ * whose fields or row range do not fit (structure index, removed atom, layers, |det| of the basis, row count) writes nothing.
+ *
+ * _supercells: jobs [n_jobs][2] = (s, a): the supercell (N0, N1, N2) = supercell[s] of structure s, atom j = image n_s + b,
+ * image = (m0 N1 + m1) N2 + m2, cart = ((r_b + m0 L0) + m1 L1) + m2 L2, cell diag(N) L; a = -1: all n_s N0 N1 N2 atoms; a >= 0:
+ * without supercell atom a, the later rows one up.
+ * _slab_build: jobs [n_jobs][11] = (s, c1 [3], c2 [3], c3 [3], layers), vacuum [n_jobs] (A): the slab of `layers` repeats of the
+ * parent re-expressed in the unimodular integer basis Bm (rows c1, c2, c3), n_s layers atoms, atom j = layer n_s + b.
+ * C = Bm L; oriented fractions o = frac Bm^-1 (integer adjugate), o -= floor(o + 1e-10); layer m at (o0 C0 + o1 C1) + (o2 + m) C2;
+ * a3 = nu ((layers C2) . nu) / (nu . nu), nu = C0 x C1; the positions wrapped (floor(f + 1e-10)) into [C0, C1, a3]; the cell
+ * written is [C0, C1, a3 + vacuum a3 / |a3|]: the slab at the bottom of the cell, the vacuum above it.
+ * ------------------------------------------------------------------------------------------ */
+int alignn_defect_supercells(const double* positions, const int32_t* atom_ptr, const double* lattice, const int32_t* supercell,
+                             int n_structures, const int32_t* jobs, const int64_t* row_off, int n_jobs, double* cells,
+                             double* cart, double* frac, int32_t* src, alignn_stream_t stream);
+int alignn_slab_build(const double* positions, const int32_t* atom_ptr, const double* lattice, int n_structures,
+                      const int32_t* jobs, const double* vacuum, const int64_t* row_off, int n_jobs, double* cells, double* cart,
+                      double* frac, int32_t* src, alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
