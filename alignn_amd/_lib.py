@@ -182,6 +182,9 @@ SIGNATURES = {
     # builders of the defect tasks' supercells and slabs (csrc/defects.hip)
     "alignn_defect_supercells": (_i32, [_p, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "alignn_slab_build": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
+    # strained structures and the equation-of-state fit of the E-V curve task (csrc/eos.hip)
+    "alignn_strain_build": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "alignn_eos_fit": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

@@ -166,10 +166,11 @@ def _common_checks(who: str, max_atoms_per_call, relax_kwargs: dict):
         raise ValueError(f"{who}: scalar_pressure is one number for every job")
 
 
-def _relax_jobs(who, model, cells, cart, src, counts, feats_all, max_atoms_per_call, relax_structures, relax_kwargs,
-                forces_fn, dev):
+def _relax_jobs_device(who, model, cells, cart, src, counts, feats_all, max_atoms_per_call, relax_structures, relax_kwargs,
+                       forces_fn, dev):
     """``relax`` over the jobs (cells [J, 3, 3], rows of cart / src split by ``counts``) in groups of whole jobs of at most
-    ``max_atoms_per_call`` atoms -> (energies [J] numpy, lattices [J, 3, 3], [positions], converged [J], n_steps [J], calls)."""
+    ``max_atoms_per_call`` atoms -> (energies [J], lattices [J, 3, 3], [positions], converged [J], n_steps [J], calls), the
+    arrays on the device (alignn_amd/eos.py keeps them there)."""
     J = len(counts)
     off = np.concatenate([[0], np.cumsum(counts)])
     groups, cur, atoms = [], [], 0
@@ -194,8 +195,13 @@ def _relax_jobs(who, model, cells, cart, src, counts, feats_all, max_atoms_per_c
         positions += res.positions
         conv.append(res.converged)
         nsteps.append(res.n_steps)
-    return (torch.cat(energies).cpu().numpy(), torch.cat(lattices), positions, torch.cat(conv).cpu().numpy(),
-            torch.cat(nsteps).cpu().numpy(), len(groups))
+    return torch.cat(energies), torch.cat(lattices), positions, torch.cat(conv), torch.cat(nsteps), len(groups)
+
+
+def _relax_jobs(*args):
+    """``_relax_jobs_device`` with the energies, flags and step counts as numpy arrays."""
+    e, lattices, positions, conv, nsteps, calls = _relax_jobs_device(*args)
+    return e.cpu().numpy(), lattices, positions, conv.cpu().numpy(), nsteps.cpu().numpy(), calls
 
 
 def _split(x, job_ptr):

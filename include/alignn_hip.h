@@ -1123,6 +1123,32 @@ int alignn_slab_build(const double* positions, const int32_t* atom_ptr, const do
                       const int32_t* jobs, const double* vacuum, const int64_t* row_off, int n_jobs, double* cells, double* cart,
                       double* frac, int32_t* src, alignn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The E-V curve task (csrc/eos.hip; alignn_amd/eos.py is the driver, tests/eos_ref.py the numpy restatement).  float64 without
+ * contraction, no atomics, fixed-order sums: a job's / a structure's bits do not depend on the launch it is in.
+ *
+ * _strain_build: the packed parents as for the builders above; job k strains parent jobs[k] by the deformation defgrad [k][3][3]
+ * (row-major F): row i of cells [k][3][3] is row i of the parent's cell times F, (x0 F0j + x1 F1j) + x2 F2j; its n_s rows
+ * [row_off[k], row_off[k+1]) of cart [.][3] are r F in the same order; volume [k] = |det| of the new cell by the cofactor
+ * expansion along its first row.  One workgroup per job.  A job whose parent index or row count does not fit writes nothing.
+ *
+ * _eos_fit: structure s has its points in volume / energy [s][0 .. K_s) of rows of `ld` doubles, K_s = n_points[s] (NULL: ld);
+ * 4 <= ld <= 64.  form 0: Murnaghan, 1: Birch-Murnaghan (ase/eos.py).  One wavefront per structure, one lane per point: the
+ * least-squares parabola in (V - mean V) / (max V - min V) gives ASE's start (E0 = parabola(vmin), B0 = 2 c vmin, BP = 4, V0 =
+ * vmin = -b / 2c); then Levenberg-Marquardt with the analytic Jacobian, (J^T J + lambda diag J^T J) delta = -J^T r by Cholesky,
+ * lambda from 1e-3: a step with a finite sum of squares S' <= S is taken (lambda = max(lambda / 10, 1e-15)) and ends the fit
+ * when max |delta| <= 1e-13 max |p| or S - S' <= 1e-16 S; otherwise lambda = 10 lambda, and lambda > 1e15 ends it too (no step
+ * lowers S).  Writes params [s][4] = (E0, B0, BP, V0), rms [s] = sqrt(S / K_s), n_iter [s] (steps taken) and status [s]: 0
+ * converged, 1 stopped after 100 steps (the parameters as they stand), 2 no start (K_s < 4 or > ld, a parabola with c <= 0, a
+ * non-finite value): NaN params and rms, n_iter 0.  log and exp are the file's own (plain arithmetic), so the results are the
+ * restatement's bits.
+ * ------------------------------------------------------------------------------------------ */
+int alignn_strain_build(const double* positions, const int32_t* atom_ptr, const double* lattice, int n_structures,
+                        const int32_t* jobs, const double* defgrad, const int64_t* row_off, int n_jobs, double* cells, double* cart,
+                        double* volume, alignn_stream_t stream);
+int alignn_eos_fit(const double* volume, const double* energy, const int32_t* n_points, int n_structures, int ld, int form,
+                   double* params, double* rms, int32_t* n_iter, int32_t* status, alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
