@@ -185,6 +185,8 @@ SIGNATURES = {
     # strained structures and the equation-of-state fit of the E-V curve task (csrc/eos.hip)
     "alignn_strain_build": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p]),
     "alignn_eos_fit": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
+    # the stress-strain fit of the elastic-tensor task (csrc/elastic.hip)
+    "alignn_elastic_fit": (_i32, [_p, _p, _p, _i32, _i32] + [_p] * 8 + [_p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

@@ -5,7 +5,8 @@
 //
 //   strain_build_kernel   one workgroup per job (parent, deformation F): cell' = cell F, r' = r F, |det cell'|;
 //   eos_fit_kernel        one wavefront per structure, one lane per strain point: the parabola start, then Levenberg-Marquardt
-//                         on (E0, B0, BP, V0) with the analytic Jacobian, the 4 x 4 normal equations solved in every lane.
+//                         on (E0, B0, BP, V0) with the analytic Jacobian, the 4 x 4 normal equations solved in every lane
+//                         (wave_sum and cholesky_solve: wave_fit.h, shared with elastic.hip).
 // float64, no contraction, no atomics, every sum in a fixed order (the sums over the strain points by the xor butterfly of
 // wave_sum, after which every lane holds the same bits, so the control flow is wave-uniform): a structure's bits do not depend
 // on what else shares the launch.  The stopping tests of the fit sit at the rounding level of its residuals, so its step count
@@ -13,6 +14,7 @@
 // has them, and the fit is the restatement's bits too.
 #include "../../include/alignn_hip.h"
 #include "common.h"
+#include "wave_fit.h"
 
 #pragma clang fp contract(off)
 
@@ -98,58 +100,6 @@ __device__ __forceinline__ double fexp(double x) {
 }
 
 // ---- the fit ----
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, ALIGNN_WAVE);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ALIGNN_WAVE));
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, ALIGNN_WAVE));
-    return v;
-}
-
-// A x = b for a symmetric positive definite A by Cholesky: the lower triangle row by row, every inner sum in ascending index
-// order; false where a pivot is not > 0 or not finite
-template <int N>
-__device__ __forceinline__ bool cholesky_solve(const double (&A)[N][N], const double (&b)[N], double (&x)[N]) {
-    double L[N][N], y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
-            if (i == j) {
-                if (!(s > 0.0 && s < INFINITY)) return false;
-                L[i][i] = sqrt(s);
-            } else {
-                L[i][j] = s / L[j][j];
-            }
-        }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
-        y[i] = s / L[i][i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; ++k) s = s - L[k][i] * x[k];
-        x[i] = s / L[i][i];
-    }
-    return true;
-}
-
 // The form at p = (E0, B0, BP, V0) and volume V, as ase/eos.py states it: the energy and (JAC) its derivatives J[1..3] by B0, BP,
 // V0 (the one by E0 is 1).
 //   Murnaghan        E = E0 + B0 V / BP (x^BP / (BP - 1) + 1) - V0 B0 / (BP - 1),               x = V0 / V

@@ -1,0 +1,73 @@
+// What the per-wavefront least-squares fits share (eos.hip, elastic.hip): the sums over a wavefront's lanes by the xor butterfly,
+// after which every lane holds the same bits, and the Cholesky solve of the small normal equations, held in registers by every
+// lane.  float64 without contraction, every sum in a fixed order; tests/eos_ref.py restates both operation for operation.
+#pragma once
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, ALIGNN_WAVE);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ALIGNN_WAVE));
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, ALIGNN_WAVE));
+    return v;
+}
+
+// A = L L^T for a symmetric positive definite A: the lower triangle row by row, every inner sum in ascending index order; false
+// where a pivot is not > 0 or not finite
+template <int N>
+__device__ __forceinline__ bool cholesky_factor(const double (&A)[N][N], double (&L)[N][N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
+            if (i == j) {
+                if (!(s > 0.0 && s < INFINITY)) return false;
+                L[i][i] = sqrt(s);
+            } else {
+                L[i][j] = s / L[j][j];
+            }
+        }
+    return true;
+}
+
+// L L^T x = b: forward, then backward substitution
+template <int N>
+__device__ __forceinline__ void cholesky_substitute(const double (&L)[N][N], const double (&b)[N], double (&x)[N]) {
+    double y[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < N; ++k) s = s - L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+}
+
+// A x = b for a symmetric positive definite A by Cholesky; false where a pivot is not > 0 or not finite
+template <int N>
+__device__ __forceinline__ bool cholesky_solve(const double (&A)[N][N], const double (&b)[N], double (&x)[N]) {
+    double L[N][N];
+    if (!cholesky_factor<N>(A, L)) return false;
+    cholesky_substitute<N>(L, b, x);
+    return true;
+}

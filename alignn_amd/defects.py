@@ -166,11 +166,12 @@ def _common_checks(who: str, max_atoms_per_call, relax_kwargs: dict):
         raise ValueError(f"{who}: scalar_pressure is one number for every job")
 
 
-def _relax_jobs_device(who, model, cells, cart, src, counts, feats_all, max_atoms_per_call, relax_structures, relax_kwargs,
-                       forces_fn, dev):
+def _relax_jobs_stress_device(who, model, cells, cart, src, counts, feats_all, max_atoms_per_call, relax_structures, relax_kwargs,
+                              forces_fn, dev):
     """``relax`` over the jobs (cells [J, 3, 3], rows of cart / src split by ``counts``) in groups of whole jobs of at most
-    ``max_atoms_per_call`` atoms -> (energies [J], lattices [J, 3, 3], [positions], converged [J], n_steps [J], calls), the
-    arrays on the device (alignn_amd/eos.py keeps them there)."""
+    ``max_atoms_per_call`` atoms -> (energies [J], lattices [J, 3, 3], [positions], converged [J], n_steps [J], calls,
+    stresses [J, 3, 3] or None without ``optimize_lattice``), the arrays on the device (alignn_amd/eos.py and
+    alignn_amd/elastic.py keep them there)."""
     J = len(counts)
     off = np.concatenate([[0], np.cumsum(counts)])
     groups, cur, atoms = [], [], 0
@@ -185,7 +186,7 @@ def _relax_jobs_device(who, model, cells, cart, src, counts, feats_all, max_atom
     kw.update(relax_kwargs)
     if not relax_structures:
         kw["steps"] = 0
-    energies, lattices, positions, conv, nsteps = [], [], [], [], []
+    energies, lattices, positions, conv, nsteps, stresses = [], [], [], [], [], []
     for g in groups:
         rows = [slice(int(off[j]), int(off[j + 1])) for j in g]
         feats = None if feats_all is None else [feats_all[src[r].long()] for r in rows]
@@ -195,7 +196,14 @@ def _relax_jobs_device(who, model, cells, cart, src, counts, feats_all, max_atom
         positions += res.positions
         conv.append(res.converged)
         nsteps.append(res.n_steps)
-    return torch.cat(energies), torch.cat(lattices), positions, torch.cat(conv), torch.cat(nsteps), len(groups)
+        stresses.append(res.stresses)
+    stress = None if stresses[0] is None else torch.cat(stresses)
+    return torch.cat(energies), torch.cat(lattices), positions, torch.cat(conv), torch.cat(nsteps), len(groups), stress
+
+
+def _relax_jobs_device(*args):
+    """``_relax_jobs_stress_device`` without the stresses."""
+    return _relax_jobs_stress_device(*args)[:6]
 
 
 def _relax_jobs(*args):

@@ -1149,6 +1149,25 @@ int alignn_strain_build(const double* positions, const int32_t* atom_ptr, const 
 int alignn_eos_fit(const double* volume, const double* energy, const int32_t* n_points, int n_structures, int ld, int form,
                    double* params, double* rms, int32_t* n_iter, int32_t* status, alignn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The elastic-tensor task (csrc/elastic.hip; alignn_amd/elastic.py is the driver, tests/elastic_ref.py the numpy restatement).
+ * float64 without contraction, no atomics, fixed-order sums: a crystal's bits do not depend on the launch it is in.
+ *
+ * _elastic_fit: crystal s has its points in strain [s][0 .. P_s)[6] and stress [s][0 .. P_s)[3][3] of rows of `ld` points, P_s =
+ * n_points[s] (NULL: ld); 7 <= ld <= 64.  strain is the applied small strain in Voigt order xx, yy, zz, yz, xz, xy with
+ * engineering shear (gamma = 2 eps); the Voigt stress is taken from the 3 x 3 one, its off-diagonals the mean of the two stored
+ * halves.  One wavefront per crystal, one lane per point: least squares of sigma_i = sigma0_i + sum_j C_ij eps_j, the columns
+ * scaled by w = max |eps|, one 7 x 7 Cholesky factorisation and six solves.  Writes c_raw [s][6][6] (the fit), c [s][6][6] =
+ * (c_raw + c_raw^T) / 2, compliance [s][6][6] = c^-1 (a 6 x 6 Cholesky), sigma0 [s][6], moduli [s][9] = (K_V, K_R, K_H, G_V,
+ * G_R, G_H, E, nu, A_U) in the Voigt-Reuss-Hill form, rms [s] (root mean square residual of the 6 P_s stress values),
+ * asymmetry [s] = max |c_raw - c_raw^T| / max |c_raw| and status [s]: 0 fitted and c positive definite (Born stable); 1 fitted,
+ * c not positive definite: compliance and every modulus but K_V and G_V are NaN; 2 no fit (P_s < 7 or > ld, a non-finite
+ * input, no non-zero strain, a rank-deficient strain set): every float output is NaN.
+ * ------------------------------------------------------------------------------------------ */
+int alignn_elastic_fit(const double* strain, const double* stress, const int32_t* n_points, int n_structures, int ld,
+                       double* c_raw, double* c, double* compliance, double* sigma0, double* moduli, double* rms,
+                       double* asymmetry, int32_t* status, alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
