@@ -11,6 +11,7 @@ from .eos import EOS_FORMS, EV_A3_TO_GPA, EVResult, eos_fit, ev_curve  # noqa: F
 from .dynamics import MDResult, run_md  # noqa: F401
 from .phonons import EV_TO_CM1, EV_TO_THZ, PhononResult, phonons  # noqa: F401
 from .ealignn_atomwise import eALIGNNAtomWise, eALIGNNAtomWiseConfig  # noqa: F401
+from .interface import InterfaceResult, MatchResult, interface_energy, match_lattices  # noqa: F401
 from .graph import CSRGraph, GraphBatch, build_csr  # noqa: F401
 from .relax import RelaxResult, relax  # noqa: F401
 

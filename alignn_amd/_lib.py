@@ -187,6 +187,10 @@ SIGNATURES = {
     "alignn_eos_fit": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
     # the stress-strain fit of the elastic-tensor task (csrc/elastic.hip)
     "alignn_elastic_fit": (_i32, [_p, _p, _p, _i32, _i32] + [_p] * 8 + [_p]),
+    # the lattice match and the builder of the interface task (csrc/interface.hip)
+    "alignn_zsl_match": (_i32, [_p, _p, _i32, _p, _p, _i32, _i32, _p, _p, _p, _p, _i64, _i64] + [_p] * 6 + [_f64] * 3 + [_p] * 5
+                         + [_p]),
+    "alignn_interface_build": (_i32, [_p, _p, _p, _p, _i32, _p, _p, _p, _p, _i32] + [_p] * 6 + [_p]),
 }
 
 # argument blocks of the composite entry points (include/alignn_hip.h: alignn_egc_fwd_args / _bwd_args / _wgrad_args), packed

@@ -1168,6 +1168,49 @@ int alignn_elastic_fit(const double* strain, const double* stress, const int32_t
                        double* c_raw, double* c, double* compliance, double* sigma0, double* moduli, double* rms,
                        double* asymmetry, int32_t* status, alignn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The interface task (csrc/interface.hip; alignn_amd/interface.py is the driver, tests/interface_ref.py the numpy restatement,
+ * INTEGRATION.md the specification).  float64 without contraction, no atomics, min / max and a total order on the match keys
+ * only: a pair's bits do not depend on the launch it is in.
+ *
+ * _zsl_match: pair p has the surface cells film_cells [p][2][2] and subs_cells [p][2][2] (rows v1, v2 in the plane, v1 x v2 > 0)
+ * and the largest multiples nmax_film [p], nmax_subs [p] <= max_film, max_subs <= 256 of its two sides (n area <= max_area; the
+ * host's).  hnf [.][3] = (n, a, b) lists the Hermite normal forms [[a, b], [0, n / a]] of every n <= 256 in the order (n, a, b),
+ * prefix [n] (n = 1 .. 257) the first entry of multiple n.  Workspaces: film_tab [film_rows][4], film_int [film_rows][4],
+ * subs_tab [subs_rows][6][4], subs_int [subs_rows][4] with pair p's prefix [nmax + 1] rows from film_off [p] / subs_off [p], and
+ * best_score, best_tag [n_pairs][max_film].  Every super-lattice u = a v1 + b v2, w = (n / a) v2 is Lagrange-reduced keeping its
+ * orientation ((u, w) <- (w, -u) while |u| > |w|, w <- w - rint(u.w / u.u) u, at most 64 rounds); a film basis is compared with
+ * the six variants (u, w), (u, w + u), (u, w - u), (w, -u), (w, -u + w), (w, -u - w) of a substrate basis where
+ * |i A_f / (j A_s) - 1| <= max_area_ratio_tol, and accepted where ru = | |u_s| / |u_f| - 1 | <= ltol, rw likewise and
+ * cos(dtheta) >= cos_atol; score = max(ru, rw, |sin(dtheta)|).  Of the accepted candidates the one with the smallest key (i,
+ * score, j, film entry, substrate entry, variant) gives status [p] = 0, multiples [p][2] = (i, j), film_matrix [p][2][2] and
+ * subs_matrix [p][2][2] (rows u, w in units of v1, v2; dets i and j) and mismatch [p][4] = (ru, rw, sin(dtheta), score).
+ * status 1: no candidate was accepted; status 2: a cell is not finite or v1 x v2 is not > 0.  With status != 0 nothing else is
+ * written for the pair.
+ *
+ * _interface_build: the slabs are alignn_slab_build's with vacuum 0 (slab_cells [n_slabs][3][3], rows slab_off [k] ..
+ * slab_off [k + 1] of slab_cart and slab_src).  jobs [n_pairs][10] = (film slab, substrate slab, film matrix [4], substrate
+ * matrix [4]); pair p writes three structures in one cell, cells [3 p + (0, 1, 2)], rows out_off [3 p + k] .. out_off [3 p + k +
+ * 1] of cart, frac (wrapped into [0, 1)), src (slab_src of the slab row) and part (0 substrate, 1 film): the substrate's j n_s
+ * rows, the film's i n_f rows, then both (substrate first).  Cell: A0 = (|u_s|, 0, 0), A1 = (u_s.w_s, u_s x w_s, 0) / |u_s|, A2 =
+ * (0, 0, Lz), u_s and w_s the substrate's super-cell vectors in the plane of its slab (x along the slab's row 0).  A slab atom
+ * with fractions f, image (m0, m1), m0 < a, m1 < det / a, a = gcd(M00, M10), row (m0 det / a + m1) n + atom, sits at the
+ * in-plane fractions g = (f0 + m0, f1 + m1) M^-1, g -= floor(g + 1e-10), of (A0, A1) - the film strained onto the substrate's
+ * cell - and at the height h = f2 |a3| of its slab: z = h - min_s h for the substrate, z = ((h - min_f h) + max_s z) +
+ * separation [p] for the film, Lz = max_f z + vacuum [p].  area [p] = |A0 x A1|.  A pair whose slab indices, dets (1 .. 256) or
+ * row ranges do not fit writes nothing.
+ * ------------------------------------------------------------------------------------------ */
+int alignn_zsl_match(const double* film_cells, const double* subs_cells, int n_pairs, const int32_t* nmax_film,
+                     const int32_t* nmax_subs, int max_film, int max_subs, const int32_t* hnf, const int32_t* prefix,
+                     const int64_t* film_off, const int64_t* subs_off, int64_t film_rows, int64_t subs_rows, double* film_tab,
+                     int32_t* film_int, double* subs_tab, int32_t* subs_int, double* best_score, int64_t* best_tag,
+                     double max_area_ratio_tol, double ltol, double cos_atol, int32_t* status, int32_t* multiples,
+                     int32_t* film_matrix, int32_t* subs_matrix, double* mismatch, alignn_stream_t stream);
+int alignn_interface_build(const double* slab_cells, const double* slab_cart, const int64_t* slab_off, const int32_t* slab_src,
+                           int n_slabs, const int32_t* jobs, const double* separation, const double* vacuum,
+                           const int64_t* out_off, int n_pairs, double* cells, double* cart, double* frac, int32_t* src,
+                           int32_t* part, double* area, alignn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
