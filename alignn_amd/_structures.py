@@ -30,9 +30,15 @@ import torch
 
 from . import neighbors
 
+EV_A3_TO_GPA = 160.21766208  # eV/A^3 -> GPa (ASE 3.22's 1e24 / kJ): the calculator's stress unit
+
 
 def shape_of(x):
     return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def host(x) -> np.ndarray:
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
 def check_inputs(who: str, model, lattices: Sequence, positions: Sequence, atom_features: Optional[Sequence],
@@ -180,7 +186,7 @@ class ForceEvaluator:
             forces = (res["grad"].detach().reshape(-1, 3) * self.force_multiplier).double()
             if self.stress_weight is not None:  # the calculator: voigt (symmetrised) stress * stress_wt / 160.21766208, float32
                 st = res["stresses"].detach().reshape(-1, 3, 3).float()
-                stress = ((st + st.transpose(1, 2)) / 2 * self.stress_weight / 160.21766208).double()
+                stress = ((st + st.transpose(1, 2)) / 2 * self.stress_weight / EV_A3_TO_GPA).double()
         else:
             out = self.forces_fn(lattices, cart)
             if self.stress_weight is not None:

@@ -10,6 +10,7 @@
 // the launch.  A job whose structure index, removed atom, layer count or row range does not fit writes nothing.
 #include "../../include/alignn_hip.h"
 #include "common.h"
+#include "cell3.h"
 
 #pragma clang fp contract(off)
 
@@ -17,26 +18,6 @@ namespace {
 
 constexpr int DF_BLOCK = 256;
 constexpr double DF_TOL = 1e-10;  // general_surface's tolerance of the wrap: s -= floor(s + tol)
-
-// inverse of a row-major 3 x 3 by cofactors, every element its cofactor / det (common.h's inverse3, here without contraction)
-__device__ __forceinline__ void inv3_cof(const double (&a)[9], double (&inv)[9]) {
-    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[3] * a[8] - a[5] * a[6], c02 = a[3] * a[7] - a[4] * a[6];
-    const double det = (a[0] * c00 - a[1] * c01) + a[2] * c02;
-    inv[0] = c00 / det;
-    inv[1] = (a[2] * a[7] - a[1] * a[8]) / det;
-    inv[2] = (a[1] * a[5] - a[2] * a[4]) / det;
-    inv[3] = -c01 / det;
-    inv[4] = (a[0] * a[8] - a[2] * a[6]) / det;
-    inv[5] = (a[2] * a[3] - a[0] * a[5]) / det;
-    inv[6] = c02 / det;
-    inv[7] = (a[1] * a[6] - a[0] * a[7]) / det;
-    inv[8] = (a[0] * a[4] - a[1] * a[3]) / det;
-}
-
-// x M for a row vector x and a row-major M: (x0 M0k + x1 M1k) + x2 M2k
-__device__ __forceinline__ double row_dot(const double (&x)[3], const double (&m)[9], int k) {
-    return (x[0] * m[k] + x[1] * m[3 + k]) + x[2] * m[6 + k];
-}
 
 // Supercell atom j = image * n + b, image = (m0 N1 + m1) N2 + m2, cart = ((r_b + m0 L0) + m1 L1) + m2 L2 (the order of
 // phonon_displace_kernel).  With a removed atom a >= 0 the rows after a move up by one.

@@ -14,6 +14,7 @@
 // has them, and the fit is the restatement's bits too.
 #include "../../include/alignn_hip.h"
 #include "common.h"
+#include "cell3.h"
 #include "wave_fit.h"
 
 #pragma clang fp contract(off)
@@ -25,11 +26,6 @@ constexpr int EOS_MIN_POINTS = 4, EOS_MAX_POINTS = ALIGNN_WAVE;
 constexpr double EOS_LAMBDA0 = 1e-3, EOS_LAMBDA_MIN = 1e-15, EOS_LAMBDA_MAX = 1e15;
 constexpr double EOS_XTOL = 1e-13, EOS_FTOL = 1e-16;
 constexpr int EOS_MAX_STEPS = 100;
-
-// x M for a row vector x and a row-major M: (x0 M0k + x1 M1k) + x2 M2k
-__device__ __forceinline__ double row_dot(const double* x, const double (&m)[9], int k) {
-    return (x[0] * m[k] + x[1] * m[3 + k]) + x[2] * m[6 + k];
-}
 
 // Row i of the new cell is row i of the parent times F, r' = r F for every atom, the volume |det| of the NEW cell along its first
 // row.  A job whose parent index or row range does not fit writes nothing.

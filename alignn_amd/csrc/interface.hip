@@ -14,6 +14,7 @@
 // depend on what else shares the launch.
 #include "../../include/alignn_hip.h"
 #include "common.h"
+#include "cell3.h"
 #include "wave_fit.h"
 
 #pragma clang fp contract(off)
@@ -247,23 +248,6 @@ __global__ __launch_bounds__(IF_BLOCK) void zsl_pick_kernel(
 
 // ---- the builder ------------------------------------------------------------------------------------------------------------------
 
-// inverse of a row-major 3 x 3 by cofactors, every element its cofactor / det (as in defects.hip)
-__device__ __forceinline__ void inv3_cof(const double (&a)[9], double (&inv)[9]) {
-    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[3] * a[8] - a[5] * a[6], c02 = a[3] * a[7] - a[4] * a[6];
-    const double det = (a[0] * c00 - a[1] * c01) + a[2] * c02;
-    inv[0] = c00 / det;
-    inv[1] = (a[2] * a[7] - a[1] * a[8]) / det;
-    inv[2] = (a[1] * a[5] - a[2] * a[4]) / det;
-    inv[3] = -c01 / det;
-    inv[4] = (a[0] * a[8] - a[2] * a[6]) / det;
-    inv[5] = (a[2] * a[3] - a[0] * a[5]) / det;
-    inv[6] = c02 / det;
-    inv[7] = (a[1] * a[6] - a[0] * a[7]) / det;
-    inv[8] = (a[0] * a[4] - a[1] * a[3]) / det;
-}
-__device__ __forceinline__ double row_dot(const double (&x)[3], const double (&m)[9], int k) {
-    return (x[0] * m[k] + x[1] * m[3 + k]) + x[2] * m[6 + k];
-}
 __device__ __forceinline__ int64_t gcd64(int64_t a, int64_t b) {
     a = a < 0 ? -a : a;
     b = b < 0 ? -b : b;

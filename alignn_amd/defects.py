@@ -9,7 +9,7 @@ atom per inequivalent site) and ``Surface.make_surface`` (one slab per Miller in
 1. the job list (host, integers): supercell sizes and removed atoms, or ``miller_basis`` and layer counts;
 2. ``alignn_defect_supercells`` / ``alignn_slab_build`` (csrc/defects.hip) write every job's cell, Cartesian positions, wrapped
    fractions and ``src``, the parent atom of every row (one gather gives the atom features);
-3. ``relax`` on the jobs, in groups of whole jobs of at most ``max_atoms_per_call`` atoms;
+3. ``relax`` on the jobs, in groups of whole jobs of at most ``max_atoms_per_call`` atoms (alignn_amd/_jobs.py);
 4. the energies reduced to formation / surface energies.
 
 The builders are float64 with fixed-order sums and ``relax`` keeps a structure's bits independent of its batch, so a parent's
@@ -27,14 +27,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._structures import check_inputs, gpu_device, pack
-from .relax import relax
+from ._jobs import (MAX_ATOMS_PER_CALL, build_slabs, check_job_options, features, offsets, positive, relax_jobs, slab_layers,
+                    split)
+from ._structures import check_inputs, gpu_device, host, pack
 
 __all__ = ["vacancy_formation", "surface_energy", "VacancyResult", "SurfaceResult", "miller_basis", "EV_A2_TO_J_M2"]
 
 EV_A2_TO_J_M2 = 16.02176634  # eV/A^2 -> J/m^2 (the elementary charge, CODATA 2018, x 1e20 / 1e19)
-MAX_ATOMS_PER_CALL = 32768
-_PER_STRUCTURE = ("fixed",)  # relax options given per structure: the jobs are not the caller's structures
 
 
 def _ext_gcd(a: int, b: int):
@@ -146,82 +145,6 @@ class SurfaceResult:
     n_relax_calls: int
 
 
-def _host(x) -> np.ndarray:
-    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-
-
-def _common_checks(who: str, max_atoms_per_call, relax_kwargs: dict):
-    if not (isinstance(max_atoms_per_call, numbers.Integral) and max_atoms_per_call >= 1):
-        raise ValueError(f"{who}: max_atoms_per_call must be an int >= 1")
-    for name in _PER_STRUCTURE:
-        if relax_kwargs.get(name) is not None:
-            raise ValueError(f"{who}: relax's {name}= is given per structure; the jobs here are derived structures")
-    for name in ("steps", "fmax"):
-        if name in relax_kwargs and not (isinstance(relax_kwargs[name], numbers.Real) and relax_kwargs[name] >= 0):
-            raise ValueError(f"{who}: {name} must be a number >= 0")
-    if "cell_mask" in relax_kwargs and relax_kwargs["cell_mask"] is not None:
-        if _host(relax_kwargs["cell_mask"]).shape not in ((6,), (3, 3)):
-            raise ValueError(f"{who}: cell_mask is one mask for every job (six Voigt flags or [3, 3])")
-    if np.ndim(relax_kwargs.get("scalar_pressure", 0.0)) != 0:
-        raise ValueError(f"{who}: scalar_pressure is one number for every job")
-
-
-def _relax_jobs_stress_device(who, model, cells, cart, src, counts, feats_all, max_atoms_per_call, relax_structures, relax_kwargs,
-                              forces_fn, dev):
-    """``relax`` over the jobs (cells [J, 3, 3], rows of cart / src split by ``counts``) in groups of whole jobs of at most
-    ``max_atoms_per_call`` atoms -> (energies [J], lattices [J, 3, 3], [positions], converged [J], n_steps [J], calls,
-    stresses [J, 3, 3] or None without ``optimize_lattice``), the arrays on the device (alignn_amd/eos.py and
-    alignn_amd/elastic.py keep them there)."""
-    J = len(counts)
-    off = np.concatenate([[0], np.cumsum(counts)])
-    groups, cur, atoms = [], [], 0
-    for j in range(J):
-        if cur and atoms + counts[j] > max_atoms_per_call:
-            groups.append(cur)
-            cur, atoms = [], 0
-        cur.append(j)
-        atoms += counts[j]
-    groups.append(cur)
-    kw = dict(steps=100, fmax=0.1, optimize_lattice=True)
-    kw.update(relax_kwargs)
-    if not relax_structures:
-        kw["steps"] = 0
-    energies, lattices, positions, conv, nsteps, stresses = [], [], [], [], [], []
-    for g in groups:
-        rows = [slice(int(off[j]), int(off[j + 1])) for j in g]
-        feats = None if feats_all is None else [feats_all[src[r].long()] for r in rows]
-        res = relax(model, [cells[j] for j in g], [cart[r] for r in rows], feats, forces_fn=forces_fn, device=dev, **kw)
-        energies.append(res.energies)
-        lattices.append(res.lattices if res.lattices is not None else cells[g[0]:g[-1] + 1].clone())
-        positions += res.positions
-        conv.append(res.converged)
-        nsteps.append(res.n_steps)
-        stresses.append(res.stresses)
-    stress = None if stresses[0] is None else torch.cat(stresses)
-    return torch.cat(energies), torch.cat(lattices), positions, torch.cat(conv), torch.cat(nsteps), len(groups), stress
-
-
-def _relax_jobs_device(*args):
-    """``_relax_jobs_stress_device`` without the stresses."""
-    return _relax_jobs_stress_device(*args)[:6]
-
-
-def _relax_jobs(*args):
-    """``_relax_jobs_device`` with the energies, flags and step counts as numpy arrays."""
-    e, lattices, positions, conv, nsteps, calls = _relax_jobs_device(*args)
-    return e.cpu().numpy(), lattices, positions, conv.cpu().numpy(), nsteps.cpu().numpy(), calls
-
-
-def _split(x, job_ptr):
-    return [x[job_ptr[s]:job_ptr[s + 1]] for s in range(len(job_ptr) - 1)]
-
-
-def _features(atom_features, forces_fn, dev):
-    if forces_fn is not None or atom_features is None:
-        return None
-    return torch.cat([torch.as_tensor(f).to(dev, torch.float32) for f in atom_features])
-
-
 def _supercell_dims(who, supercell, lattices, enforce_c_size, extend, B) -> List[tuple]:
     if supercell is None:
         if not (isinstance(enforce_c_size, numbers.Real) and np.isfinite(enforce_c_size) and enforce_c_size >= 0):
@@ -230,7 +153,7 @@ def _supercell_dims(who, supercell, lattices, enforce_c_size, extend, B) -> List
             raise ValueError(f"{who}: extend must be an int >= 0")
         out = []
         for lat in lattices:
-            lengths = np.sqrt((_host(lat).astype(np.float64) ** 2).sum(1))
+            lengths = np.sqrt((host(lat).astype(np.float64) ** 2).sum(1))
             if not (np.isfinite(lengths).all() and (lengths > 0).all()):
                 raise ValueError(f"{who}: a lattice vector has no length")
             out.append(tuple(int(enforce_c_size / x) + int(extend) for x in lengths))
@@ -269,7 +192,7 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
     optimize_lattice = bool(relax_kwargs.get("optimize_lattice", True))
     ns = check_inputs(who, model, lattices, positions, atom_features, forces_fn=forces_fn, stress=optimize_lattice)
     B = len(ns)
-    _common_checks(who, max_atoms_per_call, relax_kwargs)
+    check_job_options(who, max_atoms_per_call, relax_kwargs)
     dims = _supercell_dims(who, supercell, lattices, enforce_c_size, extend, B)
     n_bulk = [n * d[0] * d[1] * d[2] for n, d in zip(ns, dims)]
     for s, n in enumerate(n_bulk):
@@ -279,7 +202,7 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
         raise ValueError(f"{who}: site_labels needs one integer [n_i] array per structure, {B} of them")
     labels, mult, removed = [], [], []
     for s in range(B):
-        lab = np.arange(ns[s]) if site_labels is None else _host(site_labels[s])
+        lab = np.arange(ns[s]) if site_labels is None else host(site_labels[s])
         if lab.shape != (ns[s],) or lab.dtype.kind not in "iu":
             raise ValueError(f"{who}: site_labels[{s}] is {lab.dtype} {lab.shape}, need integers [{ns[s]}]")
         u, first, count = np.unique(lab, return_index=True, return_counts=True)
@@ -290,7 +213,7 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
         raise ValueError(f"{who}: chemical_potentials needs one array per structure, {B} of them")
     mus = []
     for s in range(B):
-        mu = np.zeros(len(labels[s])) if chemical_potentials is None else _host(chemical_potentials[s]).astype(np.float64)
+        mu = np.zeros(len(labels[s])) if chemical_potentials is None else host(chemical_potentials[s]).astype(np.float64)
         if mu.shape != (len(labels[s]),) or not np.isfinite(mu).all():
             raise ValueError(f"{who}: chemical_potentials[{s}] needs {len(labels[s])} finite values, one per class")
         mus.append(mu)
@@ -310,7 +233,8 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
         packed = pack(lattices, positions, ns, dev, frac=False)
         dims_d = torch.tensor(dims, dtype=torch.int32, device=dev)
         jobs_d = torch.tensor(jobs, dtype=torch.int32, device=dev)
-        off_d = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64, device=dev)
+        off = offsets(counts)
+        off_d = torch.tensor(off, dtype=torch.int64, device=dev)
         cells = torch.empty(J, 3, 3, dtype=torch.float64, device=dev)
         cart = torch.empty(rows, 3, dtype=torch.float64, device=dev)
         frac = torch.empty(rows, 3, dtype=torch.float64, device=dev)
@@ -319,18 +243,17 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
             packed.pos.data_ptr(), packed.atom_ptr.data_ptr(), packed.lat.data_ptr(), dims_d.data_ptr(), B, jobs_d.data_ptr(),
             off_d.data_ptr(), J, cells.data_ptr(), cart.data_ptr(), frac.data_ptr(), src.data_ptr(), _lib.stream()),
             "defect_supercells")
-        e, lat_out, pos_out, conv, nsteps, calls = _relax_jobs(
-            who, model, cells, cart, src, counts, _features(atom_features, forces_fn, dev), max_atoms_per_call, relax_structures,
-            relax_kwargs, forces_fn, dev)
-        off = np.concatenate([[0], np.cumsum(counts)])
+        r = relax_jobs(model, cells, cart, src, counts, features(atom_features, forces_fn, dev), max_atoms_per_call,
+                       relax_structures, relax_kwargs, forces_fn, dev)
+        e, conv, nsteps = r.energies.cpu().numpy(), r.converged.cpu().numpy(), r.n_steps.cpu().numpy()
         src_jobs = [src[off[j]:off[j + 1]] for j in range(J)]
     e_bulk = np.array([e[job_ptr[s]] for s in range(B)])
     e_def = [e[job_ptr[s] + 1:job_ptr[s + 1]] for s in range(B)]
     form = [e_def[s] - (n_bulk[s] - 1 + 1) * e_bulk[s] / n_bulk[s] + mus[s] for s in range(B)]
     return VacancyResult(supercell=dims, n_bulk=n_bulk, labels=labels, multiplicity=mult, removed_atom=removed, e_bulk=e_bulk,
-                         e_defect=e_def, formation_energy=form, lattices=_split(lat_out, job_ptr),
-                         positions=_split(pos_out, job_ptr), src=_split(src_jobs, job_ptr), converged=_split(conv, job_ptr),
-                         n_steps=_split(nsteps, job_ptr), n_relax_calls=calls)
+                         e_defect=e_def, formation_energy=form, lattices=split(r.lattices, job_ptr),
+                         positions=split(r.positions, job_ptr), src=split(src_jobs, job_ptr), converged=split(conv, job_ptr),
+                         n_steps=split(nsteps, job_ptr), n_relax_calls=r.n_calls)
 
 
 def _miller_lists(who, miller_indices, B) -> List[np.ndarray]:
@@ -372,52 +295,31 @@ def surface_energy(model, lattices: Sequence, positions: Sequence, atom_features
     optimize_lattice = bool(relax_kwargs.get("optimize_lattice", True))
     ns = check_inputs(who, model, lattices, positions, atom_features, forces_fn=forces_fn, stress=optimize_lattice)
     B = len(ns)
-    _common_checks(who, max_atoms_per_call, relax_kwargs)
-    if not (isinstance(thickness, numbers.Real) and np.isfinite(thickness) and thickness > 0):
-        raise ValueError(f"{who}: thickness must be a finite number > 0, got {thickness!r}")
-    if not (isinstance(vacuum, numbers.Real) and np.isfinite(vacuum) and vacuum >= 0):
-        raise ValueError(f"{who}: vacuum must be a finite number >= 0, got {vacuum!r}")
+    check_job_options(who, max_atoms_per_call, relax_kwargs)
+    positive(who, "thickness", thickness)
+    positive(who, "vacuum", vacuum, zero_ok=True)
     hkls = _miller_lists(who, miller_indices, B)
     bases, layers = [], []
     for s in range(B):
-        lat = _host(lattices[s]).astype(np.float64)
+        lat = host(lattices[s]).astype(np.float64)
         bs, ls = [], []
         for hkl in hkls[s]:
-            bm = miller_basis(lat, hkl)
-            C = bm.astype(np.float64) @ lat
-            nu = np.cross(C[0], C[1])
-            h3 = abs(np.dot(C[2], nu)) / np.sqrt(np.dot(nu, nu))
-            if not (np.isfinite(h3) and h3 > 0):
-                raise ValueError(f"{who}: lattices[{s}] has no volume")
-            if thickness / h3 * ns[s] > np.iinfo(np.int32).max:
-                raise ValueError(f"{who}: thickness {thickness} gives too many layers of {hkl} for structure {s}")
-            bs.append(bm)
-            ls.append(max(1, int(thickness / h3)))
+            bs.append(miller_basis(lat, hkl))
+            ls.append(slab_layers(who, f"lattices[{s}]", f"structure {s}", lat, bs[-1], hkl, thickness, ns[s]))
         bases.append(np.stack(bs))
         layers.append(np.array(ls, dtype=np.int64))
     dev = gpu_device(who, model, forces_fn, device)
-    lib = _lib.load()
 
     slab_jobs, slab_counts = [], []
     for s in range(B):
         for bm, nl in zip(bases[s], layers[s]):
             slab_jobs.append([s] + [int(v) for v in bm.reshape(-1)] + [int(nl)])
             slab_counts.append(ns[s] * int(nl))
-    S, rows = len(slab_jobs), int(sum(slab_counts))
     with _lib.device_guard(torch.empty(0, device=dev)):
         packed = pack(lattices, positions, ns, dev, frac=False)
-        jobs_d = torch.tensor(slab_jobs, dtype=torch.int32, device=dev)
-        vac_d = torch.full((S,), float(vacuum), dtype=torch.float64, device=dev)
-        off_d = torch.tensor(np.concatenate([[0], np.cumsum(slab_counts)]), dtype=torch.int64, device=dev)
-        cells = torch.empty(S, 3, 3, dtype=torch.float64, device=dev)
-        cart = torch.empty(rows, 3, dtype=torch.float64, device=dev)
-        frac = torch.empty(rows, 3, dtype=torch.float64, device=dev)
-        src = torch.empty(rows, dtype=torch.int32, device=dev)
-        _lib.check(lib.alignn_slab_build(
-            packed.pos.data_ptr(), packed.atom_ptr.data_ptr(), packed.lat.data_ptr(), B, jobs_d.data_ptr(), vac_d.data_ptr(),
-            off_d.data_ptr(), S, cells.data_ptr(), cart.data_ptr(), frac.data_ptr(), src.data_ptr(), _lib.stream()), "slab_build")
+        cells, cart, src, _ = build_slabs(packed, slab_jobs, slab_counts, vacuum, dev)
         # the job list of relax: per parent the parent itself, then its slabs
-        slab_off = np.concatenate([[0], np.cumsum(slab_counts)])
+        slab_off = offsets(slab_counts)
         order_cells, order_cart, order_src, counts, job_ptr, k = [], [], [], [], [0], 0
         for s in range(B):
             a, b = packed.ptr[s], packed.ptr[s + 1]
@@ -433,11 +335,11 @@ def surface_energy(model, lattices: Sequence, positions: Sequence, atom_features
                 k += 1
             job_ptr.append(len(counts))
         all_cells, all_cart, all_src = torch.cat(order_cells), torch.cat(order_cart), torch.cat(order_src)
-        e, lat_out, pos_out, conv, nsteps, calls = _relax_jobs(
-            who, model, all_cells, all_cart, all_src, counts, _features(atom_features, forces_fn, dev), max_atoms_per_call,
-            relax_structures, relax_kwargs, forces_fn, dev)
+        r = relax_jobs(model, all_cells, all_cart, all_src, counts, features(atom_features, forces_fn, dev), max_atoms_per_call,
+                       relax_structures, relax_kwargs, forces_fn, dev)
+        e, conv, nsteps = r.energies.cpu().numpy(), r.converged.cpu().numpy(), r.n_steps.cpu().numpy()
         cells_h = cells.cpu().numpy()
-        off = np.concatenate([[0], np.cumsum(counts)])
+        off = offsets(counts)
         src_jobs = [all_src[off[j]:off[j + 1]] for j in range(len(counts))]
     epa = np.array([e[job_ptr[s]] / ns[s] for s in range(B)])
     e_slab, n_slab, area, surf, k = [], [], [], [], 0
@@ -450,6 +352,6 @@ def surface_energy(model, lattices: Sequence, positions: Sequence, atom_features
         surf.append((e_slab[s] - epa[s] * n_slab[s]) / (2 * area[s]))
         k += M
     return SurfaceResult(miller_indices=hkls, basis=bases, layers=layers, n_slab=n_slab, area=area, epa=epa, e_slab=e_slab,
-                         surf_en=surf, surf_en_J_m2=[x * EV_A2_TO_J_M2 for x in surf], lattices=_split(lat_out, job_ptr),
-                         positions=_split(pos_out, job_ptr), src=_split(src_jobs, job_ptr), converged=_split(conv, job_ptr),
-                         n_steps=_split(nsteps, job_ptr), n_relax_calls=calls)
+                         surf_en=surf, surf_en_J_m2=[x * EV_A2_TO_J_M2 for x in surf], lattices=split(r.lattices, job_ptr),
+                         positions=split(r.positions, job_ptr), src=split(src_jobs, job_ptr), converged=split(conv, job_ptr),
+                         n_steps=split(nsteps, job_ptr), n_relax_calls=r.n_calls)

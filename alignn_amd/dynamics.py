@@ -29,14 +29,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._structures import ForceEvaluator, check_inputs, gpu_device, pack, shape_of
+from ._structures import EV_A3_TO_GPA, ForceEvaluator, check_inputs, gpu_device, pack, shape_of
 
 __all__ = ["run_md", "MDResult", "FS", "KB", "BAR"]
 
 # ASE's units (CODATA 2014, its default): the femtosecond in ASE time units (A sqrt(amu / eV)) and Boltzmann's constant (eV/K)
 FS = 0.09822694788464063
 KB = 8.617330337217213e-05
-BAR = 1e-4 / 160.21766208  # eV/A^3 (160.21766208 eV/A^3 per GPa, the constant of _structures.ForceEvaluator)
+BAR = 1e-4 / EV_A3_TO_GPA  # eV/A^3 (160.21766208 eV/A^3 per GPa, the constant of _structures.ForceEvaluator)
 
 ENSEMBLES = {"nve": 0, "nvt_langevin": 1, "nvt_berendsen": 2, "nvt_andersen": 3, "npt_berendsen": 4, "nvt_nose_hoover": 5,
              "npt_nose_hoover": 6}

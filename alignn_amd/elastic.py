@@ -7,7 +7,7 @@ strain points together:
 1. ``alignn_strain_build`` (csrc/eos.hip) writes the cells and Cartesian positions of all B P strained structures in one
    launch; job (s, p) is parent s under F = I + eps(p), a parent's jobs consecutive;
 2. ``relax(..., optimize_lattice=True)`` evaluates them, in groups of whole jobs of at most ``max_atoms_per_call`` atoms (the
-   grouping of alignn_amd/defects.py): ``steps=0`` for clamped ions, or FIRE at a fixed cell (``cell_mask`` all zero) with
+   grouping of alignn_amd/_jobs.py): ``steps=0`` for clamped ions, or FIRE at a fixed cell (``cell_mask`` all zero) with
    ``relax_ions``; either way it returns every structure's symmetrised stress;
 3. ``alignn_elastic_fit`` (csrc/elastic.hip) fits sigma_i = sigma0_i + sum_j C_ij eps_j for every parent in one launch, one
    wavefront per parent, and derives the compliance and the Voigt-Reuss-Hill moduli.  Strains, stresses and fit results stay
@@ -21,7 +21,6 @@ call.  tests/elastic_ref.py restates the strain set, the deformation and the fit
 
 from __future__ import annotations
 
-import numbers
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -29,11 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._structures import check_inputs, gpu_device, pack
-from .defects import MAX_ATOMS_PER_CALL, _features, _relax_jobs_stress_device
-from .eos import _EVALUATION as _EOS_EVALUATION
-from .eos import EV_A3_TO_GPA
-from .relax import relax
+from ._jobs import (EVALUATION, MAX_ATOMS_PER_CALL, check_max_atoms, check_steps_fmax, evaluation_options, features, prepare_parents,
+                    relax_jobs, strain_jobs)
+from ._structures import EV_A3_TO_GPA, check_inputs, gpu_device
 
 __all__ = ["elastic_tensor", "elastic_fit", "ElasticResult", "MODULI", "DEFAULT_STRAINS"]
 
@@ -41,7 +38,7 @@ MIN_POINTS, MAX_POINTS = 7, 64  # seven unknowns per stress component; one lane 
 MAX_STRAIN = 0.2  # |strain| below this: the fit is linear in the strain
 MODULI = ("k_voigt", "k_reuss", "k_hill", "g_voigt", "g_reuss", "g_hill", "youngs_modulus", "poisson_ratio",
           "universal_anisotropy")  # the columns of the kernel's ``moduli``
-_EVALUATION = _EOS_EVALUATION + ("stress_weight",)
+_EVALUATION = EVALUATION + ("stress_weight",)
 _ION_RELAXATION = ("steps", "fmax")
 DEFAULT_STRAINS = (-0.01, -0.005, 0.005, 0.01)
 
@@ -212,61 +209,30 @@ def elastic_tensor(model, lattices: Sequence, positions: Sequence, atom_features
     B = len(ns)
     e = _strain_points(who, strains, strain_set)
     P = len(e)
-    if not (isinstance(max_atoms_per_call, numbers.Integral) and max_atoms_per_call >= 1):
-        raise ValueError(f"{who}: max_atoms_per_call must be an int >= 1")
-    if not on_relaxed_struct:
-        taken = _EVALUATION + (_ION_RELAXATION if relax_ions else ())
-        extra = sorted(k for k in relax_kwargs if k not in taken)
-        if extra:
-            raise ValueError(f"{who}: {', '.join(extra)} are options of the relaxation; without on_relaxed_struct only the "
-                             f"evaluation options {', '.join(_EVALUATION)} are taken" +
-                             (f" (and {', '.join(_ION_RELAXATION)} of the ion relaxation)" if relax_ions else ""))
-    for name in _ION_RELAXATION:
-        if name in relax_kwargs and not (isinstance(relax_kwargs[name], numbers.Real) and relax_kwargs[name] >= 0):
-            raise ValueError(f"{who}: {name} must be a number >= 0")
-    job_kw = {k: v for k, v in relax_kwargs.items() if k in _EVALUATION}
+    check_max_atoms(who, max_atoms_per_call)
+    job_kw = evaluation_options(who, relax_kwargs, _EVALUATION, on_relaxed_struct, _ION_RELAXATION if relax_ions else ())
+    check_steps_fmax(who, relax_kwargs)
     job_kw["optimize_lattice"] = True
     if relax_ions:
         job_kw.update({k: v for k, v in relax_kwargs.items() if k in _ION_RELAXATION})
         job_kw["cell_mask"] = np.zeros(6)
     dev = gpu_device(who, model, forces_fn, device)
-    lib = _lib.load()
 
     with _lib.device_guard(torch.empty(0, device=dev)):
-        if on_relaxed_struct:
-            kw = dict(steps=100, fmax=0.1, optimize_lattice=True)
-            kw.update(relax_kwargs)
-            res = relax(model, lattices, positions, atom_features, forces_fn=forces_fn, device=dev, **kw)
-            lattices = res.lattices if res.lattices is not None else lattices
-            positions = res.positions
-        packed = pack(lattices, positions, ns, dev, frac=False)
-        J = B * P
-        counts = [n for n in ns for _ in range(P)]
-        off = np.concatenate([[0], np.cumsum(counts)])
-        jobs_d = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(P)
+        packed, lat_out, pos_out = prepare_parents(model, lattices, positions, atom_features, ns, on_relaxed_struct, relax_kwargs,
+                                                   forces_fn, dev)
         e_d = torch.tensor(e, dtype=torch.float64, device=dev)
-        F = torch.tensor(_defgrad(e), dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous()
-        off_d = torch.tensor(off, dtype=torch.int64, device=dev)
-        cells = torch.empty(J, 3, 3, dtype=torch.float64, device=dev)
-        cart = torch.empty(int(off[-1]), 3, dtype=torch.float64, device=dev)
-        volumes = torch.empty(J, dtype=torch.float64, device=dev)
-        _lib.check(lib.alignn_strain_build(
-            packed.pos.data_ptr(), packed.atom_ptr.data_ptr(), packed.lat.data_ptr(), B, jobs_d.data_ptr(), F.data_ptr(),
-            off_d.data_ptr(), J, cells.data_ptr(), cart.data_ptr(), volumes.data_ptr(), _lib.stream()), "strain_build")
-        # row j of a job is atom j of its parent
-        src = torch.cat([torch.arange(packed.ptr[s], packed.ptr[s + 1], dtype=torch.int32, device=dev).repeat(P)
-                         for s in range(B)])
-        _, _, _, conv, nsteps, n_calls, stress = _relax_jobs_stress_device(
-            who, model, cells, cart, src, counts, _features(atom_features, forces_fn, dev), max_atoms_per_call, bool(relax_ions),
-            job_kw, forces_fn, dev)
-        stress = stress.reshape(B, P, 3, 3).contiguous()
+        cells, cart, _, src, counts = strain_jobs(packed, ns, torch.tensor(_defgrad(e), dtype=torch.float64, device=dev), dev)
+        r = relax_jobs(model, cells, cart, src, counts, features(atom_features, forces_fn, dev), max_atoms_per_call,
+                       bool(relax_ions), job_kw, forces_fn, dev)
+        stress = r.stresses.reshape(B, P, 3, 3).contiguous()
         c_raw, c, compliance, sigma0, moduli, rms, asymmetry, status = elastic_fit(e_d.expand(B, P, 6), stress)
-        lat_out, pos_out = packed.lat.clone(), [p.clone() for p in packed.rows(packed.pos)]
         c_h, moduli_h = c.cpu().numpy(), moduli.cpu().numpy()
     named = {name: moduli_h[:, k].copy() for k, name in enumerate(MODULI)}
     named.update({name + "_GPa": named[name] * EV_A3_TO_GPA for name in MODULI[:7]})
     return ElasticResult(strains=e, stresses=_voigt(stress).cpu().numpy(), c=c_h, c_raw=c_raw.cpu().numpy(),
                          compliance=compliance.cpu().numpy(), c_GPa=c_h * EV_A3_TO_GPA, sigma0=sigma0.cpu().numpy(),
                          rms=rms.cpu().numpy(), asymmetry=asymmetry.cpu().numpy(), status=status.cpu().numpy().astype(np.int64),
-                         converged=conv.cpu().numpy().reshape(B, P), n_steps=nsteps.cpu().numpy().astype(np.int64).reshape(B, P),
-                         lattices=lat_out, positions=pos_out, n_eval_calls=n_calls, **named)
+                         converged=r.converged.cpu().numpy().reshape(B, P),
+                         n_steps=r.n_steps.cpu().numpy().astype(np.int64).reshape(B, P), lattices=lat_out, positions=pos_out,
+                         n_eval_calls=r.n_calls, **named)

@@ -8,7 +8,7 @@ together:
 1. ``alignn_strain_build`` (csrc/eos.hip) writes the cells, Cartesian positions and volumes of all B K strained structures in
    one launch; job (s, k) is parent s at ``dx[k]``, a parent's jobs consecutive;
 2. ``relax(..., steps=0)`` evaluates them, in groups of whole jobs of at most ``max_atoms_per_call`` atoms (the grouping of
-   alignn_amd/defects.py); a job's atom features are its parent's;
+   alignn_amd/_jobs.py); a job's atom features are its parent's;
 3. ``alignn_eos_fit`` fits every parent's curve in one launch, one wavefront per parent: ASE's parabola start, then
    Levenberg-Marquardt with the analytic Jacobian.  Volumes, energies and fit results stay on the device until the result is
    assembled (one copy of each array).
@@ -24,7 +24,6 @@ builder itself takes a general F (shear included).
 
 from __future__ import annotations
 
-import numbers
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -32,16 +31,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._structures import check_inputs, gpu_device, pack
-from .defects import MAX_ATOMS_PER_CALL, _features, _relax_jobs_device
-from .relax import relax
+from ._jobs import (EVALUATION, MAX_ATOMS_PER_CALL, check_max_atoms, evaluation_options, features, prepare_parents,
+                    relax_jobs, strain_jobs)
+from ._structures import EV_A3_TO_GPA, check_inputs, gpu_device
 
 __all__ = ["ev_curve", "eos_fit", "EVResult", "EOS_FORMS", "EV_A3_TO_GPA"]
 
-EV_A3_TO_GPA = 160.21766208  # eV/A^3 -> GPa, the constant of the stresses in _structures.py (ASE 3.22's 1e24 / kJ)
 EOS_FORMS = {"murnaghan": 0, "birchmurnaghan": 1}  # ase/eos.py's names -> the kernel's ``form``
 MIN_POINTS, MAX_POINTS = 4, 64  # four parameters; one lane of a wavefront per point
-_EVALUATION = ("cutoff", "max_neighbors", "neighbor_strategy", "intensive", "force_multiplier")
 
 
 @dataclass
@@ -149,50 +146,23 @@ def ev_curve(model, lattices: Sequence, positions: Sequence, atom_features: Opti
     K = len(d)
     if eos not in EOS_FORMS:
         raise ValueError(f"{who}: eos must be one of {sorted(EOS_FORMS)}, got {eos!r}")
-    if not (isinstance(max_atoms_per_call, numbers.Integral) and max_atoms_per_call >= 1):
-        raise ValueError(f"{who}: max_atoms_per_call must be an int >= 1")
-    if not on_relaxed_struct:
-        extra = sorted(k for k in relax_kwargs if k not in _EVALUATION)
-        if extra:
-            raise ValueError(f"{who}: {', '.join(extra)} are options of the relaxation; without on_relaxed_struct only the "
-                             f"evaluation options {', '.join(_EVALUATION)} are taken")
-    evaluation = {k: v for k, v in relax_kwargs.items() if k in _EVALUATION}
+    check_max_atoms(who, max_atoms_per_call)
+    evaluation = evaluation_options(who, relax_kwargs, EVALUATION, on_relaxed_struct)
     dev = gpu_device(who, model, forces_fn, device)
-    lib = _lib.load()
 
     with _lib.device_guard(torch.empty(0, device=dev)):
-        if on_relaxed_struct:
-            kw = dict(steps=100, fmax=0.1, optimize_lattice=True)
-            kw.update(relax_kwargs)
-            res = relax(model, lattices, positions, atom_features, forces_fn=forces_fn, device=dev, **kw)
-            lattices = res.lattices if res.lattices is not None else lattices
-            positions = res.positions
-        packed = pack(lattices, positions, ns, dev, frac=False)
-        J = B * K
-        counts = [n for n in ns for _ in range(K)]
-        off = np.concatenate([[0], np.cumsum(counts)])
-        jobs_d = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(K)
+        packed, lat_out, pos_out = prepare_parents(model, lattices, positions, atom_features, ns, on_relaxed_struct, relax_kwargs,
+                                                   forces_fn, dev)
         scale = torch.tensor(1.0 + d, dtype=torch.float64, device=dev)  # (1 + dx in float64, as the restatement takes it)
-        F = (scale[:, None, None] * torch.eye(3, dtype=torch.float64, device=dev)).repeat(B, 1, 1).contiguous()
-        off_d = torch.tensor(off, dtype=torch.int64, device=dev)
-        cells = torch.empty(J, 3, 3, dtype=torch.float64, device=dev)
-        cart = torch.empty(int(off[-1]), 3, dtype=torch.float64, device=dev)
-        volumes = torch.empty(J, dtype=torch.float64, device=dev)
-        _lib.check(lib.alignn_strain_build(
-            packed.pos.data_ptr(), packed.atom_ptr.data_ptr(), packed.lat.data_ptr(), B, jobs_d.data_ptr(), F.data_ptr(),
-            off_d.data_ptr(), J, cells.data_ptr(), cart.data_ptr(), volumes.data_ptr(), _lib.stream()), "strain_build")
-        # row j of a job is atom j of its parent
-        src = torch.cat([torch.arange(packed.ptr[s], packed.ptr[s + 1], dtype=torch.int32, device=dev).repeat(K)
-                         for s in range(B)])
-        e, _, _, _, _, n_calls = _relax_jobs_device(
-            who, model, cells, cart, src, counts, _features(atom_features, forces_fn, dev), max_atoms_per_call, False,
-            dict(evaluation, optimize_lattice=optimize_lattice), forces_fn, dev)
-        volumes, energies = volumes.reshape(B, K), e.reshape(B, K).contiguous()
+        cells, cart, volumes, src, counts = strain_jobs(
+            packed, ns, scale[:, None, None] * torch.eye(3, dtype=torch.float64, device=dev), dev)
+        r = relax_jobs(model, cells, cart, src, counts, features(atom_features, forces_fn, dev), max_atoms_per_call, False,
+                       dict(evaluation, optimize_lattice=optimize_lattice), forces_fn, dev)
+        volumes, energies = volumes.reshape(B, K), r.energies.reshape(B, K).contiguous()
         params, rms, n_iter, status = eos_fit(volumes, energies, eos)
         params_h = params.cpu().numpy()
-        lat_out, pos_out = packed.lat.clone(), [p.clone() for p in packed.rows(packed.pos)]
     return EVResult(dx=d, volumes=volumes.cpu().numpy(), energies=energies.cpu().numpy(), e0=params_h[:, 0].copy(),
                     b0=params_h[:, 1].copy(), bp=params_h[:, 2].copy(), v0=params_h[:, 3].copy(),
                     bulk_modulus_GPa=params_h[:, 1] * EV_A3_TO_GPA, rms=rms.cpu().numpy(),
                     n_iter=n_iter.cpu().numpy().astype(np.int64), status=status.cpu().numpy().astype(np.int64), lattices=lat_out,
-                    positions=pos_out, n_eval_calls=n_calls)
+                    positions=pos_out, n_eval_calls=r.n_calls)

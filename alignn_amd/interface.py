@@ -9,8 +9,9 @@ pairs of B_f film and B_s substrate crystals together:
 1. ``alignn_slab_build`` (csrc/defects.hip) cuts every (crystal, Miller index, thickness) once, without vacuum;
 2. ``alignn_zsl_match`` (csrc/interface.hip) finds every pair's coincidence lattice: ``match_lattices`` is this step alone;
 3. ``alignn_interface_build`` writes, per matched pair and in one common cell, the substrate, the film and the interface;
-4. ``relax`` on the 3 jobs per pair, in groups of whole jobs of at most ``max_atoms_per_call`` atoms: the two slabs with an
-   all-zero ``cell_mask`` (the reference's ``optimize_lattice=False``), the interface with ``interface_cell_mask``;
+4. ``relax`` on the 3 jobs per pair, in groups of whole jobs of at most ``max_atoms_per_call`` atoms (alignn_amd/_jobs.py): the
+   two slabs with an all-zero ``cell_mask`` (the reference's ``optimize_lattice=False``), the interface with
+   ``interface_cell_mask``;
 5. ``w_ad = -(E_interface - E_substrate - E_film) / area``.
 
 jarvis-tools, pymatgen and ASE are not dependencies of this project: the match is the one specified in INTEGRATION.md and
@@ -29,9 +30,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._structures import check_inputs, gpu_device, pack
-from .defects import EV_A2_TO_J_M2, MAX_ATOMS_PER_CALL, _common_checks, _features, _host, miller_basis
-from .relax import _full_mask, relax
+from ._jobs import MAX_ATOMS_PER_CALL, build_slabs, check_job_options, features, offsets, positive, relax_jobs, slab_layers
+from ._structures import check_inputs, gpu_device, host, pack
+from .defects import EV_A2_TO_J_M2, miller_basis
+from .relax import _full_mask
 
 __all__ = ["interface_energy", "match_lattices", "InterfaceResult", "MatchResult", "MAX_MULTIPLE"]
 
@@ -112,17 +114,11 @@ def _largest_multiple(area: float, max_area: float) -> int:
     return n
 
 
-def _positive(who, name, v, zero_ok=False):
-    if not (isinstance(v, numbers.Real) and np.isfinite(v) and (v >= 0 if zero_ok else v > 0)):
-        raise ValueError(f"{who}: {name} must be a finite number {'>= 0' if zero_ok else '> 0'}, got {v!r}")
-    return float(v)
-
-
 def _match_checks(who, max_area, max_area_ratio_tol, ltol, atol):
-    _positive(who, "max_area", max_area)
-    _positive(who, "max_area_ratio_tol", max_area_ratio_tol, zero_ok=True)
-    _positive(who, "ltol", ltol, zero_ok=True)
-    if _positive(who, "atol", atol, zero_ok=True) > 90.0:
+    positive(who, "max_area", max_area)
+    positive(who, "max_area_ratio_tol", max_area_ratio_tol, zero_ok=True)
+    positive(who, "ltol", ltol, zero_ok=True)
+    if positive(who, "atol", atol, zero_ok=True) > 90.0:
         raise ValueError(f"{who}: atol is an angle in degrees, at most 90, got {atol!r}")
 
 
@@ -187,7 +183,7 @@ def _match_device(who, film, subs, max_area, max_area_ratio_tol, ltol, atol, dev
 
 
 def _cells_2d(who, name, cells) -> np.ndarray:
-    c = _host(cells)
+    c = host(cells)
     if c.ndim != 3 or c.shape[1:] != (2, 2) or c.shape[0] < 1 or c.dtype.kind not in "iuf":
         raise ValueError(f"{who}: {name} must be numbers [P, 2, 2] with P >= 1, got {c.dtype} {c.shape}")
     return np.ascontiguousarray(c, dtype=np.float64)
@@ -228,40 +224,6 @@ def _side_inputs(who, name, side):
     return side[0], side[1], side[2] if len(side) == 3 else None
 
 
-def _relax_jobs_masked(model, cells, cart, src, counts, masks, feats_all, max_atoms_per_call, relax_structures, relax_kwargs,
-                       forces_fn, dev):
-    """``defects._relax_jobs_stress_device`` with one cell mask per job (``masks`` None: no mask; without ``optimize_lattice``)
-    -> (energies [J], lattices [J, 3, 3], [positions], converged [J], n_steps [J], calls), the arrays on the host."""
-    J = len(counts)
-    off = np.concatenate([[0], np.cumsum(counts)])
-    groups, cur, atoms = [], [], 0
-    for j in range(J):
-        if cur and atoms + counts[j] > max_atoms_per_call:
-            groups.append(cur)
-            cur, atoms = [], 0
-        cur.append(j)
-        atoms += counts[j]
-    groups.append(cur)
-    kw = dict(steps=100, fmax=0.1, optimize_lattice=True)
-    kw.update(relax_kwargs)
-    if not relax_structures:
-        kw["steps"] = 0
-    energies, lattices, positions, conv, nsteps = [], [], [], [], []
-    for g in groups:
-        rows = [slice(int(off[j]), int(off[j + 1])) for j in g]
-        feats = None if feats_all is None else [feats_all[src[r].long()] for r in rows]
-        if masks is not None:
-            kw["cell_mask"] = [masks[j] for j in g]
-        res = relax(model, [cells[j] for j in g], [cart[r] for r in rows], feats, forces_fn=forces_fn, device=dev, **kw)
-        energies.append(res.energies)
-        lattices.append(res.lattices if res.lattices is not None else cells[g[0]:g[-1] + 1].clone())
-        positions += res.positions
-        conv.append(res.converged)
-        nsteps.append(res.n_steps)
-    return (torch.cat(energies).cpu().numpy(), torch.cat(lattices), positions, torch.cat(conv).cpu().numpy(),
-            torch.cat(nsteps).cpu().numpy(), len(groups))
-
-
 def interface_energy(model, film, substrate, pairs: Sequence, *, film_thickness: float = 25.0, subs_thickness: float = 25.0,
                      separation: float = 3.0, vacuum: float = 8.0, max_area: float = 500.0, max_area_ratio_tol: float = 1.0,
                      ltol: float = 0.05, atol: float = 1.0, interface_cell_mask=(1, 1, 0, 0, 0, 1), relax_structures: bool = True,
@@ -297,10 +259,10 @@ def interface_energy(model, film, substrate, pairs: Sequence, *, film_thickness:
     Bf, ns = len(ns_f), ns_f + ns_s
     if relax_kwargs.get("cell_mask") is not None:
         raise ValueError(f"{who}: the cell masks are set per job; use interface_cell_mask")
-    _common_checks(who, max_atoms_per_call, relax_kwargs)
-    thickness = (_positive(who, "film_thickness", film_thickness), _positive(who, "subs_thickness", subs_thickness))
-    _positive(who, "separation", separation)
-    _positive(who, "vacuum", vacuum, zero_ok=True)
+    check_job_options(who, max_atoms_per_call, relax_kwargs)
+    thickness = (positive(who, "film_thickness", film_thickness), positive(who, "subs_thickness", subs_thickness))
+    positive(who, "separation", separation)
+    positive(who, "vacuum", vacuum, zero_ok=True)
     _match_checks(who, max_area, max_area_ratio_tol, ltol, atol)
     try:
         mask_if = _full_mask(interface_cell_mask, "interface_cell_mask")
@@ -308,7 +270,7 @@ def interface_energy(model, film, substrate, pairs: Sequence, *, film_thickness:
         raise ValueError(f"{who}: {e}") from None
     if not isinstance(pairs, (list, tuple)) or len(pairs) < 1:
         raise ValueError(f"{who}: pairs must be a list of (film index, film hkl, substrate index, substrate hkl)")
-    lattices = [_host(x).astype(np.float64) for x in list(lat_f) + list(lat_s)]
+    lattices = [host(x).astype(np.float64) for x in list(lat_f) + list(lat_s)]
     slab_of, slab_jobs, slab_counts, pair_slabs = {}, [], [], []
     for p, pr in enumerate(pairs):
         if not isinstance(pr, (list, tuple)) or len(pr) != 4:
@@ -322,15 +284,8 @@ def interface_energy(model, film, substrate, pairs: Sequence, *, film_thickness:
             bm = miller_basis(lattices[s], hkl)  # (checks hkl)
             key = (s, tuple(int(v) for v in bm.reshape(-1)))
             if key not in slab_of:
-                C = bm.astype(np.float64) @ lattices[s]
-                nu = np.cross(C[0], C[1])
-                with np.errstate(all="ignore"):
-                    h3 = abs(np.dot(C[2], nu)) / np.sqrt(np.dot(nu, nu))
-                if not (np.isfinite(h3) and h3 > 0):
-                    raise ValueError(f"{who}: the {('film', 'substrate')[side]} lattice {idx} has no volume")
-                if thickness[side] / h3 * ns[s] > np.iinfo(np.int32).max:
-                    raise ValueError(f"{who}: thickness {thickness[side]} gives too many layers of {hkl} for pairs[{p}]")
-                layers = max(1, int(thickness[side] / h3))
+                layers = slab_layers(who, f"the {('film', 'substrate')[side]} lattice {idx}", f"pairs[{p}]", lattices[s], bm, hkl,
+                                     thickness[side], ns[s])
                 slab_of[key] = len(slab_jobs)
                 slab_jobs.append([s] + list(key[1]) + [layers])
                 slab_counts.append(ns[s] * layers)
@@ -345,18 +300,7 @@ def interface_energy(model, film, substrate, pairs: Sequence, *, film_thickness:
 
     with _lib.device_guard(torch.empty(0, device=dev)):
         packed = pack(lattices, list(pos_f) + list(pos_s), ns, dev, frac=False)
-        slab_off = np.concatenate([[0], np.cumsum(slab_counts)]).astype(np.int64)
-        jobs_d = torch.tensor(slab_jobs, dtype=torch.int32, device=dev)
-        zero_d = torch.zeros(S, dtype=torch.float64, device=dev)
-        slab_off_d = torch.tensor(slab_off, device=dev)
-        s_cells = torch.empty(S, 3, 3, dtype=torch.float64, device=dev)
-        s_cart = torch.empty(int(slab_off[-1]), 3, dtype=torch.float64, device=dev)
-        s_frac = torch.empty_like(s_cart)
-        s_src = torch.empty(int(slab_off[-1]), dtype=torch.int32, device=dev)
-        _lib.check(lib.alignn_slab_build(
-            packed.pos.data_ptr(), packed.atom_ptr.data_ptr(), packed.lat.data_ptr(), len(ns), jobs_d.data_ptr(), zero_d.data_ptr(),
-            slab_off_d.data_ptr(), S, s_cells.data_ptr(), s_cart.data_ptr(), s_frac.data_ptr(), s_src.data_ptr(), _lib.stream()),
-            "slab_build")
+        s_cells, s_cart, s_src, slab_off_d = build_slabs(packed, slab_jobs, slab_counts, 0.0, dev)  # (without vacuum)
         planes = [_plane_cell(c) for c in s_cells.cpu().numpy()]
         m = _match_device(who, np.stack([planes[f] for f, _ in pair_slabs]), np.stack([planes[s] for _, s in pair_slabs]),
                           max_area, max_area_ratio_tol, ltol, atol, dev)
@@ -369,7 +313,7 @@ def interface_energy(model, film, substrate, pairs: Sequence, *, film_thickness:
                 jobs.append([f, s] + [int(v) for v in m.film_matrix[p].reshape(-1)] + [int(v) for v in m.subs_matrix[p].reshape(-1)])
                 n_s, n_f = int(m.subs_multiple[p]) * slab_counts[s], int(m.film_multiple[p]) * slab_counts[f]
                 counts += [n_s, n_f, n_s + n_f]
-            off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            off = offsets(counts)
             rows = int(off[-1])
             if rows > np.iinfo(np.int32).max:
                 raise ValueError(f"{who}: the interfaces have {rows} atoms in all; split the pairs over several calls")
@@ -389,17 +333,18 @@ def interface_energy(model, film, substrate, pairs: Sequence, *, film_thickness:
                 src.data_ptr(), part.data_ptr(), area.data_ptr(), _lib.stream()), "interface_build")
             feats = None
             if forces_fn is None:
-                feats = _features(list(feat_f) + list(feat_s), forces_fn, dev)
+                feats = features(list(feat_f) + list(feat_s), forces_fn, dev)
             masks = [np.zeros((3, 3)), np.zeros((3, 3)), mask_if] * K if optimize_lattice else None
-            e, lat_out, pos_out, conv, nsteps, calls = _relax_jobs_masked(
-                model, cells, cart, src, counts, masks, feats, max_atoms_per_call, relax_structures, relax_kwargs, forces_fn, dev)
+            r = relax_jobs(model, cells, cart, src, counts, feats, max_atoms_per_call, relax_structures, relax_kwargs, forces_fn,
+                           dev, masks)
+            e, conv, nsteps = r.energies.cpu().numpy(), r.converged.cpu().numpy(), r.n_steps.cpu().numpy()
             area_h = area.cpu().numpy()
-            out["n_relax_calls"] = calls
+            out["n_relax_calls"] = r.n_calls
             for k, p in enumerate(matched):
                 j = 3 * k
                 out["area"][p], out["e_subs"][p], out["e_film"][p], out["e_interface"][p] = area_h[k], e[j], e[j + 1], e[j + 2]
-                out["lattices"][p] = lat_out[j:j + 3]
-                out["positions"][p] = pos_out[j:j + 3]
+                out["lattices"][p] = r.lattices[j:j + 3]
+                out["positions"][p] = r.positions[j:j + 3]
                 out["src"][p] = [src[off[j + q]:off[j + q + 1]] for q in range(3)]
                 out["part"][p] = [part[off[j + q]:off[j + q + 1]] for q in range(3)]
                 out["converged"][p], out["n_steps"][p] = conv[j:j + 3], nsteps[j:j + 3]

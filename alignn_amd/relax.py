@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._structures import ForceEvaluator, check_inputs, gpu_device, pack
+from ._structures import ForceEvaluator, check_inputs, gpu_device, host, pack
 
 __all__ = ["relax", "RelaxResult"]
 
@@ -62,14 +62,10 @@ class RelaxResult:
     enthalpies: Optional[torch.Tensor] = None  # [B] float64: energy + scalar_pressure * volume (optimize_lattice only)
 
 
-def _host(x) -> np.ndarray:
-    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-
-
 def _full_mask(m, what: str) -> np.ndarray:
     """One cell mask, six Voigt flags (xx, yy, zz, yz, xz, xy) or [3, 3], as the full 3 x 3 of 0.0 / 1.0 (ASE's
     voigt_6_to_full_3x3_stress for the Voigt form)."""
-    m = _host(m)
+    m = host(m)
     if m.shape == (6,):
         xx, yy, zz, yz, xz, xy = m
         m = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
@@ -93,7 +89,7 @@ def _constraints(ns: List[int], fixed, cell_mask, hydrostatic_strain, constant_v
             raise ValueError(f"relax: fixed needs one boolean [n_i] array (or None) per structure, {B} of them")
         rows = []
         for i, f in enumerate(fixed):
-            f = np.zeros(ns[i], dtype=bool) if f is None else _host(f)
+            f = np.zeros(ns[i], dtype=bool) if f is None else host(f)
             if f.shape != (ns[i],) or f.dtype != np.bool_:
                 raise ValueError(f"relax: fixed[{i}] is {f.dtype} {f.shape}, need bool [{ns[i]}]")
             rows.append(f)
@@ -103,7 +99,7 @@ def _constraints(ns: List[int], fixed, cell_mask, hydrostatic_strain, constant_v
     if cell_mask is not None:
         shape = None
         try:
-            shape = _host(cell_mask).shape
+            shape = host(cell_mask).shape
         except (ValueError, TypeError):  # a ragged list: Voigt and [3, 3] masks mixed
             pass
         if shape in ((6,), (3, 3)):  # one mask for every structure
@@ -112,7 +108,7 @@ def _constraints(ns: List[int], fixed, cell_mask, hydrostatic_strain, constant_v
             raise ValueError(f"relax: cell_mask needs one mask (six Voigt flags or [3, 3]) or {B} of them")
         else:
             masks = np.stack([_full_mask(m, f"cell_mask[{i}]") for i, m in enumerate(cell_mask)])
-    press = _host(scalar_pressure)
+    press = host(scalar_pressure)
     if press.dtype.kind not in "iuf" or press.shape not in ((), (B,)):
         raise ValueError(f"relax: scalar_pressure needs one number or {B} of them (eV/A^3)")
     press = np.broadcast_to(press.astype(np.float64), (B,)).copy()

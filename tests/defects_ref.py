@@ -70,7 +70,7 @@ def miller_basis(lattice, hkl):
 
 # --- the builders ------------------------------------------------------------------------------------------------------------------
 def inv3_cof(a):
-    """Inverse of a [3, 3] by cofactors, every element its cofactor / det (defects.hip inv3_cof)."""
+    """Inverse of a [3, 3] by cofactors, every element its cofactor / det (csrc/cell3.h inv3_cof)."""
     a = [float(v) for v in np.asarray(a, dtype=np.float64).reshape(-1)]
     c00, c01, c02 = a[4] * a[8] - a[5] * a[7], a[3] * a[8] - a[5] * a[6], a[3] * a[7] - a[4] * a[6]
     det = (a[0] * c00 - a[1] * c01) + a[2] * c02
