@@ -32,16 +32,13 @@
 #include "../../include/alignn_hip.h"
 #include <type_traits>
 
-#include "common.h"
+#include "mfma_f16x3.h"
 
 #ifndef ANGLE_GRID_DEFAULT
 #define ANGLE_GRID_DEFAULT 224  // (headline step eager, one box, two rounds: 256: 14.45 / 14.59, 224: 14.31 / 14.55, 192: 14.38 / 14.54, 160: 14.56 / 14.56)
 #endif
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kE = 64;         // embedding_features: layer-1 outputs
 constexpr int kH = 256;        // hidden_features: layer-2 outputs
@@ -66,14 +63,6 @@ __device__ __forceinline__ f32x16 zero16() {
 #pragma unroll
     for (int r = 0; r < 16; ++r) z[r] = 0.0f;
     return z;
-}
-// power-of-two scale that puts max|x| just below 2^15 (csrc/gemm_x6.hip f16_scale)
-__device__ __forceinline__ float f16_scale(float amax) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 255u);
-    if (e == 0 || e == 255) return 1.0f;
-    int se = 268 - e;
-    se = se > 254 ? 254 : se;
-    return __uint_as_float((unsigned)se << 23);
 }
 // three products of a split pair
 __device__ __forceinline__ f32x16 mfma3(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, f32x16 c) {
@@ -1253,11 +1242,7 @@ __global__ void angle_unpack_dw1_kernel(const float* __restrict__ src, int bins,
     else gb[c] = src[i];
 }
 
-inline int grid_for(int64_t rows, int rows_per_block) {
-    const int64_t need = (rows + rows_per_block - 1) / rows_per_block;
-    return (int)(need < kGrid ? (need > 0 ? need : 1) : kGrid);
-}
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+inline int grid_for(int64_t rows, int rows_per_block) { return capped_blocks(rows, rows_per_block, kGrid); }
 // The T x 256 passes take whole compute units (512 threads, 64-142 KiB of LDS, up to 250 registers per lane): what the caller's
 // other streams launch beside them waits for a unit they do not use.  ALIGNN_AMD_ANGLE_GRID (default kAngleGridDefault, a
 // multiple of 8) caps their grids; every pass walks its tiles with a grid stride and hands the launched count to its reductions.

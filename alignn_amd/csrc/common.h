@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define ALIGNN_WAVE 64
 #define ALIGNN_EPS_GATE 1e-6f
 
@@ -13,6 +15,32 @@
     } while (0)
 
 static inline int alignn_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---- host-side launch predicates and grid sizes ----
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }  // float4 accesses
+// feature counts of the row kernels: whole float4 quads, at most four 256-feature chunks per wavefront
+static inline bool feat_ok(int F) { return F >= 4 && (F & 3) == 0 && F <= 1024; }
+// a [rows, cols] fp32 tensor that cannot stay in the 256 MiB last-level cache anyway: its kernels take the streaming
+// (read-once / write-once hint) variant
+static inline bool exceeds_llc(int64_t rows, int64_t cols) { return rows * cols * 4 >= (int64_t)128 << 20; }
+// arena offsets: every buffer starts on a 256-byte boundary
+static inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+// workgroups for n items at per_block each: at least one (it writes the zero slab of an empty launch), at most cap
+static inline int capped_blocks(int64_t n, int per_block, int cap) {
+    const int64_t b = (n + per_block - 1) / per_block;
+    return (int)(b < 1 ? 1 : b > cap ? cap : b);
+}
+// run-time feature count F (feat_ok) -> compile-time number NC of 256-feature chunks a lane walks, 1..4:
+// f(std::integral_constant<int, NC>) launches the kernel instantiated for it
+template <class Fn>
+static inline void with_feature_chunks(int F, Fn&& f) {
+    switch ((F + 255) / 256) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
 
 // sigmoid with the hardware reciprocal (v_rcp_f32, 1 ulp) instead of an IEEE division (v_div_scale x2, v_rcp, four fma,
 // v_div_fmas, v_div_fixup: ten instructions per element, 40 % of the line-graph backward kernel's VALU work); the exponential
@@ -84,6 +112,77 @@ __device__ __forceinline__ float silu_f(float z) { return z * fast_sigmoid(z); }
 __device__ __forceinline__ float dsilu_f(float z) {
     float s = fast_sigmoid(z);
     return s * (1.0f + z * (1.0f - s));
+}
+
+__device__ __forceinline__ float hsum4(float4 a) { return (a.x + a.y) + (a.z + a.w); }
+// silu'(z), silu''(z)
+__device__ __forceinline__ void dsilu2(float z, float& d1, float& d2) {
+    const float s = fast_sigmoid(z), sp = s * (1.0f - s);
+    d1 = s + z * sp;
+    d2 = sp * (2.0f + z * (1.0f - 2.0f * s));
+}
+
+// ---- sums over the 64 lanes of a wavefront, the result in every lane ----
+// xor butterfly (6 ds_bpermute round trips): fixed order, every lane ends with the same bits
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, ALIGNN_WAVE);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, ALIGNN_WAVE);
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, ALIGNN_WAVE);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ALIGNN_WAVE));
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, ALIGNN_WAVE));
+    return v;
+}
+// The same float sum by another instruction sequence, so another summation order and a name of its own.  Within a row of 16
+// lanes by DPP adds (xor 1, xor 2, mirror of 8, mirror of 16: every lane of the row ends with the row's sum), the four rows by
+// v_readlane - 4 DPP adds + 4 readlanes + 3 adds instead of the 6 ds_bpermute round trips of the butterfly (the LayerNorm-in-gate
+// passes of convln.hip take 2-7 such sums per row).  Fixed order: ((r0 + r1) + (r2 + r3)) over the row sums.
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+    v += dpp_mov<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+    v += dpp_mov<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+    v += dpp_mov<0x141>(v);  // row_half_mirror
+    v += dpp_mov<0x140>(v);  // row_mirror
+    const int b = __builtin_bit_cast(int, v);
+    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
+    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
+    return (r0 + r1) + (r2 + r3);
+}
+
+// Merge of two BatchNorm "pivot slabs" (norm.hip: col_stats_welford_kernel; conv.hip writes the same slabs and
+// bn_finalize_welford reads both): (n, p, S, SS) of set a  <-  union with set b, expressed about a's pivot; empty sets pass through
+__device__ __forceinline__ void pivot_merge(float& na, float4& pa, float4& Sa, float4& SSa, float nb, float4 pb, float4 Sb,
+                                            float4 SSb) {
+    if (nb == 0.0f) return;
+    if (na == 0.0f) {
+        na = nb, pa = pb, Sa = Sb, SSa = SSb;
+        return;
+    }
+    const float4 d = f4_sub(pb, pa);
+    // sum (x - pa)^2 over b = SSb + 2 d Sb + nb d^2 ;  sum (x - pa) over b = Sb + nb d
+    SSa = make_float4(SSa.x + SSb.x + d.x * (2.0f * Sb.x + nb * d.x), SSa.y + SSb.y + d.y * (2.0f * Sb.y + nb * d.y),
+                      SSa.z + SSb.z + d.z * (2.0f * Sb.z + nb * d.z), SSa.w + SSb.w + d.w * (2.0f * Sb.w + nb * d.w));
+    Sa = make_float4(Sa.x + Sb.x + nb * d.x, Sa.y + Sb.y + nb * d.y, Sa.z + Sb.z + nb * d.z, Sa.w + Sb.w + nb * d.w);
+    na += nb;
 }
 
 // Running max|x| of a tensor, tracked by the kernel that produces it (consumed by the f16x3 GEMMs to pick their

@@ -18,12 +18,7 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kThreads = kWavesPerBlock * ALIGNN_WAVE;
 constexpr int kMaxSlabs = 1024;  // workgroups of the segment kernels (= statistic slabs they emit)
 
-__host__ __device__ inline int egc_blocks(int64_t n_seg) {
-    int64_t b = (n_seg + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (b < 1) b = 1;
-    if (b > kMaxSlabs) b = kMaxSlabs;
-    return (int)b;
-}
+inline int egc_blocks(int64_t n_seg) { return capped_blocks(n_seg, kWavesPerBlock, kMaxSlabs); }
 
 // BatchNorm statistics as "pivot slabs" (csrc/norm.hip: col_stats_welford_kernel): every lane sums d = v - p and d^2 about
 // a pivot p = the first value it sees; the four waves are merged in wave order by re-centring onto wave 0's pivot (all
@@ -39,19 +34,6 @@ struct ShiftAcc {
         SS = f4_fma(d, d, SS);
     }
 };
-__device__ __forceinline__ void pivot_merge4(float& na, float4& pa, float4& Sa, float4& SSa, float nb, float4 pb, float4 Sb,
-                                             float4 SSb) {
-    if (nb == 0.0f) return;
-    if (na == 0.0f) {
-        na = nb, pa = pb, Sa = Sb, SSa = SSb;
-        return;
-    }
-    const float4 d = f4_sub(pb, pa);
-    SSa = make_float4(SSa.x + SSb.x + d.x * (2.0f * Sb.x + nb * d.x), SSa.y + SSb.y + d.y * (2.0f * Sb.y + nb * d.y),
-                      SSa.z + SSb.z + d.z * (2.0f * Sb.z + nb * d.z), SSa.w + SSb.w + d.w * (2.0f * Sb.w + nb * d.w));
-    Sa = make_float4(Sa.x + Sb.x + nb * d.x, Sa.y + Sb.y + nb * d.y, Sa.z + Sb.z + nb * d.z, Sa.w + Sb.w + nb * d.w);
-    na += nb;
-}
 // `cnt`: values this wave accumulated (wave-uniform; lane 0 is active in every panel).  Writes slab [3][H] at `slab` and, for
 // the first feature panel, the block's row count at `count_out`.
 __device__ __forceinline__ void block_moments_write(const ShiftAcc& a, float cnt, float* slab, float* count_out, int H, int f,
@@ -66,7 +48,7 @@ __device__ __forceinline__ void block_moments_write(const ShiftAcc& a, float cnt
         float n = shn[0];
         float4 p = sh[0][0][lane], S = sh[1][0][lane], SS = sh[2][0][lane];
 #pragma unroll
-        for (int w = 1; w < kWavesPerBlock; ++w) pivot_merge4(n, p, S, SS, shn[w], sh[0][w][lane], sh[1][w][lane], sh[2][w][lane]);
+        for (int w = 1; w < kWavesPerBlock; ++w) pivot_merge(n, p, S, SS, shn[w], sh[0][w][lane], sh[1][w][lane], sh[2][w][lane]);
         if (active) {
             f4_st(slab + f, p);
             f4_st(slab + H + f, S);
@@ -644,8 +626,6 @@ __global__ __launch_bounds__(kThreads) void egc_bwd_lg_dense_kernel(
     block_amax_commit(gp_am, gp_amax);
 }
 
-inline bool big_stream(int64_t rows, int H) { return rows * (int64_t)H * 4 >= (int64_t)128 << 20; }
-inline bool h_ok(int H) { return H >= 4 && (H & 3) == 0 && H <= 1024; }
 
 }  // namespace
 
@@ -656,8 +636,8 @@ int alignn_egc_slabs(int64_t n_seg) { return egc_blocks(n_seg); }
 int alignn_egc_gate_fwd(const float* P, float* M, const int32_t* seg_ptr, const int32_t* seg_node,
                         const int32_t* src, int64_t n_seg, int64_t m_rows, int H, float* XPRE, float* S0, float* HH,
                         float* e_partial, float* n_partial, alignn_stream_t stream) {
-    if (!h_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0) return (int)hipErrorInvalidValue;
-    if (big_stream(m_rows, H))  // M cannot stay in the last-level cache: read-once / write-once hints
+    if (!feat_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0) return (int)hipErrorInvalidValue;
+    if (exceeds_llc(m_rows, H))  // M cannot stay in the last-level cache: read-once / write-once hints
         hipLaunchKernelGGL((egc_gate_fwd_kernel<true, false>), dim3(egc_blocks(n_seg)), dim3(kThreads), 0,
                            (hipStream_t)stream, P, M, seg_ptr, seg_node, src, (int)n_seg, H, XPRE, S0, HH, e_partial,
                            n_partial, nullptr, nullptr, nullptr, nullptr);
@@ -672,8 +652,8 @@ int alignn_egc_gate_fwd(const float* P, float* M, const int32_t* seg_ptr, const 
 int alignn_egc_gate_fwd_pre(const float* P, float* M, const int32_t* seg_ptr, const int32_t* seg_node,
                             const int32_t* src, int64_t n_seg, int64_t m_rows, int H, float* XPRE, float* S0, float* HH,
                             float* e_partial, float* n_partial, alignn_stream_t stream) {
-    if (!h_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0) return (int)hipErrorInvalidValue;
-    if (big_stream(m_rows, H))
+    if (!feat_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0) return (int)hipErrorInvalidValue;
+    if (exceeds_llc(m_rows, H))
         hipLaunchKernelGGL((egc_gate_fwd_kernel<true, false, true>), dim3(egc_blocks(n_seg)), dim3(kThreads), 0,
                            (hipStream_t)stream, P, M, seg_ptr, seg_node, src, (int)n_seg, H, XPRE, S0, HH, e_partial,
                            n_partial, nullptr, nullptr, nullptr, nullptr);
@@ -689,9 +669,9 @@ int alignn_egc_gate_fwd_pre_norm(const float* P, const float* M, const int32_t* 
                                  const int32_t* src, int64_t n_seg, int64_t m_rows, int H, float* XPRE, float* S0,
                                  float* HH, float* n_partial, const float* e_stat, const float* Y, float* YOUT,
                                  float* y_amax, alignn_stream_t stream) {
-    if (!h_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0 || !e_stat || !YOUT) return (int)hipErrorInvalidValue;
+    if (!feat_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0 || !e_stat || !YOUT) return (int)hipErrorInvalidValue;
     float* Mm = const_cast<float*>(M);  // the <INFER, PRE> instantiation only reads it
-    if (big_stream(m_rows, H))
+    if (exceeds_llc(m_rows, H))
         hipLaunchKernelGGL((egc_gate_fwd_kernel<true, true, true>), dim3(egc_blocks(n_seg)), dim3(kThreads), 0,
                            (hipStream_t)stream, P, Mm, seg_ptr, seg_node, src, (int)n_seg, H, XPRE, S0, HH, nullptr,
                            n_partial, e_stat, Y, YOUT, y_amax);
@@ -706,9 +686,9 @@ int alignn_egc_gate_fwd_pre_norm(const float* P, const float* M, const int32_t* 
 int alignn_egc_gate_infer(const float* P, const float* C, const int32_t* seg_ptr, const int32_t* seg_node,
                           const int32_t* src, int64_t n_seg, int64_t m_rows, int H, float* XPRE, const float* e_stat,
                           const float* Y, float* YOUT, float* y_amax, alignn_stream_t stream) {
-    if (!h_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0 || (YOUT && !e_stat)) return (int)hipErrorInvalidValue;
+    if (!feat_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0 || (YOUT && !e_stat)) return (int)hipErrorInvalidValue;
     float* Cm = const_cast<float*>(C);  // the INFER instantiation only reads it
-    if (big_stream(m_rows, H))
+    if (exceeds_llc(m_rows, H))
         hipLaunchKernelGGL((egc_gate_fwd_kernel<true, true>), dim3(egc_blocks(n_seg)), dim3(kThreads), 0,
                            (hipStream_t)stream, P, Cm, seg_ptr, seg_node, src, (int)n_seg, H, XPRE, nullptr, nullptr,
                            nullptr, nullptr, e_stat, Y, YOUT, y_amax);
@@ -722,7 +702,7 @@ int alignn_egc_gate_infer(const float* P, const float* C, const int32_t* seg_ptr
 
 int alignn_egc_node_bwd(const float* GXPRE, int64_t ldg, const float* S0, const float* HH, float* GS1, float* GS0,
                         int64_t n_nodes, int H, alignn_stream_t stream) {
-    if (!h_ok(H)) return (int)hipErrorInvalidValue;
+    if (!feat_ok(H)) return (int)hipErrorInvalidValue;
     if (n_nodes == 0) return 0;
     int64_t g = (n_nodes * (H >> 2) + 255) / 256;
     if (g > 2048) g = 2048;
@@ -738,7 +718,7 @@ int alignn_egc_bwd_dst(const float* GY, const float* M, const float* P, const fl
                        float* GM, float* GP, float* gb_partial, float* gm_amax, float* gp_amax,
                        alignn_stream_t stream) {
     (void)e_gamma;
-    if (!h_ok(H) || n_seg > INT32_MAX) return (int)hipErrorInvalidValue;
+    if (!feat_ok(H) || n_seg > INT32_MAX) return (int)hipErrorInvalidValue;
     const float inv_n = m_rows > 0 ? 1.0f / (float)m_rows : 0.0f;
     dim3 grid(egc_blocks(n_seg)), block(kThreads);
     if (GY && e_stat)
@@ -763,12 +743,12 @@ int alignn_egc_bwd_lg_fused(const float* GY, const float* M, const float* P, con
                             const int32_t* seg_ptr, const int32_t* seg_node, const int32_t* dst,
                             const int32_t* out_ptr, const int32_t* out_slot, int H, float* GM, float* GP,
                             float* gb_partial, float* gm_amax, float* gp_amax, alignn_stream_t stream) {
-    if (!h_ok(H) || n_groups <= 0 || n_groups > INT32_MAX) return (int)hipErrorInvalidValue;
+    if (!feat_ok(H) || n_groups <= 0 || n_groups > INT32_MAX) return (int)hipErrorInvalidValue;
     const float inv_n = m_rows > 0 ? 1.0f / (float)m_rows : 0.0f;
     dim3 grid((int)n_groups), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
 #define ALIGNN_LGF(MODE_)                                                                                           \
-    if (big_stream(m_rows, H))                                                                                      \
+    if (exceeds_llc(m_rows, H))                                                                                      \
         hipLaunchKernelGGL((egc_bwd_lg_fused_kernel<MODE_, true>), grid, block, 0, st, GY, M, P, GS1, GS0, e_stat,     \
                            e_red, e_eval, inv_n, grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, dst, out_ptr, out_slot, \
                            H, GM, GP, gb_partial, gm_amax, gp_amax);                                                \
@@ -795,7 +775,7 @@ int alignn_egc_bwd_lg_dense(const float* GY, const float* M, const float* P, con
                             const int32_t* grp_seg_ptr, const int32_t* grp_src_ptr, int64_t n_groups,
                             int max_group_src, const int32_t* seg_ptr, const int32_t* seg_node, int H, float* GM,
                             float* GP, float* gb_partial, float* gm_amax, float* gp_amax, alignn_stream_t stream) {
-    if (!h_ok(H) || n_groups <= 0 || n_groups > INT32_MAX || !alignn_egc_bwd_lg_dense_supported(max_group_src))
+    if (!feat_ok(H) || n_groups <= 0 || n_groups > INT32_MAX || !alignn_egc_bwd_lg_dense_supported(max_group_src))
         return (int)hipErrorInvalidValue;
     const float inv_n = m_rows > 0 ? 1.0f / (float)m_rows : 0.0f;
     dim3 grid((int)n_groups), block(kThreads);
@@ -805,7 +785,7 @@ int alignn_egc_bwd_lg_dense(const float* GY, const float* M, const float* P, con
                        e_eval, inv_n, grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, H, GM, GP, gb_partial, gm_amax,  \
                        gp_amax)
 #define ALIGNN_LGD(MODE_)                            \
-    if (big_stream(m_rows, H)) {                     \
+    if (exceeds_llc(m_rows, H)) {                     \
         ALIGNN_LGD2(MODE_, true);                    \
     } else {                                         \
         ALIGNN_LGD2(MODE_, false);                   \
@@ -826,7 +806,7 @@ int alignn_egc_bwd_lg_dense(const float* GY, const float* M, const float* P, con
 int alignn_egc_bwd_src(const float* GM, const float* M, const float* GS1, const int32_t* out_ptr,
                        const int32_t* out_slot, const int32_t* dst, int64_t n_nodes, int H, float* GP,
                        float* gp_amax, alignn_stream_t stream) {
-    if (!h_ok(H) || n_nodes > INT32_MAX) return (int)hipErrorInvalidValue;
+    if (!feat_ok(H) || n_nodes > INT32_MAX) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(egc_bwd_src_kernel, dim3(egc_blocks(n_nodes)), dim3(kThreads), 0, (hipStream_t)stream, GM, M,
                        GS1, out_ptr, out_slot, dst, (int)n_nodes, H, GP, gp_amax);
     ALIGNN_CHECK_LAUNCH();

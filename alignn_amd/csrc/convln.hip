@@ -23,43 +23,13 @@ namespace {
 
 constexpr int kW = 4, kT = kW * ALIGNN_WAVE, kMaxBlocks = 1024, kK = 4;
 
-// Sum over the 64 lanes of a wavefront, the result in every lane.  Within a row of 16 lanes by DPP adds (xor 1, xor 2, mirror
-// of 8, mirror of 16: every lane of the row ends with the row's sum), the four rows by v_readlane - 4 DPP adds + 4 readlanes + 3
-// adds instead of the 6 ds_bpermute round trips of the __shfl_xor butterfly (the LayerNorm passes below take 2-7 such sums per
-// row).  Fixed order: ((r0 + r1) + (r2 + r3)) over the row sums.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum1(float v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror
-    const int b = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-    return (r0 + r1) + (r2 + r3);
-}
+// (wave_sum_dpp, not the butterfly wave_sum: the LayerNorm passes below take 2-7 wave sums per row - common.h)
 template <int K>
 __device__ __forceinline__ void wave_sum_k(float (&v)[K]) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum1(v[k]);
+    for (int k = 0; k < K; ++k) v[k] = wave_sum_dpp(v[k]);
 }
-__device__ __forceinline__ float hsum4(float4 a) { return (a.x + a.y) + (a.z + a.w); }
-__device__ __forceinline__ float sig_f(float x) { return fast_sigmoid(x); }
-__device__ __forceinline__ void dsilu2(float z, float& d1, float& d2) {  // silu'(z), silu''(z) (dual.hip)
-    const float s = sig_f(z), sp = s * (1.0f - s);
-    d1 = s + z * sp;
-    d2 = sp * (2.0f + z * (1.0f - 2.0f * s));
-}
-inline int seg_blocks(int64_t n_seg) {
-    int64_t b = (n_seg + kW - 1) / kW;
-    if (b < 1) b = 1;
-    if (b > kMaxBlocks) b = kMaxBlocks;
-    return (int)b;
-}
-inline bool big_stream(int64_t rows, int H) { return rows * (int64_t)H * 4 >= (int64_t)128 << 20; }
+inline int seg_blocks(int64_t n_seg) { return capped_blocks(n_seg, kW, kMaxBlocks); }
 
 // the workgroup's LayerNorm parameter-gradient slab: [0] = dbeta, [1] = dgamma, the four waves in wave order
 __device__ __forceinline__ void ln_slab_store(float4 db, float4 dg, float4 (*sh)[kW][ALIGNN_WAVE], float* slab, int H, int f,
@@ -358,7 +328,7 @@ __global__ __launch_bounds__(kT) void egc_gate_dual_tan_ln_kernel(
     {                                                                   \
         const float th = rs[k] * (mt[k].q - m1 - xh[k].q * m2);         \
         const float z = fmaf(xh[k].q, ga.q, be.q), zt = ga.q * th;      \
-        const float sg = sig_f(z);                                      \
+        const float sg = fast_sigmoid(z);                                \
         ot.q = (sg + z * sg * (1.0f - sg)) * zt;                        \
     }
                     ALIGNN_LN_T(x) ALIGNN_LN_T(y) ALIGNN_LN_T(z) ALIGNN_LN_T(w)
@@ -518,7 +488,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_ln_kernel(
     {                                                                                                     \
         gmt.c = rs[kk] * (a[kk].c - A1[kk] - xh[kk].c * A2[kk]);                                           \
         gm.c = rs[kk] * (b[kk].c - B1 - xh[kk].c * B2) - rs[kk] * xh[kk].c * A3[kk];                       \
-        const float sg = sig_f(m[kk].c), sp = sg * (1.0f - sg);                                           \
+        const float sg = fast_sigmoid(m[kk].c), sp = sg * (1.0f - sg);                                     \
         const float gs = q1.c * bh[k].c + q0.c + q1t.c * bht[k].c; /* adjoint of sigma */                  \
         const float gst = q1t.c * bh[k].c + q0t.c;                 /* adjoint of sigma-dot */              \
         gm.c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * t[kk].c;                                         \
@@ -641,7 +611,7 @@ __global__ __launch_bounds__(kT) void egc_bwd_dst_ln_kernel(
                 s1 = hsum4(gh);
                 s2 = hsum4(f4_mul(gh, xh));
             }
-            const float c1 = wave_sum1(s1) * inv_f, c2 = wave_sum1(s2) * inv_f;
+            const float c1 = wave_sum_dpp(s1) * inv_f, c2 = wave_sum_dpp(s2) * inv_f;
             if (active) {
                 const float4 sg = f4_sigmoid(m);
                 const float4 gsig = f4_fma(gs1, bh, gs0);
@@ -716,7 +686,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_dst_ln_kernel(
                 r0 = hsum4(t);
                 r1 = hsum4(f4_mul(xh, t));
             }
-            const float m1 = wave_sum1(r0) * inv_f, m2 = wave_sum1(r1) * inv_f;
+            const float m1 = wave_sum_dpp(r0) * inv_f, m2 = wave_sum_dpp(r1) * inv_f;
             r0 = r1 = r2 = 0.0f;
             if (active) {
 #define ALIGNN_LN_DB(q)                                              \
@@ -738,7 +708,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_dst_ln_kernel(
                 ALIGNN_LN_DB(x) ALIGNN_LN_DB(y) ALIGNN_LN_DB(z) ALIGNN_LN_DB(w)
 #undef ALIGNN_LN_DB
             }
-            const float A1 = wave_sum1(r0) * inv_f, A2 = wave_sum1(r1) * inv_f, A3 = wave_sum1(r2) * inv_f;
+            const float A1 = wave_sum_dpp(r0) * inv_f, A2 = wave_sum_dpp(r1) * inv_f, A3 = wave_sum_dpp(r2) * inv_f;
             r0 = r1 = 0.0f;
             if (active) {
                 b.x -= rs * (a.x * m2 + t.x * A2);
@@ -748,14 +718,14 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_dst_ln_kernel(
                 r0 = hsum4(b);
                 r1 = hsum4(f4_mul(b, xh));
             }
-            const float B1 = wave_sum1(r0) * inv_f, B2 = wave_sum1(r1) * inv_f;
+            const float B1 = wave_sum_dpp(r0) * inv_f, B2 = wave_sum_dpp(r1) * inv_f;
             if (active) {
                 float4 gm, gmt;
 #define ALIGNN_GD(c)                                                            \
     {                                                                           \
         gmt.c = rs * (a.c - A1 - xh.c * A2);                                    \
         gm.c = rs * (b.c - B1 - xh.c * B2) - rs * xh.c * A3;                    \
-        const float sg = sig_f(m.c), sp = sg * (1.0f - sg);                     \
+        const float sg = fast_sigmoid(m.c), sp = sg * (1.0f - sg);               \
         const float gs = q1.c * bh.c + q0.c + q1t.c * bht.c; /* adj. sigma */   \
         const float gst = q1t.c * bh.c + q0t.c;              /* adj. sigma-dot */ \
         gm.c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * t.c;                  \
@@ -805,7 +775,6 @@ inline int reverse_variant(int which) {  // (read per call: A/B runs inside one 
     if (which == 0) return e[0] - '0';
     return (e[1] >= '0' && e[1] <= '9') ? e[1] - '0' : 0;
 }
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -816,7 +785,7 @@ extern "C" {
    cache-resident line graphs (a 200-atom MD cell: 35 k rows) the separate LayerNorm kernels win by their finer grids (tools/
    ln_rev_time.py: 70 vs 93 us at 1 x 200 atoms, 134 vs 130 at 8 x 60, 727 vs 426 at 16 x 200).  ALIGNN_AMD_LN_FUSED=0: never,
    =2: whenever H allows (tests).  Read per call. */
-static bool ln_h_ok(int H) { return H >= 4 && (H & 3) == 0 && H <= 4 * ALIGNN_WAVE; }
+static bool ln_h_ok(int H) { return feat_ok(H) && H <= 4 * ALIGNN_WAVE; }
 int alignn_egc_ln_fused_supported(int H, int64_t m_rows) {
     const char* e = std::getenv("ALIGNN_AMD_LN_FUSED");
     if (e != nullptr && e[0] == '0') return 0;
@@ -832,7 +801,7 @@ int alignn_egc_gate_fwd_pre_ln(const float* P, const float* M, const int32_t* se
     if (!ln_h_ok(H) || n_seg < 0 || n_seg > INT32_MAX || m_rows < 0 || !YOUT || !e_stat || !gamma || !beta)
         return (int)hipErrorInvalidValue;
     if (n_seg == 0) return 0;
-    if (big_stream(m_rows, H))
+    if (exceeds_llc(m_rows, H))
         hipLaunchKernelGGL(egc_gate_fwd_ln_kernel<true>, dim3(seg_blocks(n_seg)), dim3(kT), 0, (hipStream_t)stream, P, M, seg_ptr,
                            seg_node, src, (int)n_seg, H, XPRE, S0, HH, gamma, beta, eps, Y, YOUT, e_stat, y_amax);
     else
@@ -851,7 +820,7 @@ int alignn_egc_bwd_lg_dense_ln(const float* GY, const float* M, const float* P, 
         !ln_partial)
         return (int)hipErrorInvalidValue;
     const dim3 grid((int)n_groups), block(kT);
-    const bool big = big_stream(m_rows, H);
+    const bool big = exceeds_llc(m_rows, H);
 #define ALIGNN_LNV(ST_, KS_, KB_)                                                                                              \
     hipLaunchKernelGGL((egc_bwd_lg_dense_ln_kernel<ST_, KS_, KB_>), grid, block, 0, (hipStream_t)stream, GY, M, P, GS1, GS0, gamma, \
                        beta, e_stat, grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, H, GM, GP, gb_partial, ln_partial, gm_amax,    \
@@ -871,7 +840,7 @@ int alignn_egc_gate_dual_tan_ln(const float* P, const float* Pt, const float* M,
                                 const int32_t* seg_node, const int32_t* src, int64_t n, int64_t m, int H, float* xpre_t,
                                 const float* s0, const float* hh, float* s0t, float* hht, const float* gamma, const float* beta,
                                 const float* e_stat, const float* Rt, float* Yt, float* amax2, alignn_stream_t stream) {
-    if (!ln_h_ok(H) || !a16(P) || !a16(M) || !e_stat || !Yt) return (int)hipErrorInvalidValue;
+    if (!ln_h_ok(H) || !aligned16(P) || !aligned16(M) || !e_stat || !Yt) return (int)hipErrorInvalidValue;
     (void)m;
     if (n == 0) return 0;
     hipLaunchKernelGGL(egc_gate_dual_tan_ln_kernel, dim3(seg_blocks(n)), dim3(kT), 0, (hipStream_t)stream, P, Pt, M, Mt, seg_ptr,
@@ -891,7 +860,7 @@ int alignn_egc_dual_bwd_lg_dense_ln(const float* GY, const float* GYt, const flo
         return (int)hipErrorInvalidValue;
     if (n_groups == 0) return 0;
     const dim3 grid((unsigned)n_groups), block(kT);
-    const bool big = big_stream(m_rows, H);
+    const bool big = exceeds_llc(m_rows, H);
 #define ALIGNN_LND(ST_, KS_, KB_, EA_)                                                                                          \
     hipLaunchKernelGGL((egc_dual_bwd_lg_dense_ln_kernel<ST_, KS_, KB_, EA_>), grid, block, 0, (hipStream_t)stream, GY, GYt, M, Mt, P, \
                        Pt, q1, q0, q1t, q0t, gamma, beta, e_stat, grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, H, GM, GMt, GP, GPt, \

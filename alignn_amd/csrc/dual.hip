@@ -24,25 +24,7 @@ namespace {
 
 constexpr int kW = 4, kT = kW * ALIGNN_WAVE, kMaxBlocks = 1024;
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float hsum4(float4 a) { return (a.x + a.y) + (a.z + a.w); }
-__device__ __forceinline__ float sig_f(float x) { return fast_sigmoid(x); }
-// silu'(z), silu''(z)
-__device__ __forceinline__ void dsilu2(float z, float& d1, float& d2) {
-    const float s = sig_f(z), sp = s * (1.0f - s);
-    d1 = s + z * sp;
-    d2 = sp * (2.0f + z * (1.0f - 2.0f * s));
-}
-inline int row_blocks(int64_t rows) {
-    int64_t b = (rows + kW - 1) / kW;
-    if (b < 1) b = 1;
-    if (b > kMaxBlocks) b = kMaxBlocks;
-    return (int)b;
-}
+inline int row_blocks(int64_t rows) { return capped_blocks(rows, kW, kMaxBlocks); }
 
 // two amax slots (value, tangent) committed by every thread of the workgroup
 __device__ __forceinline__ void amax2_commit(float a, float b, float* amax2) {
@@ -74,7 +56,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_fwd_kernel(
             t[c] = f < F ? f4_ld(Xt + r * ldx + f) : f4_zero();
             s += hsum4(x[c]);
         }
-        const float mean = wsum(s) * inv_f;
+        const float mean = wave_sum(s) * inv_f;
         float v = 0.0f, st = 0.0f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -85,8 +67,8 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_fwd_kernel(
                 st += hsum4(t[c]);
             }
         }
-        const float rstd = 1.0f / sqrtf(wsum(v) * inv_f + eps);
-        const float m1 = wsum(st) * inv_f;
+        const float rstd = 1.0f / sqrtf(wave_sum(v) * inv_f + eps);
+        const float m1 = wave_sum(st) * inv_f;
         float sxt = 0.0f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -96,7 +78,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_fwd_kernel(
                 sxt += hsum4(f4_mul(x[c], t[c]));
             }
         }
-        const float m2 = wsum(sxt) * inv_f;
+        const float m2 = wave_sum(sxt) * inv_f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int f = c * 256 + 4 * lane;
@@ -107,7 +89,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_fwd_kernel(
     {                                                                \
         const float th = rstd * (t[c].q - m1 - x[c].q * m2);         \
         const float z = fmaf(x[c].q, g.q, b.q), zt = g.q * th;       \
-        const float sg = sig_f(z);                                   \
+        const float sg = fast_sigmoid(z);                             \
         o.q = z * sg;                                                \
         ot.q = (sg + z * sg * (1.0f - sg)) * zt;                     \
     }
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
                 sxt += hsum4(f4_mul(xh[c], t[c]));
             }
         }
-        const float m1 = wsum(st) * inv_f, m2 = wsum(sxt) * inv_f;
+        const float m1 = wave_sum(st) * inv_f, m2 = wave_sum(sxt) * inv_f;
         float sa = 0.0f, sax = 0.0f, sat = 0.0f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
 #undef ALIGNN_LN_DUAL_B
             }
         }
-        const float A1 = wsum(sa) * inv_f, A2 = wsum(sax) * inv_f, A3 = wsum(sat) * inv_f;
+        const float A1 = wave_sum(sa) * inv_f, A2 = wave_sum(sax) * inv_f, A3 = wave_sum(sat) * inv_f;
         // total adjoint of x-hat: direct part - rstd (a m2 + t A2)
         float sb = 0.0f, sbx = 0.0f;
 #pragma unroll
@@ -211,7 +193,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
                 sbx += hsum4(f4_mul(b[c], xh[c]));
             }
         }
-        const float B1 = wsum(sb) * inv_f, B2 = wsum(sbx) * inv_f;
+        const float B1 = wave_sum(sb) * inv_f, B2 = wave_sum(sbx) * inv_f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int f = c * 256 + 4 * lane;
@@ -440,7 +422,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_dst_kernel(
                     float4 gmt = GL ? f4_ld(GLt + (int64_t)e * H + f) : f4_zero();
 #define ALIGNN_GD(c)                                                            \
     {                                                                           \
-        const float sg = sig_f(m.c), sp = sg * (1.0f - sg);                     \
+        const float sg = fast_sigmoid(m.c), sp = sg * (1.0f - sg);               \
         const float gs = q1.c * bh.c + q0.c + q1t.c * bht.c; /* adj. sigma */   \
         const float gst = q1t.c * bh.c + q0t.c;              /* adj. sigma-dot */ \
         gm.c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * mt.c;                 \
@@ -502,11 +484,11 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_src_kernel(
                     const float4 q1 = f4_ld(Q1 + v * H + f), q1t = f4_ld(Q1t + v * H + f);
                     ga = f4_add(ga, f4_ld(GM + slot * H + f));
                     gat = f4_add(gat, f4_ld(GMt + slot * H + f));
-#define ALIGNN_GS(c)                                              \
-    {                                                             \
-        const float sg = sig_f(m.c), sgt = sg * (1.0f - sg) * mt.c; \
-        gbh.c += sg * q1.c + sgt * q1t.c;                         \
-        gbht.c += sg * q1t.c;                                     \
+#define ALIGNN_GS(c)                                                       \
+    {                                                                      \
+        const float sg = fast_sigmoid(m.c), sgt = sg * (1.0f - sg) * mt.c; \
+        gbh.c += sg * q1.c + sgt * q1t.c;                                  \
+        gbht.c += sg * q1t.c;                                              \
     }
                     ALIGNN_GS(x) ALIGNN_GS(y) ALIGNN_GS(z) ALIGNN_GS(w)
 #undef ALIGNN_GS
@@ -592,7 +574,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_kernel(
                         if (row[k] >= 0) {
 #define ALIGNN_GDD(c)                                                                                     \
     {                                                                                                     \
-        const float sg = sig_f(m[k].c), sp = sg * (1.0f - sg);                                            \
+        const float sg = fast_sigmoid(m[k].c), sp = sg * (1.0f - sg);                                      \
         const float gs = q1.c * bh[k].c + q0.c + q1t.c * bht[k].c; /* adjoint of sigma */                  \
         const float gst = q1t.c * bh[k].c + q0t.c;                 /* adjoint of sigma-dot */              \
         gm[k].c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * mt[k].c;                                      \
@@ -661,9 +643,6 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_kernel(
     amax2_commit(pam, pamt, gp_amax2);
 }
 
-inline bool feat_ok(int F) { return F >= 4 && (F & 3) == 0 && F <= 1024; }
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -677,16 +656,10 @@ int alignn_ln_silu_dual_fwd(const float* X, const float* Xt, int64_t ldx, const 
     if (rows == 0) return 0;
     dim3 grid(row_blocks(rows)), block(kT);
     hipStream_t st = (hipStream_t)stream;
-#define ALIGNN_CASE(NC_)                                                                                              \
-    hipLaunchKernelGGL((ln_silu_dual_fwd_kernel<NC_>), grid, block, 0, st, X, Xt, ldx, R, Rt, ldr, gamma, beta, eps, Y, \
-                       Yt, ldy, stats, rows, F, amax2)
-    switch ((F + 255) / 256) {
-        case 1: ALIGNN_CASE(1); break;
-        case 2: ALIGNN_CASE(2); break;
-        case 3: ALIGNN_CASE(3); break;
-        default: ALIGNN_CASE(4); break;
-    }
-#undef ALIGNN_CASE
+    with_feature_chunks(F, [&](auto nc) {
+        hipLaunchKernelGGL((ln_silu_dual_fwd_kernel<decltype(nc)::value>), grid, block, 0, st, X, Xt, ldx, R, Rt, ldr, gamma, beta, eps,
+                           Y, Yt, ldy, stats, rows, F, amax2);
+    });
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
@@ -699,16 +672,11 @@ int alignn_ln_silu_dual_bwd(const float* GY, const float* GYt, int64_t ldg, cons
     // zeros, not whatever the workspace held (same rule as alignn_ln_silu_bwd / _node in norm.hip)
     dim3 grid(row_blocks(rows)), block(kT);
     hipStream_t st = (hipStream_t)stream;
-#define ALIGNN_CASE(NC_)                                                                                                    \
-    hipLaunchKernelGGL((ln_silu_dual_bwd_kernel<NC_, false>), grid, block, 0, st, GY, GYt, ldg, X, Xt, ldx, gamma, beta, stats, GX, \
-                       GXt, ldo, partial, rows, F, amax2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
-    switch ((F + 255) / 256) {
-        case 1: ALIGNN_CASE(1); break;
-        case 2: ALIGNN_CASE(2); break;
-        case 3: ALIGNN_CASE(3); break;
-        default: ALIGNN_CASE(4); break;
-    }
-#undef ALIGNN_CASE
+    with_feature_chunks(F, [&](auto nc) {
+        hipLaunchKernelGGL((ln_silu_dual_bwd_kernel<decltype(nc)::value, false>), grid, block, 0, st, GY, GYt, ldg, X, Xt, ldx, gamma,
+                           beta, stats, GX, GXt, ldo, partial, rows, F, amax2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr);
+    });
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
@@ -722,16 +690,10 @@ int alignn_ln_silu_dual_bwd_node(const float* GY, const float* GYt, int64_t ldg,
     // (rows == 0: one workgroup writes the zero slab, see alignn_ln_silu_dual_bwd)
     dim3 grid(row_blocks(rows)), block(kT);
     hipStream_t st = (hipStream_t)stream;
-#define ALIGNN_CASE(NC_)                                                                                                   \
-    hipLaunchKernelGGL((ln_silu_dual_bwd_kernel<NC_, true>), grid, block, 0, st, GY, GYt, ldg, X, Xt, ldx, gamma, beta, stats, GX, \
-                       GXt, ldo, partial, rows, F, amax2, s0, hh, s0t, hht, q1, q0, q1t, q0t)
-    switch ((F + 255) / 256) {
-        case 1: ALIGNN_CASE(1); break;
-        case 2: ALIGNN_CASE(2); break;
-        case 3: ALIGNN_CASE(3); break;
-        default: ALIGNN_CASE(4); break;
-    }
-#undef ALIGNN_CASE
+    with_feature_chunks(F, [&](auto nc) {
+        hipLaunchKernelGGL((ln_silu_dual_bwd_kernel<decltype(nc)::value, true>), grid, block, 0, st, GY, GYt, ldg, X, Xt, ldx, gamma,
+                           beta, stats, GX, GXt, ldo, partial, rows, F, amax2, s0, hh, s0t, hht, q1, q0, q1t, q0t);
+    });
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
@@ -739,7 +701,7 @@ int alignn_ln_silu_dual_bwd_node(const float* GY, const float* GYt, int64_t ldg,
 int alignn_egc_gate_dual_fwd(const float* P, const float* Pt, float* M, float* Mt, const int32_t* seg_ptr,
                              const int32_t* seg_node, const int32_t* src, int64_t n, int64_t m, int H, float* xpre,
                              float* xpre_t, float* s0, float* hh, float* s0t, float* hht, alignn_stream_t stream) {
-    if (!feat_ok(H) || !a16(P) || !a16(M)) return (int)hipErrorInvalidValue;
+    if (!feat_ok(H) || !aligned16(P) || !aligned16(M)) return (int)hipErrorInvalidValue;
     (void)m;
     if (n == 0) return 0;
     hipLaunchKernelGGL(egc_gate_dual_fwd_kernel, dim3(row_blocks(n)), dim3(kT), 0, (hipStream_t)stream, P, Pt, M, Mt,
@@ -805,7 +767,7 @@ int alignn_egc_dual_bwd_lg_dense(const float* GL, const float* GLt, const float*
                                  float* GPt, float* gb_partial, float* gm_amax2, float* gp_amax2, alignn_stream_t stream) {
     if (!feat_ok(H) || (GL == nullptr) != (GLt == nullptr) || n_groups < 0 || n_groups > INT32_MAX) return (int)hipErrorInvalidValue;
     if (n_groups == 0) return 0;
-    const bool big = m_rows * (int64_t)H * 4 >= ((int64_t)128 << 20);  // the T-row tensors cannot stay in the last-level cache
+    const bool big = exceeds_llc(m_rows, H);  // the T-row tensors cannot stay in the last-level cache
     const dim3 grid((unsigned)n_groups), block(kT);
     hipStream_t st = (hipStream_t)stream;
 #define ALIGNN_LAUNCH_DD(GLF, ST)                                                                                         \

@@ -8,12 +8,7 @@
 
 namespace {
 
-inline int grid_for(int64_t total, int threads = 256, int cap = 2048) {
-    int64_t g = (total + threads - 1) / threads;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
+inline int grid_for(int64_t total, int threads = 256, int cap = 2048) { return capped_blocks(total, threads, cap); }
 
 __global__ void rbf_fwd_kernel(const float* __restrict__ d, const float* __restrict__ centers, float gamma,
                                float* __restrict__ out, int64_t rows, int bins) {

@@ -16,10 +16,7 @@
 
 namespace {
 
-inline int grid_for(int64_t n, int block = 256, int cap = 65535) {
-    int64_t g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+inline int grid_for(int64_t n, int block = 256, int cap = 65535) { return capped_blocks(n, block, cap); }
 
 // largest power of two <= x (x > 0), 1 for x == 0: the normalisation of the tangent direction
 __device__ __forceinline__ float pow2_floor(float x) {

@@ -32,7 +32,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "mfma_f16x3.h"
 #include "../../include/alignn_hip.h"
 
 // Every wave runs the whole tile in lock-step with the others: per step a barrier, the step's DMA requests, its operand reads,
@@ -44,8 +44,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
 
@@ -115,23 +113,6 @@ struct Sched {
 template <int NE>
 inline constexpr Sched<NE> kSched = Sched<NE>::make();
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void block_barrier() {  // s_barrier without the vmcnt(0) drain of __syncthreads()
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// 64 lanes x 16 B -> 1 KiB of LDS at lds_wave_base (wave-uniform) + lane * 16, from sbase (wave-uniform) + lane_off
-__device__ __forceinline__ void dma16(const void* sbase, unsigned lane_off, unsigned char* lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                 :
-                 : "s"((unsigned)(size_t)lds_wave_base), "v"(lane_off), "s"(sbase)
-                 : "memory");
-}
 template <int B, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (B < E) {
@@ -140,14 +121,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-// (as gemm_x6.hip) power-of-two scale that puts a tensor with the given max|x| just below 2^15
-__device__ __forceinline__ float f16_scale(float amax) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 255u);
-    if (e == 0 || e == 255) return 1.0f;
-    int se = 268 - e;
-    se = se > 254 ? 254 : se;
-    return __uint_as_float((unsigned)se << 23);
-}
 // (as gemm_x6.hip's slice8_f16) 8 floats -> high and low fp16 slices of x s: h = RN(x s), l = RN(x s - h)
 __device__ __forceinline__ void slice8(const float4& a, const float4& b, float s, uint4& hp, uint4& lp) {
     const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -608,7 +581,6 @@ inline int dw_grid(int64_t M) {
     const int cap = dw_grid_cap();
     return (int)(tiles < cap ? tiles : cap);
 }
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -627,13 +599,13 @@ int alignn_gemm_dgrad_wgrad_f16x3(const float* G, int64_t ldg, const float* g_am
     if (!alignn_gemm_dgrad_wgrad_supported(M, H, H) || G == nullptr || Y == nullptr || Wt_split == nullptr || C == nullptr ||
         dW == nullptr || g_amax == nullptr || y_amax == nullptr || w_amax == nullptr)
         return (int)hipErrorInvalidValue;
-    if ((ldg & 3) || (ldy & 3) || (ldc & 3) || (lddw & 3) || !a16(G) || !a16(Y) || !a16(C) || !a16(dW) || !a16(Wt_split) ||
-        (addend && ((ldadd & 3) || !a16(addend))))
+    if ((ldg & 3) || (ldy & 3) || (ldc & 3) || (lddw & 3) || !aligned16(G) || !aligned16(Y) || !aligned16(C) || !aligned16(dW) || !aligned16(Wt_split) ||
+        (addend && ((ldadd & 3) || !aligned16(addend))))
         return (int)hipErrorInvalidValue;
     const bool bnred = Xn != nullptr;
-    if (bnred && (nstat == nullptr || red_partial == nullptr || (ldxn & 3) || !a16(Xn) || !a16(nstat) || !a16(red_partial)))
+    if (bnred && (nstat == nullptr || red_partial == nullptr || (ldxn & 3) || !aligned16(Xn) || !aligned16(nstat) || !aligned16(red_partial)))
         return (int)hipErrorInvalidValue;
-    if (workspace == nullptr || !a16(workspace) || workspace_bytes < alignn_gemm_dgrad_wgrad_workspace(M))
+    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < alignn_gemm_dgrad_wgrad_workspace(M))
         return (int)hipErrorInvalidValue;
     const int grid = dw_grid(M);
     DwArgs g{G, ldg, Y, ldy, (const unsigned char*)Wt_split, g_amax, y_amax, w_amax, addend, ldadd, C, ldc, Xn, ldxn, nstat,

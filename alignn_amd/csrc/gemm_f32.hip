@@ -12,12 +12,10 @@
 // (conflict-free ds_read_b32 across lanes).  Because a sum over r may be taken in any order as
 // long as both operands agree, MFMA step s of a 32-deep block uses r = 8*(s/4) + 4*(lane/32) + s%4,
 // which lets an RC operand fetch four steps' worth of values with one ds_read_b128.
-#include "common.h"
+#include "mfma_f16x3.h"  // (f32x16, the MFMA accumulator)
 #include "../../include/alignn_hip.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
 constexpr int RC_LD = BK + 4;  // padded row of an RC tile (floats)
@@ -144,6 +142,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mfma_kernel(GemmArgs g) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
 
+    // (the alignment test written out, not aligned16() of common.h: through the call hipcc emits two more instructions per kernel)
     const bool vec = ((g.No & 3) == 0) && ((g.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
                      (g.addend == nullptr || (((g.ldadd & 3) == 0) && ((reinterpret_cast<uintptr_t>(g.addend) & 15) == 0)));
     // vector epilogue: the bias is fetched HERE, ahead of the whole k-loop, so that no load sits between the
@@ -314,7 +313,6 @@ __global__ __launch_bounds__(1024) void slab_reduce_kernel(const float* __restri
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // same sum, four consecutive outputs per thread: 64 output lanes x 16 slab lanes per workgroup, every slab row read
 // as 1 KiB contiguous per wave, four loads in flight per lane; fp64 partials combined through LDS in lane order

@@ -33,14 +33,12 @@
 // with ds_read_b128.  Split-K over M into slabs; the slab partials are summed by gemm_f32.hip's slab_reduce4.
 #include <cstdlib>
 
-#include "common.h"
+#include "mfma_f16x3.h"
 #include "../../include/alignn_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WM = 2, WN = 2, NT = WM * WN * 64;  // 4 waves
@@ -67,17 +65,6 @@ struct Sch {
     static constexpr int NSTAGE = 2;  // DMA ring depth (3 measured no faster for f16x3: the kernel is HBM-bound)
     static constexpr int LDS = NSTAGE * STAGE > EPI_BYTES ? NSTAGE * STAGE : EPI_BYTES;  // two workgroups per CU
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// s_barrier without the vmcnt(0)/lgkmcnt(0) drain that __syncthreads() implies: DMA stages stay in flight across it
-__device__ __forceinline__ void block_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 struct X6Args {
     const float* A;
@@ -141,16 +128,6 @@ __device__ __forceinline__ void slice8(const float4& lo, const float4& hi4, bf16
     l = __builtin_bit_cast(bf16x8, lp);
 }
 
-// power-of-two scale that puts a tensor with the given max|x| just below 2^15 (fp16 max is 65504); 1 for an
-// all-zero / denormal / non-finite tensor (nothing to protect; inf and nan propagate through the fp16 slices)
-__device__ __forceinline__ float f16_scale(float amax) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 255u);  // amax < 2^(e-126)
-    if (e == 0 || e == 255) return 1.0f;
-    int se = 268 - e;                                           // 2^(141-e)
-    se = se > 254 ? 254 : se;
-    return __uint_as_float((unsigned)se << 23);
-}
-
 // slice 8 consecutive-k floats (scaled by s) into the two fp16x8 MFMA operands - in two halves, so that the kernel
 // can start the ah products while the VALU still works on the low slice
 __device__ __forceinline__ void slice8_f16_hi(const float4& lo, const float4& hi4, float s, float (&xs)[8], f16x8& h) {
@@ -180,20 +157,6 @@ __device__ __forceinline__ void slice8_f16(const float4& lo, const float4& hi4, 
     float xs[8];
     slice8_f16_hi(lo, hi4, s, xs, h);
     slice8_f16_lo(xs, h, l);
-}
-
-// 64 lanes x 16 B -> 1 KiB of LDS at lds_wave_base (wave-uniform) + lane*16, from sbase (wave-uniform, scalar
-// registers) + lane_off (+ OFF).  Written as the instruction itself: through __builtin_amdgcn_global_load_lds hipcc
-// builds a 64-bit vector address per piece and k-step (v_lshl_add_u64) and, in the pipelined loop, answered a ds_read
-// whose destination landed on such an address pair with s_waitcnt vmcnt(0) - a wait for the DMA issued just before.
-// The compiler neither sees these loads (every vmcnt wait on them is explicit, see wait_vmcnt) nor uses M0 for
-// anything else on gfx950.  (Default cache policy: nt on the read-once activation tile measured 10 % slower.)
-template <int OFF>
-__device__ __forceinline__ void dma16(const void* sbase, unsigned lane_off, unsigned char* lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3"
-                 :
-                 : "s"((unsigned)(size_t)lds_wave_base), "v"(lane_off), "s"(sbase), "n"(OFF)
-                 : "memory");
 }
 
 // EPI == 1: the output C is a gradient g_y = dL/dy of a tensor y = r + silu(BatchNorm(xn)) (the edge output of the previous
@@ -262,10 +225,10 @@ __device__ __forceinline__ void gemm_nt_x6_body(const X6Args& g) {
     auto issue = [&](int kt, unsigned char* stage) {
 #pragma unroll
         for (int i = 0; i < A_DMA; ++i)
-            dma16<0>(a_base + kt * BK, a_lane[i], stage + (wave * A_DMA + i) * 1024);
+            dma16(a_base + kt * BK, a_lane[i], stage + (wave * A_DMA + i) * 1024);
 #pragma unroll
         for (int i = 0; i < B_DMA; ++i)
-            dma16<0>(b_base + kt * kb_stride + i * 1024, b_lane, stage + A_BYTES + (wave * B_DMA + i) * 1024);
+            dma16(b_base + kt * kb_stride + i * 1024, b_lane, stage + A_BYTES + (wave * B_DMA + i) * 1024);
     };
 
     // reader addresses (bytes inside a stage)
@@ -611,10 +574,10 @@ __device__ __forceinline__ void gemm_nt_f16p_body(const X6Args& g) {
     auto issue_next = [&](int slot) {
         unsigned char* stage = smem + slot * STAGE_BYTES;
 #pragma unroll
-        for (int i = 0; i < A_DMA; ++i) dma16<0>(a_base + it_kt * BK, a_lane[i], stage + (wave * A_DMA + i) * 1024);
+        for (int i = 0; i < A_DMA; ++i) dma16(a_base + it_kt * BK, a_lane[i], stage + (wave * A_DMA + i) * 1024);
 #pragma unroll
         for (int i = 0; i < B_DMA; ++i)
-            dma16<0>(b_base + it_kt * kb_stride + i * 1024, b_lane, stage + A_BYTES + (wave * B_DMA + i) * 1024);
+            dma16(b_base + it_kt * kb_stride + i * 1024, b_lane, stage + A_BYTES + (wave * B_DMA + i) * 1024);
         ++issued;
         if (++it_kt == nk) {
             it_kt = 0;
@@ -1249,7 +1212,6 @@ __global__ __launch_bounds__(256) void split_f16x2_both_batched_kernel(const Wei
     }
 }
 
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int npad(int N) { return ((N + BN - 1) / BN) * BN; }
 
 }  // namespace
@@ -1407,8 +1369,8 @@ int launch_nt(const X6Args& g, hipStream_t st) {
 }
 inline bool nt_args_ok(const float* A, int64_t lda, const void* Wsplit, const float* bias, const float* addend,
                        int64_t ldadd, float* C, int64_t ldc) {
-    return !((lda & 3) || (ldc & 3) || !a16(A) || !a16(C) || !a16(Wsplit) || (bias && !a16(bias)) ||
-             (addend && ((ldadd & 3) || !a16(addend))));
+    return !((lda & 3) || (ldc & 3) || !aligned16(A) || !aligned16(C) || !aligned16(Wsplit) || (bias && !aligned16(bias)) ||
+             (addend && ((ldadd & 3) || !aligned16(addend))));
 }
 }  // namespace
 
@@ -1476,7 +1438,7 @@ int alignn_prepare_weights(const void* descs, int n_weights, float* amax_slots, 
 
 /* *amax = max(*amax, max|X|): alignn_absmax without the reset - for a slot the caller knows to hold 0 (or a bound to keep) */
 int alignn_absmax_raise(const float* X, int64_t ldx, int64_t rows, int F, float* amax, alignn_stream_t stream) {
-    if (F <= 0 || (F & 3) || (ldx & 3) || rows < 0 || amax == nullptr || !a16(X)) return (int)hipErrorInvalidValue;
+    if (F <= 0 || (F & 3) || (ldx & 3) || rows < 0 || amax == nullptr || !aligned16(X)) return (int)hipErrorInvalidValue;
     if (rows == 0) return 0;
     int64_t blocks = (rows * (F >> 2) + 256 * 8 - 1) / (256 * 8);
     if (blocks > 4096) blocks = 4096;
@@ -1487,7 +1449,7 @@ int alignn_absmax_raise(const float* X, int64_t ldx, int64_t rows, int F, float*
 }
 
 int alignn_absmax(const float* X, int64_t ldx, int64_t rows, int F, float* amax, alignn_stream_t stream) {
-    if (F <= 0 || (F & 3) || (ldx & 3) || rows < 0 || amax == nullptr || !a16(X)) return (int)hipErrorInvalidValue;
+    if (F <= 0 || (F & 3) || (ldx & 3) || rows < 0 || amax == nullptr || !aligned16(X)) return (int)hipErrorInvalidValue;
     // (zeroed by a kernel, not hipMemsetAsync: see alignn_prepare_weights)
     hipLaunchKernelGGL(zero_floats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, amax, 1);
     if (rows == 0) return 0;
@@ -1514,7 +1476,7 @@ int alignn_gemm_tn_x6_partials(const float* G, int64_t ldg, const float* g_amax,
                                const float* x_amax, int64_t M, int N, int K, void* workspace, size_t workspace_bytes,
                                alignn_stream_t stream) {
     if (!alignn_gemm_tn_x6_supported(M, N, K)) return (int)hipErrorInvalidValue;
-    if ((ldg & 3) || (ldx & 3) || !a16(G) || !a16(X) || !a16(workspace) ||
+    if ((ldg & 3) || (ldx & 3) || !aligned16(G) || !aligned16(X) || !aligned16(workspace) ||
         workspace_bytes < alignn_gemm_tn_x6_workspace(M, N, K))
         return (int)hipErrorInvalidValue;
     if ((g_amax == nullptr) != (x_amax == nullptr)) return (int)hipErrorInvalidValue;
@@ -1547,7 +1509,7 @@ int alignn_gemm_nt_x6(const float* A, int64_t lda, const void* Wsplit, const flo
     if (!alignn_gemm_nt_x6_supported(M, N, K)) return (int)hipErrorInvalidValue;
     if (!nt_args_ok(A, lda, Wsplit, bias, addend, ldadd, C, ldc)) return (int)hipErrorInvalidValue;
     X6Args g{A, lda, (const unsigned char*)Wsplit, nullptr, nullptr, bias, addend, ldadd, C, ldc, M, N, npad(N), K,
-             M * (int64_t)N * 4 >= ((int64_t)128 << 20), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+             exceeds_llc(M, N), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
     return launch_nt<false>(g, (hipStream_t)stream);
 }
 
@@ -1557,7 +1519,7 @@ int alignn_gemm_nt_f16x3(const float* A, int64_t lda, const float* a_amax, const
     if (!alignn_gemm_nt_x6_supported(M, N, K) || a_amax == nullptr || w_amax == nullptr) return (int)hipErrorInvalidValue;
     if (!nt_args_ok(A, lda, Wsplit, bias, addend, ldadd, C, ldc)) return (int)hipErrorInvalidValue;
     X6Args g{A, lda, (const unsigned char*)Wsplit, a_amax, w_amax, bias, addend, ldadd, C, ldc, M, N, npad(N), K,
-             M * (int64_t)N * 4 >= ((int64_t)128 << 20), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+             exceeds_llc(M, N), nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
     return launch_nt<true>(g, (hipStream_t)stream);
 }
 
@@ -1566,11 +1528,11 @@ int alignn_gemm_nt_f16x3_gather(const float* A, int64_t lda, const float* a_amax
                                 const int32_t* src, const int32_t* dst, float* stats_partial, alignn_stream_t stream) {
     if (!alignn_gemm_nt_x6_supported(M, N, K) || a_amax == nullptr || w_amax == nullptr) return (int)hipErrorInvalidValue;
     if (!nt_args_ok(A, lda, Wsplit, bias, nullptr, 0, C, ldc)) return (int)hipErrorInvalidValue;
-    if (P == nullptr || src == nullptr || dst == nullptr || (ldp & 3) || !a16(P) || (N & 3) || ldp < 2 * (int64_t)N ||
-        (stats_partial && !a16(stats_partial)))
+    if (P == nullptr || src == nullptr || dst == nullptr || (ldp & 3) || !aligned16(P) || (N & 3) || ldp < 2 * (int64_t)N ||
+        (stats_partial && !aligned16(stats_partial)))
         return (int)hipErrorInvalidValue;
     X6Args g{A, lda, (const unsigned char*)Wsplit, a_amax, w_amax, bias, nullptr, 0, C, ldc, M, N, npad(N), K,
-             M * (int64_t)N * 4 >= ((int64_t)128 << 20), nullptr, 0, nullptr, stats_partial, P, ldp, src, dst};
+             exceeds_llc(M, N), nullptr, 0, nullptr, stats_partial, P, ldp, src, dst};
     return launch_nt<true>(g, (hipStream_t)stream);
 }
 
@@ -1584,11 +1546,11 @@ int alignn_gemm_nt_f16x3_gather2(const float* A, int64_t lda, const float* a_ama
                                  float* stats_partial, alignn_stream_t stream) {
     if (!alignn_gemm_nt_x6_supported(M, N, K) || a_amax == nullptr || w_amax == nullptr) return (int)hipErrorInvalidValue;
     if (!nt_args_ok(A, lda, Wsplit, bias, nullptr, 0, C, ldc)) return (int)hipErrorInvalidValue;
-    if (P == nullptr || src == nullptr || Bd2 == nullptr || rank == nullptr || (ldp & 3) || (ldbd2 & 3) || !a16(P) || !a16(Bd2) ||
-        (N & 3) || (stats_partial && !a16(stats_partial)))
+    if (P == nullptr || src == nullptr || Bd2 == nullptr || rank == nullptr || (ldp & 3) || (ldbd2 & 3) || !aligned16(P) || !aligned16(Bd2) ||
+        (N & 3) || (stats_partial && !aligned16(stats_partial)))
         return (int)hipErrorInvalidValue;
     X6Args g{A, lda, (const unsigned char*)Wsplit, a_amax, w_amax, bias, nullptr, 0, C, ldc, M, N, npad(N), K,
-             M * (int64_t)N * 4 >= ((int64_t)128 << 20), nullptr, 0, nullptr, stats_partial, P, ldp, src, rank};
+             exceeds_llc(M, N), nullptr, 0, nullptr, stats_partial, P, ldp, src, rank};
     g.gp2 = Bd2;
     g.ldgp2 = ldbd2;
     return launch_nt<true>(g, (hipStream_t)stream);
@@ -1599,9 +1561,9 @@ int alignn_gemm_nt_f16x3_stats(const float* A, int64_t lda, const float* a_amax,
                                alignn_stream_t stream) {
     if (!alignn_gemm_nt_x6_supported(M, N, K) || a_amax == nullptr || w_amax == nullptr) return (int)hipErrorInvalidValue;
     if (!nt_args_ok(A, lda, Wsplit, bias, nullptr, 0, C, ldc)) return (int)hipErrorInvalidValue;
-    if (stats_partial == nullptr || !a16(stats_partial) || (N & 3)) return (int)hipErrorInvalidValue;
+    if (stats_partial == nullptr || !aligned16(stats_partial) || (N & 3)) return (int)hipErrorInvalidValue;
     X6Args g{A, lda, (const unsigned char*)Wsplit, a_amax, w_amax, bias, nullptr, 0, C, ldc, M, N, npad(N), K,
-             M * (int64_t)N * 4 >= ((int64_t)128 << 20), nullptr, 0, nullptr, stats_partial, nullptr, 0, nullptr, nullptr};
+             exceeds_llc(M, N), nullptr, 0, nullptr, stats_partial, nullptr, 0, nullptr, nullptr};
     return launch_nt<true>(g, (hipStream_t)stream);
 }
 
@@ -1613,11 +1575,11 @@ int alignn_gemm_nt_f16x3_bnred(const float* A, int64_t lda, const float* a_amax,
                                alignn_stream_t stream) {
     if (!alignn_gemm_nt_x6_supported(M, N, K) || a_amax == nullptr || w_amax == nullptr) return (int)hipErrorInvalidValue;
     if (!nt_args_ok(A, lda, Wsplit, bias, addend, ldadd, C, ldc)) return (int)hipErrorInvalidValue;
-    if (Xn == nullptr || nstat == nullptr || red_partial == nullptr || (ldxn & 3) || !a16(Xn) || !a16(nstat) ||
-        !a16(red_partial))
+    if (Xn == nullptr || nstat == nullptr || red_partial == nullptr || (ldxn & 3) || !aligned16(Xn) || !aligned16(nstat) ||
+        !aligned16(red_partial))
         return (int)hipErrorInvalidValue;
     X6Args g{A, lda, (const unsigned char*)Wsplit, a_amax, w_amax, bias, addend, ldadd, C, ldc, M, N, npad(N), K,
-             M * (int64_t)N * 4 >= ((int64_t)128 << 20), Xn, ldxn, nstat, red_partial, nullptr, 0, nullptr, nullptr};
+             exceeds_llc(M, N), Xn, ldxn, nstat, red_partial, nullptr, 0, nullptr, nullptr};
     return launch_nt<true>(g, (hipStream_t)stream);
 }
 

@@ -100,17 +100,6 @@ __device__ __forceinline__ void split_candidate(const Cell& c, int cand, int& j,
     i2 += c.s2;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_min_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // number of candidates of site i (global id) at the given level
 __device__ __forceinline__ int count_candidates(const Cell& c, const double* __restrict__ cart, int base, int n, int i,
                                                 int lane) {
@@ -124,7 +113,7 @@ __device__ __forceinline__ int count_candidates(const Cell& c, const double* __r
         const double d = image_distance(c, ci, cj, i0, i1, i2);
         cnt += (d <= c.cutoff && d > kBondTol) ? 1 : 0;
     }
-    return wave_sum_i(cnt);
+    return wave_sum(cnt);
 }
 
 // ---- pass 0: the image box of every crystal at every level, from the fractional extent of its sites (one wave per
@@ -148,8 +137,8 @@ __global__ __launch_bounds__(ALIGNN_WAVE) void knn_box_kernel(const double* __re
         mx0 = fmax(mx0, f[0]), mx1 = fmax(mx1, f[1]), mx2 = fmax(mx2, f[2]);
         bad |= !(fabs(f[0]) < 1e6 && fabs(f[1]) < 1e6 && fabs(f[2]) < 1e6);  // (NaN included)
     }
-    mn0 = wave_min_d(mn0), mn1 = wave_min_d(mn1), mn2 = wave_min_d(mn2);
-    mx0 = -wave_min_d(-mx0), mx1 = -wave_min_d(-mx1), mx2 = -wave_min_d(-mx2);
+    mn0 = wave_min(mn0), mn1 = wave_min(mn1), mn2 = wave_min(mn2);
+    mx0 = -wave_min(-mx0), mx1 = -wave_min(-mx1), mx2 = -wave_min(-mx2);
     bad = __ballot(bad) != 0ull || n <= 0;
     const int flo[3] = {bad ? 0 : (int)floor(mn0), bad ? 0 : (int)floor(mn1), bad ? 0 : (int)floor(mn2)};
     const int fhi[3] = {bad ? 0 : (int)ceil(mx0), bad ? 0 : (int)ceil(mx1), bad ? 0 : (int)ceil(mx2)};
@@ -256,9 +245,9 @@ __global__ __launch_bounds__(kThreads) void knn_kth_kernel(const double* __restr
             if (lt < k && k <= le) best = x;
             top = fmax(top, x);
         }
-        best = wave_min_d(best);
+        best = wave_min(best);
         // (fewer than k candidates cannot happen - the level guarantees k -; the search below would end at the largest one)
-        last = best < inf ? best : -wave_min_d(-top);
+        last = best < inf ? best : -wave_min(-top);
         if (lane == 0) kth[i] = last;
         return;
     }
@@ -274,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void knn_kth_kernel(const double* __restr
             const double d = image_distance(c, ci, cj, i0, i1, i2);
             if (d > last && d <= c.cutoff) mn = fmin(mn, d);
         }
-        mn = wave_min_d(mn);
+        mn = wave_min(mn);
         if (!(mn < inf)) break;  // (cannot happen: the level guarantees k candidates)
         int mult = 0;
         for (int cand = lane; cand < total; cand += ALIGNN_WAVE) {
@@ -283,7 +272,7 @@ __global__ __launch_bounds__(kThreads) void knn_kth_kernel(const double* __restr
             const double cj[3] = {cart[3 * (size_t)(base + j)], cart[3 * (size_t)(base + j) + 1], cart[3 * (size_t)(base + j) + 2]};
             mult += image_distance(c, ci, cj, i0, i1, i2) == mn ? 1 : 0;
         }
-        seen += wave_sum_i(mult);
+        seen += wave_sum(mult);
         last = mn;
     }
     if (lane == 0) kth[i] = last;

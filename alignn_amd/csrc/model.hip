@@ -122,7 +122,7 @@ struct Ctx {
     EventPool* pool = nullptr;
 
     float* alloc(size_t floats) {
-        const size_t bytes = (floats * sizeof(float) + 255) / 256 * 256;
+        const size_t bytes = al256(floats * sizeof(float));
         float* p = reinterpret_cast<float*>(base + off);
         if (launch && dbg_allocs_on()) g_dbg_allocs.emplace_back(off, bytes);
         off += bytes;
@@ -137,7 +137,7 @@ struct Ctx {
     void tmp_reset(hipStream_t st) { scur[which(st)] = 0; }
     float* tmp(hipStream_t st, size_t floats) {
         const int i = which(st);
-        const size_t bytes = (floats * sizeof(float) + 255) / 256 * 256;
+        const size_t bytes = al256(floats * sizeof(float));
         float* p = reinterpret_cast<float*>(base + sbase[i] + scur[i]);
         scur[i] += bytes;
         if (scur[i] > speak[i]) speak[i] = scur[i];
@@ -1730,8 +1730,8 @@ int alignn_ff_grad(const alignn_model_desc* d, const alignn_model_batch* b, cons
                    float* gflat_t, int64_t grad_floats, float* gsink, float* gsink_t, int64_t sink_floats, alignn_stream_t stream) {
     if (!ff_ok(d, b, f) || workspace == nullptr || gflat == nullptr || gflat_t == nullptr || grad_floats <= 0 || (grad_floats & 3))
         return (int)hipErrorInvalidValue;
-    if (gsink != nullptr && (gsink_t == nullptr || sink_floats <= 0 || (sink_floats & 3) || (reinterpret_cast<uintptr_t>(gsink) & 15) ||
-                             (reinterpret_cast<uintptr_t>(gsink_t) & 15)))
+    if (gsink != nullptr && (gsink_t == nullptr || sink_floats <= 0 || (sink_floats & 3) || !aligned16(gsink) ||
+                             !aligned16(gsink_t)))
         return (int)hipErrorInvalidValue;
     const Plan pl = make_ff_plan(d, b, f, stream);
     if (pl.unsupported) return (int)hipErrorNotSupported;

@@ -223,22 +223,7 @@ __global__ __launch_bounds__(256) void slab_fold_kernel(const float* __restrict_
 // (pivot, S, SS) with its row count, and the slabs are re-centred onto slab 0's pivot and summed in float64.  Fixed order
 // everywhere.  Layout: partial[slabs][3][F] (pivot, S = sum (x - pivot), SS = sum (x - pivot)^2) | counts[slabs] (float).
 // ---------------------------------------------------------------------------------------------
-// (n, p, S, SS) of set a  <-  union with set b, expressed about a's pivot; empty sets pass through
-__device__ __forceinline__ void pivot_merge(float& na, float4& pa, float4& Sa, float4& SSa, float nb, float4 pb, float4 Sb,
-                                            float4 SSb) {
-    if (nb == 0.0f) return;
-    if (na == 0.0f) {
-        na = nb, pa = pb, Sa = Sb, SSa = SSb;
-        return;
-    }
-    const float4 d = f4_sub(pb, pa);
-    // sum (x - pa)^2 over b = SSb + 2 d Sb + nb d^2 ;  sum (x - pa) over b = Sb + nb d
-    SSa = make_float4(SSa.x + SSb.x + d.x * (2.0f * Sb.x + nb * d.x), SSa.y + SSb.y + d.y * (2.0f * Sb.y + nb * d.y),
-                      SSa.z + SSb.z + d.z * (2.0f * Sb.z + nb * d.z), SSa.w + SSb.w + d.w * (2.0f * Sb.w + nb * d.w));
-    Sa = make_float4(Sa.x + Sb.x + nb * d.x, Sa.y + Sb.y + nb * d.y, Sa.z + Sb.z + nb * d.z, Sa.w + Sb.w + nb * d.w);
-    na += nb;
-}
-
+// (pivot_merge of common.h takes the union of two such sets)
 template <bool STREAM>
 __global__ __launch_bounds__(kThreads) void col_stats_welford_kernel(const float* __restrict__ X, int64_t ldx, int64_t rows,
                                                                      int F, int slabs, float* __restrict__ partial) {
@@ -526,13 +511,6 @@ __global__ __launch_bounds__(kThreads) void bn_silu_bwd_apply_sum_kernel(
 // two-pass variance in registers; row sums by __shfl_xor butterflies.  No global barrier is needed, so the
 // forward is one pass and the backward is one pass (+ fixed-order slabs for dgamma/dbeta).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float f4_hsum(float4 a) { return (a.x + a.y) + (a.z + a.w); }
-
 template <int NC, bool HAS_RES>
 __global__ __launch_bounds__(kThreads) void ln_silu_fwd_kernel(const float* __restrict__ X, int64_t ldx,
                                                                const float* __restrict__ R, int64_t ldr,
@@ -553,7 +531,7 @@ __global__ __launch_bounds__(kThreads) void ln_silu_fwd_kernel(const float* __re
         for (int c = 0; c < NC; ++c) {
             const int f = c * 256 + 4 * lane;
             x[c] = f < F ? f4_ld(X + r * ldx + f) : f4_zero();
-            s += f4_hsum(x[c]);
+            s += hsum4(x[c]);
         }
         const float mean = wave_sum(s) * inv_f;
         float v = 0.0f;
@@ -562,7 +540,7 @@ __global__ __launch_bounds__(kThreads) void ln_silu_fwd_kernel(const float* __re
             const int f = c * 256 + 4 * lane;
             if (f < F) {
                 float4 d = make_float4(x[c].x - mean, x[c].y - mean, x[c].z - mean, x[c].w - mean);
-                v += f4_hsum(f4_mul(d, d));
+                v += hsum4(f4_mul(d, d));
             }
         }
         const float rstd = 1.0f / sqrtf(wave_sum(v) * inv_f + eps);
@@ -632,8 +610,8 @@ __global__ __launch_bounds__(kThreads) void ln_silu_bwd_kernel(const float* __re
                 db[c] = f4_add(db[c], gz);
                 dg[c] = f4_fma(gz, xh[c], dg[c]);
                 gh[c] = f4_mul(gz, g);
-                s1 += f4_hsum(gh[c]);
-                s2 += f4_hsum(f4_mul(gh[c], xh[c]));
+                s1 += hsum4(gh[c]);
+                s2 += hsum4(f4_mul(gh[c], xh[c]));
             }
         }
         const float c1 = wave_sum(s1) * inv_f, c2 = wave_sum(s2) * inv_f;
@@ -683,14 +661,8 @@ __global__ __launch_bounds__(kThreads) void ln_silu_bwd_kernel(const float* __re
     }
 }
 
-inline int ln_blocks(int64_t rows) {
-    int64_t b = (rows + (kThreads / 64) - 1) / (kThreads / 64);
-    if (b < 1) b = 1;
-    if (b > kMaxSlabs) b = kMaxSlabs;
-    return (int)b;
-}
+inline int ln_blocks(int64_t rows) { return capped_blocks(rows, kThreads / 64, kMaxSlabs); }
 
-inline bool feat_ok(int F) { return F >= 4 && (F & 3) == 0 && F <= 1024; }
 // One float4 per thread: on MI355X a 2-read 1-write pass over 2 GB runs at 6.1 TB/s that way (6.7 with nontemporal
 // accesses) against 4.6-4.8 TB/s for a 2048-workgroup grid-stride loop (tools/stream_bench.hip) - workgroups are
 // dispatched in address order, so the accesses in flight form one moving window instead of drifting apart.
@@ -703,8 +675,6 @@ inline int stream_grid(int64_t total, bool big = true) {
     if (g < 1) g = 1;
     return (int)g;
 }
-// read-once / write-once hint only for tensors that cannot stay in the 256 MiB last-level cache anyway
-inline bool streaming(int64_t rows, int F) { return rows * (int64_t)F * 4 >= (int64_t)128 << 20; }
 
 }  // namespace
 
@@ -715,7 +685,7 @@ int alignn_col_stats_slabs(int64_t rows) { return slabs_for(rows); }
 int alignn_col_stats(const float* X, int64_t ldx, int64_t rows, int F, float* partial, alignn_stream_t stream) {
     if (!feat_ok(F) || rows < 0) return (int)hipErrorInvalidValue;
     int slabs = slabs_for(rows);
-    if (streaming(rows, F)) {
+    if (exceeds_llc(rows, F)) {
         StatsFn<true> fn{X, ldx};
         hipLaunchKernelGGL(col_reduce_kernel<StatsFn<true>>, dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, fn,
                            rows, F, slabs, partial);
@@ -731,7 +701,7 @@ int alignn_col_stats(const float* X, int64_t ldx, int64_t rows, int F, float* pa
 int alignn_col_stats_welford(const float* X, int64_t ldx, int64_t rows, int F, float* partial, alignn_stream_t stream) {
     if (!feat_ok(F) || rows < 0) return (int)hipErrorInvalidValue;
     int slabs = slabs_for(rows);
-    if (streaming(rows, F))
+    if (exceeds_llc(rows, F))
         hipLaunchKernelGGL(col_stats_welford_kernel<true>, dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, X, ldx, rows, F,
                            slabs, partial);
     else
@@ -759,7 +729,7 @@ int alignn_col_sum(const float* X, int64_t ldx, int64_t rows, int F, float* out,
     // wide matrices (the [n,4H] projection gradient) go in column panels of <= 1024
     for (int c = 0; c < F; c += 1024) {
         const int w = F - c < 1024 ? F - c : 1024;
-        if (streaming(rows, w)) {  // (a T-row gradient read once: bias gradient of the angle embedding)
+        if (exceeds_llc(rows, w)) {  // (a T-row gradient read once: bias gradient of the angle embedding)
             StatsFn<true> fn{X + c, ldx};
             hipLaunchKernelGGL(col_reduce_kernel<StatsFn<true>>, dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, fn,
                                rows, w, slabs, workspace);
@@ -795,7 +765,7 @@ int alignn_bn_silu_fwd(const float* X, int64_t ldx, const float* R, int64_t ldr,
 #define ALIGNN_BNFC(RES_, ST_)                                                                                          \
     hipLaunchKernelGGL((bn_silu_fwd_cols_kernel<RES_, ST_>), dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, X, ldx, R, \
                        ldr, stat, Y, ldy, rows, F, slabs, amax)
-        if (streaming(rows, F)) {
+        if (exceeds_llc(rows, F)) {
             if (R) ALIGNN_BNFC(true, true); else ALIGNN_BNFC(false, true);
         } else {
             if (R) ALIGNN_BNFC(true, false); else ALIGNN_BNFC(false, false);
@@ -804,11 +774,11 @@ int alignn_bn_silu_fwd(const float* X, int64_t ldx, const float* R, int64_t ldr,
         ALIGNN_CHECK_LAUNCH();
         return 0;
     }
-    int grid = stream_grid(rows * (F >> 2), streaming(rows, F));
+    int grid = stream_grid(rows * (F >> 2), exceeds_llc(rows, F));
 #define ALIGNN_BNF(RES_, ST_)                                                                                      \
     hipLaunchKernelGGL((bn_silu_fwd_kernel<RES_, ST_>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, X, ldx, R, \
                        ldr, stat, Y, ldy, rows, F, amax)
-    if (streaming(rows, F)) {
+    if (exceeds_llc(rows, F)) {
         if (R) ALIGNN_BNF(true, true); else ALIGNN_BNF(false, true);
     } else {
         if (R) ALIGNN_BNF(true, false); else ALIGNN_BNF(false, false);
@@ -822,7 +792,7 @@ int alignn_bn_silu_bwd_reduce(const float* GY, int64_t ldgy, const float* X, int
                               int64_t rows, int F, float* partial, alignn_stream_t stream) {
     if (!feat_ok(F)) return (int)hipErrorInvalidValue;
     int slabs = slabs_for(rows);
-    if (streaming(rows, F)) {  // T-sized: the re-read by the apply / conv-backward pass cannot come from cache anyway
+    if (exceeds_llc(rows, F)) {  // T-sized: the re-read by the apply / conv-backward pass cannot come from cache anyway
         BwdReduceFn<true> fn{GY, ldgy, X, ldx, stat, F};
         hipLaunchKernelGGL(col_reduce_kernel<BwdReduceFn<true>>, dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, fn,
                            rows, F, slabs, partial);
@@ -850,23 +820,17 @@ int alignn_ln_silu_fwd(const float* X, int64_t ldx, const float* R, int64_t ldr,
                        alignn_stream_t stream) {
     if (!feat_ok(F)) return (int)hipErrorInvalidValue;
     if (rows == 0) return 0;
-    const int nc = (F + 255) / 256;
     dim3 grid(ln_blocks(rows)), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
-#define ALIGNN_LN_FWD(NC_)                                                                                         \
-    if (R)                                                                                                         \
-        hipLaunchKernelGGL((ln_silu_fwd_kernel<NC_, true>), grid, block, 0, st, X, ldx, R, ldr, gamma, beta, eps, Y, \
-                           ldy, stats, rows, F, amax);                                                                   \
-    else                                                                                                           \
-        hipLaunchKernelGGL((ln_silu_fwd_kernel<NC_, false>), grid, block, 0, st, X, ldx, R, ldr, gamma, beta, eps, Y, \
-                           ldy, stats, rows, F, amax);
-    switch (nc) {
-        case 1: ALIGNN_LN_FWD(1) break;
-        case 2: ALIGNN_LN_FWD(2) break;
-        case 3: ALIGNN_LN_FWD(3) break;
-        default: ALIGNN_LN_FWD(4) break;
-    }
-#undef ALIGNN_LN_FWD
+    with_feature_chunks(F, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        if (R)
+            hipLaunchKernelGGL((ln_silu_fwd_kernel<NC, true>), grid, block, 0, st, X, ldx, R, ldr, gamma, beta, eps, Y, ldy, stats,
+                               rows, F, amax);
+        else
+            hipLaunchKernelGGL((ln_silu_fwd_kernel<NC, false>), grid, block, 0, st, X, ldx, R, ldr, gamma, beta, eps, Y, ldy, stats,
+                               rows, F, amax);
+    });
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
@@ -877,19 +841,12 @@ int alignn_ln_silu_bwd(const float* GY, int64_t ldgy, const float* X, int64_t ld
     if (!feat_ok(F) || rows < 0) return (int)hipErrorInvalidValue;
     // rows == 0 is launched on purpose (ln_blocks(0) == 1): alignn_ln_slabs(0) == 1 and alignn_ln_bwd_finalize reads that slab,
     // which this one workgroup writes as zeros
-    const int nc = (F + 255) / 256;
     dim3 grid(ln_blocks(rows)), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
-#define ALIGNN_LNB(NC_)                                                                                                        \
-    hipLaunchKernelGGL((ln_silu_bwd_kernel<NC_, false>), grid, block, 0, st, GY, ldgy, X, ldx, gamma, beta, stats, GX, ldgx, partial, \
-                       rows, F, amax, nullptr, nullptr, nullptr, nullptr)
-    switch (nc) {
-        case 1: ALIGNN_LNB(1); break;
-        case 2: ALIGNN_LNB(2); break;
-        case 3: ALIGNN_LNB(3); break;
-        default: ALIGNN_LNB(4); break;
-    }
-#undef ALIGNN_LNB
+    with_feature_chunks(F, [&](auto nc) {
+        hipLaunchKernelGGL((ln_silu_bwd_kernel<decltype(nc)::value, false>), grid, block, 0, st, GY, ldgy, X, ldx, gamma, beta, stats,
+                           GX, ldgx, partial, rows, F, amax, nullptr, nullptr, nullptr, nullptr);
+    });
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
@@ -898,19 +855,12 @@ int alignn_ln_silu_bwd_node(const float* GY, int64_t ldgy, const float* X, int64
                             const float* stats, float* GX, int64_t ldgx, float* partial, int64_t rows, int F, float* amax,
                             const float* S0, const float* HH, float* GS1, float* GS0, alignn_stream_t stream) {
     if (!feat_ok(F) || rows < 0 || !S0 || !HH || !GS1 || !GS0) return (int)hipErrorInvalidValue;
-    const int nc = (F + 255) / 256;  // (rows == 0: one workgroup writes the zero slab, as alignn_ln_silu_bwd)
-    dim3 grid(ln_blocks(rows)), block(kThreads);
+    dim3 grid(ln_blocks(rows)), block(kThreads);  // (rows == 0: one workgroup writes the zero slab, as alignn_ln_silu_bwd)
     hipStream_t st = (hipStream_t)stream;
-#define ALIGNN_LNB(NC_)                                                                                                       \
-    hipLaunchKernelGGL((ln_silu_bwd_kernel<NC_, true>), grid, block, 0, st, GY, ldgy, X, ldx, gamma, beta, stats, GX, ldgx, partial, \
-                       rows, F, amax, S0, HH, GS1, GS0)
-    switch (nc) {
-        case 1: ALIGNN_LNB(1); break;
-        case 2: ALIGNN_LNB(2); break;
-        case 3: ALIGNN_LNB(3); break;
-        default: ALIGNN_LNB(4); break;
-    }
-#undef ALIGNN_LNB
+    with_feature_chunks(F, [&](auto nc) {
+        hipLaunchKernelGGL((ln_silu_bwd_kernel<decltype(nc)::value, true>), grid, block, 0, st, GY, ldgy, X, ldx, gamma, beta, stats,
+                           GX, ldgx, partial, rows, F, amax, S0, HH, GS1, GS0);
+    });
     ALIGNN_CHECK_LAUNCH();
     return 0;
 }
@@ -938,8 +888,8 @@ int alignn_bn_silu_bwd_apply(const float* GY, int64_t ldgy, const float* X, int6
                              int64_t rows, int F, float* amax, alignn_stream_t stream) {
     if (!feat_ok(F)) return (int)hipErrorInvalidValue;
     if (rows == 0) return 0;
-    int grid = stream_grid(rows * (F >> 2), streaming(rows, F));
-    if (streaming(rows, F))
+    int grid = stream_grid(rows * (F >> 2), exceeds_llc(rows, F));
+    if (exceeds_llc(rows, F))
         hipLaunchKernelGGL((bn_silu_bwd_apply_kernel<true, false>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, GY, ldgy,
                            X, ldx, stat, gamma, red, eval_mode, GX, ldgx, rows, F, amax, nullptr, nullptr, nullptr, nullptr);
     else
@@ -955,8 +905,8 @@ int alignn_bn_silu_bwd_apply_node(const float* GY, int64_t ldgy, const float* X,
                                   alignn_stream_t stream) {
     if (!feat_ok(F) || S0 == nullptr || HH == nullptr || GS1 == nullptr || GS0 == nullptr) return (int)hipErrorInvalidValue;
     if (rows == 0) return 0;
-    int grid = stream_grid(rows * (F >> 2), streaming(rows, F));
-    if (streaming(rows, F))
+    int grid = stream_grid(rows * (F >> 2), exceeds_llc(rows, F));
+    if (exceeds_llc(rows, F))
         hipLaunchKernelGGL((bn_silu_bwd_apply_kernel<true, true>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, GY, ldgy,
                            X, ldx, stat, gamma, red, eval_mode, GX, ldgx, rows, F, amax, S0, HH, GS1, GS0);
     else
@@ -974,7 +924,7 @@ int alignn_bn_silu_bwd_apply_sum(const float* GY, int64_t ldgy, const float* X, 
     if (!feat_ok(F) || F > 4 * kThreads || partial == nullptr || (!eval_mode && red == nullptr)) return (int)hipErrorInvalidValue;
     if (rows == 0) return 0;
     const int slabs = slabs_for(rows);
-    if (streaming(rows, F))
+    if (exceeds_llc(rows, F))
         hipLaunchKernelGGL(bn_silu_bwd_apply_sum_kernel<true>, dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, GY, ldgy, X,
                            ldx, stat, red, eval_mode, GX, ldgx, rows, F, slabs, amax, partial);
     else

@@ -72,12 +72,6 @@ __device__ __forceinline__ float candidate(const Box& c, const float* __restrict
     return __fsqrt_rn((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ int count_site(const Box& c, const float* __restrict__ cart, int base, int n, int i, float atol,
                                           int lane) {
     const float ci[3] = {cart[3 * (size_t)i], cart[3 * (size_t)i + 1], cart[3 * (size_t)i + 2]};
@@ -89,7 +83,7 @@ __device__ __forceinline__ int count_site(const Box& c, const float* __restrict_
         const float d = candidate(c, cart, base, n, ci, (int)cand, j, im, r);
         cnt += (d <= c.cutoff && !(d <= atol)) ? 1 : 0;
     }
-    return wave_sum_i(cnt);
+    return wave_sum(cnt);
 }
 
 // ---- pass 1: the crystal's level = the first cutoff of the ladder at which its LAST site has a neighbour

@@ -23,7 +23,6 @@ namespace {
 
 constexpr int kT = 256;
 inline unsigned blocks(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 __global__ void iota_kernel(int32_t* __restrict__ p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;

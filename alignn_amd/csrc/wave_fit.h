@@ -1,26 +1,10 @@
-// What the per-wavefront least-squares fits share (eos.hip, elastic.hip): the sums over a wavefront's lanes by the xor butterfly,
-// after which every lane holds the same bits, and the Cholesky solve of the small normal equations, held in registers by every
+// What the per-wavefront least-squares fits share (eos.hip, elastic.hip) beside the wave sums of common.h (xor butterfly: every
+// lane ends with the same bits): the Cholesky solve of the small normal equations, held in registers by every
 // lane.  float64 without contraction, every sum in a fixed order; tests/eos_ref.py restates both operation for operation.
 #pragma once
 #include "common.h"
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, ALIGNN_WAVE);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ALIGNN_WAVE));
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = ALIGNN_WAVE / 2; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, ALIGNN_WAVE));
-    return v;
-}
 
 // A = L L^T for a symmetric positive definite A: the lower triangle row by row, every inner sum in ascending index order; false
 // where a pivot is not > 0 or not finite

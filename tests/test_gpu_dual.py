@@ -19,7 +19,7 @@ def _f(t):
     return t.float().to(DEV).contiguous()
 
 
-@pytest.mark.parametrize("rows,Fw,res", [(37, 64, True), (300, 256, True), (50, 256, False), (9, 512, True)])
+@pytest.mark.parametrize("rows,Fw,res", [(37, 64, True), (300, 256, True), (50, 256, False), (9, 512, True), (9, 768, True), (9, 1024, False)])
 def test_layernorm_silu_dual_forward_and_reverse(rows, Fw, res):
     g = torch.Generator().manual_seed(rows + Fw)
     x = torch.randn(rows, Fw, generator=g, dtype=torch.float64) * 1.5 + 0.3

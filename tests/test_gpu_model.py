@@ -330,7 +330,7 @@ def test_atomwise_vs_oracle_wide_and_guards():
     assert res["grad"].shape == (raw.num_nodes, 3) and torch.isfinite(res["grad"]).all()
 
 
-@pytest.mark.parametrize("rows,F", [(5, 16), (1000, 256), (333, 64), (77, 512), (9, 1024)])
+@pytest.mark.parametrize("rows,F", [(5, 16), (1000, 256), (333, 64), (77, 512), (9, 1024), (7, 768)])
 def test_layernorm_silu_kernels(rows, F):
     from alignn_amd import ops
 
