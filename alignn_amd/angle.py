@@ -10,13 +10,7 @@ import torch
 from . import _lib
 from .cmodel import MlpParams
 
-_p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
-
-class AngleArgs(C.Structure):
-    _fields_ = [("h", _p), ("rows", _i64), ("centers", _p), ("gamma", _f32), ("bins", _i32), ("l1", MlpParams), ("l2", MlpParams),
-                ("eps", _f32), ("momentum", _f32), ("stat1", _p), ("stat2", _p), ("scal", _p), ("z", _p), ("z_amax", _p),
-                ("gz", _p), ("workspace", _p), ("workspace_bytes", C.c_size_t)]
+AngleArgs = _lib.STRUCTS["alignn_angle_args"]
 
 
 def _mlp(lin, bn, grads):

@@ -24,6 +24,7 @@ import weakref
 import torch
 
 from . import _lib, ops
+from ._lib import ptr
 
 ENABLED = os.environ.get("ALIGNN_AMD_CMODEL", "1") != "0"
 # a convolution's edge input gradient written over its own dead gate pre-activation (csrc/model.hip edge_grad_buffer): 2.8 GB of
@@ -35,53 +36,10 @@ STATS = {"fwd": 0, "bwd": 0, "plans": 0, "rebuilds": 0, "arena_bytes": 0}
 _NOT_SUPPORTED = 801  # hipErrorNotSupported
 TIMING = None  # tools/host_profile_c.py: {"cfwd": s, "cbwd": s, "bwd_py": s} accumulated host seconds
 
-_p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
-
-class MlpParams(C.Structure):
-    _fields_ = [(n, _p) for n in ("W", "b", "gamma", "beta", "rm", "rv", "gW", "gb", "red", "img", "img_t", "w_amax")] + [
-        ("in_", _i32), ("out", _i32)]
-
-
-class ConvParams(C.Structure):
-    _fields_ = [(n, _p) for n in (
-        "wcat", "bcat", "w_eg", "b_eg", "n_gamma", "n_beta", "e_gamma", "e_beta", "n_rm", "n_rv", "e_rm", "e_rv",
-        "g_wcat", "g_bcat", "g_weg", "g_beg", "n_red", "e_red", "wcat_img", "wcat_img_t", "weg_img", "weg_img_t",
-        "wcat_amax", "weg_amax")]
-
-
-class GraphCSR(C.Structure):
-    _fields_ = [(n, _p) for n in ("seg_ptr", "seg_node", "src", "dst", "out_ptr", "out_slot", "grp_seg_ptr", "grp_src_ptr",
-                                  "seg_rank")] + [("n", _i64), ("m", _i64), ("n_groups", _i64), ("dense_max_src", _i32),
-                                                  ("pad_", _i32)]
-
-
-class ModelBatch(C.Structure):
-    _fields_ = [("g", GraphCSR), ("lg", GraphCSR), ("graph_ptr", _p), ("atom_features", _p), ("r", _p), ("h", _p),
-                ("B", _i32), ("pad_", _i32)]
-
-
-class ModelDesc(C.Structure):
-    _fields_ = [(n, _i32) for n in ("alignn_layers", "gcn_layers", "H", "out_features", "atom_in", "edge_bins", "angle_bins",
-                                    "embed")] + [
-        ("edge_gamma", _f32), ("angle_gamma", _f32), ("eps", _f32), ("momentum", _f32),
-        ("edge_centers", _p), ("angle_centers", _p),
-        ("atom", MlpParams), ("edge1", MlpParams), ("edge2", MlpParams), ("angle1", MlpParams), ("angle2", MlpParams),
-        ("convs", C.POINTER(ConvParams)),
-        ("fc_W", _p), ("fc_b", _p), ("g_fc_W", _p), ("g_fc_b", _p),
-        ("weight_descs", _p), ("weight_amax", _p), ("bump_ptrs", _p),
-        ("n_weights", _i32), ("n_bump", _i32), ("x6_min_tiles", _i32), ("bd_segment_table", _i32),
-        ("angle_fused", _i32), ("norm", _i32), ("reuse_tape", _i32), ("dw_fused", _i32),
-        ("amax_min_rows", _i64), ("lane_min_rows", _i64), ("side_min_rows", _i64),
-        ("lane_T", _p), ("side", _p), ("aux", _p)]
-
-
-class FFDesc(C.Structure):
-    """alignn_ff_desc: the force / stress head's switches (ALIGNNAtomWiseConfig) + the cell volumes of the batch"""
-    _fields_ = [(n, _i32) for n in ("lg_on_fly", "add_reverse_forces", "force_mult_natoms", "energy_mult_natoms", "has_stress",
-                                    "use_penalty", "dense_lg_reverse", "pad_")] + [
-        (n, _f32) for n in ("grad_multiplier", "stress_multiplier", "penalty_factor", "penalty_threshold")] + [("volume", _p)]
-
+# the parameter, graph and model blocks of include/alignn_hip.h (FFDesc: the force / stress head's switches,
+# ALIGNNAtomWiseConfig, + the cell volumes of the batch)
+MlpParams, ConvParams, GraphCSR, ModelBatch, ModelDesc, FFDesc = (_lib.STRUCTS[f"alignn_{n}"] for n in (
+    "mlp_params", "conv_params", "graph_csr", "model_batch", "model_desc", "ff_desc"))
 
 _SIGS_DONE = False
 
@@ -106,10 +64,10 @@ def _lib_model():
     if not _SIGS_DONE:
         for which, st in enumerate((MlpParams, ConvParams, GraphCSR, ModelBatch, ModelDesc)):
             if lib.alignn_model_sizeof(which) != C.sizeof(st):
-                raise RuntimeError(f"alignn_model struct {which}: library says {lib.alignn_model_sizeof(which)} bytes, "
-                                   f"the binding lays out {C.sizeof(st)}")
+                raise RuntimeError(f"{st.__name__}: library says {lib.alignn_model_sizeof(which)} bytes, the header gives "
+                                   f"{C.sizeof(st)} (a library built from another alignn_hip.h)")
         if lib.alignn_ff_desc_sizeof() != C.sizeof(FFDesc):
-            raise RuntimeError("alignn_ff_desc: the binding's layout differs from the library's")
+            raise RuntimeError("alignn_ff_desc: the library was built from another alignn_hip.h")
         _SIGS_DONE = True
     return lib
 
@@ -133,10 +91,6 @@ class disabled:
         global ENABLED
         ENABLED = self.prev
         return False
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class Binding:
@@ -163,7 +117,7 @@ class Binding:
         assert all(isinstance(m, EdgeGatedGraphConv) for m in self.convs) and all(isinstance(m, MLPLayer) for m in self.mlps)
         self.desc = ModelDesc()
         self.conv_arr = (ConvParams * len(self.convs))()
-        self.desc.convs = C.cast(self.conv_arr, C.POINTER(ConvParams))
+        self.desc.convs = C.addressof(self.conv_arr)  # (a HOST array: kept alive by self.conv_arr)
         with torch.cuda.device(dev):
             _lib.check(_lib_model().alignn_model_init(), "model_init")
             self.streams = [torch.cuda.Stream(device=dev) for _ in range(3)]  # lane T, side, aux
@@ -373,9 +327,9 @@ class Binding:
     def batch_struct(self, b):
         mb = ModelBatch()
         for dst, g in ((mb.g, b.g), (mb.lg, b.lg)):
-            dst.seg_ptr, dst.seg_node, dst.src, dst.dst = _ptr(g.seg_ptr), _ptr(g.seg_node), _ptr(g.src), _ptr(g.dst)
-            dst.out_ptr, dst.out_slot = _ptr(g.out_ptr), _ptr(g.out_slot)
-            dst.grp_seg_ptr, dst.grp_src_ptr, dst.seg_rank = _ptr(g.grp_seg_ptr), _ptr(g.grp_src_ptr), _ptr(g.seg_rank)
+            dst.seg_ptr, dst.seg_node, dst.src, dst.dst = ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), ptr(g.dst)
+            dst.out_ptr, dst.out_slot = ptr(g.out_ptr), ptr(g.out_slot)
+            dst.grp_seg_ptr, dst.grp_src_ptr, dst.seg_rank = ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), ptr(g.seg_rank)
             dst.n, dst.m = g.n_nodes, g.n_edges
             dst.n_groups = (g.grp_seg_ptr.numel() - 1) if g.grp_seg_ptr is not None else 0
             dst.dense_max_src = int(g.dense_max_src)
@@ -761,7 +715,7 @@ def _ff_prepare(model, b, need_grad):
     h = None if model.config.lg_on_fly else b.h.contiguous()
     if af.shape != (b.g.n_nodes, bind.desc.atom_in) or r.shape != (b.g.n_edges, 3) or (h is not None and h.numel() != b.lg.n_edges):
         raise ValueError("feature rows do not match the graphs")
-    mb.atom_features, mb.r, mb.h = af.data_ptr(), r.data_ptr(), _ptr(h)
+    mb.atom_features, mb.r, mb.h = af.data_ptr(), r.data_ptr(), ptr(h)
     ffd, vol = _ff_desc(model, b)
     key = ("ff", mb.g.n, mb.g.m, mb.lg.m, mb.B, mb.lg.dense_max_src, bool(mb.lg.grp_seg_ptr), bool(mb.lg.seg_rank),
            bool(bind.desc.lane_T), bool(bind.desc.side), bool(bind.desc.aux), bind.desc.side_min_rows, bind.desc.lane_min_rows,
@@ -803,7 +757,7 @@ class _FFFn(torch.autograd.Function):
         lib = _lib_model()
         out, forces, stress = _ff_outputs(bind, mb, ffd)
         _lib.check(lib.alignn_ff_eval(bind.desc_addr, C.addressof(mb), C.addressof(ffd), arena.data_ptr(), arena_bytes,
-                                      out.data_ptr(), forces.data_ptr(), _ptr(stress), _lib.stream()), "ff_eval")
+                                      out.data_ptr(), forces.data_ptr(), ptr(stress), _lib.stream()), "ff_eval")
         STATS["ff_eval"] = STATS.get("ff_eval", 0) + 1
         owns, gen = lease
         ctx.bind, ctx.mb, ctx.ffd, ctx.keep, ctx.arena, ctx.arena_bytes, ctx.lease = bind, mb, ffd, keep, arena, arena_bytes, _Lease(bind, owns)
@@ -855,8 +809,8 @@ class _FFFn(torch.autograd.Function):
         bind.set_mode()
         try:
             _lib.check(lib.alignn_ff_grad(bind.desc_addr, C.addressof(ctx.mb), C.addressof(ctx.ffd), ctx.arena.data_ptr(),
-                                          ctx.arena_bytes, _ptr(g_out), _ptr(g_forces), _ptr(g_stress), gflat[0].data_ptr(),
-                                          gflat[1].data_ptr(), bind.grad_floats, _ptr(sink_buf), _ptr(sink_t),
+                                          ctx.arena_bytes, ptr(g_out), ptr(g_forces), ptr(g_stress), gflat[0].data_ptr(),
+                                          gflat[1].data_ptr(), bind.grad_floats, ptr(sink_buf), ptr(sink_t),
                                           sink_buf.numel() if sink_buf is not None else 0, _lib.stream()), "ff_grad")
         finally:
             ctx.lease.release()
@@ -902,6 +856,6 @@ def ff_eval(model, b):
         bind, mb, ffd, _keep, arena, nbytes, _lease = prep
         out, forces, stress = _ff_outputs(bind, mb, ffd)
         _lib.check(_lib_model().alignn_ff_eval(bind.desc_addr, C.addressof(mb), C.addressof(ffd), arena.data_ptr(), nbytes,
-                                               out.data_ptr(), forces.data_ptr(), _ptr(stress), _lib.stream()), "ff_eval")
+                                               out.data_ptr(), forces.data_ptr(), ptr(stress), _lib.stream()), "ff_eval")
         STATS["ff_eval"] = STATS.get("ff_eval", 0) + 1
         return out, forces, stress

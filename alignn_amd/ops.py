@@ -8,6 +8,7 @@ bookkeeping calls aside), and nothing falls back if the library is missing.
 
 from __future__ import annotations
 
+import ctypes
 import weakref
 
 import torch
@@ -1545,10 +1546,6 @@ def _dgrad_kind(g, w, g_amax):
     return 3
 
 
-def _P(t):
-    return 0 if t is None else t.data_ptr()
-
-
 class _Shape:
     """What the kernel-choice helpers need of a not-yet-allocated contiguous [rows, cols] fp32 matrix."""
 
@@ -1776,16 +1773,21 @@ class EdgeGatedConvFn(torch.autograd.Function):
         yo_amax = new_amax(x) if (need_y and _track(m)) else None
         nbytes = lib.alignn_egc_conv_fwd_scratch(n, m, H, Kin, edge_kind)
         scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        args = _lib.EGC_FWD_ARGS.pack(
-            _P(graph.seg_ptr), _P(graph.seg_node), _P(graph.src), _P(graph.dst), _P(graph.seg_rank), n, m,
-            H, Kin, node_kind, edge_kind, int(residual), 0, BN_EPS, BN_MOMENTUM,
-            _P(x), _P(y), _P(x_amax), _P(y_amax),
-            _P(wcat), _P(bcat), _P(wcat_img.amax if wcat_img is not None else None), _P(wcat_img.buf if wcat_img is not None else None),
-            _P(w_eg), _P(b_eg), _P(weg_img.amax if weg_img is not None else None), _P(weg_img.buf if weg_img is not None else None),
-            _P(n_gamma), _P(n_beta), _P(e_gamma), _P(e_beta), _P(n_rm), _P(n_rv), _P(e_rm), _P(e_rv),
-            _P(P), _P(M), _P(xpre), _P(s0), _P(hh), _P(n_stat), _P(e_stat), _P(x_out), _P(y_out), _P(xo_amax), _P(yo_amax),
-            _P(scratch), nbytes)
-        check(lib.alignn_egc_conv_fwd(args, stream()), "egc_conv_fwd")
+        args = _lib.EgcFwdArgs(
+            seg_ptr=ptr(graph.seg_ptr), seg_node=ptr(graph.seg_node), src=ptr(graph.src), dst=ptr(graph.dst),
+            seg_rank=ptr(graph.seg_rank), n=n, m=m,
+            H=H, Kin=Kin, node_kind=node_kind, edge_kind=edge_kind, residual=int(residual), eps=BN_EPS, momentum=BN_MOMENTUM,
+            x=ptr(x), y=ptr(y), x_amax=ptr(x_amax), y_amax=ptr(y_amax),
+            wcat=ptr(wcat), bcat=ptr(bcat), wcat_amax=ptr(wcat_img.amax if wcat_img is not None else None),
+            wcat_img=ptr(wcat_img.buf if wcat_img is not None else None),
+            w_eg=ptr(w_eg), b_eg=ptr(b_eg), weg_amax=ptr(weg_img.amax if weg_img is not None else None),
+            weg_img=ptr(weg_img.buf if weg_img is not None else None),
+            n_gamma=ptr(n_gamma), n_beta=ptr(n_beta), e_gamma=ptr(e_gamma), e_beta=ptr(e_beta),
+            n_rm=ptr(n_rm), n_rv=ptr(n_rv), e_rm=ptr(e_rm), e_rv=ptr(e_rv),
+            P=ptr(P), M=ptr(M), xpre=ptr(xpre), s0=ptr(s0), hh=ptr(hh), n_stat=ptr(n_stat), e_stat=ptr(e_stat),
+            x_out=ptr(x_out), y_out=ptr(y_out), x_out_amax=ptr(xo_amax), y_out_amax=ptr(yo_amax),
+            scratch=ptr(scratch), scratch_bytes=nbytes)
+        check(lib.alignn_egc_conv_fwd(ctypes.byref(args), stream()), "egc_conv_fwd")
         COMPOSITE_STATS["fwd"] += 1
         if xo_amax is not None:
             set_amax(x_out, xo_amax)
@@ -1859,23 +1861,27 @@ class EdgeGatedConvFn(torch.autograd.Function):
         g_y = _empty(m, Kin, like=x)
         nbytes = lib.alignn_egc_conv_bwd_scratch(n, m, H, Kin, dx_kind, dy_kind)
         scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        args = _lib.EGC_BWD_ARGS.pack(
-            _P(graph.seg_ptr), _P(graph.seg_node), _P(graph.src), _P(graph.dst), _P(graph.out_ptr), _P(graph.out_slot),
-            _P(graph.grp_seg_ptr), _P(graph.grp_src_ptr), n, m, gslabs if lg_blocks else 0,
-            H, Kin, gate_mode, int(graph.dense_max_src) if dense else 0, dx_kind, dy_kind, int(ctx.residual), 0,
-            _P(gx_out), _P(gy_out),
-            _P(P), _P(M), _P(xpre), _P(s0), _P(hh), _P(n_stat), _P(e_stat), _P(n_gamma), _P(e_gamma),
-            _P(e_red_in),
-            _P(wcat), _P(wcat_t), _P(wcat_t_img.amax if wcat_t_img is not None else None),
-            _P(wcat_t_img.buf if wcat_t_img is not None else None),
-            _P(w_eg), _P(weg_t), _P(weg_t_img.amax if weg_t_img is not None else None),
-            _P(weg_t_img.buf if weg_t_img is not None else None),
-            _P(y_src[0] if dy_kind == 1 else None), _P(y_src[1] if dy_kind == 1 else None),
-            y_src[0].stride(0) if dy_kind == 1 else 0,
-            _P(GP), _P(GM), _P(gs[0]), _P(gs[1]), _P(n_red), _P(e_red if e_red_in is None else None), _P(gb_part), _P(g_x),
-            _P(g_y), _P(src_red), _P(gp_amax), _P(gm_amax), _aux_stream(x.device) or 0,
-            _P(scratch), nbytes)
-        check(lib.alignn_egc_conv_bwd(args, stream()), "egc_conv_bwd")
+        args = _lib.EgcBwdArgs(
+            seg_ptr=ptr(graph.seg_ptr), seg_node=ptr(graph.seg_node), src=ptr(graph.src), dst=ptr(graph.dst),
+            out_ptr=ptr(graph.out_ptr), out_slot=ptr(graph.out_slot),
+            grp_seg_ptr=ptr(graph.grp_seg_ptr), grp_src_ptr=ptr(graph.grp_src_ptr), n=n, m=m, n_groups=gslabs if lg_blocks else 0,
+            H=H, Kin=Kin, gate_mode=gate_mode, dense_max_src=int(graph.dense_max_src) if dense else 0, dx_kind=dx_kind,
+            dy_kind=dy_kind, residual=int(ctx.residual),
+            gx_out=ptr(gx_out), gy_out=ptr(gy_out),
+            P=ptr(P), M=ptr(M), xpre=ptr(xpre), s0=ptr(s0), hh=ptr(hh), n_stat=ptr(n_stat), e_stat=ptr(e_stat),
+            n_gamma=ptr(n_gamma), e_gamma=ptr(e_gamma),
+            e_red_in=ptr(e_red_in),
+            wcat=ptr(wcat), wcat_t=ptr(wcat_t), wcat_amax=ptr(wcat_t_img.amax if wcat_t_img is not None else None),
+            wcat_t_img=ptr(wcat_t_img.buf if wcat_t_img is not None else None),
+            w_eg=ptr(w_eg), weg_t=ptr(weg_t), weg_amax=ptr(weg_t_img.amax if weg_t_img is not None else None),
+            weg_t_img=ptr(weg_t_img.buf if weg_t_img is not None else None),
+            src_xn=ptr(y_src[0] if dy_kind == 1 else None), src_nstat=ptr(y_src[1] if dy_kind == 1 else None),
+            src_ldxn=y_src[0].stride(0) if dy_kind == 1 else 0,
+            GP=ptr(GP), GM=ptr(GM), gs1=ptr(gs[0]), gs0=ptr(gs[1]), n_red=ptr(n_red),
+            e_red=ptr(e_red if e_red_in is None else None), gb_part=ptr(gb_part), g_x=ptr(g_x),
+            g_y=ptr(g_y), src_red=ptr(src_red), gp_amax=ptr(gp_amax), gm_amax=ptr(gm_amax), aux_stream=_aux_stream(x.device),
+            scratch=ptr(scratch), scratch_bytes=nbytes)
+        check(lib.alignn_egc_conv_bwd(ctypes.byref(args), stream()), "egc_conv_bwd")
         COMPOSITE_STATS["bwd"] += 1
         if dy_kind == 1:
             BNRED_STATS["fused"] += 1
@@ -1892,10 +1898,11 @@ class EdgeGatedConvFn(torch.autograd.Function):
             g_wcat, g_bcat = _empty(4 * H, Kin, like=x), _empty(4 * H, like=x)
             wb = lib.alignn_egc_conv_wgrad_scratch(n, m, H, Kin)
             ws = torch.empty(wb // 4, dtype=torch.float32, device=x.device)
-            wargs = _lib.EGC_WGRAD_ARGS.pack(n, m, H, Kin, gslabs, 0, _P(GM), _P(GP), _P(x), _P(y), _P(gb_part), _P(tn_gm[0]),
-                                             _P(tn_gp[0]), _P(tn_gp[1]), _P(tn_gm[1]), _P(g_weg), _P(g_beg), _P(g_wcat), _P(g_bcat),
-                                             _P(ws), wb)
-            check(lib.alignn_egc_conv_wgrad(wargs, stream()), "egc_conv_wgrad")
+            wargs = _lib.EgcWgradArgs(
+                n=n, m=m, H=H, Kin=Kin, gb_slabs=gslabs, GM=ptr(GM), GP=ptr(GP), x=ptr(x), y=ptr(y), gb_part=ptr(gb_part),
+                gm_amax=ptr(tn_gm[0]), gp_amax=ptr(tn_gp[0]), x_amax=ptr(tn_gp[1]), y_amax=ptr(tn_gm[1]),
+                g_weg=ptr(g_weg), g_beg=ptr(g_beg), g_wcat=ptr(g_wcat), g_bcat=ptr(g_bcat), scratch=ptr(ws), scratch_bytes=wb)
+            check(lib.alignn_egc_conv_wgrad(ctypes.byref(wargs), stream()), "egc_conv_wgrad")
             COMPOSITE_STATS["wgrad"] += 1
             return g_weg, g_beg, g_wcat, g_bcat
 

@@ -21,7 +21,7 @@ def _desc(H=256, la=4, lg=4, images=True, lanes=True):
         if not images:
             for f in ("wcat_img", "wcat_img_t", "weg_img", "weg_img_t"):
                 setattr(arr[i], f, None)
-    d.convs = C.cast(arr, C.POINTER(cmodel.ConvParams))
+    d.convs = C.addressof(arr)
     d.alignn_layers, d.gcn_layers, d.H, d.out_features = la, lg, H, 1
     d.atom_in, d.edge_bins, d.angle_bins, d.embed = 92, 80, 40, 64
     for name, (i, o) in dict(atom=(92, H), edge1=(80, 64), edge2=(64, H), angle1=(40, 64), angle2=(64, H)).items():
