@@ -14,5 +14,6 @@ from .ealignn_atomwise import eALIGNNAtomWise, eALIGNNAtomWiseConfig  # noqa: F4
 from .interface import InterfaceResult, MatchResult, interface_energy, match_lattices  # noqa: F401
 from .graph import CSRGraph, GraphBatch, build_csr  # noqa: F401
 from .relax import RelaxResult, relax  # noqa: F401
+from .thermo import QHAResult, ThermalResult, qha, thermal_properties, thermal_sums  # noqa: F401
 
 __version__ = "0.1.0"
