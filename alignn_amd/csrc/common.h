@@ -30,6 +30,10 @@ static inline int capped_blocks(int64_t n, int per_block, int cap) {
     const int64_t b = (n + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : b > cap ? cap : b);
 }
+// ops.FOLD_ABOVE: more reduction slabs than this are pre-summed to alignn_slab_fold_slabs() before a finaliser reads them
+constexpr int kFoldAbove = 1024;
+// per-device tables of events (the stream forks of composite.hip and model.hip) have this many entries
+constexpr int kMaxDevices = 32;
 // run-time feature count F (feat_ok) -> compile-time number NC of 256-feature chunks a lane walks, 1..4:
 // f(std::integral_constant<int, NC>) launches the kernel instantiated for it
 template <class Fn>

@@ -23,8 +23,6 @@ inline size_t al(size_t floats) { return (floats + 63) / 64 * 64; }  // 256-byte
         if (rc__ != 0) return rc__; \
     } while (0)
 
-constexpr int kFoldAbove = 1024;  // ops.FOLD_ABOVE: more slabs than this are pre-summed to alignn_slab_fold_slabs() first
-
 // forward scratch: [e_part | e_fold | n_part | bd2 (edge_kind 2)]
 struct FwdScratch {
     size_t e_part, e_fold, n_part, bd2, total;
@@ -78,7 +76,6 @@ int bn_finalize_folded(const float* partial, int slabs, float* fold, int64_t row
 }
 
 // fork / join events of the composite entry points, one pair per device (alignn_fork_events_init)
-constexpr int kMaxDevices = 32;
 hipEvent_t g_fork_ev[kMaxDevices][2];
 bool g_fork_ok[kMaxDevices];
 

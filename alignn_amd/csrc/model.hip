@@ -29,9 +29,7 @@
 
 namespace {
 
-constexpr int kFoldAbove = 1024;  // ops.FOLD_ABOVE
 constexpr int kEvents = 512;
-constexpr int kMaxDevices = 32;
 constexpr int kAmaxSlots = 1024;
 
 struct EventPool {
@@ -253,10 +251,15 @@ void bn_bwd_finalize_folded(Ctx& c, float* partial, int slabs, int F, float* red
 // forward pieces
 // ---------------------------------------------------------------------------------------------------------------------
 
-// MLPLayer = Linear + BatchNorm1d (batch statistics) + SiLU, alignn/models/alignn.py:170-184  (ops.MLPLayerFn._fwd)
-Act mlp_fwd_ln(Ctx& c, MlpTape& t, const alignn_mlp_params& p, const Act& x, int64_t rows);
+// Both layer types come in two normalisation flavours, c.d->norm: BatchNorm (ALIGNN: alignn/models/alignn.py) keeps [4, F]
+// column statistics that a grid-wide reduction has to finish before anything is normalised; LayerNorm (ALIGNNAtomWise:
+// alignn/models/alignn_atomwise.py, alignn/models/utils.py:277-292) keeps stat = [rows, 2] (mean, rstd) per row, no grid-wide
+// dependency.  Like ops.MLPLayerFn / ops.EdgeGatedConvFn each function below is ONE body that branches only where the flavours
+// launch different kernels or keep different statistics - and follows them launch for launch in either flavour.
+
+// MLPLayer = Linear + norm (batch statistics) + SiLU, alignn/models/alignn.py:170-184  (ops.MLPLayerFn._fwd)
 Act mlp_fwd(Ctx& c, MlpTape& t, const alignn_mlp_params& p, const Act& x, int64_t rows) {
-    if (c.d->norm == 1) return mlp_fwd_ln(c, t, p, x, rows);
+    const bool ln = c.d->norm == 1;
     const int F = p.out, K = p.in;
     t.p = &p;
     t.x = x;
@@ -265,8 +268,8 @@ Act mlp_fwd(Ctx& c, MlpTape& t, const alignn_mlp_params& p, const Act& x, int64_
     hipStream_t st = t.lane ? c.T : c.main;
     if (t.lane != x.on_T) c.sync(st, x.on_T ? c.T : c.main);
     t.pre = c.alloc((size_t)rows * F);
-    t.stat = c.alloc((size_t)4 * F);
-    const bool fused_stats = x.amax != nullptr && x6_shape_ok(c, rows, K, F, K);
+    t.stat = c.alloc(ln ? (size_t)rows * 2 : (size_t)4 * F);
+    const bool fused_stats = !ln && x.amax != nullptr && x6_shape_ok(c, rows, K, F, K);
     if (fused_stats) {  // the projection's epilogue leaves the column sums BatchNorm needs
         if (p.img == nullptr) {
             UNSUP();
@@ -278,29 +281,34 @@ Act mlp_fwd(Ctx& c, MlpTape& t, const alignn_mlp_params& p, const Act& x, int64_
         bn_finalize_folded(c, partial, tiles, rows, F, p.gamma, p.beta, p.rm, p.rv, t.stat, st);
     } else {
         project(c, x.p, K, x.amax, p.W, K, p.img, p.w_amax, p.b, t.pre, F, rows, F, K, st);
-        const int slabs = alignn_col_stats_slabs(rows);
-        float* partial = c.alloc((size_t)slabs * (3 * F + 1));
-        L(alignn_col_stats_welford(t.pre, F, rows, F, partial, st));
-        L(alignn_bn_finalize_welford(partial, slabs, rows, F, p.gamma, p.beta, c.d->eps, c.d->momentum, p.rm, p.rv, t.stat, st));
+        if (!ln) {
+            const int slabs = alignn_col_stats_slabs(rows);
+            float* partial = c.alloc((size_t)slabs * (3 * F + 1));
+            L(alignn_col_stats_welford(t.pre, F, rows, F, partial, st));
+            L(alignn_bn_finalize_welford(partial, slabs, rows, F, p.gamma, p.beta, c.d->eps, c.d->momentum, p.rm, p.rv, t.stat, st));
+        }
     }
     Act y;
     y.p = c.alloc((size_t)rows * F);
     y.amax = c.track(rows) ? c.new_amax() : nullptr;
-    L(alignn_bn_silu_fwd(t.pre, F, nullptr, 0, t.stat, y.p, F, rows, F, y.amax, st));
-    y.xn = t.pre;
-    y.stat = t.stat;
-    y.red = p.red;
+    if (ln)
+        L(alignn_ln_silu_fwd(t.pre, F, nullptr, 0, p.gamma, p.beta, c.d->eps, y.p, F, t.stat, rows, F, y.amax, st));
+    else {
+        L(alignn_bn_silu_fwd(t.pre, F, nullptr, 0, t.stat, y.p, F, rows, F, y.amax, st));
+        y.xn = t.pre;
+        y.stat = t.stat;
+        y.red = p.red;
+    }
     y.on_T = t.lane;
     t.y = y;
     return y;
 }
 
-// EdgeGatedGraphConv.forward, alignn/models/alignn.py:78-129  (ops.EdgeGatedConvFn.forward, BatchNorm / training)
-void conv_fwd_ln(Ctx& c, ConvTape& t, const alignn_conv_params& p, const alignn_graph_csr& g, const Act& x, const Act& y,
-                 bool need_y);
+// EdgeGatedGraphConv.forward in training mode, alignn/models/alignn.py:78-129 and alignn/models/alignn_atomwise.py:127-208
+// (ops.EdgeGatedConvFn.forward)
 void conv_fwd(Ctx& c, ConvTape& t, const alignn_conv_params& p, const alignn_graph_csr& g, const Act& x, const Act& y,
               bool need_y) {
-    if (c.d->norm == 1) return conv_fwd_ln(c, t, p, g, x, y, need_y);
+    const bool ln = c.d->norm == 1;
     const int H = c.d->H, Kin = H;
     const int64_t n = g.n, m = g.m;
     t.p = &p;
@@ -318,27 +326,38 @@ void conv_fwd(Ctx& c, ConvTape& t, const alignn_conv_params& p, const alignn_gra
     t.xpre = c.alloc((size_t)n * H);
     t.s0 = c.alloc((size_t)n * H);
     t.hh = c.alloc((size_t)n * H);
-    const int n_slabs = alignn_egc_slabs(n);
-    float* n_part = c.alloc((size_t)n_slabs * (3 * H + 1));
     t.M = c.alloc((size_t)m * H);
-    t.n_stat = c.alloc((size_t)8 * H);
-    t.e_stat = t.n_stat + 4 * H;
+    // the statistics: BatchNorm's two [4, H] tables and the slabs of column sums the gate passes leave for them (LayerNorm: none,
+    // the gate passes get NULL), LayerNorm's [rows, 2] - of the edge rows only when somebody reads the edge output
+    const int n_slabs = alignn_egc_slabs(n);
+    float *n_part = nullptr, *e_part = nullptr;
+    if (ln)
+        t.n_stat = c.alloc((size_t)n * 2);
+    else {
+        n_part = c.alloc((size_t)n_slabs * (3 * H + 1));
+        t.n_stat = c.alloc((size_t)8 * H);
+        t.e_stat = t.n_stat + 4 * H;
+    }
     // u_add_v (and the BatchNorm statistics) in the edge projection's epilogue when it runs on the split-product kernel
-    const bool pre_added = y.amax != nullptr && x6_shape_ok(c, m, Kin, H, Kin);
-    if (!pre_added && x6_shape_ok(c, m, Kin, H, Kin)) UNSUP();  // (bf16x6 scheme: per-operator path)
-    if (t.lane) c.sync(T, main);  // lane T reads P (and y, if the caller's stream produced it)
+    const bool x6 = x6_shape_ok(c, m, Kin, H, Kin);
+    const bool pre_added = y.amax != nullptr && x6;
+    if (!pre_added && x6) UNSUP();  // (bf16x6 scheme: per-operator path)
+    if (t.lane) c.sync(T, main);    // lane T reads P (and y, if the caller's stream produced it)
     Act yo;
     if (need_y) {
         yo.p = c.alloc((size_t)m * H);
         yo.amax = c.track(m) ? c.new_amax() : nullptr;
+        if (ln) t.e_stat = c.alloc((size_t)m * 2);
+        yo.on_T = t.lane;
     }
+    bool y_normed = false;  // the gate pass normalised the edge output as well: one read of m less
     if (pre_added) {
         if (p.weg_img == nullptr) {
             UNSUP();
             return;
         }
         const int tiles = alignn_gemm_nt_x6_row_tiles(m, H, Kin);
-        float* e_part = c.alloc((size_t)(tiles + 1) * 2 * H);
+        if (!ln) e_part = c.alloc((size_t)(tiles + 1) * 2 * H);
         if (c.d->bd_segment_table && g.seg_node != nullptr && g.seg_rank != nullptr) {
             // line graphs: the destination term from a segment-ordered copy of Bd (consecutive rows, same values)
             float* bd2 = c.alloc((size_t)n * H);
@@ -348,125 +367,47 @@ void conv_fwd(Ctx& c, ConvTape& t, const alignn_conv_params& p, const alignn_gra
         } else
             L(alignn_gemm_nt_f16x3_gather(y.p, Kin, y.amax, p.weg_img, p.weg_amax, p.b_eg, t.M, H, m, H, Kin, t.P, 4 * H, g.src,
                                           g.dst, e_part, T));
-        bn_finalize_folded(c, e_part, tiles, m, H, p.e_gamma, p.e_beta, p.e_rm, p.e_rv, t.e_stat, T);
-        if (need_y)
+        if (!ln) bn_finalize_folded(c, e_part, tiles, m, H, p.e_gamma, p.e_beta, p.e_rm, p.e_rv, t.e_stat, T);
+        y_normed = need_y && (!ln || alignn_egc_ln_fused_supported(H, m));
+        if (!y_normed)
+            L(alignn_egc_gate_fwd_pre(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, nullptr, n_part, T));
+        else if (ln)  // (csrc/convln.hip)
+            L(alignn_egc_gate_fwd_pre_ln(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, p.e_gamma, p.e_beta, c.d->eps,
+                                         y.p, yo.p, t.e_stat, yo.amax, T));
+        else
             L(alignn_egc_gate_fwd_pre_norm(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, n_part, t.e_stat,
                                            y.p, yo.p, yo.amax, T));
-        else
-            L(alignn_egc_gate_fwd_pre(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, nullptr, n_part, T));
-        if (t.lane) c.sync(main, T);
     } else {
         L(alignn_gemm_nt(y.p, Kin, p.w_eg, Kin, p.b_eg, nullptr, 0, t.M, H, m, H, Kin, T));
-        float* e_part = c.alloc((size_t)n_slabs * (3 * H + 1));
+        if (!ln) e_part = c.alloc((size_t)n_slabs * (3 * H + 1));
         L(alignn_egc_gate_fwd(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, e_part, n_part, T));
-        if (t.lane) c.sync(main, T);
+    }
+    if (t.lane) c.sync(main, T);  // xpre (and, BatchNorm, n_part): the node norm goes on beside the separate edge norm
+    if (!ln && !pre_added)
         L(alignn_bn_finalize_welford(e_part, n_slabs, m, H, p.e_gamma, p.e_beta, c.d->eps, c.d->momentum, p.e_rm, p.e_rv,
                                      t.e_stat, T));
-        if (need_y) L(alignn_bn_silu_fwd(t.M, H, y.p, Kin, t.e_stat, yo.p, H, m, H, yo.amax, T));
+    if (need_y && !y_normed) {
+        if (ln)
+            L(alignn_ln_silu_fwd(t.M, H, y.p, Kin, p.e_gamma, p.e_beta, c.d->eps, yo.p, H, t.e_stat, m, H, yo.amax, T));
+        else
+            L(alignn_bn_silu_fwd(t.M, H, y.p, Kin, t.e_stat, yo.p, H, m, H, yo.amax, T));
     }
     // ---- node side, part 2: node norm
-    L(alignn_bn_finalize_welford(n_part, n_slabs, n, H, p.n_gamma, p.n_beta, c.d->eps, c.d->momentum, p.n_rm, p.n_rv, t.n_stat,
-                                 main));
     Act xo;
     xo.p = c.alloc((size_t)n * H);
     xo.amax = c.track(n) ? c.new_amax() : nullptr;
-    L(alignn_bn_silu_fwd(t.xpre, H, x.p, Kin, t.n_stat, xo.p, H, n, H, xo.amax, main));
-    if (need_y) {
-        yo.xn = t.M;
-        yo.stat = t.e_stat;
-        yo.red = p.e_red;
-        yo.on_T = t.lane;
-    }
-    t.x_out = xo;
-    t.y_out = yo;
-}
-
-// ---- LayerNorm flavour (ALIGNNAtomWise: alignn/models/alignn_atomwise.py:127-208 EdgeGatedGraphConv, alignn/models/utils.py:277-292
-// MLPLayer): per-row statistics, no grid-wide dependency, stat = [rows, 2] (mean, rstd).  ops.MLPLayerFn / ops.EdgeGatedConvFn
-// with norm == "layer", launch for launch.
-Act mlp_fwd_ln(Ctx& c, MlpTape& t, const alignn_mlp_params& p, const Act& x, int64_t rows) {
-    const int F = p.out, K = p.in;
-    t.p = &p;
-    t.x = x;
-    t.rows = rows;
-    t.lane = c.T != c.main && rows >= c.d->lane_min_rows;
-    hipStream_t st = t.lane ? c.T : c.main;
-    if (t.lane != x.on_T) c.sync(st, x.on_T ? c.T : c.main);
-    t.pre = c.alloc((size_t)rows * F);
-    project(c, x.p, K, x.amax, p.W, K, p.img, p.w_amax, p.b, t.pre, F, rows, F, K, st);
-    t.stat = c.alloc((size_t)rows * 2);
-    Act y;
-    y.p = c.alloc((size_t)rows * F);
-    y.amax = c.track(rows) ? c.new_amax() : nullptr;
-    L(alignn_ln_silu_fwd(t.pre, F, nullptr, 0, p.gamma, p.beta, c.d->eps, y.p, F, t.stat, rows, F, y.amax, st));
-    y.on_T = t.lane;
-    t.y = y;
-    return y;
-}
-
-void conv_fwd_ln(Ctx& c, ConvTape& t, const alignn_conv_params& p, const alignn_graph_csr& g, const Act& x, const Act& y,
-                 bool need_y) {
-    const int H = c.d->H, Kin = H;
-    const int64_t n = g.n, m = g.m;
-    t.p = &p;
-    t.g = &g;
-    t.x = x;
-    t.y = y;
-    t.need_y = need_y;
-    t.lane = c.T != c.main && m >= c.d->lane_min_rows;
-    hipStream_t main = c.main, T = t.lane ? c.T : c.main;
-    if (x.on_T) c.sync(main, c.T);
-    if (!t.lane && y.on_T) c.sync(main, c.T);
-    t.P = c.alloc((size_t)n * 4 * H);
-    project(c, x.p, Kin, x.amax, p.wcat, Kin, p.wcat_img, p.wcat_amax, p.bcat, t.P, 4 * H, n, 4 * H, Kin, main);
-    t.xpre = c.alloc((size_t)n * H);
-    t.s0 = c.alloc((size_t)n * H);
-    t.hh = c.alloc((size_t)n * H);
-    t.M = c.alloc((size_t)m * H);
-    const bool x6 = x6_shape_ok(c, m, Kin, H, Kin);
-    const bool pre_added = y.amax != nullptr && x6;  // u_add_v in the edge projection's epilogue (no statistics to take)
-    if (!pre_added && x6) UNSUP();                   // (bf16x6 scheme: per-operator path)
-    if (t.lane) c.sync(T, main);
-    if (pre_added) {
-        if (p.weg_img == nullptr) {
-            UNSUP();
-            return;
+    if (ln)
+        L(alignn_ln_silu_fwd(t.xpre, H, x.p, Kin, p.n_gamma, p.n_beta, c.d->eps, xo.p, H, t.n_stat, n, H, xo.amax, main));
+    else {
+        L(alignn_bn_finalize_welford(n_part, n_slabs, n, H, p.n_gamma, p.n_beta, c.d->eps, c.d->momentum, p.n_rm, p.n_rv, t.n_stat,
+                                     main));
+        L(alignn_bn_silu_fwd(t.xpre, H, x.p, Kin, t.n_stat, xo.p, H, n, H, xo.amax, main));
+        if (need_y) {
+            yo.xn = t.M;
+            yo.stat = t.e_stat;
+            yo.red = p.e_red;
         }
-        if (c.d->bd_segment_table && g.seg_node != nullptr && g.seg_rank != nullptr) {
-            float* bd2 = c.alloc((size_t)n * H);
-            L(alignn_gather_rows_ld(t.P + H, 4 * H, g.seg_node, bd2, H, n, H, T));
-            L(alignn_gemm_nt_f16x3_gather2(y.p, Kin, y.amax, p.weg_img, p.weg_amax, p.b_eg, t.M, H, m, H, Kin, t.P, 4 * H, g.src,
-                                           bd2, H, g.seg_rank, nullptr, T));
-        } else
-            L(alignn_gemm_nt_f16x3_gather(y.p, Kin, y.amax, p.weg_img, p.weg_amax, p.b_eg, t.M, H, m, H, Kin, t.P, 4 * H, g.src,
-                                          g.dst, nullptr, T));
-        if (!(need_y && alignn_egc_ln_fused_supported(H, m)))
-            L(alignn_egc_gate_fwd_pre(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, nullptr, nullptr, T));
-    } else {
-        L(alignn_gemm_nt(y.p, Kin, p.w_eg, Kin, p.b_eg, nullptr, 0, t.M, H, m, H, Kin, T));
-        L(alignn_egc_gate_fwd(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, nullptr, nullptr, T));
     }
-    Act yo;
-    if (need_y) {
-        yo.p = c.alloc((size_t)m * H);
-        yo.amax = c.track(m) ? c.new_amax() : nullptr;
-        t.e_stat = c.alloc((size_t)m * 2);
-        yo.on_T = t.lane;
-    }
-    if (need_y && pre_added && alignn_egc_ln_fused_supported(H, m)) {
-        // the edge LayerNorm inside the gate pass (csrc/convln.hip): one read of m less
-        L(alignn_egc_gate_fwd_pre_ln(t.P, t.M, g.seg_ptr, g.seg_node, g.src, n, m, H, t.xpre, t.s0, t.hh, p.e_gamma, p.e_beta, c.d->eps,
-                                     y.p, yo.p, t.e_stat, yo.amax, T));
-        if (t.lane) c.sync(main, T);
-    } else {
-        if (t.lane) c.sync(main, T);
-        if (need_y) L(alignn_ln_silu_fwd(t.M, H, y.p, Kin, p.e_gamma, p.e_beta, c.d->eps, yo.p, H, t.e_stat, m, H, yo.amax, T));
-    }
-    t.n_stat = c.alloc((size_t)n * 2);
-    Act xo;
-    xo.p = c.alloc((size_t)n * H);
-    xo.amax = c.track(n) ? c.new_amax() : nullptr;
-    L(alignn_ln_silu_fwd(t.xpre, H, x.p, Kin, p.n_gamma, p.n_beta, c.d->eps, xo.p, H, t.n_stat, n, H, xo.amax, main));
     t.x_out = xo;
     t.y_out = yo;
 }
@@ -703,10 +644,10 @@ bool dgrad_wgrad(Ctx& c, const ConvTape& t, const float* GM, const float* gm_ama
     return true;
 }
 
-// ops.MLPLayerFn.backward
-Grad mlp_bwd_ln(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx);
+// ops.MLPLayerFn.backward.  Without parameter gradients (c.param_grads == false: the reverse pass of alignn_ff_eval) only the
+// input gradient is produced.
 Grad mlp_bwd(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx) {
-    if (c.d->norm == 1) return mlp_bwd_ln(c, t, gy, need_gx);
+    const bool ln = c.d->norm == 1;
     const alignn_mlp_params& p = *t.p;
     const int F = p.out, K = p.in;
     const int64_t rows = t.rows;
@@ -714,25 +655,32 @@ Grad mlp_bwd(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx) {
     if (t.lane != gy.on_T) c.sync(st, gy.on_T ? c.T : c.main);
     float* gpre = c.alloc((size_t)rows * F);
     float* g_amax = c.track(rows) ? c.new_amax() : nullptr;
-    const int slabs = alignn_col_stats_slabs(rows);
-    if (!gy.pre_red) {
-        float* part = c.alloc((size_t)slabs * 2 * F);
-        L(alignn_bn_silu_bwd_reduce(gy.p, F, t.pre, F, t.stat, rows, F, part, st));
-        L(alignn_bn_bwd_finalize(part, slabs, F, p.red, st));
-    }
+    const int slabs = ln ? alignn_ln_slabs(rows) : alignn_col_stats_slabs(rows);
     float* gb_part = nullptr;
-    if (F <= 1024) {  // the pass that writes gpre also sums its columns (the Linear's bias gradient)
-        gb_part = c.alloc((size_t)slabs * F);
-        L(alignn_bn_silu_bwd_apply_sum(gy.p, F, t.pre, F, t.stat, p.red, 0, gpre, F, rows, F, g_amax, gb_part, st));
-    } else
-        L(alignn_bn_silu_bwd_apply(gy.p, F, t.pre, F, t.stat, p.gamma, p.red, 0, gpre, F, rows, F, g_amax, st));
+    if (ln) {  // one pass: the row statistics need no reduction first
+        float* part = c.alloc((size_t)slabs * 2 * F);
+        L(alignn_ln_silu_bwd(gy.p, F, t.pre, F, p.gamma, p.beta, t.stat, gpre, F, part, rows, F, g_amax, st));
+        if (c.param_grads) L(alignn_bn_bwd_finalize(part, slabs, F, p.red, st));
+    } else {
+        if (!gy.pre_red) {
+            float* part = c.alloc((size_t)slabs * 2 * F);
+            L(alignn_bn_silu_bwd_reduce(gy.p, F, t.pre, F, t.stat, rows, F, part, st));
+            L(alignn_bn_bwd_finalize(part, slabs, F, p.red, st));
+        }
+        if (F <= 1024) {  // the pass that writes gpre also sums its columns (the Linear's bias gradient)
+            gb_part = c.alloc((size_t)slabs * F);
+            L(alignn_bn_silu_bwd_apply_sum(gy.p, F, t.pre, F, t.stat, p.red, 0, gpre, F, rows, F, g_amax, gb_part, st));
+        } else
+            L(alignn_bn_silu_bwd_apply(gy.p, F, t.pre, F, t.stat, p.gamma, p.red, 0, gpre, F, rows, F, g_amax, st));
+    }
     Grad gx;
     if (need_gx) {
         gx.p = c.alloc((size_t)rows * K);
         gx.on_T = t.lane;
-        const Act* src = (t.x.xn != nullptr && g_amax != nullptr) ? &t.x : nullptr;
+        const Act* src = (t.x.xn != nullptr && g_amax != nullptr) ? &t.x : nullptr;  // (BatchNorm producers only set xn)
         dgrad(c, gpre, F, g_amax, p.W, F, K, p.img_t, p.w_amax, nullptr, 0, gx.p, rows, st, src, &gx.pre_red);
     }
+    if (!c.param_grads) return gx;
     hipStream_t sd = side_for(c, rows);
     if (sd != st) {
         c.sync(sd, c.main);
@@ -747,10 +695,10 @@ Grad mlp_bwd(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx) {
     return gx;
 }
 
-// ops.EdgeGatedConvFn.backward: -> gradients w.r.t. the node and edge inputs
-void conv_bwd_ln(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out, Grad& g_x, Grad& g_y, bool need_gx);
+// ops.EdgeGatedConvFn.backward: -> gradients w.r.t. the node and edge inputs.  need_gx == false: nobody reads the gradient of
+// the node input (the first convolution of the force evaluation: the atom features are data)
 void conv_bwd(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out, Grad& g_x, Grad& g_y, bool need_gx = true) {
-    if (c.d->norm == 1) return conv_bwd_ln(c, t, gx_out, gy_out, g_x, g_y, need_gx);
+    const bool ln = c.d->norm == 1;
     const alignn_conv_params& p = *t.p;
     const alignn_graph_csr& g = *t.g;
     const int H = c.d->H, Kin = H;
@@ -762,20 +710,43 @@ void conv_bwd(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out,
     float* gp_amax = c.track(n) ? c.new_amax() : nullptr;
     float* gm_amax = c.track(m) ? c.new_amax() : nullptr;
     float* g_xpre = GP + 3 * (size_t)H;
-    // ---- node branch: BatchNorm / SiLU backward -> g_xpre (the Ux block of GP), the quotient's adjoints
-    const int n_slabs = alignn_col_stats_slabs(n);
+    // ---- node branch: norm / SiLU backward -> g_xpre (the Ux block of GP), the quotient's adjoints
+    const int n_slabs = ln ? alignn_ln_slabs(n) : alignn_col_stats_slabs(n);
     float* n_part = c.alloc((size_t)n_slabs * 2 * H);
-    L(alignn_bn_silu_bwd_reduce(gx_out.p, H, t.xpre, H, t.n_stat, n, H, n_part, main));
-    L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, main));
     float* gs1 = c.alloc((size_t)n * H);
     float* gs0 = c.alloc((size_t)n * H);
-    L(alignn_bn_silu_bwd_apply_node(gx_out.p, H, t.xpre, H, t.n_stat, p.n_gamma, p.n_red, 0, g_xpre, 4 * H, n, H, gp_amax, t.s0,
-                                    t.hh, gs1, gs0, main));
-    // ---- edge branch (lane T for the line graph)
+    if (ln) {
+        L(alignn_ln_silu_bwd_node(gx_out.p, H, t.xpre, H, p.n_gamma, p.n_beta, t.n_stat, g_xpre, 4 * H, n_part, n, H, gp_amax, t.s0, t.hh,
+                                  gs1, gs0, main));
+        if (c.param_grads) L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, main));
+    } else {
+        L(alignn_bn_silu_bwd_reduce(gx_out.p, H, t.xpre, H, t.n_stat, n, H, n_part, main));
+        L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, main));
+        L(alignn_bn_silu_bwd_apply_node(gx_out.p, H, t.xpre, H, t.n_stat, p.n_gamma, p.n_red, 0, g_xpre, 4 * H, n, H, gp_amax, t.s0,
+                                        t.hh, gs1, gs0, main));
+    }
+    // ---- edge branch (lane T for the line graph).  What the gate reverse kernels are handed as the edge output's gradient:
+    // BatchNorm - gy itself with the statistics and the finished sums `e_red`, they apply the norm's backward on the way;
+    // LayerNorm - the same through the kernels of csrc/convln.hip where one fits (ln_inside: dense line-graph blocks, ln_dst:
+    // the bond graph), otherwise the finished normalised-branch gradient `g_branch` and no statistics
     const float* gy = gy_out != nullptr ? gy_out->p : nullptr;
     if (t.lane && gy_out != nullptr && !gy_out->on_T) c.sync(T, main);
-    const float* e_red = nullptr;
-    if (gy != nullptr) {
+    const bool lg_blocks = g.grp_seg_ptr != nullptr;
+    const bool dense = lg_blocks && g.dense_max_src > 0 && alignn_egc_bwd_lg_dense_supported(g.dense_max_src);
+    const bool ln_inside = ln && gy != nullptr && dense && alignn_egc_ln_fused_supported(H, m);
+    const bool ln_dst = ln && gy != nullptr && !lg_blocks && alignn_egc_ln_dst_supported(H);
+    const float *ge = gy, *e_stat = t.e_stat, *e_red = nullptr;
+    if (ln) {
+        ge = e_stat = nullptr;
+        if (gy != nullptr && !ln_inside && !ln_dst) {
+            float* g_branch = c.alloc((size_t)m * H);
+            const int e_slabs = alignn_ln_slabs(m);
+            float* e_part = c.alloc((size_t)e_slabs * 2 * H);
+            L(alignn_ln_silu_bwd(gy, H, t.M, H, p.e_gamma, p.e_beta, t.e_stat, g_branch, H, e_part, m, H, nullptr, T));
+            if (c.param_grads) L(alignn_bn_bwd_finalize(e_part, e_slabs, H, p.e_red, T));
+            ge = g_branch;
+        }
+    } else if (gy != nullptr) {
         if (!gy_out->pre_red) {
             const int e_slabs = alignn_col_stats_slabs(m);
             float* e_part = c.alloc((size_t)e_slabs * 2 * H);
@@ -786,159 +757,41 @@ void conv_bwd(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out,
     }
     if (t.lane) c.sync(T, main);  // gs1, gs0, the Ux block of GP and its maximum are ready
     float* GM = c.alloc((size_t)m * H);
-    const bool lg_blocks = g.grp_seg_ptr != nullptr;
-    const bool dense = lg_blocks && g.dense_max_src > 0 && alignn_egc_bwd_lg_dense_supported(g.dense_max_src);
-    const int gslabs = lg_blocks ? (int)g.n_groups : alignn_egc_slabs(n);
-    float* gb_part = c.alloc((size_t)gslabs * H);
-    if (dense)
-        L(alignn_egc_bwd_lg_dense(gy, t.M, t.P, gs1, gs0, t.e_stat, e_red, 0, m, g.grp_seg_ptr, g.grp_src_ptr, g.n_groups,
-                                  g.dense_max_src, g.seg_ptr, g.seg_node, H, GM, GP, gb_part, gm_amax, gp_amax, T));
-    else if (lg_blocks)
-        L(alignn_egc_bwd_lg_fused(gy, t.M, t.P, gs1, gs0, t.e_stat, e_red, 0, m, g.grp_seg_ptr, g.grp_src_ptr, g.n_groups,
-                                  g.seg_ptr, g.seg_node, g.dst, g.out_ptr, g.out_slot, H, GM, GP, gb_part, gm_amax, gp_amax, T));
-    else {
-        L(alignn_egc_bwd_dst(gy, t.M, t.P, gs1, gs0, t.e_stat, p.e_gamma, e_red, 0, m, g.seg_ptr, g.seg_node, g.src, n, H, GM, GP,
-                             gb_part, gm_amax, gp_amax, T));
-        L(alignn_egc_bwd_src(GM, t.M, gs1, g.out_ptr, g.out_slot, g.dst, n, H, GP, gp_amax, T));
-    }
-    if (t.lane) c.sync(main, T);  // GP complete
-    // ---- input gradients (critical path): g_x = GP wcat (+ gx_out) beside g_y = GM w_eg (+ gy_out)
-    g_x.p = c.alloc((size_t)n * Kin);
-    g_y.p = edge_grad_buffer(c, t, m, Kin);
-    hipStream_t sx = main;
-    if (!t.lane && c.aux != main) {  // bond graph: the (shorter) node product on the aux stream beside the edge product
-        c.sync(c.aux, main);
-        sx = c.aux;
-    }
-    dgrad(c, GP, 4 * H, gp_amax, p.wcat, 4 * H, Kin, p.wcat_img_t, p.wcat_amax, gx_out.p, H, g_x.p, n, sx, nullptr, nullptr);
-    const Act* src = (t.y.xn != nullptr && gm_amax != nullptr) ? &t.y : nullptr;
-    const bool dw = dgrad_wgrad(c, t, GM, gm_amax, gy, g_y.p, m, H, Kin, T, src, &g_y.pre_red);
-    if (!dw) dgrad(c, GM, H, gm_amax, p.w_eg, H, Kin, p.weg_img_t, p.weg_amax, gy, H, g_y.p, m, T, src, &g_y.pre_red);
-    g_y.on_T = t.lane;
-    g_x.on_T = false;
-    if (sx != main) c.sync(main, sx);
-    // ---- weight / bias gradients
-    hipStream_t sd = side_for(c, m);
-    if (sd != main) {
-        c.sync(sd, main);
-        if (t.lane) c.sync(sd, c.T);
-    } else if (t.lane)
-        c.sync(main, c.T);
-    c.tmp_reset(sd);
-    L(alignn_slab_sum(gb_part, gslabs, H, p.g_beg, sd));
-    if (!dw) gemm_tn(c, GM, H, gm_amax, t.y.p, Kin, t.y.amax, p.g_weg, m, H, Kin, sd);
-    gemm_tn(c, GP, 4 * H, gp_amax, t.x.p, Kin, t.x.amax, p.g_wcat, n, 4 * H, Kin, sd);
-    col_sum(c, GP, 4 * H, n, 4 * H, p.g_bcat, sd);
-}
-
-// ops.MLPLayerFn.backward, norm == "layer"
-Grad mlp_bwd_ln(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx) {
-    const alignn_mlp_params& p = *t.p;
-    const int F = p.out, K = p.in;
-    const int64_t rows = t.rows;
-    hipStream_t st = t.lane ? c.T : c.main;
-    if (t.lane != gy.on_T) c.sync(st, gy.on_T ? c.T : c.main);
-    float* gpre = c.alloc((size_t)rows * F);
-    float* g_amax = c.track(rows) ? c.new_amax() : nullptr;
-    const int slabs = alignn_ln_slabs(rows);
-    float* part = c.alloc((size_t)slabs * 2 * F);
-    L(alignn_ln_silu_bwd(gy.p, F, t.pre, F, p.gamma, p.beta, t.stat, gpre, F, part, rows, F, g_amax, st));
-    if (c.param_grads) L(alignn_bn_bwd_finalize(part, slabs, F, p.red, st));
-    Grad gx;
-    if (need_gx) {
-        gx.p = c.alloc((size_t)rows * K);
-        gx.on_T = t.lane;
-        dgrad(c, gpre, F, g_amax, p.W, F, K, p.img_t, p.w_amax, nullptr, 0, gx.p, rows, st, nullptr, nullptr);
-    }
-    if (!c.param_grads) return gx;
-    hipStream_t sd = side_for(c, rows);
-    if (sd != st) {
-        c.sync(sd, c.main);
-        if (t.lane) c.sync(sd, c.T);
-    }
-    c.tmp_reset(sd);
-    gemm_tn(c, gpre, F, g_amax, t.x.p, K, t.x.amax, p.gW, rows, F, K, sd);
-    col_sum(c, gpre, F, rows, F, p.gb, sd);
-    return gx;
-}
-
-// ops.EdgeGatedConvFn.backward, norm == "layer".  need_gx == false: nobody reads the gradient of the node input (the first
-// convolution of the force evaluation: the atom features are data)
-void conv_bwd_ln(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out, Grad& g_x, Grad& g_y, bool need_gx) {
-    const alignn_conv_params& p = *t.p;
-    const alignn_graph_csr& g = *t.g;
-    const int H = c.d->H, Kin = H;
-    const int64_t n = g.n, m = g.m;
-    hipStream_t main = c.main, T = t.lane ? c.T : c.main;
-    if (gx_out.on_T) c.sync(main, c.T);
-    if (!t.lane && gy_out != nullptr && gy_out->on_T) c.sync(main, c.T);
-    float* GP = c.alloc((size_t)n * 4 * H);
-    float* gp_amax = c.track(n) ? c.new_amax() : nullptr;
-    float* gm_amax = c.track(m) ? c.new_amax() : nullptr;
-    float* g_xpre = GP + 3 * (size_t)H;
-    // ---- node branch: LayerNorm / SiLU backward straight into the Ux block of GP, the quotient's adjoints
-    const int n_slabs = alignn_ln_slabs(n);
-    float* n_part = c.alloc((size_t)n_slabs * 2 * H);
-    float* gs1 = c.alloc((size_t)n * H);
-    float* gs0 = c.alloc((size_t)n * H);
-    L(alignn_ln_silu_bwd_node(gx_out.p, H, t.xpre, H, p.n_gamma, p.n_beta, t.n_stat, g_xpre, 4 * H, n_part, n, H, gp_amax, t.s0, t.hh,
-                              gs1, gs0, main));  // (+ the quotient's adjoints: alignn_egc_node_bwd in the same pass)
-    if (c.param_grads) L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, main));
-    // ---- edge branch (lane T for the line graph): the finished normalised-branch gradient, handed over as it is
-    const float* gy = gy_out != nullptr ? gy_out->p : nullptr;
-    if (t.lane && gy_out != nullptr && !gy_out->on_T) c.sync(T, main);
-    const bool lg_blocks = g.grp_seg_ptr != nullptr;
-    const bool dense = lg_blocks && g.dense_max_src > 0 && alignn_egc_bwd_lg_dense_supported(g.dense_max_src);
-    const bool ln_inside = gy != nullptr && dense && alignn_egc_ln_fused_supported(H, m);  // (csrc/convln.hip)
-    const bool ln_dst = gy != nullptr && !lg_blocks && alignn_egc_ln_dst_supported(H);       // (the bond graph: same file)
-    float* g_branch = nullptr;
-    if (gy != nullptr && !ln_inside && !ln_dst) {
-        g_branch = c.alloc((size_t)m * H);
-        const int e_slabs = alignn_ln_slabs(m);
-        float* e_part = c.alloc((size_t)e_slabs * 2 * H);
-        L(alignn_ln_silu_bwd(gy, H, t.M, H, p.e_gamma, p.e_beta, t.e_stat, g_branch, H, e_part, m, H, nullptr, T));
-        if (c.param_grads) L(alignn_bn_bwd_finalize(e_part, e_slabs, H, p.e_red, T));
-    }
-    if (t.lane) c.sync(T, main);
-    float* GM = c.alloc((size_t)m * H);
     const int gslabs = lg_blocks ? (int)g.n_groups : (ln_dst ? alignn_egc_ln_dst_slabs(n) : alignn_egc_slabs(n));
     float* gb_part = c.alloc((size_t)gslabs * H);
-    if (ln_dst) {
-        float* e_part = c.alloc((size_t)gslabs * 2 * H);
-        L(alignn_egc_bwd_dst_ln(gy, t.M, t.P, gs1, gs0, p.e_gamma, p.e_beta, t.e_stat, g.seg_ptr, g.seg_node, g.src, n, H, GM, GP, gb_part,
-                                e_part, gm_amax, gp_amax, T));
-        if (c.param_grads) L(alignn_bn_bwd_finalize(e_part, gslabs, H, p.e_red, T));
-        L(alignn_egc_bwd_src(GM, t.M, gs1, g.out_ptr, g.out_slot, g.dst, n, H, GP, gp_amax, T));
-    } else if (ln_inside) {
-        float* e_part = c.alloc((size_t)gslabs * 2 * H);
+    float* e_part = (ln_inside || ln_dst) ? c.alloc((size_t)gslabs * 2 * H) : nullptr;  // the sums of the LayerNorm inside
+    if (ln_inside)
         L(alignn_egc_bwd_lg_dense_ln(gy, t.M, t.P, gs1, gs0, p.e_gamma, p.e_beta, t.e_stat, m, g.grp_seg_ptr, g.grp_src_ptr, g.n_groups,
                                      g.dense_max_src, g.seg_ptr, g.seg_node, H, GM, GP, gb_part, e_part, gm_amax, gp_amax, T));
-        if (c.param_grads) L(alignn_bn_bwd_finalize(e_part, gslabs, H, p.e_red, T));
-    } else if (dense)
-        L(alignn_egc_bwd_lg_dense(g_branch, t.M, t.P, gs1, gs0, nullptr, nullptr, 0, m, g.grp_seg_ptr, g.grp_src_ptr, g.n_groups,
+    else if (dense)
+        L(alignn_egc_bwd_lg_dense(ge, t.M, t.P, gs1, gs0, e_stat, e_red, 0, m, g.grp_seg_ptr, g.grp_src_ptr, g.n_groups,
                                   g.dense_max_src, g.seg_ptr, g.seg_node, H, GM, GP, gb_part, gm_amax, gp_amax, T));
     else if (lg_blocks)
-        L(alignn_egc_bwd_lg_fused(g_branch, t.M, t.P, gs1, gs0, nullptr, nullptr, 0, m, g.grp_seg_ptr, g.grp_src_ptr, g.n_groups,
+        L(alignn_egc_bwd_lg_fused(ge, t.M, t.P, gs1, gs0, e_stat, e_red, 0, m, g.grp_seg_ptr, g.grp_src_ptr, g.n_groups,
                                   g.seg_ptr, g.seg_node, g.dst, g.out_ptr, g.out_slot, H, GM, GP, gb_part, gm_amax, gp_amax, T));
-    else {
-        L(alignn_egc_bwd_dst(g_branch, t.M, t.P, gs1, gs0, nullptr, p.e_gamma, nullptr, 0, m, g.seg_ptr, g.seg_node, g.src, n, H, GM,
-                             GP, gb_part, gm_amax, gp_amax, T));
-        L(alignn_egc_bwd_src(GM, t.M, gs1, g.out_ptr, g.out_slot, g.dst, n, H, GP, gp_amax, T));
-    }
-    if (t.lane) c.sync(main, T);
-    // ---- input gradients
+    else if (ln_dst)
+        L(alignn_egc_bwd_dst_ln(gy, t.M, t.P, gs1, gs0, p.e_gamma, p.e_beta, t.e_stat, g.seg_ptr, g.seg_node, g.src, n, H, GM, GP, gb_part,
+                                e_part, gm_amax, gp_amax, T));
+    else
+        L(alignn_egc_bwd_dst(ge, t.M, t.P, gs1, gs0, e_stat, p.e_gamma, e_red, 0, m, g.seg_ptr, g.seg_node, g.src, n, H, GM, GP,
+                             gb_part, gm_amax, gp_amax, T));
+    if (e_part != nullptr && c.param_grads) L(alignn_bn_bwd_finalize(e_part, gslabs, H, p.e_red, T));
+    if (!lg_blocks) L(alignn_egc_bwd_src(GM, t.M, gs1, g.out_ptr, g.out_slot, g.dst, n, H, GP, gp_amax, T));
+    if (t.lane) c.sync(main, T);  // GP complete
+    // ---- input gradients (critical path): g_x = GP wcat (+ gx_out) beside g_y = GM w_eg (+ gy_out)
     g_y.p = edge_grad_buffer(c, t, m, Kin);
     hipStream_t sx = main;
     if (need_gx) {
         g_x.p = c.alloc((size_t)n * Kin);
-        if (!t.lane && c.aux != main) {
+        if (!t.lane && c.aux != main) {  // bond graph: the (shorter) node product on the aux stream beside the edge product
             c.sync(c.aux, main);
             sx = c.aux;
         }
         dgrad(c, GP, 4 * H, gp_amax, p.wcat, 4 * H, Kin, p.wcat_img_t, p.wcat_amax, gx_out.p, H, g_x.p, n, sx, nullptr, nullptr);
     }
-    const bool dw = dgrad_wgrad(c, t, GM, gm_amax, gy, g_y.p, m, H, Kin, T, nullptr, nullptr);
-    if (!dw) dgrad(c, GM, H, gm_amax, p.w_eg, H, Kin, p.weg_img_t, p.weg_amax, gy, H, g_y.p, m, T, nullptr, nullptr);
+    const Act* src = (t.y.xn != nullptr && gm_amax != nullptr) ? &t.y : nullptr;  // (BatchNorm producers only set xn)
+    const bool dw = dgrad_wgrad(c, t, GM, gm_amax, gy, g_y.p, m, H, Kin, T, src, &g_y.pre_red);
+    if (!dw) dgrad(c, GM, H, gm_amax, p.w_eg, H, Kin, p.weg_img_t, p.weg_amax, gy, H, g_y.p, m, T, src, &g_y.pre_red);
     g_y.on_T = t.lane;
     g_x.on_T = false;
     if (sx != main) c.sync(main, sx);
@@ -1268,7 +1121,7 @@ void dual_conv_fwd(Ctx& c, DConvTape& t, const alignn_conv_params& p, const Conv
     t.x = x;
     t.y = y;
     t.need_y = need_y;
-    // lane T for the line graph (as in conv_fwd_ln): the T-row tangent projection and the gate pass run there, beside the
+    // lane T for the line graph (as in conv_fwd): the T-row tangent projection and the gate pass run there, beside the
     // bond-row kernels of the caller's stream - the next convolution's node side, the bond-graph convolution that follows
     t.lane = c.T != c.main && m >= c.d->lane_min_rows;
     hipStream_t main = c.main, T = t.lane ? c.T : c.main;
@@ -1372,7 +1225,7 @@ void dual_conv_bwd(Ctx& c, const DConvTape& t, const DAct& gx, const DAct& gy, D
     const alignn_graph_csr& g = *t.g;
     const int H = c.d->H, Kin = H;
     const int64_t n = g.n, m = g.m;
-    // lane T for the line graph (as in conv_bwd_ln): the gate reverse and the edge input gradients - every T-row kernel - run
+    // lane T for the line graph (as in conv_bwd): the gate reverse and the edge input gradients - every T-row kernel - run
     // there, the node branch, the node input gradient and whatever bond-row work follows on the caller's stream
     hipStream_t main = c.main, T = t.lane ? c.T : c.main;
     if (gx.on_T) c.sync(main, c.T);
@@ -1628,23 +1481,6 @@ struct Plan {
     }
 };
 
-Plan make_plan(const alignn_model_desc* d, const alignn_model_batch* b, alignn_stream_t stream) {
-    Plan pl;
-    Ctx c{d, b, reinterpret_cast<char*>(4096)};  // (any non-null base: pointers are compared with NULL, never used)
-    set_streams(c, stream);
-    Tape tp;
-    run_forward(c, tp, nullptr);
-    pl.fwd_persist = c.off;
-    for (int i = 0; i < 4; ++i) pl.peak_fwd[i] = c.speak[i];
-    if (!c.unsupported) run_backward(c, tp, nullptr);
-    pl.all_persist = c.off;
-    for (int i = 0; i < 4; ++i) pl.peak_all[i] = c.speak[i];
-    pl.unsupported = c.unsupported;
-    pl.line = c.unsupported_line;
-    pl.rc = c.rc;
-    return pl;
-}
-
 bool ff_ok(const alignn_model_desc* d, const alignn_model_batch* b, const alignn_ff_desc* f) {
     if (!desc_ok(d, b) || f == nullptr || d->norm != 1 || d->out_features != 1) return false;
     if (b->g.out_ptr == nullptr || b->g.out_slot == nullptr || b->lg.out_ptr == nullptr || b->lg.out_slot == nullptr) return false;
@@ -1653,22 +1489,51 @@ bool ff_ok(const alignn_model_desc* d, const alignn_model_batch* b, const alignn
     return true;
 }
 
-Plan make_ff_plan(const alignn_model_desc* d, const alignn_model_batch* b, const alignn_ff_desc* f, alignn_stream_t stream) {
+// the layout of alignn_model_fwd + _bwd, or - with a force-field description - of alignn_ff_eval + _grad
+Plan make_plan(const alignn_model_desc* d, const alignn_model_batch* b, const alignn_ff_desc* f, alignn_stream_t stream) {
     Plan pl;
-    Ctx c{d, b, reinterpret_cast<char*>(4096)};
+    Ctx c{d, b, reinterpret_cast<char*>(4096)};  // (any non-null base: pointers are compared with NULL, never used)
     c.ff = f;
     set_streams(c, stream);
     Tape tp;
-    run_ff_eval(c, tp, nullptr, nullptr, nullptr);
+    if (f != nullptr)
+        run_ff_eval(c, tp, nullptr, nullptr, nullptr);
+    else
+        run_forward(c, tp, nullptr);
     pl.fwd_persist = c.off;
     for (int i = 0; i < 4; ++i) pl.peak_fwd[i] = c.speak[i];
-    if (!c.unsupported) run_ff_dual(c, tp, nullptr, nullptr, nullptr);
+    if (!c.unsupported) {
+        if (f != nullptr)
+            run_ff_dual(c, tp, nullptr, nullptr, nullptr);
+        else
+            run_backward(c, tp, nullptr);
+    }
     pl.all_persist = c.off;
     for (int i = 0; i < 4; ++i) pl.peak_all[i] = c.speak[i];
     pl.unsupported = c.unsupported;
     pl.line = c.unsupported_line;
     pl.rc = c.rc;
     return pl;
+}
+
+// What a launching entry point does to its context before it walks the model: the caller's block and streams, the scratch
+// regions of the plan - the full layout, or, where the forward alone is enough (`need_full` == false: a forward nobody will
+// differentiate, MD, validation) and the block is too small for more, the forward's - and the event pool if there is a helper
+// stream.  `pl` == NULL: inference, which has no plan, no scratch and no helper stream but lane T.  -> 0, or what the entry
+// point returns
+int open_ctx(Ctx& c, const Plan* pl, size_t workspace_bytes, alignn_stream_t stream, bool need_full) {
+    c.cap = workspace_bytes;
+    set_streams(c, stream);
+    if (pl == nullptr)
+        c.side = c.aux = c.main;
+    else {
+        if (pl->unsupported) return (int)hipErrorNotSupported;
+        const bool full = workspace_bytes >= pl->total();
+        if (!full && (need_full || workspace_bytes < pl->fwd_total())) return (int)hipErrorInvalidValue;
+        pl->place_scratch(c, full);
+    }
+    if ((c.T != c.main || c.side != c.main || c.aux != c.main) && !take_pool(c)) return (int)hipErrorNotInitialized;
+    return 0;
 }
 
 }  // namespace
@@ -1692,7 +1557,7 @@ int alignn_debug_allocs(size_t* out, int cap) {
 int alignn_ff_plan(const alignn_model_desc* d, const alignn_model_batch* b, const alignn_ff_desc* f, size_t* eval_bytes,
                    size_t* total_bytes) {
     if (!ff_ok(d, b, f) || eval_bytes == nullptr || total_bytes == nullptr) return (int)hipErrorInvalidValue;
-    Plan pl = make_ff_plan(d, b, f, nullptr);
+    Plan pl = make_plan(d, b, f, nullptr);
     if (pl.unsupported) {
         if (getenv("ALIGNN_AMD_DEBUG")) fprintf(stderr, "alignn_ff_plan: kernel choice not carried (model.hip:%d)\n", pl.line);
         return (int)hipErrorNotSupported;
@@ -1705,20 +1570,11 @@ int alignn_ff_plan(const alignn_model_desc* d, const alignn_model_batch* b, cons
 int alignn_ff_eval(const alignn_model_desc* d, const alignn_model_batch* b, const alignn_ff_desc* f, void* workspace,
                    size_t workspace_bytes, float* out, float* forces, float* stress, alignn_stream_t stream) {
     if (!ff_ok(d, b, f) || workspace == nullptr || out == nullptr || forces == nullptr) return (int)hipErrorInvalidValue;
-    const Plan pl = make_ff_plan(d, b, f, stream);
-    if (pl.unsupported) return (int)hipErrorNotSupported;
+    const Plan pl = make_plan(d, b, f, stream);
     Ctx c{d, b, static_cast<char*>(workspace)};
-    c.cap = workspace_bytes;
-    c.launch = true;
     c.ff = f;
-    set_streams(c, stream);
-    if (workspace_bytes >= pl.total())
-        pl.place_scratch(c, true);
-    else if (workspace_bytes >= pl.fwd_total())
-        pl.place_scratch(c, false);  // (values only: MD, validation)
-    else
-        return (int)hipErrorInvalidValue;
-    if ((c.T != c.main || c.side != c.main || c.aux != c.main) && !take_pool(c)) return (int)hipErrorNotInitialized;
+    if (const int rc = open_ctx(c, &pl, workspace_bytes, stream, false)) return rc;
+    c.launch = true;
     Tape tp;
     run_ff_eval(c, tp, out, forces, stress);
     if (c.unsupported) return (int)hipErrorNotSupported;
@@ -1733,15 +1589,10 @@ int alignn_ff_grad(const alignn_model_desc* d, const alignn_model_batch* b, cons
     if (gsink != nullptr && (gsink_t == nullptr || sink_floats <= 0 || (sink_floats & 3) || !aligned16(gsink) ||
                              !aligned16(gsink_t)))
         return (int)hipErrorInvalidValue;
-    const Plan pl = make_ff_plan(d, b, f, stream);
-    if (pl.unsupported) return (int)hipErrorNotSupported;
-    if (workspace_bytes < pl.total()) return (int)hipErrorInvalidValue;
+    const Plan pl = make_plan(d, b, f, stream);
     Ctx c{d, b, static_cast<char*>(workspace)};
-    c.cap = workspace_bytes;
     c.ff = f;
-    set_streams(c, stream);
-    pl.place_scratch(c, true);
-    if ((c.T != c.main || c.side != c.main || c.aux != c.main) && !take_pool(c)) return (int)hipErrorNotInitialized;
+    if (const int rc = open_ctx(c, &pl, workspace_bytes, stream, true)) return rc;
     Tape tp;
     run_ff_eval(c, tp, nullptr, nullptr, nullptr);  // (plan only: where the evaluation left its tape)
     if (c.unsupported) return (int)hipErrorNotSupported;
@@ -1788,7 +1639,7 @@ size_t alignn_model_sizeof(int which) {
 
 int alignn_model_plan(const alignn_model_desc* d, const alignn_model_batch* b, size_t* fwd_bytes, size_t* total_bytes) {
     if (!desc_ok(d, b) || fwd_bytes == nullptr || total_bytes == nullptr) return (int)hipErrorInvalidValue;
-    Plan pl = make_plan(d, b, nullptr);
+    Plan pl = make_plan(d, b, nullptr, nullptr);
     if (pl.unsupported) {
         if (getenv("ALIGNN_AMD_DEBUG")) fprintf(stderr, "alignn_model_plan: kernel choice not carried (model.hip:%d)\n", pl.line);
         return (int)hipErrorNotSupported;
@@ -1803,21 +1654,12 @@ int alignn_model_fwd(const alignn_model_desc* d, const alignn_model_batch* b, vo
     if (!desc_ok(d, b) || workspace == nullptr || out == nullptr) return (int)hipErrorInvalidValue;
     const bool timing = getenv("ALIGNN_AMD_DEBUG_TIME") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    const Plan pl = make_plan(d, b, stream);
+    const Plan pl = make_plan(d, b, nullptr, stream);
     const auto t1 = std::chrono::steady_clock::now();
-    if (pl.unsupported) return (int)hipErrorNotSupported;
     Ctx c{d, b, static_cast<char*>(workspace)};
-    c.cap = workspace_bytes;
+    if (const int rc = open_ctx(c, &pl, workspace_bytes, stream, false)) return rc;
     c.launch = true;
     c.timing = timing;
-    set_streams(c, stream);
-    if (workspace_bytes >= pl.total())
-        pl.place_scratch(c, true);
-    else if (workspace_bytes >= pl.fwd_total())
-        pl.place_scratch(c, false);  // (a forward nobody will differentiate: the tape and the forward's scratch only)
-    else
-        return (int)hipErrorInvalidValue;
-    if ((c.T != c.main || c.side != c.main || c.aux != c.main) && !take_pool(c)) return (int)hipErrorNotInitialized;
     Tape tp;
     run_forward(c, tp, out);
     if (timing) {
@@ -1834,15 +1676,10 @@ int alignn_model_bwd(const alignn_model_desc* d, const alignn_model_batch* b, vo
     if (!desc_ok(d, b) || workspace == nullptr || g_out == nullptr) return (int)hipErrorInvalidValue;
     const bool timing = getenv("ALIGNN_AMD_DEBUG_TIME") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    const Plan pl = make_plan(d, b, stream);
-    if (pl.unsupported) return (int)hipErrorNotSupported;
-    if (workspace_bytes < pl.total()) return (int)hipErrorInvalidValue;
+    const Plan pl = make_plan(d, b, nullptr, stream);
     Ctx c{d, b, static_cast<char*>(workspace)};
-    c.cap = workspace_bytes;
+    if (const int rc = open_ctx(c, &pl, workspace_bytes, stream, true)) return rc;
     c.timing = timing;
-    set_streams(c, stream);
-    pl.place_scratch(c, true);
-    if ((c.T != c.main || c.side != c.main || c.aux != c.main) && !take_pool(c)) return (int)hipErrorNotInitialized;
     Tape tp;
     run_forward(c, tp, nullptr);  // (plan only: where the forward left its tape)
     if (c.unsupported) return (int)hipErrorNotSupported;
@@ -1870,10 +1707,8 @@ int alignn_model_infer(const alignn_model_desc* d, const alignn_model_batch* b, 
                        float* out, alignn_stream_t stream) {
     if (!desc_ok(d, b) || workspace == nullptr || out == nullptr) return (int)hipErrorInvalidValue;
     Ctx c{d, b, static_cast<char*>(workspace)};
-    c.cap = workspace_bytes;
+    if (const int rc = open_ctx(c, nullptr, workspace_bytes, stream, false)) return rc;
     c.launch = true;
-    set_streams(c, stream);
-    if (c.T != c.main && !take_pool(c)) return (int)hipErrorNotInitialized;
     run_infer(c, out);
     if (c.unsupported) return (int)hipErrorNotSupported;
     return c.rc;
