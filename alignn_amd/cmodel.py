@@ -17,6 +17,7 @@ features, kernel choices the C side does not carry (``hipErrorNotSupported``) - 
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 import time
 import weakref
@@ -91,6 +92,22 @@ class disabled:
         global ENABLED
         ENABLED = self.prev
         return False
+
+
+# What a cached plan depends on - not a hand-picked list per planner (a field missing from one hands a later step the byte
+# count of another kernel choice): EVERY field Binding.set_mode() writes, every integer switch of alignn_ff_desc, every graph
+# array by presence.  What refresh() writes stays out: refresh() empties the cache.
+MODE_FIELDS = ("lane_T", "lane_min_rows", "side", "side_min_rows", "aux", "angle_fused", "reuse_tape", "dw_fused")
+_MODE_OF = operator.attrgetter(*MODE_FIELDS)
+_ARRAYS_OF = operator.attrgetter(*(n for n, t in GraphCSR._fields_ if t is C.c_void_p))
+_SWITCHES_OF = operator.attrgetter(*(n for n, t in FFDesc._fields_ if t is C.c_int32))
+
+
+def plan_key(kind, desc, mb, ffd=None):
+    """The cache key of ``Binding.plan``, from the bare structs"""
+    g, lg = mb.g, mb.lg
+    key = (kind, g.n, g.m, lg.m, mb.B, lg.dense_max_src, lg.n_groups) + tuple(map(bool, _ARRAYS_OF(g) + _ARRAYS_OF(lg)))
+    return key + _MODE_OF(desc) + (_SWITCHES_OF(ffd) if ffd is not None else ())
 
 
 class Binding:
@@ -336,21 +353,23 @@ class Binding:
         mb.graph_ptr, mb.B = b.graph_ptr.data_ptr(), b.batch_size
         return mb
 
-    def plan(self, mb):
-        key = (mb.g.n, mb.g.m, mb.lg.m, mb.B, mb.lg.dense_max_src, bool(mb.lg.grp_seg_ptr), bool(mb.lg.seg_rank),
-               bool(mb.g.seg_node), bool(self.desc.lane_T), bool(self.desc.side), bool(self.desc.aux),
-               self.desc.side_min_rows, self.desc.lane_min_rows, self.desc.angle_fused, self.desc.reuse_tape, self.desc.dw_fused)
+    def plan(self, kind, mb, ffd=None):
+        """Workspace bytes -> (forward / evaluation alone, with the backward) from alignn_model_plan ("model"), alignn_ff_plan
+        ("ff") or alignn_model_infer_workspace ("infer": one size), cached; (None, None): a kernel choice is not carried."""
+        key = plan_key(kind, self.desc, mb, ffd)
         hit = self.plans.get(key)
         if hit is None:
-            fwd, tot = C.c_size_t(0), C.c_size_t(0)
-            rc = _lib_model().alignn_model_plan(self.desc_addr, C.addressof(mb), C.addressof(fwd), C.addressof(tot))
-            STATS["plans"] += 1
-            if rc == _NOT_SUPPORTED:
-                hit = (None, None)
+            lib, first, tot = _lib_model(), C.c_size_t(0), C.c_size_t(0)
+            args = (self.desc_addr, C.addressof(mb)) + ((C.addressof(ffd),) if kind == "ff" else ())
+            if kind == "infer":
+                rc, first.value = 0, lib.alignn_model_infer_workspace(*args)
+                tot.value = first.value
             else:
-                _lib.check(rc, "model_plan")
-                hit = (fwd.value, tot.value)
-            self.plans[key] = hit
+                rc = (lib.alignn_ff_plan if kind == "ff" else lib.alignn_model_plan)(*args, C.addressof(first), C.addressof(tot))
+            STATS["plans"] += kind != "infer"  # (calls of the two planners; the inference size was never counted)
+            if rc != _NOT_SUPPORTED:
+                _lib.check(rc, kind + "_plan")
+            hit = self.plans[key] = (first.value, tot.value) if rc == 0 and tot.value else (None, None)
         return hit
 
     def take_arena(self, nbytes, capturing, need_backward):
@@ -417,15 +436,15 @@ class _Lease:
 
 def release_captured_workspaces(model) -> int:
     """Tell the binding that every hipGraph captured over ``model`` so far has been destroyed: the workspace blocks those graphs
-    replayed into are no longer kept alive (-> number of blocks released).  Without this call a block is kept for the life of
-    the model - a replay into freed memory would be silent corruption, and the binding cannot see a graph die."""
-    b = model_cache(model).get("binding")
-    if b is None:
-        return 0
-    n = len(b.pinned)
-    if b.arena is not None and any(b.arena is a for a in b.pinned) and b.spare is not None and not b.arena_busy:
-        b.arena, b.spare = b.spare, None
-    b.pinned = []
+    replayed into are no longer kept alive (-> number of blocks released, over every binding of the model: slot 0 and those of
+    ``cmodel.slot(k)``).  Without this call a block is kept for the life of the model - a replay into freed memory would be
+    silent corruption, and the binding cannot see a graph die."""
+    n = 0
+    for b in [v for k, v in model_cache(model).items() if k.startswith("binding") and isinstance(v, Binding)]:
+        n += len(b.pinned)
+        if b.arena is not None and any(b.arena is a for a in b.pinned) and b.spare is not None and not b.arena_busy:
+            b.arena, b.spare = b.spare, None
+        b.pinned = []
     return n
 
 
@@ -435,7 +454,7 @@ _SLOT = [0]
 class slot:
     """``with cmodel.slot(k):`` - forwards issued inside use the model's k-th binding: its own workspace block and its own helper
     streams (lane T, side, aux).  Two forwards of ONE model under different slots, each on its own torch stream, overlap on the GPU
-    - what alignn_amd/microbatch.py uses to run the bond-row chains of one part of a batch under the triplet-row kernels of
+    - what tools/microbatch_probe.py uses to run the bond-row chains of one part of a batch under the triplet-row kernels of
     another.  (Slot 0 is the default; a backward finds its binding through the forward's context, not through the slot.)"""
 
     def __init__(self, k):
@@ -459,85 +478,118 @@ def binding_of(model) -> Binding:
     return b
 
 
+# ---- what the two autograd functions share (inputs: the parameters; one node per forward)
+def _keep_tape(ctx, bind, mb, ffd, keep, arena, arena_bytes, lease):
+    owns, gen = lease
+    ctx.bind, ctx.mb, ctx.ffd, ctx.keep, ctx.arena, ctx.arena_bytes = bind, mb, ffd, keep, arena, arena_bytes
+    ctx.lease, ctx.sig, ctx.tape_spent = _Lease(bind, owns), bind.sig, False
+    ctx.shared_gen = gen if arena is bind.arena else 0  # (0: a block of its own - nobody else writes into it)
+
+
+def _check_tape(ctx):
+    """May a backward still read what its forward left in the workspace?"""
+    bind = ctx.bind
+    if ctx.arena is None:
+        raise RuntimeError("alignn_amd.cmodel: backward called twice on a forward that ran in a workspace of its own "
+                           "(released after the first backward)")
+    if ctx.tape_spent:  # (set by _launch_backward for the calls that write over the tape: never for the force field)
+        raise RuntimeError("alignn_amd.cmodel: second backward through the same forward - the first one reused parts of the "
+                           "forward's workspace (cmodel.REUSE_TAPE); set alignn_amd.cmodel.REUSE_TAPE = False (or "
+                           "ALIGNN_AMD_REUSE_TAPE=0) for loss.backward(retain_graph=True) followed by another backward")
+    if ctx.shared_gen and (bind.arena is not ctx.arena or bind.arena_gen != ctx.shared_gen):
+        # loss.backward(retain_graph=True) followed by another backward is fine as long as the forward's tape is intact
+        # (the backward only reads it); once another forward has taken the shared workspace it is not.  The generation tells:
+        # only take_arena() sets ``arena_busy`` and it bumps ``arena_gen`` with it, so at an unchanged generation a busy
+        # block is busy on behalf of THIS forward ("busy, and the lease is not ours" cannot happen and is not asked).
+        raise RuntimeError("alignn_amd.cmodel: backward through a forward whose workspace another forward has reused "
+                           "(retain_graph across model calls: set ALIGNN_AMD_CMODEL=0 for the per-operator path)")
+    if bind.sig != ctx.sig:
+        raise RuntimeError("alignn_amd.cmodel: the model's parameters moved between forward and backward")
+
+
+def _grad_destinations(bind, rows, stat, sink_ok=None):
+    """Point every gradient field of the description at its destination -> (flat buffer, ``rows`` x grad_floats, sink plan or
+    None): straight into the optimizer's packed gradient buffer where it has one, ``sink_ok`` accepts it and this is the first
+    gradient of the step (p.grad is None everywhere: otherwise autograd ACCUMULATES and the slot already holds the earlier
+    gradient - counted in ``STATS[stat]``), else into the flat buffer's first row."""
+    gflat = torch.empty(rows * bind.grad_floats, dtype=torch.float32, device=bind.device)
+    base = gflat.data_ptr()
+    plan = bind.sink_plan() if GRAD_SINK else None
+    if plan is not None and (any(p.grad is not None for p in bind.params) or not (sink_ok is None or sink_ok(bind.sink()))):
+        plan = None
+    for k, (owner, field, off) in enumerate(bind.grad_fields):
+        dest = plan[0][k] if plan is not None else None
+        setattr(owner, field, dest if dest is not None else base + 4 * off)
+    STATS[stat] = STATS.get(stat, 0) + (plan is not None)
+    if plan is not None:
+        bind.sink().sink_in_flight = True
+    return gflat, plan
+
+
+def _launch_backward(ctx, what, stat, spends_tape, call):
+    """The C call of a backward (``call() -> hipError``); afterwards the next forward may take the shared block (a second backward
+    of THIS graph goes through _check_tape again) and a block of its own (up to 20 GB) is not kept for as long as the graph
+    object lives.  ``spends_tape``: the call writes over the tape where ``desc.reuse_tape`` says so (csrc/model.hip
+    edge_grad_buffer does only without a force-field head: never derive this from ``desc.reuse_tape`` alone)."""
+    bind = ctx.bind
+    bind.set_mode()
+    t0 = time.perf_counter() if TIMING is not None else 0.0
+    try:
+        _lib.check(call(), what)
+    finally:
+        if TIMING is not None:
+            TIMING["cbwd"] = TIMING.get("cbwd", 0.0) + time.perf_counter() - t0
+        ctx.lease.release()
+        if not ctx.shared_gen:
+            ctx.arena = None
+    STATS[stat] = STATS.get(stat, 0) + 1
+    ctx.tape_spent = spends_tape and bool(bind.desc.reuse_tape)
+
+
+def _grad_views(bind, gflat, plan):
+    """-> one gradient per parameter: its slot of the sink where the backward wrote there, else its piece of the flat buffer"""
+    n = bind.grad_floats  # (a second row is alignn_ff_grad's scratch)
+    pieces = (gflat if gflat.numel() == n else gflat[:n]).split_with_sizes(bind.sizes)
+    slots = plan[1] if plan is not None else None
+    grads = []
+    for j, (i, shape, dead) in enumerate(zip(bind.keep, bind.shapes, bind.no_grad)):
+        if dead:
+            grads.append(None)
+        elif slots is not None and slots[j] is not None:
+            # (a FRESH view object: autograd's AccumulateGrad adopts an incoming gradient only if nobody else holds it -
+            # a cached view would be cloned, param by param)
+            grads.append(slots[j].view(shape))
+        else:
+            grads.append(pieces[i] if len(shape) == 1 else pieces[i].view(shape))
+    return tuple(grads)
+
+
 class _ModelFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, bind, mb, keep, arena, arena_bytes, lease, *params):
-        lib = _lib_model()
+    def forward(ctx, bind, mb, ffd, keep, arena, arena_bytes, lease, *params):
         out = torch.empty(mb.B, bind.desc.out_features, dtype=torch.float32, device=bind.device)
         t0 = time.perf_counter() if TIMING is not None else 0.0
-        _lib.check(lib.alignn_model_fwd(bind.desc_addr, C.addressof(mb), arena.data_ptr(), arena_bytes, out.data_ptr(),
-                                        _lib.stream()), "model_fwd")
+        _lib.check(_lib_model().alignn_model_fwd(bind.desc_addr, C.addressof(mb), arena.data_ptr(), arena_bytes, out.data_ptr(),
+                                                 _lib.stream()), "model_fwd")
         if TIMING is not None:
             TIMING["cfwd"] = TIMING.get("cfwd", 0.0) + time.perf_counter() - t0
         STATS["fwd"] += 1
-        owns, gen = lease
-        ctx.bind, ctx.mb, ctx.keep, ctx.arena, ctx.arena_bytes, ctx.lease = bind, mb, keep, arena, arena_bytes, _Lease(bind, owns)
-        ctx.shared_gen = gen if arena is bind.arena else 0  # (0: a block of its own - nobody else writes into it)
-        ctx.sig = bind.sig
+        _keep_tape(ctx, bind, mb, ffd, keep, arena, arena_bytes, lease)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        bind = ctx.bind
-        lib = _lib_model()
-        if ctx.arena is None:
-            raise RuntimeError("alignn_amd.cmodel: backward called twice on a forward that ran in a workspace of its own "
-                               "(released after the first backward)")
-        if getattr(ctx, "tape_spent", False):
-            raise RuntimeError("alignn_amd.cmodel: second backward through the same forward - the first one reused parts of the "
-                               "forward's workspace (cmodel.REUSE_TAPE); set alignn_amd.cmodel.REUSE_TAPE = False (or "
-                               "ALIGNN_AMD_REUSE_TAPE=0) for loss.backward(retain_graph=True) followed by another backward")
-        if ctx.shared_gen and (bind.arena is not ctx.arena or bind.arena_gen != ctx.shared_gen or
-                               (bind.arena_busy and not ctx.lease.owns)):
-            # loss.backward(retain_graph=True) followed by another backward is fine as long as the forward's tape is intact
-            # (the backward only reads it); once another forward has taken the shared workspace it is not
-            raise RuntimeError("alignn_amd.cmodel: backward through a forward whose workspace another forward has reused "
-                               "(retain_graph across model calls: set ALIGNN_AMD_CMODEL=0 for the per-operator path)")
-        if bind.sig != ctx.sig:
-            raise RuntimeError("alignn_amd.cmodel: the model's parameters moved between forward and backward")
+        bind, lib = ctx.bind, _lib_model()
+        _check_tape(ctx)
         t_in = time.perf_counter() if TIMING is not None else 0.0
         g_out = g_out.contiguous()
-        gflat = torch.empty(bind.grad_floats, dtype=torch.float32, device=bind.device)
-        base = gflat.data_ptr()
-        # straight into the optimizer's packed gradient buffer where it has one and this is the first gradient of the step
-        # (p.grad is None everywhere: otherwise autograd ACCUMULATES and the slot already holds the earlier gradient)
-        plan = bind.sink_plan() if GRAD_SINK else None
-        if plan is not None and any(p.grad is not None for p in bind.params):
-            plan = None
-        for k, (owner, field, off) in enumerate(bind.grad_fields):
-            dest = plan[0][k] if plan is not None else None
-            setattr(owner, field, dest if dest is not None else base + 4 * off)
-        STATS["sink"] = STATS.get("sink", 0) + (plan is not None)
-        if plan is not None:
-            bind.sink().sink_in_flight = True
-        bind.set_mode()
-        t0 = time.perf_counter() if TIMING is not None else 0.0
-        try:
-            _lib.check(lib.alignn_model_bwd(bind.desc_addr, C.addressof(ctx.mb), ctx.arena.data_ptr(), ctx.arena_bytes,
-                                            g_out.data_ptr(), _lib.stream()), "model_bwd")
-        finally:
-            if TIMING is not None:
-                TIMING["cbwd"] = TIMING.get("cbwd", 0.0) + time.perf_counter() - t0
-            ctx.lease.release()  # (the next forward may take the block; a second backward of THIS graph re-checks above)
-            if not ctx.shared_gen:
-                ctx.arena = None  # a block of its own (up to 20 GB): do not keep it for as long as the graph object lives
-        STATS["bwd"] += 1
-        ctx.tape_spent = bool(bind.desc.reuse_tape)
-        pieces = gflat.split_with_sizes(bind.sizes)
-        grads = []
-        slots = plan[1] if plan is not None else None
-        for j, (i, shape, dead) in enumerate(zip(bind.keep, bind.shapes, bind.no_grad)):
-            if dead:
-                grads.append(None)
-            elif slots is not None and slots[j] is not None:
-                # (a FRESH view object: autograd's AccumulateGrad adopts an incoming gradient only if nobody else holds it -
-                # a cached view would be cloned, param by param)
-                grads.append(slots[j].view(shape))
-            else:
-                grads.append(pieces[i] if len(shape) == 1 else pieces[i].view(shape))
+        gflat, plan = _grad_destinations(bind, 1, "sink")
+        _launch_backward(ctx, "model_bwd", "bwd", True, lambda: lib.alignn_model_bwd(
+            bind.desc_addr, C.addressof(ctx.mb), ctx.arena.data_ptr(), ctx.arena_bytes, g_out.data_ptr(), _lib.stream()))
+        grads = _grad_views(bind, gflat, plan)
         if TIMING is not None:
             TIMING["bwd_py"] = TIMING.get("bwd_py", 0.0) + time.perf_counter() - t_in
-        return (None,) * 6 + tuple(grads)
+        return (None,) * 7 + grads
 
 
 def applicable(model, b) -> bool:
@@ -622,57 +674,65 @@ def _structure_ok(model, b, need_grad, flavour="ALIGNN") -> bool:
     return True
 
 
+def _prepare(model, b, kind, need_h=True, h=None, backward=False):
+    """What every entry point does before its C call -> (bind, batch struct, force-field switches or None, keep-alive tuple,
+    workspace, its bytes, (owns the shared block, its generation)), or None when the C side does not carry a kernel choice this
+    (model, batch) needs.  ``kind``: the call family ("model", "ff", "infer"); ``need_h``: it reads bond-angle cosines - ``h``
+    instead of ``b.h`` if given; ``backward``: one follows (its share of the workspace, the shared block leased until it ran)."""
+    bind = binding_of(model)
+    bind.refresh()
+    capturing = bind.set_mode()
+    mb = bind.batch_struct(b)
+    af, r = b.atom_features.contiguous(), b.r.contiguous()
+    h = (b.h if h is None else h).contiguous() if need_h else None
+    if af.shape != (b.g.n_nodes, bind.desc.atom_in) or r.shape != (b.g.n_edges, 3) or (h is not None and h.numel() != b.lg.n_edges):
+        raise ValueError("feature rows do not match the graphs")
+    mb.atom_features, mb.r, mb.h = af.data_ptr(), r.data_ptr(), ptr(h)
+    ffd, vol = _ff_desc(model, b) if kind == "ff" else (None, None)
+    first, total = bind.plan(kind, mb, ffd)
+    if total is None:
+        return None
+    nbytes = total if backward else first
+    arena, owns, gen = bind.take_arena(nbytes, capturing, backward)
+    if kind != "infer":
+        # a forward of a training step starts a new weight generation, so that its backward never meets the slice image or
+        # max|w| of an earlier step (ops._WGEN).  Inference has no backward and moves no weight: the images made for the
+        # weights' current version stay good from one evaluation to the next, and a new generation would slice them again.
+        ops.new_weight_generation()
+    return bind, mb, ffd, (b, af, r, h, vol), arena, nbytes, (owns, gen)
+
+
+def _apply(fn, prep):
+    """One autograd node over a prepared call (inputs: the parameters)."""
+    bind, (owns, _gen) = prep[0], prep[-1]
+    try:
+        return fn.apply(*prep, *bind.params)
+    except BaseException:
+        if owns:  # (the forward raised before a lease existed: hand the shared workspace back)
+            bind.arena_busy = False
+        raise
+
+
 def forward(model, b, h=None):
     """-> ``fc(AvgPooling(...))`` [B, out_features] of a training-mode forward, or None when the C side does not carry a
     kernel choice this (model, batch) needs (the caller then takes the per-operator path).  ``h``: bond-angle cosines to use
     instead of ``b.h`` (ALIGNNAtomWise with lg_on_fly recomputes them from the bond vectors)."""
-    bind = binding_of(model)
     with _lib.device_guard(model.fc.weight):
-        bind.refresh()
-        capturing = bind.set_mode()
-        mb = bind.batch_struct(b)
-        af, r, h = b.atom_features.contiguous(), b.r.contiguous(), (b.h if h is None else h).contiguous()
-        if af.shape != (b.g.n_nodes, bind.desc.atom_in) or r.shape != (b.g.n_edges, 3) or h.numel() != b.lg.n_edges:
-            raise ValueError("feature rows do not match the graphs")
-        mb.atom_features, mb.r, mb.h = af.data_ptr(), r.data_ptr(), h.data_ptr()
-        fwd_bytes, total = bind.plan(mb)
-        if total is None:
-            return None
-        need_bwd = torch.is_grad_enabled()
-        nbytes = total if need_bwd else fwd_bytes
-        arena, owns, gen = bind.take_arena(nbytes, capturing, need_bwd)
-        ops.new_weight_generation()
-        try:
-            return _ModelFn.apply(bind, mb, (b, af, r, h), arena, nbytes, (owns, gen), *bind.params)
-        except BaseException:
-            if owns:  # (the forward raised before a lease existed: hand the shared workspace back)
-                bind.arena_busy = False
-            raise
+        prep = _prepare(model, b, "model", h=h, backward=torch.is_grad_enabled())
+        return None if prep is None else _apply(_ModelFn, prep)
 
 
 def infer(model, b):
     """-> ``fc(AvgPooling(...))`` [B, out_features] of an eval-mode forward without autograd (one C call), or None when the C
     side does not carry a kernel choice this (model, batch) needs."""
-    bind = binding_of(model)
-    lib = _lib_model()
     with _lib.device_guard(model.fc.weight):
-        bind.refresh()
-        capturing = bind.set_mode()
-        mb = bind.batch_struct(b)
-        af, r, h = b.atom_features.contiguous(), b.r.contiguous(), b.h.contiguous()
-        if af.shape != (b.g.n_nodes, bind.desc.atom_in) or r.shape != (b.g.n_edges, 3) or h.numel() != b.lg.n_edges:
-            raise ValueError("feature rows do not match the graphs")
-        mb.atom_features, mb.r, mb.h = af.data_ptr(), r.data_ptr(), h.data_ptr()
-        key = ("infer", mb.g.n, mb.g.m, mb.lg.m, mb.B, bool(bind.desc.lane_T), bind.desc.lane_min_rows, bind.desc.angle_fused)
-        nbytes = bind.plans.get(key)
-        if nbytes is None:
-            nbytes = bind.plans[key] = lib.alignn_model_infer_workspace(bind.desc_addr, C.addressof(mb))
-        if not nbytes:
+        prep = _prepare(model, b, "infer")
+        if prep is None:
             return None
-        arena, _owns, _gen = bind.take_arena(nbytes, capturing, False)
+        bind, mb, _ffd, _keep, arena, nbytes, _lease = prep
         out = torch.empty(mb.B, bind.desc.out_features, dtype=torch.float32, device=bind.device)
-        _lib.check(lib.alignn_model_infer(bind.desc_addr, C.addressof(mb), arena.data_ptr(), nbytes, out.data_ptr(), _lib.stream()),
-                   "model_infer")
+        _lib.check(_lib_model().alignn_model_infer(bind.desc_addr, C.addressof(mb), arena.data_ptr(), nbytes, out.data_ptr(),
+                                                   _lib.stream()), "model_infer")
         STATS["infer"] = STATS.get("infer", 0) + 1
         return out
 
@@ -705,46 +765,23 @@ def _ff_desc(model, b):
     return f, vol
 
 
-def _ff_prepare(model, b, need_grad):
-    """-> (bind, mb, ffd, keep-alive tuple, arena, bytes, (owns, gen)) or None (kernel choice not carried)"""
-    bind = binding_of(model)
-    bind.refresh()
-    capturing = bind.set_mode()
-    mb = bind.batch_struct(b)
-    af, r = b.atom_features.contiguous(), b.r.contiguous()
-    h = None if model.config.lg_on_fly else b.h.contiguous()
-    if af.shape != (b.g.n_nodes, bind.desc.atom_in) or r.shape != (b.g.n_edges, 3) or (h is not None and h.numel() != b.lg.n_edges):
-        raise ValueError("feature rows do not match the graphs")
-    mb.atom_features, mb.r, mb.h = af.data_ptr(), r.data_ptr(), ptr(h)
-    ffd, vol = _ff_desc(model, b)
-    key = ("ff", mb.g.n, mb.g.m, mb.lg.m, mb.B, mb.lg.dense_max_src, bool(mb.lg.grp_seg_ptr), bool(mb.lg.seg_rank),
-           bool(bind.desc.lane_T), bool(bind.desc.side), bool(bind.desc.aux), bind.desc.side_min_rows, bind.desc.lane_min_rows,
-           ffd.lg_on_fly, ffd.has_stress, ffd.dense_lg_reverse)
-    hit = bind.plans.get(key)
-    if hit is None:
-        ev, tot = C.c_size_t(0), C.c_size_t(0)
-        rc = _lib_model().alignn_ff_plan(bind.desc_addr, C.addressof(mb), C.addressof(ffd), C.addressof(ev), C.addressof(tot))
-        STATS["plans"] += 1
-        if rc == _NOT_SUPPORTED:
-            hit = (None, None)
-        else:
-            _lib.check(rc, "ff_plan")
-            hit = (ev.value, tot.value)
-        bind.plans[key] = hit
-    if hit[1] is None:
-        return None
-    nbytes = hit[1] if need_grad else hit[0]
-    arena, owns, gen = bind.take_arena(nbytes, capturing, need_grad)
-    ops.new_weight_generation()
-    return bind, mb, ffd, (b, af, r, h, vol), arena, nbytes, (owns, gen)
-
-
-def _ff_outputs(bind, mb, ffd):
+def _ff_eval_call(bind, mb, ffd, arena, arena_bytes):
+    """alignn_ff_eval into fresh outputs -> (out [B], forces [N, 3], stresses [B, 3, 3] or None)"""
     dev = bind.device
     out = torch.empty(mb.B, dtype=torch.float32, device=dev)
     forces = torch.empty(mb.g.n, 3, dtype=torch.float32, device=dev)
     stress = torch.empty(mb.B, 3, 3, dtype=torch.float32, device=dev) if ffd.has_stress else None
+    _lib.check(_lib_model().alignn_ff_eval(bind.desc_addr, C.addressof(mb), C.addressof(ffd), arena.data_ptr(), arena_bytes,
+                                           out.data_ptr(), forces.data_ptr(), ptr(stress), _lib.stream()), "ff_eval")
+    STATS["ff_eval"] = STATS.get("ff_eval", 0) + 1
     return out, forces, stress
+
+
+def _ff_sink_ok(sink):
+    """alignn_ff_grad adds the tangent halves over the optimizer's WHOLE packed buffer, with float4 accesses"""
+    buf = getattr(sink, "_grad_all", None)
+    return (buf is not None and buf.dtype == torch.float32 and buf.numel() % 4 == 0 and buf.data_ptr() % 16 == 0
+            and buf.is_contiguous())
 
 
 class _FFFn(torch.autograd.Function):
@@ -754,15 +791,8 @@ class _FFFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, bind, mb, ffd, keep, arena, arena_bytes, lease, *params):
-        lib = _lib_model()
-        out, forces, stress = _ff_outputs(bind, mb, ffd)
-        _lib.check(lib.alignn_ff_eval(bind.desc_addr, C.addressof(mb), C.addressof(ffd), arena.data_ptr(), arena_bytes,
-                                      out.data_ptr(), forces.data_ptr(), ptr(stress), _lib.stream()), "ff_eval")
-        STATS["ff_eval"] = STATS.get("ff_eval", 0) + 1
-        owns, gen = lease
-        ctx.bind, ctx.mb, ctx.ffd, ctx.keep, ctx.arena, ctx.arena_bytes, ctx.lease = bind, mb, ffd, keep, arena, arena_bytes, _Lease(bind, owns)
-        ctx.shared_gen = gen if arena is bind.arena else 0
-        ctx.sig = bind.sig
+        out, forces, stress = _ff_eval_call(bind, mb, ffd, arena, arena_bytes)
+        _keep_tape(ctx, bind, mb, ffd, keep, arena, arena_bytes, lease)
         ctx.has_stress = stress is not None
         if stress is None:
             stress = torch.empty(1, device=out.device)
@@ -771,91 +801,38 @@ class _FFFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_forces, g_stress):
-        bind = ctx.bind
-        lib = _lib_model()
-        if ctx.arena is None:
-            raise RuntimeError("alignn_amd.cmodel: backward called twice on a forward that ran in a workspace of its own")
-        if ctx.shared_gen and (bind.arena is not ctx.arena or bind.arena_gen != ctx.shared_gen):
-            raise RuntimeError("alignn_amd.cmodel: backward through a forward whose workspace another forward has reused "
-                               "(retain_graph across model calls: set ALIGNN_AMD_CMODEL=0 for the per-operator path)")
-        if bind.sig != ctx.sig:
-            raise RuntimeError("alignn_amd.cmodel: the model's parameters moved between forward and backward")
+        bind, lib = ctx.bind, _lib_model()
+        _check_tape(ctx)
         g_out = None if g_out is None else g_out.reshape(-1).to(torch.float32).contiguous()
         g_forces = None if g_forces is None else g_forces.reshape(-1, 3).to(torch.float32).contiguous()
         g_stress = None if (g_stress is None or not ctx.has_stress) else g_stress.reshape(-1, 3, 3).to(torch.float32).contiguous()
-        gflat = torch.empty(2, bind.grad_floats, dtype=torch.float32, device=bind.device)
-        base = gflat.data_ptr()
-        # straight into the optimizer's packed gradient buffer where it has one (as _ModelFn.backward; the tangent halves of the
-        # weight gradients of those blocks go to a scratch twin of the buffer and are added in place by the C call)
-        plan = bind.sink_plan() if GRAD_SINK else None
-        sink_buf = sink_t = None
-        if plan is not None and not any(p.grad is not None for p in bind.params):
-            ref = model_cache(bind.model).get("grad_sink")
-            sink = ref() if ref is not None else None
-            sink_buf = getattr(sink, "_grad_all", None)
-            if (sink_buf is None or sink_buf.dtype != torch.float32 or sink_buf.numel() % 4 or sink_buf.data_ptr() % 16
-                    or not sink_buf.is_contiguous()):
-                sink_buf = None
-        if sink_buf is None:
-            plan = None
-        else:
-            sink_t = torch.empty_like(sink_buf)
-        for k, (owner, field, off) in enumerate(bind.grad_fields):
-            dest = plan[0][k] if plan is not None else None
-            setattr(owner, field, dest if dest is not None else base + 4 * off)
-        STATS["ff_sink"] = STATS.get("ff_sink", 0) + (plan is not None)
-        if plan is not None:
-            bind.sink().sink_in_flight = True
-        bind.set_mode()
-        try:
-            _lib.check(lib.alignn_ff_grad(bind.desc_addr, C.addressof(ctx.mb), C.addressof(ctx.ffd), ctx.arena.data_ptr(),
-                                          ctx.arena_bytes, ptr(g_out), ptr(g_forces), ptr(g_stress), gflat[0].data_ptr(),
-                                          gflat[1].data_ptr(), bind.grad_floats, ptr(sink_buf), ptr(sink_t),
-                                          sink_buf.numel() if sink_buf is not None else 0, _lib.stream()), "ff_grad")
-        finally:
-            ctx.lease.release()
-            if not ctx.shared_gen:
-                ctx.arena = None
-        STATS["ff_grad"] = STATS.get("ff_grad", 0) + 1
-        pieces = gflat[0].split_with_sizes(bind.sizes)
-        grads = []
-        slots = plan[1] if plan is not None else None
-        for j, (i, shape, dead) in enumerate(zip(bind.keep, bind.shapes, bind.no_grad)):
-            if dead:
-                grads.append(None)
-            elif slots is not None and slots[j] is not None:
-                grads.append(slots[j].view(shape))  # (a fresh view object: AccumulateGrad adopts it instead of cloning)
-            else:
-                grads.append(pieces[i] if len(shape) == 1 else pieces[i].view(shape))
-        return (None,) * 7 + tuple(grads)
+        # two rows: the tangent halves of the weight gradients go to the second and are added in place by the C call; those of
+        # the blocks that live in the optimizer's packed buffer go to a scratch twin of that buffer
+        gflat, plan = _grad_destinations(bind, 2, "ff_sink", _ff_sink_ok)
+        sink_buf = bind.sink()._grad_all if plan is not None else None
+        sink_t = None if sink_buf is None else torch.empty_like(sink_buf)
+        n = bind.grad_floats
+        _launch_backward(ctx, "ff_grad", "ff_grad", False, lambda: lib.alignn_ff_grad(
+            bind.desc_addr, C.addressof(ctx.mb), C.addressof(ctx.ffd), ctx.arena.data_ptr(), ctx.arena_bytes, ptr(g_out),
+            ptr(g_forces), ptr(g_stress), gflat.data_ptr(), gflat.data_ptr() + 4 * n, n, ptr(sink_buf), ptr(sink_t),
+            sink_buf.numel() if sink_buf is not None else 0, _lib.stream()))
+        return (None,) * 7 + _grad_views(bind, gflat, plan)
 
 
 def ff_train(model, b):
     """-> (out [B], forces [N, 3], stresses [B, 3, 3] or a placeholder) differentiable w.r.t. the parameters, or None when the C
     side does not carry a kernel choice this (model, batch) needs."""
     with _lib.device_guard(model.fc.weight):
-        prep = _ff_prepare(model, b, True)
-        if prep is None:
-            return None
-        bind, mb, ffd, keep, arena, nbytes, lease = prep
-        try:
-            return _FFFn.apply(bind, mb, ffd, keep, arena, nbytes, lease, *bind.params)
-        except BaseException:
-            if lease[0]:
-                bind.arena_busy = False
-            raise
+        prep = _prepare(model, b, "ff", need_h=not model.config.lg_on_fly, backward=True)
+        return None if prep is None else _apply(_FFFn, prep)
 
 
 def ff_eval(model, b):
     """-> (out, forces, stresses or None) as plain values (MD / calculators: alignn/ff/calculators.py:280-291), ONE C call; None
     when the C side does not carry a kernel choice this (model, batch) needs."""
     with _lib.device_guard(model.fc.weight):
-        prep = _ff_prepare(model, b, False)
+        prep = _prepare(model, b, "ff", need_h=not model.config.lg_on_fly)
         if prep is None:
             return None
         bind, mb, ffd, _keep, arena, nbytes, _lease = prep
-        out, forces, stress = _ff_outputs(bind, mb, ffd)
-        _lib.check(_lib_model().alignn_ff_eval(bind.desc_addr, C.addressof(mb), C.addressof(ffd), arena.data_ptr(), nbytes,
-                                               out.data_ptr(), forces.data_ptr(), ptr(stress), _lib.stream()), "ff_eval")
-        STATS["ff_eval"] = STATS.get("ff_eval", 0) + 1
-        return out, forces, stress
+        return _ff_eval_call(bind, mb, ffd, arena, nbytes)

@@ -196,3 +196,53 @@ def test_where_the_fused_layernorm_passes_apply(monkeypatch):
     assert f(256, 100) == 1 and f(512, 10 ** 7) == 0
     monkeypatch.setenv("ALIGNN_AMD_LN_FUSED", "0")
     assert f(256, 10 ** 7) == 0
+
+
+def test_plan_keys_cover_what_the_planners_read():
+    """``cmodel.plan_key`` is what ``Binding.plan`` caches a planner's answer under: whenever a per-call switch, a force-field
+    switch or a missing graph array changes what the planner says, it must change the key too - else a later step of the same
+    shape under another switch gets the byte count of the earlier one (the force-field key used to lack ``dw_fused``: 39.54 GB
+    with the fused dW pass off, 39.50 GB with it on, at the batch below).  One field at a time against the real planners; the
+    minimum counts keep the test from passing because nothing moved the planners."""
+    import inspect
+    import re
+
+    lib = cmodel._lib_model()
+
+    def model(d, mb, f):
+        return _plan(d, mb)
+
+    def ff(d, mb, f):
+        return _ff_plan(d, mb, f)
+
+    def infer(d, mb, f):
+        return 0, lib.alignn_model_infer_workspace(C.addressof(d), C.addressof(mb))
+
+    desc_edits = [(k, v) for k, v in dict(dw_fused=65536, angle_fused=1, reuse_tape=1, lane_T=None, side=None, aux=None,
+                                          side_min_rows=0, lane_min_rows=1 << 40).items()]
+    ff_flips = ["lg_on_fly", "has_stress", "dense_lg_reverse", "use_penalty"]
+    cases = {"model": (model, 0, (3840, 50712, 676200, 64), 8), "ff": (ff, 1, (3200, 42224, 561792, 16), 7),
+             "infer": (infer, 0, (3840, 50712, 676200, 64), 1)}
+    for kind, (planner, norm, shape, at_least) in cases.items():
+        def answer(edit):
+            (d, _keep), mb, f = _desc(), _batch(*shape), (_ff() if kind == "ff" else None)
+            d.norm = norm
+            edit(d, mb, f)
+            return planner(d, mb, f), cmodel.plan_key(kind, d, mb, f)
+
+        base, base_key = answer(lambda d, mb, f: None)
+        assert base[0] == 0 and base[-1] > 0, (kind, base)
+        edits = {name: (lambda d, mb, f, name=name, v=v: setattr(d, name, v)) for name, v in desc_edits}
+        edits["lg.seg_rank"] = lambda d, mb, f: setattr(mb.lg, "seg_rank", None)
+        if kind == "ff":
+            edits.update({name: (lambda d, mb, f, name=name: setattr(f, name, 1 - getattr(f, name))) for name in ff_flips})
+        moved = []
+        for name, edit in edits.items():
+            got, key = answer(edit)
+            if got != base:
+                moved.append(name)
+                assert key != base_key, (kind, name, base, got)
+        assert len(moved) >= at_least, (kind, moved)
+    # "every field set_mode() writes" stays true when set_mode() learns another one
+    written = set(re.findall(r"\bd\.(\w+) = ", inspect.getsource(cmodel.Binding.set_mode)))
+    assert written == set(cmodel.MODE_FIELDS), written ^ set(cmodel.MODE_FIELDS)

@@ -174,6 +174,34 @@ def test_alternating_captures_and_eager_steps_keep_two_workspace_blocks():
     assert all(torch.isfinite(p.grad).all() for p in model.parameters() if p.grad is not None) and len(ref) > 50
 
 
+def test_release_captured_workspaces_reaches_the_bindings_of_other_slots():
+    """A graph captured under ``cmodel.slot(1)`` pins a block of THAT slot's binding; once the graph is gone
+    ``release_captured_workspaces`` lets it go too, not only the blocks of slot 0."""
+    raw = make_batch(4, 20, seed0=3)
+    batch = GraphBatch.from_raw(raw, device=DEV)
+    target = torch.randn(4, generator=torch.Generator().manual_seed(2)).to(DEV)
+    model = _mk(alignn_layers=2, gcn_layers=2)
+    l1 = torch.nn.functional.l1_loss
+    with cmodel.slot(1):
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            l1(model(batch), target).backward()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        for p in model.parameters():
+            p.grad = None
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            l1(model(batch), target).backward()
+        bind = cmodel.binding_of(model)
+    assert bind is cmodel.model_cache(model)["binding1"] and "binding" not in cmodel.model_cache(model)
+    assert len(bind.pinned) == 1
+    torch.cuda.synchronize()
+    del g
+    assert cmodel.release_captured_workspaces(model) == 1 and bind.pinned == []
+
+
 def test_two_bindings_of_one_model_on_two_streams():
     """``cmodel.slot(k)``: a second binding (workspace + helper streams) of the same model, so that two forwards on two torch
     streams are independent on the GPU; predictions have the bits of the one-binding run, the summed gradients agree."""

@@ -91,6 +91,44 @@ def test_force_training_equals_the_per_operator_path_bit_for_bit(B, atoms):
     assert all(bool(torch.isfinite(t).all()) for t in a.values())
 
 
+def test_switching_the_fused_dw_pass_between_steps_plans_the_workspace_again():
+    """``ops.DGRAD_WGRAD_FUSED`` on, off, on over three steps of ONE model and one batch: the workspace of alignn_ff_plan depends
+    on the switch (fewer bytes with the fused pass), so a plan cached under a key without it hands the second step the first
+    one's smaller byte count and alignn_ff_grad refuses the workspace.  Every step stays on the C calls and gives the gradients
+    of the per-operator path under the same switch sequence, bit for bit."""
+    raw = make_batch(8, 60, seed0=44)
+    assert raw.num_triplets >= ops.DW_MIN_ROWS  # (where the fused dW pass starts to apply)
+    batch = GraphBatch.from_raw(raw, device=DEV)
+    te, tf, ts = _targets(raw, 2)
+    l1 = torch.nn.functional.l1_loss
+
+    def run(use_c):
+        saved, prev, cmodel.ENABLED = ops.DGRAD_WGRAD_FUSED, cmodel.ENABLED, use_c
+        try:
+            m = _mk(10)
+            opt = torch.optim.AdamW(m.parameters(), lr=1e-3, fused=True)
+            grads = []
+            for fused in (True, False, True):
+                ops.DGRAD_WGRAD_FUSED = fused
+                opt.zero_grad(set_to_none=True)
+                o = m(batch)
+                (l1(o["out"], te) + l1(o["grad"], tf) + l1(o["stresses"], ts)).backward()
+                torch.cuda.synchronize()
+                grads.append({"g." + k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None})
+                opt.step()
+            return grads
+        finally:
+            ops.DGRAD_WGRAD_FUSED, cmodel.ENABLED = saved, prev
+
+    _reset_stats()
+    a = run(True)
+    assert cmodel.STATS.get("ff_grad", 0) == 3, cmodel.STATS
+    b = run(False)
+    for i, (ga, gb) in enumerate(zip(a, b)):
+        assert len(ga) > 100
+        _same(ga, gb, f"step {i}")
+
+
 def test_force_training_switches_energy_only_forces_only_no_reverse_natoms():
     raw = make_batch(4, 24, seed0=7)
     batch = GraphBatch.from_raw(raw, device=DEV)
