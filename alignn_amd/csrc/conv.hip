@@ -604,7 +604,8 @@ __global__ __launch_bounds__(kThreads) void egc_bwd_lg_dense_kernel(
                     float* out = GP + (int64_t)i * ldp + H + f;
                     if (qb > 0) a = f4_add(f4_ld(out), a);  // written by this very thread in the previous pass
                     f4_st(out, a);
-                    gp_am = fmaxf(gp_am, f4_absmax(a));
+                    // (only what stays in memory counts: an earlier pass's partial sum is overwritten by the next)
+                    if (qb + kWavesPerBlock * KMAX >= n_src) gp_am = fmaxf(gp_am, f4_absmax(a));
                 }
             }
             if (active) {

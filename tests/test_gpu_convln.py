@@ -15,7 +15,6 @@ Errors are max |a - b| / max |b| over the whole tensor (tests/helpers.rel_err); 
 An ``amax`` output (zeroed before the launch) must EQUAL the largest magnitude among the elements the launch wrote: the next
 f16x3 product takes its power-of-two scale from it, and a value too small overflows the fp16 slices silently."""
 
-import functools
 import os
 import zlib
 
@@ -25,10 +24,12 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from alignn_amd import GraphBatch, _lib  # noqa: E402
+from alignn_amd import _lib  # noqa: E402
 from alignn_amd._lib import ptr, stream  # noqa: E402
-from alignn_amd.graph import build_csr  # noqa: E402
-from alignn_amd.synthetic import make_batch  # noqa: E402
+from tests.gate_parity import Report as _Report  # noqa: E402
+from tests.gate_parity import err as _err  # noqa: E402
+from tests.gate_parity import graph as _graph  # noqa: E402
+from tests.gate_parity import is_line_graph as _is_line_graph  # noqa: E402
 
 DEV = "cuda"
 EPS, EPS_GATE = 1e-5, 1e-6  # nn.LayerNorm's default; ALIGNN_EPS_GATE (csrc/common.h)
@@ -37,40 +38,6 @@ HS = (4, 36, 64, 100, 128, 252, 256)
 DATA = ("normal", "mean_over_spread", "constant_rows", "rows_1e-4_1e4", "gamma_zero_negative")
 # bounds on N(0,1) operands (see the module docstring) and floors of everything else
 B_LN_FWD, B_GATE_FWD, B_LN_PARAM, B_REVERSE = 2e-6, 2e-5, 2e-5, 5e-5
-SEG_LENGTHS = (0, 1, 2, 3, 4, 5, 0, 7, 8, 9, 0, 0, 331, 1, 11, 12, 13, 15, 16, 17, 0, 64, 3)  # around multiples of the row unroll 4
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-# graphs
-# ----------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _graph(name):
-    if name == "synthetic":  # empty segments next to a long one, a one-row segment, lengths on and around multiples of 4
-        n = len(SEG_LENGTHS)
-        g = torch.Generator().manual_seed(3)
-        v = torch.repeat_interleave(torch.arange(n), torch.tensor(SEG_LENGTHS))
-        u = torch.randint(0, n, (int(v.numel()),), generator=g)
-        return build_csr(u.to(DEV), v.to(DEV), n)
-    raw = {"lg_small": lambda: make_batch(3, 14, seed0=31), "bond": lambda: make_batch(3, 14, seed0=31),
-           "lg_deg17": lambda: make_batch(4, 3, seed0=11),  # atoms with more than 16 in-edges: several dense passes
-           "lg_4096seg": lambda: make_batch(8, 60, seed0=5),  # more than 4 x 1024 segments: a wave owns several
-           "lg_stream": lambda: make_batch(16, 60, seed0=3)}[name]()  # >= 128 MiB per [rows, 256] tensor: STREAM = true
-    batch = GraphBatch.from_raw(raw, device=DEV)
-    if name == "bond":
-        return batch.g
-    lg = batch.lg
-    assert lg.dense_max_src > 0 and lg.grp_seg_ptr is not None
-    if name == "lg_deg17":
-        assert lg.dense_max_src > 16
-    if name == "lg_4096seg":
-        assert lg.n_nodes > 4096
-    if name == "lg_stream":
-        assert lg.n_edges * 256 * 4 >= 128 << 20
-    return lg
-
-
-def _is_line_graph(g):
-    return g.grp_seg_ptr is not None and g.dense_max_src > 0
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -179,40 +146,6 @@ def _reverse_ref(dt, g, o, H, dual):
     if dual:
         out.update(GMt=gr["Mt"], GPt=gr["Pt"][:, :3 * H], GPt_bd=gr["Pt"][:, H:2 * H])
     return out
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-# comparison
-# ----------------------------------------------------------------------------------------------------------------------
-def _err(a, b, floor=1e-30):
-    """tests/helpers.rel_err on the device"""
-    return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(floor))
-
-
-class _Report:
-    def __init__(self, case):
-        self.case, self.failed, self.worst = case, [], {}
-
-    def close(self, entry, name, got, ref64, ref32, bound, floor=1e-30):
-        e = _err(got, ref64, floor)
-        e32 = None if ref32 is None else _err(ref32, ref64, floor)
-        allowed = bound if e32 is None else 4 * e32 + bound
-        key = (entry.split(" ")[0], name)
-        if key not in self.worst or e / allowed > self.worst[key][0] / self.worst[key][2]:
-            self.worst[key] = (e, e32, allowed, entry)
-        if not e < allowed:
-            self.failed.append((entry, name, e, e32, allowed))
-
-    def amax(self, entry, name, slot, written):
-        got, want = float(slot), float(written.abs().max()) if written.numel() else 0.0
-        if got != want:
-            self.failed.append((entry, name, got, "amax: largest magnitude written", want))
-
-    def finish(self):
-        for (entry, name), (e, e32, allowed, where) in sorted(self.worst.items()):
-            f32 = "       -" if e32 is None else f"{e32:8.2e}"
-            print(f"convln-parity {self.case:<38s} {entry:<32s} {name:<8s} err {e:8.2e}  float32 {f32}  allowed {allowed:8.2e}  [{where}]")
-        assert not self.failed, self.failed
 
 
 def _run_case(H, gname, data):
