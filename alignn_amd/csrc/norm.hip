@@ -714,7 +714,9 @@ int alignn_col_stats_welford(const float* X, int64_t ldx, int64_t rows, int F, f
 int alignn_bn_finalize_welford(const float* partial, int slabs, int64_t rows, int F, const float* gamma, const float* beta,
                                float eps, float momentum, float* running_mean, float* running_var, float* stat,
                                alignn_stream_t stream) {
-    if (F <= 0 || slabs <= 0 || partial == nullptr) return (int)hipErrorInvalidValue;
+    if (F <= 0 || slabs <= 0 || partial == nullptr || rows < 0) return (int)hipErrorInvalidValue;
+    if (rows == 0)  // (an empty batch: see alignn_bn_finalize)
+        return alignn_bn_finalize(nullptr, 0, 0, F, gamma, beta, eps, momentum, running_mean, running_var, stat, stream);
     hipLaunchKernelGGL(bn_finalize_welford_kernel, dim3(alignn_ceil_div(F, kWfCols)), dim3(kWfCols, kWfLanes), 0,
                        (hipStream_t)stream, partial, partial + (size_t)slabs * 3 * F, slabs, rows, F, gamma, beta, eps, momentum,
                        running_mean, running_var, stat);
@@ -748,7 +750,12 @@ int alignn_col_sum(const float* X, int64_t ldx, int64_t rows, int F, float* out,
 int alignn_bn_finalize(const float* partial, int slabs, int64_t rows, int F, const float* gamma, const float* beta,
                        float eps, float momentum, float* running_mean, float* running_var, float* stat,
                        alignn_stream_t stream) {
-    if (F <= 0 || (slabs == 0 && running_mean == nullptr)) return (int)hipErrorInvalidValue;
+    if (F <= 0 || slabs < 0 || rows < 0) return (int)hipErrorInvalidValue;
+    // An empty batch has no statistics of its own (sum / 0 rows is NaN, and the running statistics would keep it for good): it
+    // takes the evaluation form - stat from the running statistics, which stay as they are (torch's batch_norm leaves them alone
+    // on an empty input too).  The later launches of the step (alignn_bn_silu_bwd_apply_sum) read stat at rows == 0.
+    if (rows == 0) slabs = 0;
+    if (slabs == 0 && (running_mean == nullptr || running_var == nullptr)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(alignn_ceil_div(F, kRedCols)), dim3(kRedCols, kRedLanes), 0,
                        (hipStream_t)stream, partial, slabs, rows, F, gamma, beta, eps, momentum, running_mean,
                        running_var, stat);
@@ -790,8 +797,8 @@ int alignn_bn_silu_fwd(const float* X, int64_t ldx, const float* R, int64_t ldr,
 
 int alignn_bn_silu_bwd_reduce(const float* GY, int64_t ldgy, const float* X, int64_t ldx, const float* stat,
                               int64_t rows, int F, float* partial, alignn_stream_t stream) {
-    if (!feat_ok(F)) return (int)hipErrorInvalidValue;
-    int slabs = slabs_for(rows);
+    if (!feat_ok(F) || rows < 0) return (int)hipErrorInvalidValue;
+    int slabs = slabs_for(rows);  // (rows == 0: one workgroup writes the zero slab alignn_bn_bwd_finalize then reads)
     if (exceeds_llc(rows, F)) {  // T-sized: the re-read by the apply / conv-backward pass cannot come from cache anyway
         BwdReduceFn<true> fn{GY, ldgy, X, ldx, stat, F};
         hipLaunchKernelGGL(col_reduce_kernel<BwdReduceFn<true>>, dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, fn,
@@ -921,8 +928,10 @@ int alignn_bn_silu_bwd_apply_node(const float* GY, int64_t ldgy, const float* X,
 int alignn_bn_silu_bwd_apply_sum(const float* GY, int64_t ldgy, const float* X, int64_t ldx, const float* stat,
                                  const float* red, int eval_mode, float* GX, int64_t ldgx, int64_t rows, int F,
                                  float* amax, float* partial, alignn_stream_t stream) {
-    if (!feat_ok(F) || F > 4 * kThreads || partial == nullptr || (!eval_mode && red == nullptr)) return (int)hipErrorInvalidValue;
-    if (rows == 0) return 0;
+    if (!feat_ok(F) || F > 4 * kThreads || partial == nullptr || (!eval_mode && red == nullptr) || rows < 0)
+        return (int)hipErrorInvalidValue;
+    // rows == 0 is launched on purpose, as alignn_ln_silu_bwd: alignn_col_stats_slabs(0) == 1 and the callers' alignn_slab_sum
+    // reads that slab, which this one workgroup writes as zeros
     const int slabs = slabs_for(rows);
     if (exceeds_llc(rows, F))
         hipLaunchKernelGGL(bn_silu_bwd_apply_sum_kernel<true>, dim3(slabs), dim3(kThreads), 0, (hipStream_t)stream, GY, ldgy, X,

@@ -227,7 +227,9 @@ int alignn_col_sum(const float* X, int64_t ldx, int64_t rows, int F, float* out,
 /* Finalise: from `slabs` partial slabs over `rows` rows produce, per feature,
  *   stat[0]=mean, stat[1]=rstd, stat[2]=scale=gamma*rstd, stat[3]=beta   (stat is [4][F])
  * and (if running_mean != NULL) update running_mean/var in place with `momentum`.
- * slabs == 0: evaluation mode - take mean/var from running_mean/running_var. */
+ * slabs == 0: evaluation mode - take mean/var from running_mean/running_var.
+ * rows == 0 (an empty batch, here and in alignn_bn_finalize_welford): the evaluation form too - stat comes from the running
+ * statistics, which are required then and stay unchanged (no 0 / 0 reaches them). */
 int alignn_bn_finalize(const float* partial, int slabs, int64_t rows, int F, const float* gamma,
                        const float* beta, float eps, float momentum, float* running_mean,
                        float* running_var, float* stat, alignn_stream_t stream);
@@ -240,7 +242,7 @@ int alignn_bn_silu_fwd(const float* X, int64_t ldx, const float* R, int64_t ldr,
                        float* Y, int64_t ldy, int64_t rows, int F, float* amax, alignn_stream_t stream);
 
 /* backward, phase 1: partial[s][0][f] = sum_r gz, partial[s][1][f] = sum_r gz*xhat, where
- * z = (X-mean)*scale+beta, gz = GY * silu'(z), xhat = (X-mean)*rstd */
+ * z = (X-mean)*scale+beta, gz = GY * silu'(z), xhat = (X-mean)*rstd   (rows == 0: the one slab is written as zeros) */
 int alignn_bn_silu_bwd_reduce(const float* GY, int64_t ldgy, const float* X, int64_t ldx,
                               const float* stat, int64_t rows, int F, float* partial,
                               alignn_stream_t stream);
@@ -284,7 +286,8 @@ int alignn_bn_silu_bwd_apply_node(const float* GY, int64_t ldgy, const float* X,
                                   int64_t rows, int F, float* amax, const float* S0, const float* HH, float* GS1, float* GS0,
                                   alignn_stream_t stream);
 /* ... and, in the same pass, the column sums of GX - the bias gradient of the nn.Linear in front of the BatchNorm
- * (MLPLayer, alignn/models/alignn.py:170-184) - as [alignn_col_stats_slabs(rows)][F] slabs for alignn_slab_sum. */
+ * (MLPLayer, alignn/models/alignn.py:170-184) - as [alignn_col_stats_slabs(rows)][F] slabs for alignn_slab_sum
+ * (rows == 0: the one slab is written as zeros). */
 int alignn_bn_silu_bwd_apply_sum(const float* GY, int64_t ldgy, const float* X, int64_t ldx, const float* stat,
                                  const float* red, int eval_mode, float* GX, int64_t ldgx, int64_t rows, int F,
                                  float* amax, float* partial, alignn_stream_t stream);

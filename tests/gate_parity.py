@@ -1,6 +1,7 @@
 """What the float64 parity tests of the edge-gated convolution kernels share (tests/test_gpu_convln.py: the LayerNorm flavour,
 csrc/convln.hip; tests/test_gpu_conv_bn.py: the BatchNorm flavour, csrc/conv.hip): the hard graphs, the error measure and the
-report that collects every failure of a case before it asserts and prints the worst error per (entry point, output)."""
+report that collects every failure of a case before it asserts and prints the worst error per (entry point, output) - which
+tests/test_gpu_norm.py (csrc/norm.hip) uses too."""
 
 import functools
 
