@@ -13,6 +13,7 @@ from .phonons import EV_TO_CM1, EV_TO_THZ, PhononResult, phonons  # noqa: F401
 from .ealignn_atomwise import eALIGNNAtomWise, eALIGNNAtomWiseConfig  # noqa: F401
 from .interface import InterfaceResult, MatchResult, interface_energy, match_lattices  # noqa: F401
 from .graph import CSRGraph, GraphBatch, build_csr  # noqa: F401
+from .neb import NEBResult, neb, neb_interpolate  # noqa: F401
 from .relax import RelaxResult, relax  # noqa: F401
 from .thermo import QHAResult, ThermalResult, qha, thermal_properties, thermal_sums  # noqa: F401
 

@@ -126,7 +126,7 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
           neighbor_strategy: str = "k-nearest", intensive: bool = True, force_multiplier: float = 1.0,
           forces_fn: Optional[Callable] = None, device=None, optimize_lattice: bool = False,
           stress_weight: float = 1.0, fixed: Optional[Sequence] = None, cell_mask=None, hydrostatic_strain: bool = False,
-          constant_volume: bool = False, scalar_pressure=0.0) -> RelaxResult:
+          constant_volume: bool = False, scalar_pressure=0.0, evaluator: Optional[Callable] = None) -> RelaxResult:
     """Relax the atomic positions of B crystals with FIRE until max_i |F_i| < ``fmax`` or ``steps`` steps; at fixed cell, or
     with the cells too when ``optimize_lattice``.
 
@@ -147,7 +147,14 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
     names (``cell_mask`` its ``mask``); they need ``optimize_lattice``.  ``cell_mask``: which cell components may relax, six
     Voigt flags (xx, yy, zz, yz, xz, xy) or a [3, 3] array of 0 / 1, one for all structures or B of them (a [3, 3] array is
     always one mask).  ``scalar_pressure``: the target pressure in eV/A^3, ASE's unit (``dynamics.BAR`` converts from bar),
-    one number or B; the run then minimises the enthalpy ``E + scalar_pressure * V``, returned as ``enthalpies``."""
+    one number or B; the run then minimises the enthalpy ``E + scalar_pressure * V``, returned as ``enthalpies``.
+
+    ``evaluator``: an object called exactly as ``ForceEvaluator`` is, ``(which, lattices, frac, cart) -> (energy, forces,
+    stress)`` with ``which`` the active structures' indices, ``frac`` the wrapped fractional coordinates the step kernel wrote
+    and ``cart`` views of the packed position array; it replaces the evaluator built from the model or ``forces_fn``, and
+    ``model`` may then be ``None`` (``alignn_amd.neb`` turns the forces of a band's images into NEB forces this way)."""
+    if evaluator is not None:
+        forces_fn = evaluator  # (to the checks below: no model needed, the device is ``device`` or the current one)
     ns = check_inputs("relax", model, lattices, positions, atom_features, forces_fn=forces_fn, stress=optimize_lattice)
     if steps < 0 or fmax < 0 or maxstep <= 0 or dt <= 0:
         raise ValueError("relax: need steps >= 0, fmax >= 0, maxstep > 0, dt > 0")
@@ -160,9 +167,10 @@ def relax(model, lattices: Sequence, positions: Sequence, atom_features: Optiona
     with _lib.device_guard(torch.empty(0, device=dev)):
         packed = pack(lattices, positions, ns, dev)
         lat, pos, inv, frac, atom_ptr = packed.lat, packed.pos, packed.inv, packed.frac, packed.atom_ptr
-        evaluate = ForceEvaluator("relax", model, forces_fn, atom_features, ns, dev, cutoff=cutoff, max_neighbors=max_neighbors,
-                                  neighbor_strategy=neighbor_strategy, intensive=intensive, force_multiplier=force_multiplier,
-                                  stress_weight=stress_weight if optimize_lattice else None)
+        evaluate = evaluator if evaluator is not None else ForceEvaluator(
+            "relax", model, forces_fn, atom_features, ns, dev, cutoff=cutoff, max_neighbors=max_neighbors,
+            neighbor_strategy=neighbor_strategy, intensive=intensive, force_multiplier=force_multiplier,
+            stress_weight=stress_weight if optimize_lattice else None)
         vel = torch.zeros_like(pos)
         forces_all = torch.zeros_like(pos)
         energy_all = torch.zeros(B, dtype=torch.float64, device=dev)
