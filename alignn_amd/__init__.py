@@ -15,6 +15,8 @@ from .interface import InterfaceResult, MatchResult, interface_energy, match_lat
 from .graph import CSRGraph, GraphBatch, build_csr  # noqa: F401
 from .neb import NEBResult, neb, neb_interpolate  # noqa: F401
 from .relax import RelaxResult, relax  # noqa: F401
+from .symmetry import (SymmetryResult, distinct_miller_indices, find_symmetry, symmetrize_forces,  # noqa: F401
+                       symmetrize_positions, symmetrize_stress)
 from .thermo import QHAResult, ThermalResult, qha, thermal_properties, thermal_sums  # noqa: F401
 from .trajectory import (A2_FS_TO_CM2_S, DiffusionResult, MSDResult, RDFResult, TrajectoryAnalysis, VACFResult,  # noqa: F401
                          VDOSResult, analyze_md, diffusion, green_kubo, msd, pair_row, rdf, vacf, vdos)

@@ -173,14 +173,16 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
                       site_labels: Optional[Sequence] = None, supercell=None, enforce_c_size: float = 15.0, extend: int = 1,
                       chemical_potentials: Optional[Sequence] = None, relax_structures: bool = True,
                       max_atoms_per_call: int = MAX_ATOMS_PER_CALL, forces_fn: Optional[Callable] = None, device=None,
-                      **relax_kwargs) -> VacancyResult:
+                      species: Optional[Sequence] = None, symprec: float = 1e-3, **relax_kwargs) -> VacancyResult:
     """Vacancy formation energies of B crystals, the reference's ``vacancy_formation`` (ff.py:808) for each: per parent one
     pristine supercell and one supercell with an atom removed per class of sites, all relaxed together.
 
     The structures, the model (or ``forces_fn``) and the device: alignn_amd/_structures.py.  ``supercell``: (N1, N2, N3) for all
     or one per structure; by default jarvis-tools' rule, ``int(enforce_c_size / |a_k|) + extend`` along axis k.
     ``site_labels``: B integer arrays [n_s], one class per distinct label (e.g. the Wyckoff classes of spglib, the reference's
-    ``using_wyckoffs``); default: every atom its own class.  The atom removed is the class's lowest-index atom, in image 0.
+    ``using_wyckoffs``); default: every atom its own class; ``"auto"``: the orbits of ``find_symmetry(lattices, positions,
+    species, symprec=symprec)``, the atoms the crystal's own symmetry makes equivalent (``species``: B integer arrays, None: all
+    atoms alike; both are used by ``"auto"`` only).  The atom removed is the class's lowest-index atom, in image 0.
     ``chemical_potentials``: B arrays with one value (eV) per class in ascending label order, added to the formation energy;
     default 0 (the reference reads jarvis' unary-energy table).
 
@@ -198,8 +200,16 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
     for s, n in enumerate(n_bulk):
         if n < 2:
             raise ValueError(f"{who}: the supercell of structure {s} has one atom; without it nothing is left")
-    if site_labels is not None and len(site_labels) != B:
+    auto = isinstance(site_labels, str)
+    if auto and site_labels != "auto":
+        raise ValueError(f"{who}: site_labels is B integer arrays, None or \"auto\", got {site_labels!r}")
+    if site_labels is not None and not auto and len(site_labels) != B:
         raise ValueError(f"{who}: site_labels needs one integer [n_i] array per structure, {B} of them")
+    if auto:
+        from .symmetry import find_symmetry
+
+        site_labels = find_symmetry(lattices, positions, species, symprec=symprec,
+                                    device=gpu_device(who, model, forces_fn, device)).orbits
     labels, mult, removed = [], [], []
     for s in range(B):
         lab = np.arange(ns[s]) if site_labels is None else host(site_labels[s])
