@@ -450,7 +450,9 @@ int alignn_gemm_nt(const float* A, int64_t lda, const float* W, int64_t ldw, con
     if (M == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const bool vec_ok = (K % 4 == 0) && (lda % 4 == 0) && (ldw % 4 == 0) && aligned16(A) && aligned16(W);
-    if (!vec_ok || N < 16)
+    // (the MFMA kernel's vector epilogue fetches the bias as float4 and its `vec` predicate does not look at the bias
+    // pointer: a bias that is not 16-byte aligned goes to the kernel that reads it by elements)
+    if (!vec_ok || N < 16 || (bias != nullptr && !aligned16(bias)))
         return naive(A, lda, 1, W, ldw, 1, bias, addend, ldadd, C, ldc, M, N, K, st);
     GemmArgs g{A, lda, W, ldw, bias, addend, ldadd, C, ldc, M, N, K, K, 0, 0, 0, 0, 0};
     // tile choice: the big 128x256 tile (A read once, 1 workgroup/CU) needs >= ~4 waves of workgroups to

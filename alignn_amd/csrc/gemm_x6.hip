@@ -1502,7 +1502,7 @@ int alignn_gemm_tn_x6_partials(const float* G, int64_t ldg, const float* g_amax,
     return 0;
 }
 
-int alignn_gemm_nt_x6_supported(int64_t M, int N, int K) { return (M > 0 && N >= 128 && N % 4 == 0 && K % BK == 0) ? 1 : 0; }
+int alignn_gemm_nt_x6_supported(int64_t M, int N, int K) { return (M > 0 && N >= 128 && N % 4 == 0 && K > 0 && K % BK == 0) ? 1 : 0; }
 
 int alignn_gemm_nt_x6(const float* A, int64_t lda, const void* Wsplit, const float* bias, const float* addend,
                       int64_t ldadd, float* C, int64_t ldc, int64_t M, int N, int K, alignn_stream_t stream) {
@@ -1547,7 +1547,7 @@ int alignn_gemm_nt_f16x3_gather2(const float* A, int64_t lda, const float* a_ama
     if (!alignn_gemm_nt_x6_supported(M, N, K) || a_amax == nullptr || w_amax == nullptr) return (int)hipErrorInvalidValue;
     if (!nt_args_ok(A, lda, Wsplit, bias, nullptr, 0, C, ldc)) return (int)hipErrorInvalidValue;
     if (P == nullptr || src == nullptr || Bd2 == nullptr || rank == nullptr || (ldp & 3) || (ldbd2 & 3) || !aligned16(P) || !aligned16(Bd2) ||
-        (N & 3) || (stats_partial && !aligned16(stats_partial)))
+        (N & 3) || ldp < (int64_t)N || ldbd2 < (int64_t)N || (stats_partial && !aligned16(stats_partial)))
         return (int)hipErrorInvalidValue;
     X6Args g{A, lda, (const unsigned char*)Wsplit, a_amax, w_amax, bias, nullptr, 0, C, ldc, M, N, npad(N), K,
              exceeds_llc(M, N), nullptr, 0, nullptr, stats_partial, P, ldp, src, rank};

@@ -518,8 +518,13 @@ class WeightPrep:
             return False
         sig = tuple([w.data_ptr() for w in weights])
         if sig != self.sig or len(weights) != len(self.keep) or any(a is not b for a, b in zip(weights, self.keep)):
+            # (the device reads the records unchecked: only what alignn_hip.h allows in one may get into the table - N, K
+            # positive multiples of 16, ldw of 4, 16-byte aligned rows, image sizes alignn_split_f16x2_both takes)
+            pad = lambda n: (n + 255) // 256 * 256  # noqa: E731
             ok = [w for w in weights if (w.dim() == 2 and w.is_cuda and w.dtype == torch.float32 and w.stride(1) == 1
-                                         and w.stride(0) % 4 == 0 and w.shape[0] % 16 == 0 and w.shape[1] % 16 == 0)]
+                                         and w.stride(0) % 4 == 0 and w.shape[0] % 16 == 0 and w.shape[1] % 16 == 0
+                                         and w.shape[0] > 0 and w.shape[1] > 0 and w.data_ptr() % 16 == 0
+                                         and pad(w.shape[0]) * w.shape[1] <= 1 << 28 and pad(w.shape[1]) * w.shape[0] <= 1 << 28)]
             if len(ok) != len(weights) or not ok:
                 self.sig = None
                 return False

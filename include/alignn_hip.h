@@ -44,7 +44,9 @@ const char* alignn_version(void);
  * (src_gate, dst_gate, edge_gate, dst_update, src_update), :175-177 (MLPLayer) and :341 (fc).
  * ------------------------------------------------------------------------------------------ */
 
-/* C[M,N] = A[M,K] * W[N,K]^T (+ bias[N]) (+ addend[M,N])      -- nn.Linear forward */
+/* C[M,N] = A[M,K] * W[N,K]^T (+ bias[N]) (+ addend[M,N])      -- nn.Linear forward.
+ * No alignment is required of any operand: what is not 16-byte aligned (or a K, lda, ldw that is no multiple of 4) takes an
+ * element-wise kernel - a `bias` that is not 16-byte aligned included, whatever the other operands are. */
 int alignn_gemm_nt(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
                    const float* addend, int64_t ldadd, float* C, int64_t ldc,
                    int64_t M, int N, int K, alignn_stream_t stream);
@@ -123,6 +125,25 @@ int alignn_split_f16x2_both(const float* W, int64_t ldw, int N, int K, const flo
 int alignn_prepare_weights(const void* descs, int n_weights, float* amax_slots, alignn_stream_t stream);
 /* *amax = max(*amax, max|X|): alignn_absmax (below) without its reset, for a slot known to hold 0 */
 int alignn_absmax_raise(const float* X, int64_t ldx, int64_t rows, int F, float* amax, alignn_stream_t stream);
+/* alignn_gemm_nt_f16x3 and its variants below (_bnred, _gather, _gather2, _stats):
+ * - Leading dimensions.  Long products without an addend (K >= 80, N % 256 == 0, at least 1024 tiles of 128 x 256) run on a
+ *   persistent kernel that addresses C, the addend and Xn with 32-bit offsets inside a row tile: it refuses (invalid value)
+ *   ldc, ldadd or ldxn >= 2^20.  Every other shape takes any multiple of 4.  A caller that wants one answer for every
+ *   row count keeps all three below 2^20.
+ * - Slabs.  `stats_partial` / `red_partial` hold alignn_gemm_nt_x6_row_tiles(M, N, K) + 1 slabs of [2][N] floats.  Slab t
+ *   (t < row_tiles) receives the sums over rows [t R, min((t + 1) R, M)), R = 64 or 128 being the unit
+ *   alignn_gemm_nt_x6_row_tiles counts with (row_tiles = ceil(M / R)): 64 wherever the persistent kernel's shape test holds,
+ *   with or without an addend; otherwise the block tile of the one-tile kernel, 64 rows for K <= 64 or fewer than 256
+ *   tiles of 128 x 256, else 128 (ALIGNN_AMD_X6_PERSIST=0 switches the shape test off for the count and the launch alike).
+ *   Every one of these slabs is written by every call.  The slab behind them is scratch: the persistent kernel parks the
+ *   sums of a wave strip that lies past row M there (zeros), the one-tile kernels leave it alone.  Nothing behind it is
+ *   touched.
+ * - Small maxima.  The operand scale is 2^(141 - e) for a maximum in [2^(e-127), 2^(e-126)), clamped to 2^127: a tensor
+ *   whose maximum is below 2^-113 is scaled to less than 2^14, and what the slices resolve - 2^-25 absolute after scaling,
+ *   2^-39 of the maximum at full scale - coarsens by a factor of two per factor of two below 2^-113 (max|A| = 2^-120:
+ *   2^-32 of the maximum, still below fp32's 2^-24).  Maxima down to 2^-113 are scaled in full.
+ *   The inverse scale of a clamped operand is the fp32 subnormal 2^-127; the library is built with fp32 denormals kept,
+ *   and the two inverse scales are applied one after the other, so nothing underflows that the result itself does not. */
 int alignn_gemm_nt_f16x3(const float* A, int64_t lda, const float* a_amax, const void* Wsplit,
                          const float* w_amax, const float* bias, const float* addend, int64_t ldadd, float* C,
                          int64_t ldc, int64_t M, int N, int K, alignn_stream_t stream);
@@ -147,7 +168,8 @@ int alignn_gemm_nt_f16x3_gather(const float* A, int64_t lda, const float* a_amax
                                 float* stats_partial, alignn_stream_t stream);
 /* The same with the second gathered row from its own table: C[e] = A[e] W^T + bias + P[src[e]][0:N] + Bd2[rank[e]][0:N].
  * For a line graph: Bd2 = the Bd block of P with its rows in SEGMENT order (alignn_gather_rows_ld by seg_node), rank[e] =
- * the segment of edge row e - consecutive rows then read consecutive table rows instead of one random row per segment. */
+ * the segment of edge row e - consecutive rows then read consecutive table rows instead of one random row per segment.
+ * Only P's first N columns are read here: ldp >= N and ldbd2 >= N (alignn_gemm_nt_f16x3_gather: ldp >= 2 N). */
 int alignn_gemm_nt_f16x3_gather2(const float* A, int64_t lda, const float* a_amax, const void* Wsplit, const float* w_amax,
                                  const float* bias, float* C, int64_t ldc, int64_t M, int N, int K, const float* P, int64_t ldp,
                                  const int32_t* src, const float* Bd2, int64_t ldbd2, const int32_t* rank,

@@ -320,35 +320,7 @@ def test_bitwise_reproducible():
 F16X3_K = (0, 8, 16, 20, 24, 28, 32, 36)
 
 
-def _f16x3_error_bound(a, w):
-    """Elementwise bound [rows of a, rows of w] on |f16x3(a w^T) - a w^T|, from the scheme as written (csrc/gemm_x6.hip:12-18,
-    f16_scale) and nothing the kernel returns.  Per operand x with tensor maximum amax:
-
-    * x' = x * 2^s with s chosen so that amax * 2^s lies in [2^14, 2^15): |x'| < 2^15, no fp16 overflow.
-    * h = RN16(x'), l = RN16(x' - h).  fp16 rounds to 11 significant bits above 2^-14 and to a spacing of 2^-24 below, so
-      |x' - h| <= max(2^-11 |x'|, 2^-25) and e(x') = |x' - h - l| <= max(2^-11 |x' - h|, 2^-25) <= max(2^-22 |x'|, 2^-25);
-      |l| <= L(x') = max(2^-11 (1 + 2^-11) |x'|, 2^-24); a zero is exact.
-    * the product keeps hh + hl + lh and drops ll: with a' = ha + la + ea, w' = hw + lw + ew,
-      a'w' - (hh + hl + lh) = la lw + ea w' + (ha + la) ew, in magnitude <= L(a') L(w') + e(a') |w'| + (|a'| + e(a')) e(w').
-
-    The fp16 x fp16 products are exact in the fp32 accumulators and the power-of-two scales are undone exactly, so the sum of
-    those terms over the reduction index, divided by the two scales, bounds the scheme's own error; one factor 4 covers the
-    order of the fp32 accumulation (the margin test_gemm_x6_accuracy gives a reordered fp32 sum)."""
-    import math
-
-    def scaled(x):
-        x = x.double().cpu().abs()
-        s = 2.0 ** (15 - math.frexp(float(x.max()))[1])  # f16_scale: the maximum lands in [2^14, 2^15)
-        return x * s, s
-
-    def e(x):
-        return torch.where(x > 0, (x * 2.0 ** -22).clamp_min(2.0 ** -25), 0.0)
-
-    def low(x):
-        return torch.where(x > 0, (x * 2.0 ** -11 * (1 + 2.0 ** -11)).clamp_min(2.0 ** -24), 0.0)
-
-    (A, sa), (W, sw) = scaled(a), scaled(w)
-    return 4 * (low(A) @ low(W).t() + e(A) @ W.t() + (A + e(A)) @ e(W).t()) / (sa * sw)
+from tests.gemm_ref import f16x3_scheme_bound as _f16x3_error_bound  # noqa: E402  (derived there)
 
 
 def _row_block_operand(rows, cols, seed):
