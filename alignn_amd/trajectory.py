@@ -25,7 +25,8 @@ Units.  Positions in A, momenta in amu A per ASE time unit (what ``run_md`` reco
 squared.  ``dtau_fs`` is the time between two selected frames in fs: ``timestep * interval * step``.  Diffusion coefficients are
 returned in A^2/fs; multiply by ``A2_FS_TO_CM2_S`` for cm^2/s.
 
-Not here: accumulation inside ``run_md`` without a stored trajectory, angle distributions, ionic conductivity.
+Not here: accumulation inside ``run_md`` without a stored trajectory, ionic conductivity.  Angle distributions, Steinhardt order
+parameters and the static structure factor of the same trajectories: ``alignn_amd.order``.
 """
 
 from __future__ import annotations
