@@ -497,7 +497,9 @@ int alignn_egc_dual_bwd_src(const float* GM, const float* GMt, const float* M, c
 /* egc_dual_bwd_dst + egc_dual_bwd_src as ONE pass for line graphs with dense, source-sorted blocks (see
  * alignn_egc_bwd_lg_dense: one workgroup per centre atom, rows by index arithmetic): M, Mt, GL, GLt read once, GM, GMt
  * written once - 6 T-row passes instead of 10; same outputs, sums in a different but fixed order; gb_partial
- * [n_groups][H]. */
+ * [n_groups][H].  m_rows (the rows of M) is not used to index anything: it only chooses between the cached loads and
+ * stores and the streaming ones, taken when a [m_rows, H] fp32 tensor reaches 128 MiB, i.e. m_rows >= (128 << 20) / (4 H).
+ * A caller may therefore pass such a value with a small graph to run the streaming instantiations (the tests do). */
 int alignn_egc_dual_bwd_lg_dense(const float* GL, const float* GLt, const float* M, const float* Mt, const float* P,
                                  const float* Pt, const float* q1, const float* q0, const float* q1t, const float* q0t,
                                  int64_t m_rows, const int32_t* grp_seg_ptr, const int32_t* grp_src_ptr, int64_t n_groups,

@@ -1,5 +1,5 @@
 """csrc/convln.hip - the line-graph and bond-graph convolutions of ALIGNNAtomWise with the edge LayerNorm formed inside the
-gate passes - against float64 torch restatements of alignn/models/alignn_atomwise.py:151-208, entry point by entry point and
+gate passes - against float64 restatements (tests/dual_ref.py) of alignn/models/alignn_atomwise.py:151-208, entry point by entry point and
 output by output.  tests/test_gpu_dual.py compares these kernels with the separate HIP kernels they replace (which pins the
 summation order, but lets a formula shared by both pass); here the other side is ``index_add`` / ``layer_norm`` / ``silu`` /
 ``sigmoid`` in float64, explicit value + tangent expressions for the dual passes (validated by central differences), and
@@ -20,12 +20,12 @@ import zlib
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
 from alignn_amd import _lib  # noqa: E402
 from alignn_amd._lib import ptr, stream  # noqa: E402
+from tests.dual_ref import _blocks, _duals, _values  # noqa: E402  (the restatements, any dtype)
 from tests.gate_parity import Report as _Report  # noqa: E402
 from tests.gate_parity import err as _err  # noqa: E402
 from tests.gate_parity import graph as _graph  # noqa: E402
@@ -64,49 +64,6 @@ def _operands(H, gname, data):
     elif data == "gamma_zero_negative":
         o["gamma"] = torch.where(torch.arange(H, device=DEV) % 3 == 0, 0.0, 1.0) * R(H)
     return g, o
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-# restatements (any dtype; alignn/models/alignn_atomwise.py:151-208 with m = A[u] + Bd[v] + C already formed)
-# ----------------------------------------------------------------------------------------------------------------------
-def _blocks(P, H):
-    return P[:, :H], P[:, H:2 * H], P[:, 2 * H:3 * H], P[:, 3 * H:]
-
-
-def _values(P, M, gamma, beta, u, v, n, H):
-    """what the forward pass writes: the LayerNorm branch y = silu(LN(m)), the row statistics, the two segment sums of
-    sigma(m) and the node pre-activation Ux + s1 / (s0 + eps)"""
-    _, _, Bh, Ux = _blocks(P, H)
-    y = F.silu(F.layer_norm(M, (H,), gamma, beta, EPS))
-    mean = M.mean(1)
-    rstd = (((M - mean[:, None]) ** 2).mean(1) + EPS).rsqrt()
-    sg = torch.sigmoid(M)
-    z = lambda: torch.zeros(n, H, dtype=M.dtype, device=M.device)  # noqa: E731
-    s1, s0 = z().index_add(0, v, sg * Bh[u]), z().index_add(0, v, sg)
-    hh = s1 / (s0 + EPS_GATE)
-    return dict(y=y, mean=mean, rstd=rstd, s1=s1, s0=s0, hh=hh, xpre=Ux + hh)
-
-
-def _duals(P, Pt, M, Mt, gamma, beta, u, v, n, H):
-    """value and tangent of the same, written out with differentiable torch operations (the explicit style of
-    tests/test_gpu_dual.py: torch's jvp tangents do not differentiate correctly w.r.t. the primal)"""
-    _, _, Bh, Ux = _blocks(P, H)
-    _, _, Bht, Uxt = _blocks(Pt, H)
-    mean = M.mean(1, keepdim=True)
-    rho = (((M - mean) ** 2).mean(1, keepdim=True) + EPS).rsqrt()
-    xh = (M - mean) * rho
-    th = rho * (Mt - Mt.mean(1, keepdim=True) - xh * (xh * Mt).mean(1, keepdim=True))
-    zz, zt = gamma * xh + beta, gamma * th
-    sz = torch.sigmoid(zz)
-    y, yt = zz * sz, (sz + zz * sz * (1 - sz)) * zt
-    sg = torch.sigmoid(M)
-    sgt = sg * (1 - sg) * Mt
-    z = lambda: torch.zeros(n, H, dtype=M.dtype, device=M.device)  # noqa: E731
-    s1, s0 = z().index_add(0, v, sg * Bh[u]), z().index_add(0, v, sg)
-    s1t, s0t = z().index_add(0, v, sgt * Bh[u] + sg * Bht[u]), z().index_add(0, v, sgt)
-    hh = s1 / (s0 + EPS_GATE)
-    hht = (s1t - hh * s0t) / (s0 + EPS_GATE)
-    return dict(y=y, yt=yt, s1=s1, s0=s0, s1t=s1t, s0t=s0t, hh=hh, hht=hht, xpre=Ux + hh, xpre_t=Uxt + hht)
 
 
 def _forward_ref(dt, g, o, H):
