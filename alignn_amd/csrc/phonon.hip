@@ -13,22 +13,14 @@
 // No float atomics: every sum runs in a fixed order, so a structure's result is the same bits alone or in a batch.
 #include "../../include/alignn_hip.h"
 #include "common.h"
+#include "phonon_rows.h"
 
 namespace {
 
-constexpr int PH_BLOCK = 256;
-constexpr int PH_WAVES = PH_BLOCK / ALIGNN_WAVE;
 constexpr int PH_MAX_M = 96;           // 3n limit of the eigen launch: 96 x 97 x 16 B of LDS for the matrix
 constexpr int PH_PHASE_CHUNK = 128;    // cells whose phase factors are staged in LDS at a time
 constexpr int PH_MAX_SWEEPS = 40;      // Jacobi sweep cap (status word when hit)
 constexpr double PH_OFF_TOL = 1e-14;   // converged: off-diagonal Frobenius norm <= PH_OFF_TOL * ||D(q)||_F
-enum { DRIFT_NONE = 0, DRIFT_FREDERIKSEN = 1, DRIFT_MEAN = 2 };
-
-struct Cells {
-    int n0, n1, n2;
-    __device__ __forceinline__ int count() const { return n0 * n1 * n2; }
-};
-__device__ __forceinline__ Cells cells_of(const int32_t* dims, int s) { return {dims[3 * s], dims[3 * s + 1], dims[3 * s + 2]}; }
 
 // Supercell atom j = image * n + b, image = (m0 N1 + m1) N2 + m2 (ASE's atoms * (N0, N1, N2)).  Displacement d = 6a + 2i + sg
 // moves atom a of image 0 along axis i by -delta (sg = 0) or +delta (sg = 1).  The arithmetic is the restatement's, operation
@@ -83,39 +75,12 @@ __global__ __launch_bounds__(PH_BLOCK) void phonon_fc_rows_kernel(
     const int s = pairs[2 * p], x = pairs[2 * p + 1];
     const int n = atom_ptr[s + 1] - atom_ptr[s], m = 3 * n;
     const int n_sc = n * cells_of(dims, s).count();
-    const int a = x / 3;
     const double* Fm = forces + 3 * pair_rows[p];
-    const double* Fp = Fm + 3 * (int64_t)n_sc;
-    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (drift != DRIFT_NONE) {
-        for (int j = threadIdx.x; j < n_sc; j += PH_BLOCK) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                sum[k] += Fm[3 * j + k];
-                sum[3 + k] += Fp[3 * j + k];
-            }
-        }
-        block_reduce<6, false>(sum, sh);
-        if (drift == DRIFT_MEAN) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) sum[k] /= (double)n_sc;
-        }
-    }
-    const double two_delta = 2.0 * delta;
     double* C = fc + fc_off[s];
-    for (int j = threadIdx.x; j < n_sc; j += PH_BLOCK) {
+    difference_rows(Fm, Fm + 3 * (int64_t)n_sc, n_sc, x / 3, drift, delta, sh, [&](int j, int k, double v) {
         const int cell = j / n, b = j - cell * n;
-        const bool sub = drift == DRIFT_MEAN || (drift == DRIFT_FREDERIKSEN && j == a);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            double fm = Fm[3 * j + k], fp = Fp[3 * j + k];
-            if (sub) {
-                fm -= sum[k];
-                fp -= sum[3 + k];
-            }
-            C[((int64_t)cell * m + x) * m + 3 * b + k] = (fm - fp) / two_delta;
-        }
-    }
+        C[((int64_t)cell * m + x) * m + 3 * b + k] = v;
+    });
 }
 
 // ASE's symmetrize with offset 0: per axis k = (l + N/2) mod N is the fftshifted index; cells with k >= 1 - N % 2 on every

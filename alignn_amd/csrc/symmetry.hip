@@ -53,10 +53,6 @@ __device__ __forceinline__ void heights(const double (&A)[9], double (&h)[3]) {
     }
 }
 
-__device__ __forceinline__ void load9(const double* p, double (&A)[9]) {
-#pragma unroll
-    for (int j = 0; j < 9; ++j) A[j] = p[j];
-}
 
 __device__ __forceinline__ int det3i(const int (&W)[9]) {
     return W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
@@ -459,21 +455,6 @@ __device__ __forceinline__ int owner(const int32_t* ptr, int B, int r) {
         if (ptr[mid] <= r) lo = mid; else hi = mid;
     }
     return lo;
-}
-
-// Q = A^T W A^-T: M = A^T W, then M A^-T
-__device__ __forceinline__ void cartesian_rotation(const double (&A)[9], const double (&Ai)[9], const int32_t* Wg, double (&Q)[9]) {
-    double W[9], M[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) W[j] = (double)Wg[j];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) M[3 * r + c] = (A[r] * W[c] + A[3 + r] * W[3 + c]) + A[6 + r] * W[6 + c];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) Q[3 * r + d] = (M[3 * r] * Ai[3 * d] + M[3 * r + 1] * Ai[3 * d + 1]) + M[3 * r + 2] * Ai[3 * d + 2];
 }
 
 struct Ops {

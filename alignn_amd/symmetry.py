@@ -19,8 +19,8 @@ batch and at any place of it.  One array of B x 8 integers (counts, crystal syst
 the launch that fills the results; nothing else.
 
 Not here: space-group numbers and symbols, Wyckoff letters, standardised / conventional / primitive cells, symmetrising the
-lattice itself, symmetry-reduced displacements, strains and q-meshes, a symmetry constraint inside ``relax``, magnetic or
-site-property-aware symmetry.
+lattice itself, symmetry-reduced strains and q-meshes, a symmetry constraint inside ``relax``, magnetic or site-property-aware
+symmetry.  (Symmetry-reduced displacements: ``phonons(displacements="symmetry", symmetry=...)``, alignn_amd/phonons.py.)
 """
 
 from __future__ import annotations

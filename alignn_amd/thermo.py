@@ -36,7 +36,7 @@ from ._jobs import (EVALUATION, MAX_ATOMS_PER_CALL, check_max_atoms, check_steps
                     prepare_parents, relax_jobs, strain_jobs)
 from ._structures import EV_A3_TO_GPA, check_inputs, gpu_device
 from .eos import EOS_FORMS, MAX_POINTS, MIN_POINTS, _check_dx, eos_fit
-from .phonons import MAX_DIM, PhononResult, _supercells, monkhorst_pack, phonons
+from .phonons import DISPLACEMENTS, MAX_DIM, PhononResult, _supercells, monkhorst_pack, phonons, repeat_symmetry
 
 __all__ = ["thermal_sums", "thermal_properties", "qha", "ThermalResult", "QHAResult", "KB"]
 
@@ -266,7 +266,8 @@ def qha(model, lattices: Sequence, positions: Sequence, atom_features: Optional[
         dx=DEFAULT_DX, temperatures=DEFAULT_TEMPERATURES, eos: str = "murnaghan", supercell=(2, 2, 2), delta: float = 0.01,
         mesh=(20, 20, 20), cutoff: float = 0.0, relax_ions: bool = False, on_relaxed_struct: bool = False,
         max_atoms_per_call: int = MAX_ATOMS_PER_CALL, max_atoms_per_eval: Optional[int] = None,
-        forces_fn: Optional[Callable] = None, device=None, **relax_kwargs) -> QHAResult:
+        forces_fn: Optional[Callable] = None, device=None, displacements: str = "all", symmetry=None,
+        **relax_kwargs) -> QHAResult:
     """The quasi-harmonic approximation at zero pressure for B crystals (primitive cells): every parent strained isotropically
     by each ``dx[p]`` as ``ev_curve`` does, E(V) and the phonons of all B P strained structures evaluated together, E(V) +
     F_phonon(V, T) fitted at every temperature, and the fits reduced to the thermal quantities of ``QHAResult`` - what a loop
@@ -274,8 +275,11 @@ def qha(model, lattices: Sequence, positions: Sequence, atom_features: Optional[
 
     The structures, ``masses``, the model (or ``forces_fn``) and the device: alignn_amd/_structures.py.  ``dx``, ``eos``,
     ``on_relaxed_struct`` and ``max_atoms_per_call``: ``ev_curve``.  ``temperatures`` (K): finite, >= 0, strictly increasing.
-    ``supercell``, ``delta`` and ``max_atoms_per_eval``: ``phonons`` (its other options at their defaults; 3n <= 96).  ``mesh``
-    and ``cutoff`` (eV, the mode cutoff): ``thermal_properties``.
+    ``supercell``, ``delta``, ``max_atoms_per_eval``, ``displacements`` and ``symmetry``: ``phonons`` (its other options at
+    their defaults; 3n <= 96).  ``symmetry`` is the ``SymmetryResult`` of the B parents: the strains are isotropic, so every
+    strained copy of a parent has the parent's operations, and with ``displacements="symmetry"`` every volume evaluates only
+    the symmetry-inequivalent displacements (a relaxation that breaks the parents' symmetry is the caller's to exclude).
+    ``mesh`` and ``cutoff`` (eV, the mode cutoff): ``thermal_properties``.
 
     ``relax_ions``: relax the atoms of every strained structure at its fixed cell before its energy and phonons are taken
     (``steps`` and ``fmax`` from ``relax_kwargs``); without it the ions follow the strain affinely, which is the whole answer
@@ -293,6 +297,12 @@ def qha(model, lattices: Sequence, positions: Sequence, atom_features: Optional[
     optimize_lattice = bool(on_relaxed_struct) and bool(relax_kwargs.get("optimize_lattice", True))
     ns = check_inputs(who, model, lattices, positions, atom_features, masses, forces_fn=forces_fn, stress=optimize_lattice)
     B = len(ns)
+    if displacements not in DISPLACEMENTS:
+        raise ValueError(f"{who}: displacements must be 'all' or 'symmetry', got {displacements!r}")
+    if (displacements == "symmetry") != (symmetry is not None):
+        raise ValueError(f"{who}: displacements='symmetry' and symmetry= (the SymmetryResult of the parents) go together")
+    if symmetry is not None and list(getattr(symmetry, "ns", [])) != list(ns):
+        raise ValueError(f"{who}: symmetry= must be the SymmetryResult of find_symmetry for these {B} structures")
     d = _check_dx(who, dx)
     P = len(d)
     t = _check_temperatures(who, temperatures, increasing=True)
@@ -337,7 +347,9 @@ def qha(model, lattices: Sequence, positions: Sequence, atom_features: Optional[
         # (clamped ions: the strained structures as built; relaxed ions: as ``relax`` left them, the cells unchanged)
         job_pos = r.positions if relax_ions else list(torch.split(cart, counts))
         ph = phonons(model, list(cells), job_pos, job_feats, job_masses, supercell=scs, delta=delta, qpoints=None,
-                     dos_kpts=None, max_atoms_per_eval=max_atoms_per_eval, forces_fn=forces_fn, device=dev, **evaluation)
+                     dos_kpts=None, max_atoms_per_eval=max_atoms_per_eval, forces_fn=forces_fn, device=dev,
+                     displacements=displacements, symmetry=None if symmetry is None else repeat_symmetry(symmetry, P),
+                     **evaluation)
         th = thermal_properties(ph, t, mesh=mesh, cutoff=cutoff)
         F = th.free_energy.view(B, P, NT)
 

@@ -3,12 +3,15 @@
 one displaced supercell per model call, then host numpy D(q) + eigvalsh over the same q-path and mesh, structure after
 structure (timed on the first --ref-structures structures and scaled to B: the loop is sequential in B).  --eigh: the eigen
 launch alone against host numpy eigvalsh for K q-points and m in {12, 24, 48, 96}.  --chunks: time and peak memory of
-phonons() per max_atoms_per_eval.  Prints one JSON line per measurement."""
+phonons() per max_atoms_per_eval.  --displacements all|symmetry|all,symmetry: diamond, rocksalt and wurtzite (built here: the
+random cells have no symmetry) at (3, 3, 3), each alone and the three together, with every atom displaced along x, y, z and / or
+with the symmetry-reduced displacements (find_symmetry timed apart); both modes in one invocation put the supercell counts and
+times side by side.  Prints one JSON line per measurement."""
 import argparse, json, os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from alignn_amd import ALIGNNAtomWise, ALIGNNAtomWiseConfig, neighbors, phonons
+from alignn_amd import ALIGNNAtomWise, ALIGNNAtomWiseConfig, find_symmetry, neighbors, phonons
 from alignn_amd.phonons import FREQ_SCALE, _eigh, lattice_points, monkhorst_pack
 from alignn_amd.synthetic import make_crystal
 
@@ -21,6 +24,7 @@ ap.add_argument("--eigh-k", type=int, default=8000)
 ap.add_argument("--eigh-host-k", type=int, default=500)
 ap.add_argument("--chunks", default="")
 ap.add_argument("--skip-batches", action="store_true")
+ap.add_argument("--displacements", default="", help="all, symmetry or all,symmetry: time the symmetric crystals")
 args = ap.parse_args()
 dev = "cuda"
 SC = (3, 3, 3)
@@ -95,6 +99,43 @@ if args.chunks:
         print(json.dumps({"what": "chunk", "max_atoms_per_eval": c, "B": 8, "atoms": 8, "supercell": SC, "n_evals": res.n_evals,
                           "s": round(t, 3), "peak_workspace_GiB": round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 3)}),
               flush=True)
+
+
+
+def symmetric_crystals():
+    """name -> (cell, Cartesian positions, species, masses): diamond and rocksalt on the fcc primitive cell, wurtzite."""
+    fcc = lambda a: 0.5 * a * np.array([[0.0, 1.0, 1.0], [1.0, 0.0, 1.0], [1.0, 1.0, 0.0]])
+    hexa = lambda a, c: np.array([[a, 0.0, 0.0], [-0.5 * a, 0.5 * np.sqrt(3.0) * a, 0.0], [0.0, 0.0, c]])
+    raw = {"diamond": (fcc(3.57), [[0, 0, 0], [0.25, 0.25, 0.25]], [6, 6], [12.011, 12.011]),
+           "rocksalt": (fcc(5.64), [[0, 0, 0], [0.5, 0.5, 0.5]], [11, 17], [22.99, 35.45]),
+           "wurtzite": (hexa(3.25, 5.21), [[1 / 3, 2 / 3, 0.0], [2 / 3, 1 / 3, 0.5], [1 / 3, 2 / 3, 0.382], [2 / 3, 1 / 3, 0.882]],
+                        [30, 30, 8, 8], [65.38, 65.38, 15.999, 15.999])}
+    return {k: (A, np.asarray(f, dtype=np.float64) @ A, np.asarray(z), np.asarray(m)) for k, (A, f, z, m) in raw.items()}
+
+
+if args.displacements:
+    modes = args.displacements.split(",")
+    if any(m not in ("all", "symmetry") for m in modes):
+        ap.error("--displacements takes all, symmetry or all,symmetry")
+    crystals = symmetric_crystals()
+    g = torch.Generator(device="cpu").manual_seed(1)
+    kinds = {z: torch.randn(92, generator=g).to(dev) for z in (6, 11, 17, 30, 8)}
+    groups = [[k] for k in crystals] + [list(crystals)]
+    for names in groups:
+        lats, pos, zs, masses = ([crystals[k][i] for k in names] for i in range(4))
+        feats = [torch.stack([kinds[int(v)] for v in z]) for z in zs]
+        find_symmetry(lats, pos, zs)  # warm-up
+        t_sym, sym = sync_time(lambda: find_symmetry(lats, pos, zs))
+        for mode in modes:
+            extra = dict(displacements="symmetry", symmetry=sym) if mode == "symmetry" else {}
+            no_q = {**kw, "qpoints": None, "dos_kpts": None, **extra}
+            phonons(model, lats, pos, feats, masses, **{**kw, **extra})  # warm-up
+            t_all, res = sync_time(lambda: phonons(model, lats, pos, feats, masses, **{**kw, **extra}))
+            t_fc, _ = sync_time(lambda: phonons(model, lats, pos, feats, masses, **no_q))
+            print(json.dumps({"what": "displacements", "crystals": "+".join(names), "mode": mode, "supercell": SC,
+                              "supercells": res.n_supercells, "n_evals": res.n_evals, "force_constants_s": round(t_fc, 4),
+                              "with_q_path_and_dos_s": round(t_all, 4),
+                              "find_symmetry_s": round(t_sym, 4) if mode == "symmetry" else None}), flush=True)
 
 if not args.skip_batches:
     for n in [int(x) for x in args.atoms.split(",")]:
