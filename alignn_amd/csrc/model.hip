@@ -13,12 +13,18 @@
 // Streams: the caller's stream plus up to three helpers (all optional; NULL = stay on the caller's stream):
 //   lane_T  - the kernels over T = |edges of L(g)| rows (edge projection, gate pass, their backward, the angle embedding);
 //   side    - weight / bias gradients (nothing on the critical path reads them);
-//   aux     - the node input gradient of a bond-graph convolution beside the edge one.
-// Dependencies are HIP events from a per-device pool (alignn_model_init); every helper stream is joined back into the
-// caller's stream before a call returns, so the caller sees ordinary stream semantics and the calls are capture-safe.
+//   aux     - the node input gradient g_x of a bond-graph convolution beside the edge one, and behind it the node branch of the
+//             next bond-graph convolution's backward (which reads nothing else) - beside the line-graph backward in between.
+// Dependencies are HIP events from a per-device pool (alignn_model_init).  A tensor carries where it becomes ready (Ready: the
+// producing stream and, where it pays, an event recorded right behind the producer): a reader on that stream waits for nothing,
+// a reader elsewhere waits for that event where it READS - the caller's stream does not wait for g_x at the end of conv_bwd, the
+// gate reverse kernels wait for the hoisted node branch, the atom embedding's backward waits for the last g_x.  Every helper
+// stream - aux too, when something on it has not been waited for by the caller's stream - is joined back into the caller's
+// stream before a call returns, so the caller sees ordinary stream semantics and the calls are capture-safe.
 //
 // Workspace = [forward tape | backward temporaries]; the forward's tape (pre-activations, projections, statistics ...) is
 // found again by the backward by re-running the same deterministic plan without launching.
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -60,17 +66,25 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
         if (c0 + j < cols && r0 + tx < rows) out[(int64_t)(c0 + j) * rows + r0 + tx] = tile[tx][j];
 }
 
+// When a tensor is complete: the stream that wrote it last and - where the producer marked it - the event recorded right behind
+// its last writer.  A reader on that stream waits for nothing; a reader on another stream waits for the event, or, without one,
+// for everything enqueued on the producing stream so far (Ctx::need).
+struct Ready {
+    hipStream_t st = nullptr;  // NULL: the caller's stream (or data) - a helper stream is never NULL
+    hipEvent_t ev = nullptr;
+    int at = 0;  // Ctx::n_mark when `ev` was recorded
+};
 struct Act {  // an activation [rows, F] and what its producer knows about it
     float* p = nullptr;
     float* amax = nullptr;  // device scalar max|p|, tracked by the producing kernel (NULL: not tracked)
     float* xn = nullptr;    // p = r + silu(BatchNorm(xn)): the pre-activation,
     float* stat = nullptr;  // its [4, F] statistics,
     float* red = nullptr;   // and where the producer's backward expects (sum gz, sum gz * xhat) [2, F]
-    bool on_T = false;      // last written on lane T
+    Ready rdy;              // where it was last written
 };
 struct Grad {
     float* p = nullptr;
-    bool on_T = false;
+    Ready rdy;
     bool pre_red = false;  // the projection that wrote p also left the BatchNorm-backward sums in the producer's `red`
 };
 
@@ -98,6 +112,8 @@ struct Tape {
     std::vector<ConvTape> convs;
 };
 
+// debugging aid (alignn_debug_joins): what the launching calls did with deferred events since the last query
+std::atomic<int64_t> g_dbg_aux_marks{0}, g_dbg_late_waits{0}, g_dbg_max_dist{0};
 std::vector<std::pair<size_t, size_t>> g_dbg_allocs;  // (offset, bytes) of every persistent allocation of the last launching call
 bool dbg_allocs_on() {
     static int on = -1;
@@ -177,12 +193,69 @@ struct Ctx {
     void sync(hipStream_t waiter, hipStream_t src) {
         if (!launch || rc != 0 || waiter == src) return;
         const auto t0 = timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+        wait(waiter, mark(src));
+        ++n_sync;
+        if (timing) t_sync += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    // The two halves of sync, for a dependency that is waited for later than it is recorded: the event stands for everything
+    // enqueued on `src` up to here.  The pool rotates, so an event must be waited for before kEvents further marks re-record it:
+    // n_mark counts them and need() fails the call rather than wait for a recycled event.
+    int n_mark = 0;
+    hipEvent_t mark(hipStream_t src) {
+        if (!launch || rc != 0) return nullptr;
         hipEvent_t e = pool->ev[pool->next];
         pool->next = (pool->next + 1) % kEvents;
         rc = (int)hipEventRecord(e, src);
-        if (rc == 0) rc = (int)hipStreamWaitEvent(waiter, e, 0);
-        ++n_sync;
-        if (timing) t_sync += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        ++n_mark;
+        return e;
+    }
+    void wait(hipStream_t waiter, hipEvent_t e) {
+        if (!launch || rc != 0 || e == nullptr) return;
+        rc = (int)hipStreamWaitEvent(waiter, e, 0);
+    }
+    hipStream_t where(const Ready& r) const { return r.st != nullptr ? r.st : main; }
+    Ready by(hipStream_t st) const {  // written on `st`, not marked
+        Ready r;
+        r.st = st;
+        return r;
+    }
+    Ready marked(hipStream_t st) {  // written on `st`, marked here - unless that is the caller's stream, which every helper is
+        Ready r = by(st);           // ordered behind often enough that an event of its own buys nothing
+        if (st != main) {
+            r.ev = mark(st);
+            r.at = n_mark;
+            if (st == aux && r.ev != nullptr) {
+                aux_at = r.at;
+                g_dbg_aux_marks.fetch_add(1, std::memory_order_relaxed);
+            }
+        }
+        return r;
+    }
+    // `reader` continues only after the tensor `r` stands for is complete
+    void need(hipStream_t reader, const Ready& r) {
+        const hipStream_t src = where(r);
+        if (src == reader) return;
+        if (r.ev == nullptr) {
+            sync(reader, src);
+            return;
+        }
+        if (!launch || rc != 0) return;
+        const int dist = n_mark - r.at;
+        g_dbg_late_waits.fetch_add(1, std::memory_order_relaxed);
+        if (dist > g_dbg_max_dist.load(std::memory_order_relaxed)) g_dbg_max_dist.store(dist, std::memory_order_relaxed);
+        if (dist >= kEvents - 1) {
+            rc = (int)hipErrorInvalidValue;
+            return;
+        }
+        wait(reader, r.ev);
+        if (reader == main && src == aux && r.at == aux_at) aux_at = 0;
+    }
+    // Everything enqueued on the aux stream ends in a marked() there; aux_at is the mark of the last one while the caller's
+    // stream has not waited for it (0: aux is joined, or was never used).
+    int aux_at = 0;
+    void join_aux() {
+        if (aux_at != 0) sync(main, aux);
+        aux_at = 0;
     }
 };
 
@@ -266,7 +339,7 @@ Act mlp_fwd(Ctx& c, MlpTape& t, const alignn_mlp_params& p, const Act& x, int64_
     t.rows = rows;
     t.lane = c.T != c.main && rows >= c.d->lane_min_rows;
     hipStream_t st = t.lane ? c.T : c.main;
-    if (t.lane != x.on_T) c.sync(st, x.on_T ? c.T : c.main);
+    c.need(st, x.rdy);
     t.pre = c.alloc((size_t)rows * F);
     t.stat = c.alloc(ln ? (size_t)rows * 2 : (size_t)4 * F);
     const bool fused_stats = !ln && x.amax != nullptr && x6_shape_ok(c, rows, K, F, K);
@@ -299,7 +372,7 @@ Act mlp_fwd(Ctx& c, MlpTape& t, const alignn_mlp_params& p, const Act& x, int64_
         y.stat = t.stat;
         y.red = p.red;
     }
-    y.on_T = t.lane;
+    y.rdy = c.by(st);
     t.y = y;
     return y;
 }
@@ -318,8 +391,8 @@ void conv_fwd(Ctx& c, ConvTape& t, const alignn_conv_params& p, const alignn_gra
     t.need_y = need_y;
     t.lane = c.T != c.main && m >= c.d->lane_min_rows;
     hipStream_t main = c.main, T = t.lane ? c.T : c.main;
-    if (x.on_T) c.sync(main, c.T);
-    if (!t.lane && y.on_T) c.sync(main, c.T);
+    c.need(main, x.rdy);
+    if (!t.lane) c.need(main, y.rdy);
     // ---- node side, part 1: P = x [W_sg; W_dg; W_du; W_su]^T + b = A | Bd | Bh | Ux
     t.P = c.alloc((size_t)n * 4 * H);
     project(c, x.p, Kin, x.amax, p.wcat, Kin, p.wcat_img, p.wcat_amax, p.bcat, t.P, 4 * H, n, 4 * H, Kin, main);
@@ -348,7 +421,7 @@ void conv_fwd(Ctx& c, ConvTape& t, const alignn_conv_params& p, const alignn_gra
         yo.p = c.alloc((size_t)m * H);
         yo.amax = c.track(m) ? c.new_amax() : nullptr;
         if (ln) t.e_stat = c.alloc((size_t)m * 2);
-        yo.on_T = t.lane;
+        yo.rdy = c.by(T);
     }
     bool y_normed = false;  // the gate pass normalised the edge output as well: one read of m less
     if (pre_added) {
@@ -483,7 +556,7 @@ void run_forward(Ctx& c, Tape& tp, float* out) {
         alignn_angle_args a = angle_args(c, tp);
         z.p = c.alloc((size_t)Tn * H);
         z.amax = c.track(Tn) ? c.new_amax() : nullptr;
-        z.on_T = tp.angle_lane;
+        z.rdy = c.by(st);
         a.z = z.p;
         a.z_amax = z.amax;
         a.workspace_bytes = alignn_angle_embed_workspace(Tn, d.angle_bins, 0);
@@ -535,7 +608,7 @@ void run_forward(Ctx& c, Tape& tp, float* out) {
         if (c.unsupported) return;
     }
     // ---- readout: AvgPooling + fc, alignn.py:325,341
-    if (x.on_T) c.sync(c.main, c.T);
+    c.need(c.main, x.rdy);
     tp.pool = c.alloc((size_t)b.B * H);
     L(alignn_segment_mean_fwd(x.p, b.graph_ptr, tp.pool, b.B, H, c.main));
     L(alignn_gemm_nt(tp.pool, H, d.fc_W, H, d.fc_b, nullptr, 0, out, d.out_features, b.B, d.out_features, H, c.main));
@@ -652,7 +725,7 @@ Grad mlp_bwd(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx) {
     const int F = p.out, K = p.in;
     const int64_t rows = t.rows;
     hipStream_t st = t.lane ? c.T : c.main;
-    if (t.lane != gy.on_T) c.sync(st, gy.on_T ? c.T : c.main);
+    c.need(st, gy.rdy);
     float* gpre = c.alloc((size_t)rows * F);
     float* g_amax = c.track(rows) ? c.new_amax() : nullptr;
     const int slabs = ln ? alignn_ln_slabs(rows) : alignn_col_stats_slabs(rows);
@@ -676,7 +749,7 @@ Grad mlp_bwd(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx) {
     Grad gx;
     if (need_gx) {
         gx.p = c.alloc((size_t)rows * K);
-        gx.on_T = t.lane;
+        gx.rdy = c.by(st);
         const Act* src = (t.x.xn != nullptr && g_amax != nullptr) ? &t.x : nullptr;  // (BatchNorm producers only set xn)
         dgrad(c, gpre, F, g_amax, p.W, F, K, p.img_t, p.w_amax, nullptr, 0, gx.p, rows, st, src, &gx.pre_red);
     }
@@ -695,42 +768,64 @@ Grad mlp_bwd(Ctx& c, const MlpTape& t, const Grad& gy, bool need_gx) {
     return gx;
 }
 
-// ops.EdgeGatedConvFn.backward: -> gradients w.r.t. the node and edge inputs.  need_gx == false: nobody reads the gradient of
-// the node input (the first convolution of the force evaluation: the atom features are data)
-void conv_bwd(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out, Grad& g_x, Grad& g_y, bool need_gx = true) {
+// ops.EdgeGatedConvFn.backward in two parts.  The node branch - norm / SiLU backward of the node output's gradient into g_xpre
+// (the Ux block of GP) and the quotient's adjoints gs1, gs0 - reads nothing but that gradient and the forward's tape, so it goes
+// where the gradient was made: a bond-graph convolution's, whose gx_out the aux stream produced, right behind it on aux, beside
+// the whole line-graph backward that the caller's stream and lane T run in between.  Everything it writes is allocated here,
+// before the first launch that touches it.
+struct NodeBranch {
+    float *GP = nullptr, *gp_amax = nullptr, *gm_amax = nullptr, *gs1 = nullptr, *gs0 = nullptr;
+    Ready rdy;
+};
+NodeBranch conv_bwd_node(Ctx& c, const ConvTape& t, const Grad& gx_out) {
+    const bool ln = c.d->norm == 1;
+    const alignn_conv_params& p = *t.p;
+    const int H = c.d->H;
+    const int64_t n = t.g->n, m = t.g->m;
+    hipStream_t st = (!t.lane && c.aux != c.main && c.where(gx_out.rdy) == c.aux) ? c.aux : c.main;
+    c.need(st, gx_out.rdy);
+    NodeBranch nb;
+    nb.GP = c.alloc((size_t)n * 4 * H);
+    nb.gp_amax = c.track(n) ? c.new_amax() : nullptr;
+    nb.gm_amax = c.track(m) ? c.new_amax() : nullptr;
+    float* g_xpre = nb.GP + 3 * (size_t)H;
+    const int n_slabs = ln ? alignn_ln_slabs(n) : alignn_col_stats_slabs(n);
+    float* n_part = c.alloc((size_t)n_slabs * 2 * H);
+    nb.gs1 = c.alloc((size_t)n * H);
+    nb.gs0 = c.alloc((size_t)n * H);
+    if (ln) {
+        L(alignn_ln_silu_bwd_node(gx_out.p, H, t.xpre, H, p.n_gamma, p.n_beta, t.n_stat, g_xpre, 4 * H, n_part, n, H, nb.gp_amax, t.s0,
+                                  t.hh, nb.gs1, nb.gs0, st));
+        if (c.param_grads) L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, st));
+    } else {
+        L(alignn_bn_silu_bwd_reduce(gx_out.p, H, t.xpre, H, t.n_stat, n, H, n_part, st));
+        L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, st));
+        L(alignn_bn_silu_bwd_apply_node(gx_out.p, H, t.xpre, H, t.n_stat, p.n_gamma, p.n_red, 0, g_xpre, 4 * H, n, H, nb.gp_amax, t.s0,
+                                        t.hh, nb.gs1, nb.gs0, st));
+    }
+    nb.rdy = c.marked(st);
+    return nb;
+}
+
+// The rest: -> gradients w.r.t. the node and edge inputs.  need_gx == false: nobody reads the gradient of the node input (the
+// first convolution of the force evaluation: the atom features are data).  A bond-graph convolution's g_x is made on the aux
+// stream and leaves with its event: whoever reads it waits for it (Ctx::need), the caller's stream does not.
+void conv_bwd(Ctx& c, const ConvTape& t, const NodeBranch& nb, const Grad& gx_out, const Grad* gy_out, Grad& g_x, Grad& g_y,
+              bool need_gx = true) {
     const bool ln = c.d->norm == 1;
     const alignn_conv_params& p = *t.p;
     const alignn_graph_csr& g = *t.g;
     const int H = c.d->H, Kin = H;
     const int64_t n = g.n, m = g.m;
     hipStream_t main = c.main, T = t.lane ? c.T : c.main;
-    if (gx_out.on_T) c.sync(main, c.T);
-    if (!t.lane && gy_out != nullptr && gy_out->on_T) c.sync(main, c.T);
-    float* GP = c.alloc((size_t)n * 4 * H);
-    float* gp_amax = c.track(n) ? c.new_amax() : nullptr;
-    float* gm_amax = c.track(m) ? c.new_amax() : nullptr;
-    float* g_xpre = GP + 3 * (size_t)H;
-    // ---- node branch: norm / SiLU backward -> g_xpre (the Ux block of GP), the quotient's adjoints
-    const int n_slabs = ln ? alignn_ln_slabs(n) : alignn_col_stats_slabs(n);
-    float* n_part = c.alloc((size_t)n_slabs * 2 * H);
-    float* gs1 = c.alloc((size_t)n * H);
-    float* gs0 = c.alloc((size_t)n * H);
-    if (ln) {
-        L(alignn_ln_silu_bwd_node(gx_out.p, H, t.xpre, H, p.n_gamma, p.n_beta, t.n_stat, g_xpre, 4 * H, n_part, n, H, gp_amax, t.s0, t.hh,
-                                  gs1, gs0, main));
-        if (c.param_grads) L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, main));
-    } else {
-        L(alignn_bn_silu_bwd_reduce(gx_out.p, H, t.xpre, H, t.n_stat, n, H, n_part, main));
-        L(alignn_bn_bwd_finalize(n_part, n_slabs, H, p.n_red, main));
-        L(alignn_bn_silu_bwd_apply_node(gx_out.p, H, t.xpre, H, t.n_stat, p.n_gamma, p.n_red, 0, g_xpre, 4 * H, n, H, gp_amax, t.s0,
-                                        t.hh, gs1, gs0, main));
-    }
+    float *GP = nb.GP, *gp_amax = nb.gp_amax, *gm_amax = nb.gm_amax, *gs1 = nb.gs1, *gs0 = nb.gs0;
+    if (!t.lane && gy_out != nullptr) c.need(main, gy_out->rdy);
     // ---- edge branch (lane T for the line graph).  What the gate reverse kernels are handed as the edge output's gradient:
     // BatchNorm - gy itself with the statistics and the finished sums `e_red`, they apply the norm's backward on the way;
     // LayerNorm - the same through the kernels of csrc/convln.hip where one fits (ln_inside: dense line-graph blocks, ln_dst:
     // the bond graph), otherwise the finished normalised-branch gradient `g_branch` and no statistics
     const float* gy = gy_out != nullptr ? gy_out->p : nullptr;
-    if (t.lane && gy_out != nullptr && !gy_out->on_T) c.sync(T, main);
+    if (t.lane && gy_out != nullptr) c.need(T, gy_out->rdy);
     const bool lg_blocks = g.grp_seg_ptr != nullptr;
     const bool dense = lg_blocks && g.dense_max_src > 0 && alignn_egc_bwd_lg_dense_supported(g.dense_max_src);
     const bool ln_inside = ln && gy != nullptr && dense && alignn_egc_ln_fused_supported(H, m);
@@ -755,7 +850,8 @@ void conv_bwd(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out,
         }
         e_red = p.e_red;
     }
-    if (t.lane) c.sync(T, main);  // gs1, gs0, the Ux block of GP and its maximum are ready
+    c.need(main, nb.rdy);         // gs1, gs0, the Ux block of GP and its maximum are ready
+    if (t.lane) c.sync(T, main);
     float* GM = c.alloc((size_t)m * H);
     const int gslabs = lg_blocks ? (int)g.n_groups : (ln_dst ? alignn_egc_ln_dst_slabs(n) : alignn_egc_slabs(n));
     float* gb_part = c.alloc((size_t)gslabs * H);
@@ -787,14 +883,14 @@ void conv_bwd(Ctx& c, const ConvTape& t, const Grad& gx_out, const Grad* gy_out,
             c.sync(c.aux, main);
             sx = c.aux;
         }
+        c.need(sx, gx_out.rdy);
         dgrad(c, GP, 4 * H, gp_amax, p.wcat, 4 * H, Kin, p.wcat_img_t, p.wcat_amax, gx_out.p, H, g_x.p, n, sx, nullptr, nullptr);
     }
     const Act* src = (t.y.xn != nullptr && gm_amax != nullptr) ? &t.y : nullptr;  // (BatchNorm producers only set xn)
     const bool dw = dgrad_wgrad(c, t, GM, gm_amax, gy, g_y.p, m, H, Kin, T, src, &g_y.pre_red);
     if (!dw) dgrad(c, GM, H, gm_amax, p.w_eg, H, Kin, p.weg_img_t, p.weg_amax, gy, H, g_y.p, m, T, src, &g_y.pre_red);
-    g_y.on_T = t.lane;
-    g_x.on_T = false;
-    if (sx != main) c.sync(main, sx);
+    g_y.rdy = c.by(T);
+    if (need_gx) g_x.rdy = c.marked(sx);
     if (!c.param_grads) return;
     // ---- weight / bias gradients
     hipStream_t sd = side_for(c, m);
@@ -843,7 +939,8 @@ void run_backward(Ctx& c, const Tape& tp, const float* g_out) {
     bool have_gy = false, have_gz = false;
     for (int i = d.gcn_layers - 1; i >= 0; --i, --k) {
         Grad nx, ny;
-        conv_bwd(c, tp.convs[k], gx, have_gy ? &gy : nullptr, nx, ny);
+        const NodeBranch nb = conv_bwd_node(c, tp.convs[k], gx);
+        conv_bwd(c, tp.convs[k], nb, gx, have_gy ? &gy : nullptr, nx, ny);
         gx = nx;
         gy = ny;
         have_gy = true;
@@ -853,15 +950,18 @@ void run_backward(Ctx& c, const Tape& tp, const float* g_out) {
     const bool angle_geom = c.geom && c.ff != nullptr && c.ff->lg_on_fly;
     for (int i = d.alignn_layers - 1; i >= 0; --i) {
         // line-graph convolution: node output = the bond features (gradient gy), edge output = the triplet features (gz)
+        // (the bond-graph convolution's node branch first: its input has been ready since the layer before)
+        const NodeBranch nb_g = conv_bwd_node(c, tp.convs[k - 1], gx);
         Grad gm, nz;
-        conv_bwd(c, tp.convs[k], gy, have_gz ? &gz : nullptr, gm, nz);
+        const NodeBranch nb_lg = conv_bwd_node(c, tp.convs[k], gy);
+        conv_bwd(c, tp.convs[k], nb_lg, gy, have_gz ? &gz : nullptr, gm, nz);
         --k;
         gz = nz;
         have_gz = true;
         if (i == 0) {  // the angle embedding's backward (lane T) can start now, under the last bond-graph backward
             if (tp.angle_fused) {
                 hipStream_t st = tp.angle_lane ? c.T : c.main;
-                if (tp.angle_lane != gz.on_T) c.sync(st, gz.on_T ? c.T : c.main);
+                c.need(st, gz.rdy);
                 alignn_angle_args a = angle_args(c, tp);
                 a.gz = gz.p;
                 a.workspace_bytes = alignn_angle_embed_workspace(a.rows, d.angle_bins, 1);
@@ -871,22 +971,24 @@ void run_backward(Ctx& c, const Tape& tp, const float* g_out) {
                 Grad ga = mlp_bwd(c, tp.a2, gz, true);
                 Grad gr = mlp_bwd(c, tp.a1, ga, angle_geom);
                 c.g_rbf_a = gr.p;
-                c.g_rbf_a_on_T = gr.on_T;
+                c.g_rbf_a_on_T = c.where(gr.rdy) != c.main;
             }
         }
         Grad nx, ny;
         // (the atom features are data: without parameter gradients nobody reads the node input gradient of the first convolution)
-        conv_bwd(c, tp.convs[k], gx, &gm, nx, ny, i > 0 || c.param_grads);
+        conv_bwd(c, tp.convs[k], nb_g, gx, &gm, nx, ny, i > 0 || c.param_grads);
         --k;
         gx = nx;
         gy = ny;
         if (c.unsupported) return;
     }
-    // ---- embeddings
+    // ---- embeddings (the atom embedding waits for the last g_x here; issuing the bond rows first measured no faster eagerly and
+    // 0.03-0.12 ms slower replayed - profiles/bwd_joins_parts_ab.txt)
     if (c.param_grads) mlp_bwd(c, tp.atom, gx, false);
     Grad ge = mlp_bwd(c, tp.e2, gy, true);
     Grad gre = mlp_bwd(c, tp.e1, ge, c.geom);
     c.g_rbf_e = gre.p;
+    c.join_aux();
     c.sync(c.main, c.T);
     c.sync(c.main, c.side);
 }
@@ -900,7 +1002,7 @@ Act mlp_infer(Ctx& c, const alignn_mlp_params& p, const Act& x, int64_t rows) {
     const int F = p.out, K = p.in;
     const bool lane = c.T != c.main && rows >= c.d->lane_min_rows;
     hipStream_t st = lane ? c.T : c.main;
-    if (lane != x.on_T) c.sync(st, x.on_T ? c.T : c.main);
+    c.need(st, x.rdy);
     float* pre = c.alloc((size_t)rows * F);
     float* stat = c.alloc((size_t)4 * F);
     project(c, x.p, K, x.amax, p.W, K, p.img, p.w_amax, p.b, pre, F, rows, F, K, st);
@@ -909,7 +1011,7 @@ Act mlp_infer(Ctx& c, const alignn_mlp_params& p, const Act& x, int64_t rows) {
     y.p = c.alloc((size_t)rows * F);
     y.amax = c.track(rows) ? c.new_amax() : nullptr;
     L(alignn_bn_silu_fwd(pre, F, nullptr, 0, stat, y.p, F, rows, F, y.amax, st));
-    y.on_T = lane;
+    y.rdy = c.by(st);
     return y;
 }
 
@@ -919,8 +1021,8 @@ void conv_infer(Ctx& c, const alignn_conv_params& p, const alignn_graph_csr& g, 
     const int64_t n = g.n, m = g.m;
     const bool lane = c.T != c.main && m >= c.d->lane_min_rows;
     hipStream_t main = c.main, T = lane ? c.T : c.main;
-    if (x.on_T) c.sync(main, c.T);
-    if (!lane && y.on_T) c.sync(main, c.T);
+    c.need(main, x.rdy);
+    if (!lane) c.need(main, y.rdy);
     float* P = c.alloc((size_t)n * 4 * H);
     project(c, x.p, Kin, x.amax, p.wcat, Kin, p.wcat_img, p.wcat_amax, p.bcat, P, 4 * H, n, 4 * H, Kin, main);
     float* stats = c.alloc((size_t)8 * H);
@@ -934,7 +1036,7 @@ void conv_infer(Ctx& c, const alignn_conv_params& p, const alignn_graph_csr& g, 
     if (need_y) {
         yo.p = c.alloc((size_t)m * H);
         yo.amax = c.track(m) ? c.new_amax() : nullptr;
-        yo.on_T = lane;
+        yo.rdy = c.by(T);
     }
     L(alignn_egc_gate_infer(P, Cm, g.seg_ptr, g.seg_node, g.src, n, m, H, xpre, stats + 4 * H, y.p, yo.p, yo.amax, T));
     if (lane) c.sync(main, T);
@@ -965,7 +1067,7 @@ void run_infer(Ctx& c, float* out) {
         alignn_angle_args a = angle_args(c, tp);
         z.p = c.alloc((size_t)Tn * d.H);
         z.amax = c.track(Tn) ? c.new_amax() : nullptr;
-        z.on_T = lane;
+        z.rdy = c.by(lane ? c.T : c.main);
         a.z = z.p;
         a.z_amax = z.amax;
         L(alignn_angle_embed_infer(&a, lane ? c.T : c.main));
@@ -1001,7 +1103,7 @@ void run_infer(Ctx& c, float* out) {
         x = xo, y = yo;
         if (c.unsupported) return;
     }
-    if (x.on_T) c.sync(c.main, c.T);
+    c.need(c.main, x.rdy);
     float* pool = c.alloc((size_t)b.B * d.H);
     L(alignn_segment_mean_fwd(x.p, b.graph_ptr, pool, b.B, d.H, c.main));
     L(alignn_gemm_nt(pool, d.H, d.fc_W, d.H, d.fc_b, nullptr, 0, out, d.out_features, b.B, d.out_features, d.H, c.main));
@@ -1552,6 +1654,17 @@ int alignn_debug_allocs(size_t* out, int cap) {
     }
     g_dbg_allocs.clear();
     return n;
+}
+
+// debugging aid: how the launching calls since the last query used deferred events - out[0] events recorded on the aux stream
+// for a later wait, out[1] waits of another stream for such an event (any stream's), out[2] the most marks between an event's
+// record and a wait for it (the pool holds 512).  A hook for tests/test_gpu_backward_joins.py, which binds it by name: it is
+// not part of the interface that include/alignn_hip.h declares.
+int alignn_debug_joins(int64_t* out) {
+    out[0] = g_dbg_aux_marks.exchange(0);
+    out[1] = g_dbg_late_waits.exchange(0);
+    out[2] = g_dbg_max_dist.exchange(0);
+    return 0;
 }
 
 int alignn_ff_plan(const alignn_model_desc* d, const alignn_model_batch* b, const alignn_ff_desc* f, size_t* eval_bytes,
