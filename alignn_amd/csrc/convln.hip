@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "ln_gate_rows.h"
 #include "../../include/alignn_hip.h"
 
 namespace {
@@ -30,25 +31,6 @@ __device__ __forceinline__ void wave_sum_k(float (&v)[K]) {
     for (int k = 0; k < K; ++k) v[k] = wave_sum_dpp(v[k]);
 }
 inline int seg_blocks(int64_t n_seg) { return capped_blocks(n_seg, kW, kMaxBlocks); }
-
-// the workgroup's LayerNorm parameter-gradient slab: [0] = dbeta, [1] = dgamma, the four waves in wave order
-__device__ __forceinline__ void ln_slab_store(float4 db, float4 dg, float4 (*sh)[kW][ALIGNN_WAVE], float* slab, int H, int f,
-                                              bool active, int wave, int lane) {
-    __syncthreads();
-    sh[0][wave][lane] = db;
-    sh[1][wave][lane] = dg;
-    __syncthreads();
-    if (wave == 0 && active) {
-        float4 a = sh[0][0][lane], b = sh[1][0][lane];
-#pragma unroll
-        for (int w = 1; w < kW; ++w) {
-            a = f4_add(a, sh[0][w][lane]);
-            b = f4_add(b, sh[1][w][lane]);
-        }
-        f4_st(slab + f, a);
-        f4_st(slab + H + f, b);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // forward: egc_gate_fwd_kernel<STREAM, false, PRE = true> (M holds m = A[u] + Bd[v] + C already) + ln_silu_fwd_kernel on m
@@ -138,7 +120,10 @@ __global__ __launch_bounds__(kT) void egc_gate_fwd_ln_kernel(
 // reverse: ln_silu_bwd_kernel on (GY, M) + egc_bwd_lg_dense_kernel<2, STREAM> (dense, source-sorted line-graph blocks: the
 // index arithmetic is explained there)
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool STREAM, int KS, int KB>
+// Per row, both dense kernels and their destination-ordered siblings further down run the same calls of ln_gate_rows.h between
+// the wave sums; Bh and the segment's adjoints come from registers here (a wave's kK sources per pass, a segment's g1 / g0 loaded
+// once), from a load per row there.
+template <bool STREAM>
 __global__ __launch_bounds__(kT) void egc_bwd_lg_dense_ln_kernel(
     const float* __restrict__ GY, const float* __restrict__ M, const float* __restrict__ P, const float* __restrict__ GS1,
     const float* __restrict__ GS0, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -159,10 +144,10 @@ __global__ __launch_bounds__(kT) void egc_bwd_lg_dense_ln_kernel(
     const float4 lg = active ? f4_ld(gamma + f) : f4_zero(), lb = active ? f4_ld(beta + f) : f4_zero();
     float gm_am = 0.0f, gp_am = 0.0f;
     float4 gb = f4_zero(), db = f4_zero(), dg = f4_zero();
-    for (int qb = 0; qb < n_src || qb == 0; qb += kW * KS) {
-        float4 bh[KS], ga[KS], gbh[KS];
+    for (int qb = 0; qb < n_src || qb == 0; qb += kW * kK) {
+        float4 bh[kK], ga[kK], gbh[kK];
 #pragma unroll
-        for (int k = 0; k < KS; ++k) {
+        for (int k = 0; k < kK; ++k) {
             const int q = qb + wave + kW * k;
             bh[k] = (active && q < n_src) ? f4_ld(P + (int64_t)(p_beg + q) * ldp + 2 * H + f) : f4_zero();
             ga[k] = gbh[k] = f4_zero();
@@ -175,63 +160,32 @@ __global__ __launch_bounds__(kT) void egc_bwd_lg_dense_ln_kernel(
             const float4 g1 = active ? f4_ld(GS1 + (int64_t)i * H + f) : f4_zero();
             const float4 g0 = active ? f4_ld(GS0 + (int64_t)i * H + f) : f4_zero();
             float4 gbd = f4_zero();
-            // (rows in sub-batches of KB: the LayerNorm part keeps three rows' worth of registers per row alive across its
-            // wave reductions - all four at once cost the pass a wave per SIMD)
+            // (one row at a time: the LayerNorm part keeps three rows' worth of registers per row alive across its wave
+            // reductions - all four rows at once cost the pass a wave per SIMD; rows in pairs were slower, see the launch site)
 #pragma unroll
-            for (int kb = 0; kb < KS; kb += KB) {
-                float4 m[KB], xh[KB], gh[KB];
-                float s1[KB], s2[KB], rs[KB];
-                int row[KB];
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    const int q = qb + wave + kW * (kb + kk);
-                    row[kk] = (q < n_src && q != self_q) ? e0 + q - ((self_q >= 0 && q > self_q) ? 1 : 0) : -1;
-                    m[kk] = xh[kk] = gh[kk] = f4_zero();
-                    s1[kk] = s2[kk] = rs[kk] = 0.0f;
-                    if (row[kk] >= 0) {  // (wave-uniform)
-                        const float mean = e_stat[2 * (int64_t)row[kk]];
-                        rs[kk] = e_stat[2 * (int64_t)row[kk] + 1];
-                        if (active) {
-                            m[kk] = f4_lds<STREAM>(M + (int64_t)row[kk] * H + f);
-                            const float4 gy = f4_lds<STREAM>(GY + (int64_t)row[kk] * H + f);
-                            xh[kk] = make_float4((m[kk].x - mean) * rs[kk], (m[kk].y - mean) * rs[kk], (m[kk].z - mean) * rs[kk],
-                                                 (m[kk].w - mean) * rs[kk]);
-                            const float4 z = f4_fma(xh[kk], lg, lb);
-                            const float4 gz = make_float4(gy.x * dsilu_f(z.x), gy.y * dsilu_f(z.y), gy.z * dsilu_f(z.z), gy.w * dsilu_f(z.w));
-                            db = f4_add(db, gz);
-                            dg = f4_fma(gz, xh[kk], dg);
-                            gh[kk] = f4_mul(gz, lg);
-                            s1[kk] = hsum4(gh[kk]);
-                            s2[kk] = hsum4(f4_mul(gh[kk], xh[kk]));
-                        }
+            for (int k = 0; k < kK; ++k) {
+                const int q = qb + wave + kW * k;
+                const int row = (q < n_src && q != self_q) ? e0 + q - ((self_q >= 0 && q > self_q) ? 1 : 0) : -1;
+                float4 m = f4_zero(), xh = f4_zero(), gh = f4_zero();
+                float s1 = 0.0f, s2 = 0.0f, rstd = 0.0f;
+                if (row >= 0) {  // (wave-uniform)
+                    const float mean = e_stat[2 * (int64_t)row];
+                    rstd = e_stat[2 * (int64_t)row + 1];
+                    if (active) {
+                        m = f4_lds<STREAM>(M + (int64_t)row * H + f);
+                        const float4 gy = f4_lds<STREAM>(GY + (int64_t)row * H + f);
+                        ln_bwd_gh(m, gy, mean, rstd, lg, lb, xh, gh, db, dg, s1, s2);
                     }
                 }
-                wave_sum_k(s1);
-                wave_sum_k(s2);
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    const int k = kb + kk;
-                    if (row[kk] >= 0 && active) {
-                        const float c1 = s1[kk] * inv_f, c2 = s2[kk] * inv_f;
-                        const float4 sg = f4_sigmoid(m[kk]);
-                        const float4 gsig = f4_fma(g1, bh[k], g0);
-                        float4 gm;
-                        gm.x = gsig.x * sg.x * (1.0f - sg.x);
-                        gm.y = gsig.y * sg.y * (1.0f - sg.y);
-                        gm.z = gsig.z * sg.z * (1.0f - sg.z);
-                        gm.w = gsig.w * sg.w * (1.0f - sg.w);
-                        float4 gl;
-                        gl.x = rs[kk] * (gh[kk].x - c1 - xh[kk].x * c2);
-                        gl.y = rs[kk] * (gh[kk].y - c1 - xh[kk].y * c2);
-                        gl.z = rs[kk] * (gh[kk].z - c1 - xh[kk].z * c2);
-                        gl.w = rs[kk] * (gh[kk].w - c1 - xh[kk].w * c2);
-                        gm = f4_add(gm, gl);
-                        f4_sts<STREAM>(GM + (int64_t)row[kk] * H + f, gm);
-                        gm_am = fmaxf(gm_am, f4_absmax(gm));
-                        ga[k] = f4_add(ga[k], gm);
-                        gbh[k] = f4_fma(sg, g1, gbh[k]);
-                        gbd = f4_add(gbd, gm);
-                    }
+                const float c1 = wave_sum_dpp(s1) * inv_f, c2 = wave_sum_dpp(s2) * inv_f;
+                if (row >= 0 && active) {
+                    const float4 sg = f4_sigmoid(m);
+                    const float4 gm = f4_add(gate_bwd(sg, g1, g0, bh[k]), ln_bwd_gx(gh, xh, rstd, c1, c2));
+                    f4_sts<STREAM>(GM + (int64_t)row * H + f, gm);
+                    gm_am = fmaxf(gm_am, f4_absmax(gm));
+                    ga[k] = f4_add(ga[k], gm);
+                    gbh[k] = f4_fma(sg, g1, gbh[k]);
+                    gbd = f4_add(gbd, gm);
                 }
             }
             float4(*buf)[ALIGNN_WAVE] = sh[(s - s_beg) & 1];
@@ -245,12 +199,12 @@ __global__ __launch_bounds__(kT) void egc_bwd_lg_dense_ln_kernel(
                 float* out = GP + (int64_t)i * ldp + H + f;
                 if (qb > 0) a = f4_add(f4_ld(out), a);  // written by this very thread in the previous pass
                 f4_st(out, a);
-                if (qb + kW * KS >= n_src) gp_am = fmaxf(gp_am, f4_absmax(a));  // (the sum is complete in the last pass only)
+                if (qb + kW * kK >= n_src) gp_am = fmaxf(gp_am, f4_absmax(a));  // (the sum is complete in the last pass only)
             }
         }
         if (active) {
 #pragma unroll
-            for (int k = 0; k < KS; ++k) {
+            for (int k = 0; k < kK; ++k) {
                 const int q = qb + wave + kW * k;
                 if (q < n_src) {
                     f4_st(GP + (int64_t)(p_beg + q) * ldp + f, ga[k]);
@@ -360,7 +314,7 @@ __global__ __launch_bounds__(kT) void egc_gate_dual_tan_ln_kernel(
 // ---------------------------------------------------------------------------------------------------------------------
 // dual reverse: ln_silu_dual_bwd_kernel on (GY, GYt, M, Mt) + egc_dual_bwd_lg_dense_kernel<true, STREAM>
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool STREAM, int KS, int KB, bool EARLY>
+template <bool STREAM>
 __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_ln_kernel(
     const float* __restrict__ GY, const float* __restrict__ GYt, const float* __restrict__ M, const float* __restrict__ Mt,
     const float* __restrict__ P, const float* __restrict__ Pt, const float* __restrict__ Q1, const float* __restrict__ Q0,
@@ -382,10 +336,10 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_ln_kernel(
     const float4 lg = active ? f4_ld(gamma + f) : f4_zero(), lb = active ? f4_ld(beta + f) : f4_zero();
     float am = 0.0f, amt = 0.0f, pam = 0.0f, pamt = 0.0f;
     float4 gb = f4_zero(), db = f4_zero(), dg = f4_zero();
-    for (int qb = 0; qb < n_src || qb == 0; qb += kW * KS) {
-        float4 bh[KS], bht[KS], ga[KS], gat[KS], gbh[KS], gbht[KS];
+    for (int qb = 0; qb < n_src || qb == 0; qb += kW * kK) {
+        float4 bh[kK], bht[kK], ga[kK], gat[kK], gbh[kK], gbht[kK];
 #pragma unroll
-        for (int k = 0; k < KS; ++k) {
+        for (int k = 0; k < kK; ++k) {
             const int q = qb + wave + kW * k;
             const bool have = active && q < n_src;
             bh[k] = have ? f4_ld(P + (int64_t)(p_beg + q) * ldp + 2 * H + f) : f4_zero();
@@ -400,114 +354,44 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_ln_kernel(
             const float4 q1 = active ? f4_ld(Q1 + (int64_t)i * H + f) : f4_zero(), q0 = active ? f4_ld(Q0 + (int64_t)i * H + f) : f4_zero();
             const float4 q1t = active ? f4_ld(Q1t + (int64_t)i * H + f) : f4_zero(), q0t = active ? f4_ld(Q0t + (int64_t)i * H + f) : f4_zero();
             float4 gbd = f4_zero(), gbdt = f4_zero();
-            // per row: m, x-hat, t = mt, the LayerNorm adjoints a (of t-hat) and b (of x-hat); rows in sub-batches of KB
+            // per row: m, x-hat, t = mt, the LayerNorm adjoints a (of t-hat) and b (of x-hat); one row at a time
 #pragma unroll
-            for (int kb = 0; kb < KS; kb += KB) {
-                float4 m[KB], xh[KB], t[KB], a[KB], b[KB], gye[EARLY ? KB : 1], gyte[EARLY ? KB : 1];
-                float r0[KB], r1[KB], r2[KB], rs[KB], m2[KB];
-                int row[KB];
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    const int q = qb + wave + kW * (kb + kk);
-                    row[kk] = (q < n_src && q != self_q) ? e0 + q - ((self_q >= 0 && q > self_q) ? 1 : 0) : -1;
-                    m[kk] = xh[kk] = t[kk] = a[kk] = b[kk] = f4_zero();
-                    r0[kk] = r1[kk] = rs[kk] = 0.0f;
-                    if (row[kk] >= 0) {  // (wave-uniform)
-                        const float mean = e_stat[2 * (int64_t)row[kk]];
-                        rs[kk] = e_stat[2 * (int64_t)row[kk] + 1];
-                        if (active) {
-                            m[kk] = f4_lds<STREAM>(M + (int64_t)row[kk] * H + f);
-                            t[kk] = f4_lds<STREAM>(Mt + (int64_t)row[kk] * H + f);
-                            if (EARLY) {  // (requested with m and mt: one exposed latency per sub-batch instead of two)
-                                gye[kk] = f4_lds<STREAM>(GY + (int64_t)row[kk] * H + f);
-                                gyte[kk] = f4_lds<STREAM>(GYt + (int64_t)row[kk] * H + f);
-                            }
-                            xh[kk] = make_float4((m[kk].x - mean) * rs[kk], (m[kk].y - mean) * rs[kk], (m[kk].z - mean) * rs[kk],
-                                                 (m[kk].w - mean) * rs[kk]);
-                            r0[kk] = hsum4(t[kk]);
-                            r1[kk] = hsum4(f4_mul(xh[kk], t[kk]));
-                        }
+            for (int k = 0; k < kK; ++k) {
+                const int q = qb + wave + kW * k;
+                const int row = (q < n_src && q != self_q) ? e0 + q - ((self_q >= 0 && q > self_q) ? 1 : 0) : -1;
+                float4 m = f4_zero(), t = f4_zero(), xh = f4_zero(), a = f4_zero(), b = f4_zero();
+                float4 gy, gyt;  // (set and read under the same condition; zeroed here they cost the pass 4 %: 905 against 867 us)
+                float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f, rs = 0.0f;
+                if (row >= 0) {  // (wave-uniform)
+                    const float mean = e_stat[2 * (int64_t)row];
+                    rs = e_stat[2 * (int64_t)row + 1];
+                    if (active) {  // (all four requested together: one exposed latency per row instead of two)
+                        m = f4_lds<STREAM>(M + (int64_t)row * H + f);
+                        t = f4_lds<STREAM>(Mt + (int64_t)row * H + f);
+                        gy = f4_lds<STREAM>(GY + (int64_t)row * H + f);
+                        gyt = f4_lds<STREAM>(GYt + (int64_t)row * H + f);
+                        ln_dual_bwd_xhat(m, t, mean, rs, xh, r0, r1);
                     }
                 }
-                wave_sum_k(r0);
-                wave_sum_k(r1);
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    const float m1 = r0[kk] * inv_f;
-                    m2[kk] = r1[kk] * inv_f;
-                    r0[kk] = r1[kk] = r2[kk] = 0.0f;  // -> sum a, sum a x-hat, sum a t-hat
-                    if (row[kk] >= 0 && active) {
-                        const float4 gy = EARLY ? gye[kk] : f4_lds<STREAM>(GY + (int64_t)row[kk] * H + f);
-                        const float4 gyt = EARLY ? gyte[kk] : f4_lds<STREAM>(GYt + (int64_t)row[kk] * H + f);
-#define ALIGNN_LN_DB(q)                                                                     \
-    {                                                                                       \
-        const float th = rs[kk] * (t[kk].q - m1 - xh[kk].q * m2[kk]);                       \
-        const float z = fmaf(xh[kk].q, lg.q, lb.q), zt = lg.q * th;                         \
-        float d1, d2;                                                                       \
-        dsilu2(z, d1, d2);                                                                  \
-        const float gzt = gyt.q * d1;                                                       \
-        const float gz = gy.q * d1 + gyt.q * d2 * zt;                                       \
-        db.q += gz;                                                                         \
-        dg.q += gz * xh[kk].q + gzt * th;                                                   \
-        a[kk].q = lg.q * gzt;                                                               \
-        b[kk].q = lg.q * gz;                                                                \
-        r0[kk] += a[kk].q;                                                                  \
-        r1[kk] += a[kk].q * xh[kk].q;                                                       \
-        r2[kk] += a[kk].q * th;                                                             \
-    }
-                        ALIGNN_LN_DB(x) ALIGNN_LN_DB(y) ALIGNN_LN_DB(z) ALIGNN_LN_DB(w)
-#undef ALIGNN_LN_DB
-                    }
-                }
-                wave_sum_k(r0);
-                wave_sum_k(r1);
-                wave_sum_k(r2);
-                float A1[KB], A2[KB], A3[KB];
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    A1[kk] = r0[kk] * inv_f, A2[kk] = r1[kk] * inv_f, A3[kk] = r2[kk] * inv_f;
-                    r0[kk] = r1[kk] = 0.0f;  // -> sum b, sum b x-hat
-                    if (row[kk] >= 0 && active) {
-                        b[kk].x -= rs[kk] * (a[kk].x * m2[kk] + t[kk].x * A2[kk]);
-                        b[kk].y -= rs[kk] * (a[kk].y * m2[kk] + t[kk].y * A2[kk]);
-                        b[kk].z -= rs[kk] * (a[kk].z * m2[kk] + t[kk].z * A2[kk]);
-                        b[kk].w -= rs[kk] * (a[kk].w * m2[kk] + t[kk].w * A2[kk]);
-                        r0[kk] = hsum4(b[kk]);
-                        r1[kk] = hsum4(f4_mul(b[kk], xh[kk]));
-                    }
-                }
-                wave_sum_k(r0);
-                wave_sum_k(r1);
-#pragma unroll
-                for (int kk = 0; kk < KB; ++kk) {
-                    const int k = kb + kk;
-                    if (row[kk] >= 0 && active) {
-                        const float B1 = r0[kk] * inv_f, B2 = r1[kk] * inv_f;
-                        float4 gm, gmt;
-#define ALIGNN_GDL(c)                                                                                     \
-    {                                                                                                     \
-        gmt.c = rs[kk] * (a[kk].c - A1[kk] - xh[kk].c * A2[kk]);                                           \
-        gm.c = rs[kk] * (b[kk].c - B1 - xh[kk].c * B2) - rs[kk] * xh[kk].c * A3[kk];                       \
-        const float sg = fast_sigmoid(m[kk].c), sp = sg * (1.0f - sg);                                     \
-        const float gs = q1.c * bh[k].c + q0.c + q1t.c * bht[k].c; /* adjoint of sigma */                  \
-        const float gst = q1t.c * bh[k].c + q0t.c;                 /* adjoint of sigma-dot */              \
-        gm.c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * t[kk].c;                                         \
-        gmt.c += gst * sp;                                                                                \
-        const float sgt = sp * t[kk].c;                                                                   \
-        gbh[k].c += sg * q1.c + sgt * q1t.c;                                                              \
-        gbht[k].c += sg * q1t.c;                                                                          \
-    }
-                        ALIGNN_GDL(x) ALIGNN_GDL(y) ALIGNN_GDL(z) ALIGNN_GDL(w)
-#undef ALIGNN_GDL
-                        f4_sts<STREAM>(GM + (int64_t)row[kk] * H + f, gm);
-                        f4_sts<STREAM>(GMt + (int64_t)row[kk] * H + f, gmt);
-                        am = fmaxf(am, f4_absmax(gm));
-                        amt = fmaxf(amt, f4_absmax(gmt));
-                        ga[k] = f4_add(ga[k], gm);
-                        gat[k] = f4_add(gat[k], gmt);
-                        gbd = f4_add(gbd, gm);
-                        gbdt = f4_add(gbdt, gmt);
-                    }
+                const float m1 = wave_sum_dpp(r0) * inv_f, m2 = wave_sum_dpp(r1) * inv_f;
+                r0 = r1 = r2 = 0.0f;  // -> sum a, sum a x-hat, sum a t-hat
+                if (row >= 0 && active) ln_dual_bwd_ab(xh, t, gy, gyt, rs, m1, m2, lg, lb, a, b, db, dg, r0, r1, r2);
+                const float A1 = wave_sum_dpp(r0) * inv_f, A2 = wave_sum_dpp(r1) * inv_f, A3 = wave_sum_dpp(r2) * inv_f;
+                r0 = r1 = 0.0f;  // -> sum b, sum b x-hat
+                if (row >= 0 && active) ln_dual_bwd_b(a, t, xh, rs, m2, A2, b, r0, r1);
+                const float B1 = wave_sum_dpp(r0) * inv_f, B2 = wave_sum_dpp(r1) * inv_f;
+                if (row >= 0 && active) {
+                    float4 gm, gmt;
+                    ln_dual_bwd_gx(a, b, xh, rs, A1, A2, A3, B1, B2, gm, gmt);
+                    ALIGNN_GATE_DUAL_BWD(true, m, t, bh[k], bht[k], q1, q0, q1t, q0t, gm, gmt, gbh[k], gbht[k])
+                    f4_sts<STREAM>(GM + (int64_t)row * H + f, gm);
+                    f4_sts<STREAM>(GMt + (int64_t)row * H + f, gmt);
+                    am = fmaxf(am, f4_absmax(gm));
+                    amt = fmaxf(amt, f4_absmax(gmt));
+                    ga[k] = f4_add(ga[k], gm);
+                    gat[k] = f4_add(gat[k], gmt);
+                    gbd = f4_add(gbd, gm);
+                    gbdt = f4_add(gbdt, gmt);
                 }
             }
             float4(*buf)[kW][ALIGNN_WAVE] = sh[(s - s_beg) & 1];
@@ -530,7 +414,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_ln_kernel(
                 }
                 f4_st(out, sa);
                 f4_st(outt, sat);
-                if (qb + kW * KS >= n_src) {  // (the sums are complete in the last pass only)
+                if (qb + kW * kK >= n_src) {  // (the sums are complete in the last pass only)
                     pam = fmaxf(pam, f4_absmax(sa));
                     pamt = fmaxf(pamt, f4_absmax(sat));
                 }
@@ -538,7 +422,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_ln_kernel(
         }
         if (active) {
 #pragma unroll
-            for (int k = 0; k < KS; ++k) {
+            for (int k = 0; k < kK; ++k) {
                 const int q = qb + wave + kW * k;
                 if (q < n_src) {
                     f4_st(GP + (int64_t)(p_beg + q) * ldp + f, ga[k]);
@@ -591,8 +475,8 @@ __global__ __launch_bounds__(kT) void egc_bwd_dst_ln_kernel(
     for (int s = first; s < n_seg; s += stride) {
         const int beg = seg_ptr[s], end = seg_ptr[s + 1];
         const int i = seg_node ? seg_node[s] : s;
-        const float4 gs1 = active ? f4_ld(GS1 + (int64_t)i * H + f) : f4_zero();
-        const float4 gs0 = active ? f4_ld(GS0 + (int64_t)i * H + f) : f4_zero();
+        const float4 g1 = active ? f4_ld(GS1 + (int64_t)i * H + f) : f4_zero();
+        const float4 g0 = active ? f4_ld(GS0 + (int64_t)i * H + f) : f4_zero();
         float4 gbd = f4_zero();
         for (int e = beg; e < end; ++e) {
             const float mean = e_stat[2 * (int64_t)e], rstd = e_stat[2 * (int64_t)e + 1];
@@ -602,24 +486,12 @@ __global__ __launch_bounds__(kT) void egc_bwd_dst_ln_kernel(
                 m = f4_ld(M + (int64_t)e * H + f);
                 bh = f4_ld(P + (int64_t)src[e] * ldp + 2 * H + f);
                 const float4 gy = f4_ld(GY + (int64_t)e * H + f);
-                xh = make_float4((m.x - mean) * rstd, (m.y - mean) * rstd, (m.z - mean) * rstd, (m.w - mean) * rstd);
-                const float4 z = f4_fma(xh, lg, lb);
-                const float4 gz = make_float4(gy.x * dsilu_f(z.x), gy.y * dsilu_f(z.y), gy.z * dsilu_f(z.z), gy.w * dsilu_f(z.w));
-                db = f4_add(db, gz);
-                dg = f4_fma(gz, xh, dg);
-                gh = f4_mul(gz, lg);
-                s1 = hsum4(gh);
-                s2 = hsum4(f4_mul(gh, xh));
+                ln_bwd_gh(m, gy, mean, rstd, lg, lb, xh, gh, db, dg, s1, s2);
             }
             const float c1 = wave_sum_dpp(s1) * inv_f, c2 = wave_sum_dpp(s2) * inv_f;
             if (active) {
                 const float4 sg = f4_sigmoid(m);
-                const float4 gsig = f4_fma(gs1, bh, gs0);
-                float4 gm;
-                gm.x = gsig.x * sg.x * (1.0f - sg.x) + rstd * (gh.x - c1 - xh.x * c2);
-                gm.y = gsig.y * sg.y * (1.0f - sg.y) + rstd * (gh.y - c1 - xh.y * c2);
-                gm.z = gsig.z * sg.z * (1.0f - sg.z) + rstd * (gh.z - c1 - xh.z * c2);
-                gm.w = gsig.w * sg.w * (1.0f - sg.w) + rstd * (gh.w - c1 - xh.w * c2);
+                const float4 gm = f4_add(gate_bwd(sg, g1, g0, bh), ln_bwd_gx(gh, xh, rstd, c1, c2));
                 f4_st(GM + (int64_t)e * H + f, gm);
                 gm_am = fmaxf(gm_am, f4_absmax(gm));
                 gbd = f4_add(gbd, gm);
@@ -682,57 +554,19 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_dst_ln_kernel(
                 gyt = f4_ld(GYt + (int64_t)e * H + f);
                 bh = f4_ld(P + u * ldp + 2 * H + f);
                 bht = f4_ld(Pt + u * ldp + 2 * H + f);
-                xh = make_float4((m.x - mean) * rs, (m.y - mean) * rs, (m.z - mean) * rs, (m.w - mean) * rs);
-                r0 = hsum4(t);
-                r1 = hsum4(f4_mul(xh, t));
+                ln_dual_bwd_xhat(m, t, mean, rs, xh, r0, r1);
             }
             const float m1 = wave_sum_dpp(r0) * inv_f, m2 = wave_sum_dpp(r1) * inv_f;
-            r0 = r1 = r2 = 0.0f;
-            if (active) {
-#define ALIGNN_LN_DB(q)                                              \
-    {                                                                \
-        const float th = rs * (t.q - m1 - xh.q * m2);                \
-        const float z = fmaf(xh.q, lg.q, lb.q), zt = lg.q * th;      \
-        float d1, d2;                                                \
-        dsilu2(z, d1, d2);                                           \
-        const float gzt = gyt.q * d1;                                \
-        const float gz = gy.q * d1 + gyt.q * d2 * zt;                \
-        db.q += gz;                                                  \
-        dg.q += gz * xh.q + gzt * th;                                \
-        a.q = lg.q * gzt;                                            \
-        b.q = lg.q * gz;                                             \
-        r0 += a.q;                                                   \
-        r1 += a.q * xh.q;                                            \
-        r2 += a.q * th;                                              \
-    }
-                ALIGNN_LN_DB(x) ALIGNN_LN_DB(y) ALIGNN_LN_DB(z) ALIGNN_LN_DB(w)
-#undef ALIGNN_LN_DB
-            }
+            r0 = r1 = r2 = 0.0f;  // -> sum a, sum a x-hat, sum a t-hat
+            if (active) ln_dual_bwd_ab(xh, t, gy, gyt, rs, m1, m2, lg, lb, a, b, db, dg, r0, r1, r2);
             const float A1 = wave_sum_dpp(r0) * inv_f, A2 = wave_sum_dpp(r1) * inv_f, A3 = wave_sum_dpp(r2) * inv_f;
-            r0 = r1 = 0.0f;
-            if (active) {
-                b.x -= rs * (a.x * m2 + t.x * A2);
-                b.y -= rs * (a.y * m2 + t.y * A2);
-                b.z -= rs * (a.z * m2 + t.z * A2);
-                b.w -= rs * (a.w * m2 + t.w * A2);
-                r0 = hsum4(b);
-                r1 = hsum4(f4_mul(b, xh));
-            }
+            r0 = r1 = 0.0f;  // -> sum b, sum b x-hat
+            if (active) ln_dual_bwd_b(a, t, xh, rs, m2, A2, b, r0, r1);
             const float B1 = wave_sum_dpp(r0) * inv_f, B2 = wave_sum_dpp(r1) * inv_f;
             if (active) {
                 float4 gm, gmt;
-#define ALIGNN_GD(c)                                                            \
-    {                                                                           \
-        gmt.c = rs * (a.c - A1 - xh.c * A2);                                    \
-        gm.c = rs * (b.c - B1 - xh.c * B2) - rs * xh.c * A3;                    \
-        const float sg = fast_sigmoid(m.c), sp = sg * (1.0f - sg);               \
-        const float gs = q1.c * bh.c + q0.c + q1t.c * bht.c; /* adj. sigma */   \
-        const float gst = q1t.c * bh.c + q0t.c;              /* adj. sigma-dot */ \
-        gm.c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * t.c;                  \
-        gmt.c += gst * sp;                                                      \
-    }
-                ALIGNN_GD(x) ALIGNN_GD(y) ALIGNN_GD(z) ALIGNN_GD(w)
-#undef ALIGNN_GD
+                ln_dual_bwd_gx(a, b, xh, rs, A1, A2, A3, B1, B2, gm, gmt);
+                gate_dual_bwd(m, t, bh, bht, q1, q0, q1t, q0t, gm, gmt);
                 f4_st(GM + (int64_t)e * H + f, gm);
                 f4_st(GMt + (int64_t)e * H + f, gmt);
                 am = fmaxf(am, f4_absmax(gm));
@@ -766,14 +600,6 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_dst_ln_kernel(
         block_amax_commit(pam, gp_amax2);
         block_amax_commit(pamt, gp_amax2 + 1);
     }
-}
-
-// sources per wave and pass / rows per sub-batch of the two reverse kernels (ALIGNN_AMD_LN_REV = "<value><dual>", A/B runs)
-inline int reverse_variant(int which) {  // (read per call: A/B runs inside one process)
-    const char* e = std::getenv("ALIGNN_AMD_LN_REV");
-    if (e == nullptr || e[0] < '0' || e[0] > '9') return 0;
-    if (which == 0) return e[0] - '0';
-    return (e[1] >= '0' && e[1] <= '9') ? e[1] - '0' : 0;
 }
 
 }  // namespace
@@ -821,16 +647,12 @@ int alignn_egc_bwd_lg_dense_ln(const float* GY, const float* M, const float* P, 
         return (int)hipErrorInvalidValue;
     const dim3 grid((int)n_groups), block(kT);
     const bool big = exceeds_llc(m_rows, H);
-#define ALIGNN_LNV(ST_, KS_, KB_)                                                                                              \
-    hipLaunchKernelGGL((egc_bwd_lg_dense_ln_kernel<ST_, KS_, KB_>), grid, block, 0, (hipStream_t)stream, GY, M, P, GS1, GS0, gamma, \
-                       beta, e_stat, grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, H, GM, GP, gb_partial, ln_partial, gm_amax,    \
-                       gp_amax)
-    // (tools/ln_rev_time.py, line graph of 16 x 200 atoms: one row at a time 426 us, rows in pairs 478; separate kernels 715-745)
-    switch (reverse_variant(0)) {
-        case 1: if (big) ALIGNN_LNV(true, 4, 2); else ALIGNN_LNV(false, 4, 2); break;
-        case 2: if (big) ALIGNN_LNV(true, 2, 2); else ALIGNN_LNV(false, 2, 2); break;
-        default: if (big) ALIGNN_LNV(true, 4, 1); else ALIGNN_LNV(false, 4, 1); break;
-    }
+#define ALIGNN_LNV(ST_)                                                                                                        \
+    hipLaunchKernelGGL(egc_bwd_lg_dense_ln_kernel<ST_>, grid, block, 0, (hipStream_t)stream, GY, M, P, GS1, GS0, gamma, beta, e_stat, \
+                       grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, H, GM, GP, gb_partial, ln_partial, gm_amax, gp_amax)
+    // 4 sources per wave and pass, one row at a time.  (tools/ln_rev_time.py, line graph of 16 x 200 atoms: one row at a time
+    // 426 us, rows in pairs 478; separate kernels 715-745.  The variants that lost are no longer in the file.)
+    if (big) ALIGNN_LNV(true); else ALIGNN_LNV(false);
 #undef ALIGNN_LNV
     ALIGNN_CHECK_LAUNCH();
     return 0;
@@ -861,18 +683,15 @@ int alignn_egc_dual_bwd_lg_dense_ln(const float* GY, const float* GYt, const flo
     if (n_groups == 0) return 0;
     const dim3 grid((unsigned)n_groups), block(kT);
     const bool big = exceeds_llc(m_rows, H);
-#define ALIGNN_LND(ST_, KS_, KB_, EA_)                                                                                          \
-    hipLaunchKernelGGL((egc_dual_bwd_lg_dense_ln_kernel<ST_, KS_, KB_, EA_>), grid, block, 0, (hipStream_t)stream, GY, GYt, M, Mt, P, \
-                       Pt, q1, q0, q1t, q0t, gamma, beta, e_stat, grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, H, GM, GMt, GP, GPt, \
-                       gb_partial, ln_partial, gm_amax2, gp_amax2)
+#define ALIGNN_LND(ST_)                                                                                                         \
+    hipLaunchKernelGGL(egc_dual_bwd_lg_dense_ln_kernel<ST_>, grid, block, 0, (hipStream_t)stream, GY, GYt, M, Mt, P, Pt, q1, q0, q1t, \
+                       q0t, gamma, beta, e_stat, grp_seg_ptr, grp_src_ptr, seg_ptr, seg_node, H, GM, GMt, GP, GPt, gb_partial,         \
+                       ln_partial, gm_amax2, gp_amax2)
     // measured on the line graph of 16 x 200 atoms (tools/ln_rev_time.py; separate kernels 1 390-1 450 us): 4 sources per wave
     // and pass, one row at a time, all four loads of a row requested together: 850-900 us; rows in pairs 1 020-1 050; 2 sources
-    // per wave (two passes over the segments, three waves per SIMD) 875-940
-    switch (reverse_variant(1)) {
-        case 1: if (big) ALIGNN_LND(true, 4, 2, false); else ALIGNN_LND(false, 4, 2, false); break;
-        case 2: if (big) ALIGNN_LND(true, 2, 1, false); else ALIGNN_LND(false, 2, 1, false); break;
-        default: if (big) ALIGNN_LND(true, 4, 1, true); else ALIGNN_LND(false, 4, 1, true); break;
-    }
+    // per wave (two passes over the segments, three waves per SIMD) 875-940.  The kernel is the first of these; the others are
+    // no longer in the file.
+    if (big) ALIGNN_LND(true); else ALIGNN_LND(false);
 #undef ALIGNN_LND
     ALIGNN_CHECK_LAUNCH();
     return 0;

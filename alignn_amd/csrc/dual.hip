@@ -18,6 +18,7 @@
 // Layout as in conv.hip / norm.hip: one wavefront per row (LayerNorm) or per segment (gate), lane l owns features
 // [4l, 4l+4) of each 256-feature chunk; no atomics; fixed summation orders.  "t" suffixes are tangents.
 #include "common.h"
+#include "ln_gate_rows.h"
 #include "../../include/alignn_hip.h"
 
 namespace {
@@ -145,9 +146,10 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
             if (f < F) {
                 const float4 x = f4_ld(X + r * ldx + f);
                 t[c] = f4_ld(Xt + r * ldx + f);
-                xh[c] = make_float4((x.x - mean) * rstd, (x.y - mean) * rstd, (x.z - mean) * rstd, (x.w - mean) * rstd);
-                st += hsum4(t[c]);
-                sxt += hsum4(f4_mul(xh[c], t[c]));
+                float p0, p1;
+                ln_dual_bwd_xhat(x, t[c], mean, rstd, xh[c], p0, p1);
+                st += p0;
+                sxt += p1;
             }
         }
         const float m1 = wave_sum(st) * inv_f, m2 = wave_sum(sxt) * inv_f;
@@ -158,24 +160,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
             if (f < F) {
                 const float4 g = f4_ld(gamma + f), be = f4_ld(beta + f);
                 const float4 gy = f4_ld(GY + r * ldg + f), gyt = f4_ld(GYt + r * ldg + f);
-#define ALIGNN_LN_DUAL_B(q)                                                          \
-    {                                                                                \
-        const float th = rstd * (t[c].q - m1 - xh[c].q * m2);                        \
-        const float z = fmaf(xh[c].q, g.q, be.q), zt = g.q * th;                     \
-        float d1, d2;                                                                \
-        dsilu2(z, d1, d2);                                                           \
-        const float gzt = gyt.q * d1;                /* adjoint of zdot */           \
-        const float gz = gy.q * d1 + gyt.q * d2 * zt; /* adjoint of z    */          \
-        db[c].q += gz;                                                               \
-        dg[c].q += gz * xh[c].q + gzt * th;                                          \
-        a[c].q = g.q * gzt;                          /* adjoint of t-hat */          \
-        b[c].q = g.q * gz;                           /* direct adjoint of x-hat */   \
-        sa += a[c].q;                                                                \
-        sax += a[c].q * xh[c].q;                                                     \
-        sat += a[c].q * th;                                                          \
-    }
-                ALIGNN_LN_DUAL_B(x) ALIGNN_LN_DUAL_B(y) ALIGNN_LN_DUAL_B(z) ALIGNN_LN_DUAL_B(w)
-#undef ALIGNN_LN_DUAL_B
+                ln_dual_bwd_ab(xh[c], t[c], gy, gyt, rstd, m1, m2, g, be, a[c], b[c], db[c], dg[c], sa, sax, sat);
             }
         }
         const float A1 = wave_sum(sa) * inv_f, A2 = wave_sum(sax) * inv_f, A3 = wave_sum(sat) * inv_f;
@@ -185,12 +170,10 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
         for (int c = 0; c < NC; ++c) {
             const int f = c * 256 + 4 * lane;
             if (f < F) {
-                b[c].x -= rstd * (a[c].x * m2 + t[c].x * A2);
-                b[c].y -= rstd * (a[c].y * m2 + t[c].y * A2);
-                b[c].z -= rstd * (a[c].z * m2 + t[c].z * A2);
-                b[c].w -= rstd * (a[c].w * m2 + t[c].w * A2);
-                sb += hsum4(b[c]);
-                sbx += hsum4(f4_mul(b[c], xh[c]));
+                float p0, p1;
+                ln_dual_bwd_b(a[c], t[c], xh[c], rstd, m2, A2, b[c], p0, p1);
+                sb += p0;
+                sbx += p1;
             }
         }
         const float B1 = wave_sum(sb) * inv_f, B2 = wave_sum(sbx) * inv_f;
@@ -199,11 +182,7 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
             const int f = c * 256 + 4 * lane;
             if (f < F) {
                 float4 gx, gxt;
-#define ALIGNN_LN_DUAL_O(q)                                                              \
-    gxt.q = rstd * (a[c].q - A1 - xh[c].q * A2);                                          \
-    gx.q = rstd * (b[c].q - B1 - xh[c].q * B2) - rstd * xh[c].q * A3;
-                ALIGNN_LN_DUAL_O(x) ALIGNN_LN_DUAL_O(y) ALIGNN_LN_DUAL_O(z) ALIGNN_LN_DUAL_O(w)
-#undef ALIGNN_LN_DUAL_O
+                ln_dual_bwd_gx(a[c], b[c], xh[c], rstd, A1, A2, A3, B1, B2, gx, gxt);
                 f4_st(GX + r * ldo + f, gx);
                 f4_st(GXt + r * ldo + f, gxt);
                 am = fmaxf(am, f4_absmax(gx));
@@ -234,21 +213,8 @@ __global__ __launch_bounds__(kT) void ln_silu_dual_bwd_kernel(
     amax2_commit(am, amt, amax2);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        sh[0][wave][lane] = db[c];
-        sh[1][wave][lane] = dg[c];
-        __syncthreads();
         const int f = c * 256 + 4 * lane;
-        if (wave == 0 && f < F) {
-            float4 s0 = sh[0][0][lane], s1 = sh[1][0][lane];
-#pragma unroll
-            for (int w = 1; w < kW; ++w) {
-                s0 = f4_add(s0, sh[0][w][lane]);
-                s1 = f4_add(s1, sh[1][w][lane]);
-            }
-            f4_st(partial + (size_t)blockIdx.x * 2 * F + f, s0);
-            f4_st(partial + (size_t)blockIdx.x * 2 * F + F + f, s1);
-        }
-        __syncthreads();
+        ln_slab_store(db[c], dg[c], sh, partial + (size_t)blockIdx.x * 2 * F, F, f, f < F, wave, lane);
     }
 }
 
@@ -420,16 +386,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_dst_kernel(
                     const float4 bh = f4_ld(P + u * ldp + 2 * H + f), bht = f4_ld(Pt + u * ldp + 2 * H + f);
                     float4 gm = GL ? f4_ld(GL + (int64_t)e * H + f) : f4_zero();
                     float4 gmt = GL ? f4_ld(GLt + (int64_t)e * H + f) : f4_zero();
-#define ALIGNN_GD(c)                                                            \
-    {                                                                           \
-        const float sg = fast_sigmoid(m.c), sp = sg * (1.0f - sg);               \
-        const float gs = q1.c * bh.c + q0.c + q1t.c * bht.c; /* adj. sigma */   \
-        const float gst = q1t.c * bh.c + q0t.c;              /* adj. sigma-dot */ \
-        gm.c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * mt.c;                 \
-        gmt.c += gst * sp;                                                      \
-    }
-                    ALIGNN_GD(x) ALIGNN_GD(y) ALIGNN_GD(z) ALIGNN_GD(w)
-#undef ALIGNN_GD
+                    gate_dual_bwd(m, mt, bh, bht, q1, q0, q1t, q0t, gm, gmt);
                     f4_st(GM + (int64_t)e * H + f, gm);
                     f4_st(GMt + (int64_t)e * H + f, gmt);
                     am = fmaxf(am, f4_absmax(gm));
@@ -572,19 +529,7 @@ __global__ __launch_bounds__(kT) void egc_dual_bwd_lg_dense_kernel(
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) {
                         if (row[k] >= 0) {
-#define ALIGNN_GDD(c)                                                                                     \
-    {                                                                                                     \
-        const float sg = fast_sigmoid(m[k].c), sp = sg * (1.0f - sg);                                      \
-        const float gs = q1.c * bh[k].c + q0.c + q1t.c * bht[k].c; /* adjoint of sigma */                  \
-        const float gst = q1t.c * bh[k].c + q0t.c;                 /* adjoint of sigma-dot */              \
-        gm[k].c += gs * sp + gst * sp * (1.0f - 2.0f * sg) * mt[k].c;                                      \
-        gmt[k].c += gst * sp;                                                                             \
-        const float sgt = sp * mt[k].c;                                                                   \
-        gbh[k].c += sg * q1.c + sgt * q1t.c;                                                              \
-        gbht[k].c += sg * q1t.c;                                                                          \
-    }
-                            ALIGNN_GDD(x) ALIGNN_GDD(y) ALIGNN_GDD(z) ALIGNN_GDD(w)
-#undef ALIGNN_GDD
+                            ALIGNN_GATE_DUAL_BWD(true, m[k], mt[k], bh[k], bht[k], q1, q0, q1t, q0t, gm[k], gmt[k], gbh[k], gbht[k])
                             f4_sts<STREAM>(GM + (int64_t)row[k] * H + f, gm[k]);
                             f4_sts<STREAM>(GMt + (int64_t)row[k] * H + f, gmt[k]);
                             am = fmaxf(am, f4_absmax(gm[k]));

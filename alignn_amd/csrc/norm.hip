@@ -4,6 +4,7 @@
 // Reference semantics: torch.nn.BatchNorm1d in training mode followed by F.silu and the residual
 // add, alignn/models/alignn.py:122-127 (conv) and :175-179 (MLPLayer).
 #include "common.h"
+#include "ln_gate_rows.h"
 #include "../../include/alignn_hip.h"
 
 namespace {
@@ -604,14 +605,10 @@ __global__ __launch_bounds__(kThreads) void ln_silu_bwd_kernel(const float* __re
             if (f < F) {
                 float4 x = f4_ld(X + r * ldx + f), gy = f4_ld(GY + r * ldgy + f);
                 float4 g = f4_ld(gamma + f), b = f4_ld(beta + f);
-                xh[c] = make_float4((x.x - mean) * rstd, (x.y - mean) * rstd, (x.z - mean) * rstd, (x.w - mean) * rstd);
-                float4 z = f4_fma(xh[c], g, b);
-                float4 gz = make_float4(gy.x * dsilu_f(z.x), gy.y * dsilu_f(z.y), gy.z * dsilu_f(z.z), gy.w * dsilu_f(z.w));
-                db[c] = f4_add(db[c], gz);
-                dg[c] = f4_fma(gz, xh[c], dg[c]);
-                gh[c] = f4_mul(gz, g);
-                s1 += hsum4(gh[c]);
-                s2 += hsum4(f4_mul(gh[c], xh[c]));
+                float p1, p2;
+                ln_bwd_gh(x, gy, mean, rstd, g, b, xh[c], gh[c], db[c], dg[c], p1, p2);
+                s1 += p1;
+                s2 += p2;
             }
         }
         const float c1 = wave_sum(s1) * inv_f, c2 = wave_sum(s2) * inv_f;
@@ -619,11 +616,7 @@ __global__ __launch_bounds__(kThreads) void ln_silu_bwd_kernel(const float* __re
         for (int c = 0; c < NC; ++c) {
             const int f = c * 256 + 4 * lane;
             if (f < F) {
-                float4 o;
-                o.x = rstd * (gh[c].x - c1 - xh[c].x * c2);
-                o.y = rstd * (gh[c].y - c1 - xh[c].y * c2);
-                o.z = rstd * (gh[c].z - c1 - xh[c].z * c2);
-                o.w = rstd * (gh[c].w - c1 - xh[c].w * c2);
+                const float4 o = ln_bwd_gx(gh[c], xh[c], rstd, c1, c2);
                 f4_st(GX + r * ldgx + f, o);
                 am = fmaxf(am, f4_absmax(o));
                 if (NODE) {
@@ -643,21 +636,8 @@ __global__ __launch_bounds__(kThreads) void ln_silu_bwd_kernel(const float* __re
     // slab [blockIdx.x][2][F]: row 0 = dbeta partial (sum gz), row 1 = dgamma partial (sum gz*xhat)
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        sh[0][wave][lane] = db[c];
-        sh[1][wave][lane] = dg[c];
-        __syncthreads();
         const int f = c * 256 + 4 * lane;
-        if (wave == 0 && f < F) {
-            float4 a = sh[0][0][lane], b = sh[1][0][lane];
-#pragma unroll
-            for (int w = 1; w < kThreads / 64; ++w) {
-                a = f4_add(a, sh[0][w][lane]);
-                b = f4_add(b, sh[1][w][lane]);
-            }
-            f4_st(partial + (size_t)blockIdx.x * 2 * F + f, a);
-            f4_st(partial + (size_t)blockIdx.x * 2 * F + F + f, b);
-        }
-        __syncthreads();
+        ln_slab_store(db[c], dg[c], sh, partial + (size_t)blockIdx.x * 2 * F, F, f, f < F, wave, lane);
     }
 }
 

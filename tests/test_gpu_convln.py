@@ -15,7 +15,6 @@ Errors are max |a - b| / max |b| over the whole tensor (tests/helpers.rel_err); 
 An ``amax`` output (zeroed before the launch) must EQUAL the largest magnitude among the elements the launch wrote: the next
 f16x3 product takes its power-of-two scale from it, and a value too small overflows the fp16 slices silently."""
 
-import os
 import zlib
 
 import pytest
@@ -208,41 +207,32 @@ def _run_case(H, gname, data):
     rep.close("dual_bwd_dst_ln + dual_bwd_src", "GPt", GPt[:, :3 * H], d64["GPt"], d32.get("GPt"), B_REVERSE,
               1e-2 * float(d64["GPt"].abs().max()))
 
-    # dense-block kernels (line graphs), every launch variant of both
+    # dense-block kernels (line graphs)
     if _is_line_graph(g):
         groups = g.grp_seg_ptr.numel() - 1
-        prev = os.environ.get("ALIGNN_AMD_LN_REV")
-        try:
-            for var in (a + b for a in "012" for b in "012"):
-                os.environ["ALIGNN_AMD_LN_REV"] = var
-                GM, GP, gb, lnp, gma, gpa = E(m, H), Z(n, 4 * H), E(groups, H), E(groups, 2, H), Z(1), Z(1)
-                assert lib.alignn_egc_bwd_lg_dense_ln(ptr(GY), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(gamma), ptr(beta), ptr(e_stat), m,
-                                                      ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, g.dense_max_src, ptr(g.seg_ptr),
-                                                      ptr(g.seg_node), H, ptr(GM), ptr(GP), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
-                assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
-                torch.cuda.synchronize()
-                ent = "bwd_lg_dense_ln " + var
-                reverse_asserts(ent, v64, v32, GM, GP[:, :3 * H], gb, red, "GP")
-                assert float(GP[:, 3 * H:].abs().max()) == 0.0
-                rep.amax(ent, "gm_amax", gma[0], GM)
-                rep.amax(ent, "gp_amax", gpa[0], GP)
-                GM, GMt, GP, GPt, gma, gpa = E(m, H), E(m, H), Z(n, 4 * H), Z(n, 4 * H), Z(2), Z(2)
-                assert lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(Q1), ptr(Q0), ptr(Q1t),
-                                                           ptr(Q0t), ptr(gamma), ptr(beta), ptr(e_stat), m, ptr(g.grp_seg_ptr),
-                                                           ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr), ptr(g.seg_node), H, ptr(GM), ptr(GMt),
-                                                           ptr(GP), ptr(GPt), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
-                assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
-                torch.cuda.synchronize()
-                ent = "dual_bwd_lg_dense_ln " + var
-                reverse_asserts(ent, d64, d32, GM, GP[:, :3 * H], gb, red, "GP", GMt, GPt[:, :3 * H])
-                for w, (a, b) in enumerate(((GM, GP), (GMt, GPt))):
-                    rep.amax(ent, f"gm_amax2[{w}]", gma[w], a)
-                    rep.amax(ent, f"gp_amax2[{w}]", gpa[w], b)
-        finally:
-            if prev is None:
-                os.environ.pop("ALIGNN_AMD_LN_REV", None)
-            else:
-                os.environ["ALIGNN_AMD_LN_REV"] = prev
+        GM, GP, gb, lnp, gma, gpa = E(m, H), Z(n, 4 * H), E(groups, H), E(groups, 2, H), Z(1), Z(1)
+        assert lib.alignn_egc_bwd_lg_dense_ln(ptr(GY), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(gamma), ptr(beta), ptr(e_stat), m,
+                                              ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, g.dense_max_src, ptr(g.seg_ptr),
+                                              ptr(g.seg_node), H, ptr(GM), ptr(GP), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
+        assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
+        torch.cuda.synchronize()
+        ent = "bwd_lg_dense_ln"
+        reverse_asserts(ent, v64, v32, GM, GP[:, :3 * H], gb, red, "GP")
+        assert float(GP[:, 3 * H:].abs().max()) == 0.0
+        rep.amax(ent, "gm_amax", gma[0], GM)
+        rep.amax(ent, "gp_amax", gpa[0], GP)
+        GM, GMt, GP, GPt, gma, gpa = E(m, H), E(m, H), Z(n, 4 * H), Z(n, 4 * H), Z(2), Z(2)
+        assert lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(Q1), ptr(Q0), ptr(Q1t),
+                                                   ptr(Q0t), ptr(gamma), ptr(beta), ptr(e_stat), m, ptr(g.grp_seg_ptr),
+                                                   ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr), ptr(g.seg_node), H, ptr(GM), ptr(GMt),
+                                                   ptr(GP), ptr(GPt), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
+        assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
+        torch.cuda.synchronize()
+        ent = "dual_bwd_lg_dense_ln"
+        reverse_asserts(ent, d64, d32, GM, GP[:, :3 * H], gb, red, "GP", GMt, GPt[:, :3 * H])
+        for w, (a, b) in enumerate(((GM, GP), (GMt, GPt))):
+            rep.amax(ent, f"gm_amax2[{w}]", gma[w], a)
+            rep.amax(ent, f"gp_amax2[{w}]", gpa[w], b)
     rep.finish()
 
 
@@ -255,8 +245,7 @@ CASES = ([(H, gname, "normal") for H in HS for gname in SMALL]
 
 @pytest.mark.parametrize("H,gname,data", CASES)
 def test_entry_points_against_float64(H, gname, data):
-    """Every output of the six entry points of csrc/convln.hip against the float64 restatements: on line graphs all six (every
-    ALIGNN_AMD_LN_REV variant of the two dense-block reverse kernels), on other graphs the forward, the dual forward and the
+    """Every output of the six entry points of csrc/convln.hip against the float64 restatements: on line graphs all six, on other graphs the forward, the dual forward and the
     two destination-ordered reverse passes (completed by the source-ordered halves).  See the module docstring for the
     bounds; the worst error per entry point and output is printed."""
     _run_case(H, gname, data)

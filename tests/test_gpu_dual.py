@@ -319,9 +319,7 @@ def test_reverse_kernels_with_the_layernorm_inside_against_the_separate_kernels(
     """csrc/convln.hip at the kernel level: alignn_egc_bwd_lg_dense_ln and alignn_egc_dual_bwd_lg_dense_ln against
     alignn_ln_silu_bwd + alignn_egc_bwd_lg_dense(MODE 2) and alignn_ln_silu_dual_bwd + alignn_egc_dual_bwd_lg_dense on the
     same random operands - every output: the edge adjoints GM (GMt), all blocks of GP (GPt) the kernels write, the bias-gradient
-    slabs and the LayerNorm parameter gradients - and every launch variant of the two kernels (ALIGNN_AMD_LN_REV)."""
-    import os
-
+    slabs and the LayerNorm parameter gradients."""
     from alignn_amd import _lib
     from alignn_amd.ops import ptr, stream
 
@@ -353,55 +351,44 @@ def test_reverse_kernels_with_the_layernorm_inside_against_the_separate_kernels(
     assert lib.alignn_egc_bwd_lg_dense(ptr(GL), ptr(M), ptr(P), ptr(q1), ptr(q0), None, None, 0, m, ptr(lg.grp_seg_ptr),
                                        ptr(lg.grp_src_ptr), groups, lg.dense_max_src, ptr(lg.seg_ptr), ptr(lg.seg_node), H, ptr(GMs),
                                        ptr(GPs), ptr(gbs), None, None, st) == 0
-    prev = os.environ.get("ALIGNN_AMD_LN_REV")
-    try:
-        for v in "012":
-            os.environ["ALIGNN_AMD_LN_REV"] = v + "0"
-            GMf, GPf = torch.empty(m, H, device=DEV), torch.zeros(n, 4 * H, device=DEV)
-            gbf, lnp, red_f = torch.empty(groups, H, device=DEV), torch.empty(groups, 2, H, device=DEV), torch.empty(2, H, device=DEV)
-            assert lib.alignn_egc_bwd_lg_dense_ln(ptr(GY), ptr(M), ptr(P), ptr(q1), ptr(q0), ptr(gamma), ptr(beta), ptr(e_stat), m,
-                                                  ptr(lg.grp_seg_ptr), ptr(lg.grp_src_ptr), groups, lg.dense_max_src, ptr(lg.seg_ptr),
-                                                  ptr(lg.seg_node), H, ptr(GMf), ptr(GPf), ptr(gbf), ptr(lnp), None, None, st) == 0
-            assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red_f), st) == 0
-            torch.cuda.synchronize()
-            close(GMf, GMs, "GM " + v)
-            close(GPf[:, :3 * H], GPs[:, :3 * H], "GP " + v)
-            close(gbf.sum(0), gbs.sum(0), "bias gradient " + v)
-            close(red_f, red_s, "LayerNorm parameter gradients " + v, 1e-4)
-        # ---- dual reverse
-        GLp, GLt = torch.empty(m, H, device=DEV), torch.empty(m, H, device=DEV)
-        dslabs = lib.alignn_dual_slabs(m)
-        dpart = torch.empty(dslabs, 2, H, device=DEV)
-        assert lib.alignn_ln_silu_dual_bwd(ptr(GY), ptr(GYt), H, ptr(M), ptr(Mt), H, ptr(gamma), ptr(beta), ptr(e_stat), ptr(GLp),
-                                           ptr(GLt), H, ptr(dpart), m, H, None, st) == 0
-        assert lib.alignn_bn_bwd_finalize(ptr(dpart), dslabs, H, ptr(red_s), st) == 0
-        outs_s = [torch.empty(m, H, device=DEV), torch.empty(m, H, device=DEV), torch.zeros(n, 4 * H, device=DEV),
-                  torch.zeros(n, 4 * H, device=DEV)]
-        assert lib.alignn_egc_dual_bwd_lg_dense(ptr(GLp), ptr(GLt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(q1), ptr(q0), ptr(q1t), ptr(q0t),
-                                                m, ptr(lg.grp_seg_ptr), ptr(lg.grp_src_ptr), groups, ptr(lg.seg_ptr), ptr(lg.seg_node), H,
-                                                ptr(outs_s[0]), ptr(outs_s[1]), ptr(outs_s[2]), ptr(outs_s[3]), ptr(gbs), None, None,
-                                                st) == 0
-        for v in "012":
-            os.environ["ALIGNN_AMD_LN_REV"] = "0" + v
-            outs_f = [torch.empty(m, H, device=DEV), torch.empty(m, H, device=DEV), torch.zeros(n, 4 * H, device=DEV),
-                      torch.zeros(n, 4 * H, device=DEV)]
-            gbf, lnp, red_f = torch.empty(groups, H, device=DEV), torch.empty(groups, 2, H, device=DEV), torch.empty(2, H, device=DEV)
-            assert lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(q1), ptr(q0), ptr(q1t),
-                                                       ptr(q0t), ptr(gamma), ptr(beta), ptr(e_stat), m, ptr(lg.grp_seg_ptr),
-                                                       ptr(lg.grp_src_ptr), groups, ptr(lg.seg_ptr), ptr(lg.seg_node), H, ptr(outs_f[0]),
-                                                       ptr(outs_f[1]), ptr(outs_f[2]), ptr(outs_f[3]), ptr(gbf), ptr(lnp), None, None,
-                                                       st) == 0
-            assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red_f), st) == 0
-            torch.cuda.synchronize()
-            for a, b, name in zip(outs_f, outs_s, ("GM", "GMt", "GP", "GPt")):
-                close(a[:, :3 * H] if a.shape[1] == 4 * H else a, b[:, :3 * H] if b.shape[1] == 4 * H else b, name + " dual " + v)
-            close(gbf.sum(0), gbs.sum(0), "bias gradient, dual " + v)
-            close(red_f, red_s, "LayerNorm parameter gradients, dual " + v, 1e-4)
-    finally:
-        if prev is None:
-            os.environ.pop("ALIGNN_AMD_LN_REV", None)
-        else:
-            os.environ["ALIGNN_AMD_LN_REV"] = prev
+    GMf, GPf = torch.empty(m, H, device=DEV), torch.zeros(n, 4 * H, device=DEV)
+    gbf, lnp, red_f = torch.empty(groups, H, device=DEV), torch.empty(groups, 2, H, device=DEV), torch.empty(2, H, device=DEV)
+    assert lib.alignn_egc_bwd_lg_dense_ln(ptr(GY), ptr(M), ptr(P), ptr(q1), ptr(q0), ptr(gamma), ptr(beta), ptr(e_stat), m,
+                                          ptr(lg.grp_seg_ptr), ptr(lg.grp_src_ptr), groups, lg.dense_max_src, ptr(lg.seg_ptr),
+                                          ptr(lg.seg_node), H, ptr(GMf), ptr(GPf), ptr(gbf), ptr(lnp), None, None, st) == 0
+    assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red_f), st) == 0
+    torch.cuda.synchronize()
+    close(GMf, GMs, "GM")
+    close(GPf[:, :3 * H], GPs[:, :3 * H], "GP")
+    close(gbf.sum(0), gbs.sum(0), "bias gradient")
+    close(red_f, red_s, "LayerNorm parameter gradients", 1e-4)
+    # ---- dual reverse
+    GLp, GLt = torch.empty(m, H, device=DEV), torch.empty(m, H, device=DEV)
+    dslabs = lib.alignn_dual_slabs(m)
+    dpart = torch.empty(dslabs, 2, H, device=DEV)
+    assert lib.alignn_ln_silu_dual_bwd(ptr(GY), ptr(GYt), H, ptr(M), ptr(Mt), H, ptr(gamma), ptr(beta), ptr(e_stat), ptr(GLp),
+                                       ptr(GLt), H, ptr(dpart), m, H, None, st) == 0
+    assert lib.alignn_bn_bwd_finalize(ptr(dpart), dslabs, H, ptr(red_s), st) == 0
+    outs_s = [torch.empty(m, H, device=DEV), torch.empty(m, H, device=DEV), torch.zeros(n, 4 * H, device=DEV),
+              torch.zeros(n, 4 * H, device=DEV)]
+    assert lib.alignn_egc_dual_bwd_lg_dense(ptr(GLp), ptr(GLt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(q1), ptr(q0), ptr(q1t), ptr(q0t),
+                                            m, ptr(lg.grp_seg_ptr), ptr(lg.grp_src_ptr), groups, ptr(lg.seg_ptr), ptr(lg.seg_node), H,
+                                            ptr(outs_s[0]), ptr(outs_s[1]), ptr(outs_s[2]), ptr(outs_s[3]), ptr(gbs), None, None,
+                                            st) == 0
+    outs_f = [torch.empty(m, H, device=DEV), torch.empty(m, H, device=DEV), torch.zeros(n, 4 * H, device=DEV),
+              torch.zeros(n, 4 * H, device=DEV)]
+    gbf, lnp, red_f = torch.empty(groups, H, device=DEV), torch.empty(groups, 2, H, device=DEV), torch.empty(2, H, device=DEV)
+    assert lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(q1), ptr(q0), ptr(q1t),
+                                               ptr(q0t), ptr(gamma), ptr(beta), ptr(e_stat), m, ptr(lg.grp_seg_ptr),
+                                               ptr(lg.grp_src_ptr), groups, ptr(lg.seg_ptr), ptr(lg.seg_node), H, ptr(outs_f[0]),
+                                               ptr(outs_f[1]), ptr(outs_f[2]), ptr(outs_f[3]), ptr(gbf), ptr(lnp), None, None,
+                                               st) == 0
+    assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red_f), st) == 0
+    torch.cuda.synchronize()
+    for a, b, name in zip(outs_f, outs_s, ("GM", "GMt", "GP", "GPt")):
+        close(a[:, :3 * H] if a.shape[1] == 4 * H else a, b[:, :3 * H] if b.shape[1] == 4 * H else b, name + " dual")
+    close(gbf.sum(0), gbs.sum(0), "bias gradient, dual")
+    close(red_f, red_s, "LayerNorm parameter gradients, dual", 1e-4)
 
 
 @pytest.mark.parametrize("shape,H", [("small", 256), ("deg_over_16", 64)])

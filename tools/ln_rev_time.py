@@ -1,6 +1,6 @@
 """Kernel-level timing of the line-graph reverse passes with the edge LayerNorm inside (csrc/convln.hip) against the separate
-kernels they replace, on the line graph of a BASELINE configs[3] batch (16 x 200 atoms), and of the launch variants
-(ALIGNN_AMD_LN_REV = "<value><dual>": sources per wave and pass / rows per sub-batch / early loads).
+kernels they replace, on the line graph of a BASELINE configs[3] batch (16 x 200 atoms): the value pair and the dual pair,
+with the largest difference between the fused and the separate results.
 
     python tools/ln_rev_time.py [batch] [atoms]
 """
@@ -92,24 +92,17 @@ def val_fused():
 
 row_bytes = m * H * 4
 print(f"value reverse, separate kernels (ln_silu_bwd + egc_bwd_lg_dense<2>): {timed(val_sep):7.1f} us  (6 row passes)")
-ref = None
-for v, name in ((0, "4 sources/wave, 1 row"), (1, "4 sources/wave, 2 rows"), (2, "2 sources/wave, 2 rows")):
-    os.environ["ALIGNN_AMD_LN_REV"] = f"{v}0"
-    t = timed(val_fused)
-    gm = GM.clone()
-    if ref is None:
-        val_sep()
-        torch.cuda.synchronize()
-        print("   max |fused - separate| / max|.|:", float((gm - GM).abs().max() / GM.abs().max()))
-    print(f"value reverse, LayerNorm inside, {name}: {t:7.1f} us  = {3 * row_bytes / t / 1e6:5.2f} TB/s over 3 row passes")
-    ref = gm
+t = timed(val_fused)
+gm = GM.clone()
+val_sep()
+torch.cuda.synchronize()
+print(f"value reverse, LayerNorm inside: {t:7.1f} us  = {3 * row_bytes / t / 1e6:5.2f} TB/s over 3 row passes  "
+      f"(max |fused - separate| / max|.|: {float((gm - GM).abs().max() / GM.abs().max()):.1e})")
 print(f"dual reverse, separate kernels (ln_silu_dual_bwd + egc_dual_bwd_lg_dense): {timed(dual_sep):7.1f} us  (12 row passes)")
 dual_sep()
 torch.cuda.synchronize()
 gm_s, gmt_s = GM.clone(), GMt.clone()
-for v, name in ((0, "4 sources/wave, 1 row, loads together"), (1, "4 sources/wave, 2 rows"), (2, "2 sources/wave, 1 row")):
-    os.environ["ALIGNN_AMD_LN_REV"] = f"0{v}"
-    t = timed(dual_fused)
-    e1 = float((GM - gm_s).abs().max() / gm_s.abs().max())
-    e2 = float((GMt - gmt_s).abs().max() / gmt_s.abs().max())
-    print(f"dual reverse, LayerNorm inside, {name}: {t:7.1f} us  = {6 * row_bytes / t / 1e6:5.2f} TB/s over 6 row passes  (vs separate: {e1:.1e} {e2:.1e})")
+t = timed(dual_fused)
+e1 = float((GM - gm_s).abs().max() / gm_s.abs().max())
+e2 = float((GMt - gmt_s).abs().max() / gmt_s.abs().max())
+print(f"dual reverse, LayerNorm inside: {t:7.1f} us  = {6 * row_bytes / t / 1e6:5.2f} TB/s over 6 row passes  (vs separate: {e1:.1e} {e2:.1e})")
