@@ -1,5 +1,6 @@
 """ctypes binding of libalignn_hip.so.  The C ABI is declared once, in include/alignn_hip.h: the prototypes and argument
-structs used here are read from that header (_abi.py), not restated.
+structs used here are read from that header (_abi.py), not restated.  The batched workflows declare theirs in headers of
+their own; ``bind`` types those of one such header on the same library.
 
 The product path has NO fallback: if the shared library is missing or a GPU call fails, an
 exception is raised.  PyTorch appears here only as the owner of device memory and streams.
@@ -25,6 +26,19 @@ FireArgs, MdArgs = STRUCTS["alignn_fire_args"], STRUCTS["alignn_md_args"]
 
 
 _lib = None
+_bound = {}  # header path -> the library object its entry points were last typed on
+
+
+def _type(lib, signatures):
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+def _check_size(name, size, block):
+    if size != C.sizeof(block):  # (a library built from another header than the one read here)
+        raise RuntimeError(f"argument block {name}: library says {size} bytes, the header gives {C.sizeof(block)}")
 
 
 def load() -> C.CDLL:
@@ -37,17 +51,24 @@ def load() -> C.CDLL:
                 "(hipcc --offload-arch=gfx950); alignn_amd has no CPU/eager fallback."
             )
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        _type(lib, SIGNATURES)
         sizes = [lib.alignn_egc_args_sizeof(k) for k in range(3)] + [lib.alignn_fire_args_sizeof(), lib.alignn_md_args_sizeof()]
         for size, block in zip(sizes, (EgcFwdArgs, EgcBwdArgs, EgcWgradArgs, FireArgs, MdArgs)):
-            if size != C.sizeof(block):  # (a library built from another alignn_hip.h than the one read here)
-                raise RuntimeError(f"argument block {block.__name__}: library says {size} bytes, the header gives "
-                                   f"{C.sizeof(block)}")
+            _check_size(block.__name__, size, block)
         _lib = lib
     return _lib
+
+
+def bind(header, lib=None):
+    """The library of ``load()`` (or ``lib``) with the entry points of ``header`` (an ``_abi.Header``) typed, once per library
+    object; every argument block ``S`` of the header is checked against the library's ``S_size()``."""
+    lib = load() if lib is None else lib
+    if _bound.get(header.path) is not lib:
+        _type(lib, header.signatures)
+        for name, block in header.structs.items():
+            _check_size(name, getattr(lib, name + "_size")(), block)
+        _bound[header.path] = lib
+    return lib
 
 
 def ptr(t):

@@ -14,6 +14,8 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
+from ._abi import WORKFLOW_HEADERS
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
@@ -71,7 +73,7 @@ def faulting_packed_forms(lib: str = None) -> list:
 def _headers():
     include = os.path.join(os.path.dirname(HERE), "include")
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
-        os.path.join(include, f) for f in ("alignn_hip.h", "alignn_thermo.h", "alignn_neb.h", "alignn_traj.h", "alignn_sym.h", "alignn_order.h", "alignn_phsym.h")]
+        os.path.join(include, f) for f in ("alignn_hip.h",) + WORKFLOW_HEADERS]
 
 
 def _stale(target, deps) -> bool:

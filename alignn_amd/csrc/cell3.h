@@ -1,6 +1,8 @@
 // What the builders of derived structures share (defects.hip, interface.hip, eos.hip): the inverse of a 3 x 3 cell by cofactors and
-// the product of a row vector with a cell; and, for symmetry.hip and phonon_sym.hip, the Cartesian rotation of an operation.  float64 without contraction, every sum in a fixed order; tests/defects_ref.py restates
-// both operation for operation (inv3_cof, row_dot).
+// the product of a row vector with a cell; for symmetry.hip and phonon_sym.hip, the Cartesian rotation of an operation; and, for
+// trajectory.hip, order.hip and symmetry.hip, the determinant, the heights and the range of periodic images of a cell.  float64
+// without contraction, every sum in a fixed order; tests/defects_ref.py restates the first two operation for operation (inv3_cof,
+// row_dot), tests/traj_ref.py the image range.
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +21,44 @@ __device__ __forceinline__ void inv3_cof(const double (&a)[9], double (&inv)[9])
     inv[6] = c02 / det;
     inv[7] = (a[1] * a[6] - a[0] * a[7]) / det;
     inv[8] = (a[0] * a[4] - a[1] * a[3]) / det;
+}
+
+// det A along its first row, the association of inv3_cof
+__device__ __forceinline__ double det3_cof(const double (&a)[9]) {
+    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[3] * a[8] - a[5] * a[6], c02 = a[3] * a[7] - a[4] * a[6];
+    return (a[0] * c00 - a[1] * c01) + a[2] * c02;
+}
+
+// the height h_k = vol / |a_{k+1} x a_{k+2}| of a cell of volume vol = |det A|
+__device__ __forceinline__ double height(const double (&A)[9], double vol, int k) {
+    const double* u = A + 3 * ((k + 1) % 3);
+    const double* v = A + 3 * ((k + 2) % 3);
+    const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
+    return vol / sqrt((cx * cx + cy * cy) + cz * cz);
+}
+
+__device__ __forceinline__ void heights(const double (&A)[9], double (&h)[3]) {
+    const double vol = fabs(det3_cof(A));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) h[k] = height(A, vol, k);
+}
+
+// the periodic images a sphere of radius r reaches: M_k = floor(r / h_k + 1/2) per axis; false when an axis needs more than
+// max_range (or the cell is singular or not finite)
+__device__ __forceinline__ bool image_range(const double (&C)[9], double r, int max_range, int (&M)[3]) {
+    const double vol = fabs(det3_cof(C));
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double q = floor(r / height(C, vol, k) + 0.5);
+        if (!(q >= 0.0 && q <= (double)max_range)) {  // (a NaN fails both)
+            ok = false;
+            M[k] = 0;
+        } else {
+            M[k] = (int)q;
+        }
+    }
+    return ok;
 }
 
 // x M for a row vector x and a row-major M: (x0 M0k + x1 M1k) + x2 M2k

@@ -41,34 +41,6 @@ constexpr double PI = 3.14159265358979323846, TWO_PI = 2.0 * PI;
 using AngleArgs = alignn_order_angle_args;
 using SqArgs = alignn_order_sq_args;
 
-// det C along its first row, the association of cell3.h's inv3_cof
-__device__ __forceinline__ double det3_cof(const double (&a)[9]) {
-    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[3] * a[8] - a[5] * a[6], c02 = a[3] * a[7] - a[4] * a[6];
-    return (a[0] * c00 - a[1] * c01) + a[2] * c02;
-}
-
-// floor(r_cut / h_k + 1/2) per axis, h_k = |det| / |C_{k+1} x C_{k+2}| (trajectory.hip's image_range); false when an axis needs
-// more than the range (or the cell is singular, or r_cut is not a number > 0)
-__device__ __forceinline__ bool image_range(const double (&C)[9], double r_cut, int (&M)[3]) {
-    const double vol = fabs(det3_cof(C));
-    bool ok = r_cut > 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double* u = C + 3 * ((k + 1) % 3);
-        const double* v = C + 3 * ((k + 2) % 3);
-        const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
-        const double h = vol / sqrt((cx * cx + cy * cy) + cz * cz);
-        const double q = floor(r_cut / h + 0.5);
-        if (!(q >= 0.0 && q <= (double)ALIGNN_ORDER_MAX_IMAGE_RANGE)) {  // (a NaN fails both)
-            ok = false;
-            M[k] = 0;
-        } else {
-            M[k] = (int)q;
-        }
-    }
-    return ok;
-}
-
 // the pair index t = k (k - 1) / 2 + j, j < k  ->  (j, k)
 __device__ __forceinline__ void pair_of(int t, int& j, int& k) {
     k = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
@@ -119,7 +91,7 @@ __global__ __launch_bounds__(ANG_BLOCK) void angles_kernel(const AngleArgs a, in
             const int64_t cell_at = a.lattice_per_frame ? (int64_t)frame * a.n_structs + b : b;
 #pragma unroll
             for (int j = 0; j < 9; ++j) C[j] = a.lattice[9 * cell_at + j];
-            if (!image_range(C, r_cut, M)) {
+            if (!image_range(C, r_cut, ALIGNN_ORDER_MAX_IMAGE_RANGE, M) || !(r_cut > 0.0)) {  // (or r_cut is not a number > 0)
                 if (lane == 0) atomicOr(a.status, ALIGNN_ORDER_STATUS_IMAGES);
                 continue;
             }

@@ -35,25 +35,6 @@ using ApplyArgs = alignn_sym_apply_args;
 
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
 
-// det A along its first row, the association of cell3.h's inv3_cof
-__device__ __forceinline__ double det3_cof(const double (&a)[9]) {
-    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[3] * a[8] - a[5] * a[6], c02 = a[3] * a[7] - a[4] * a[6];
-    return (a[0] * c00 - a[1] * c01) + a[2] * c02;
-}
-
-// the heights h_k = |det A| / |a_{k+1} x a_{k+2}|
-__device__ __forceinline__ void heights(const double (&A)[9], double (&h)[3]) {
-    const double vol = fabs(det3_cof(A));
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double* u = A + 3 * ((k + 1) % 3);
-        const double* v = A + 3 * ((k + 2) % 3);
-        const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
-        h[k] = vol / norm3(cx, cy, cz);
-    }
-}
-
-
 __device__ __forceinline__ int det3i(const int (&W)[9]) {
     return W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
 }

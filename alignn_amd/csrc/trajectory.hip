@@ -39,34 +39,6 @@ __device__ __forceinline__ void load_cell(const RdfArgs& a, int b, int frame, do
     for (int j = 0; j < 9; ++j) C[j] = a.lattice[9 * at + j];
 }
 
-// det C along its first row, the association of cell3.h's inv3_cof
-__device__ __forceinline__ double det3_cof(const double (&a)[9]) {
-    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[3] * a[8] - a[5] * a[6], c02 = a[3] * a[7] - a[4] * a[6];
-    return (a[0] * c00 - a[1] * c01) + a[2] * c02;
-}
-
-// floor(r_max / h_k + 1/2) per axis, h_k = |det| / |C_{k+1} x C_{k+2}|; false when an axis needs more than the range (or the
-// cell is singular or not finite)
-__device__ __forceinline__ bool image_range(const double (&C)[9], double r_max, int (&M)[3]) {
-    const double vol = fabs(det3_cof(C));
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double* u = C + 3 * ((k + 1) % 3);
-        const double* v = C + 3 * ((k + 2) % 3);
-        const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
-        const double h = vol / sqrt((cx * cx + cy * cy) + cz * cz);
-        const double q = floor(r_max / h + 0.5);
-        if (!(q >= 0.0 && q <= (double)ALIGNN_TRAJ_MAX_IMAGE_RANGE)) {  // (a NaN fails both)
-            ok = false;
-            M[k] = 0;
-        } else {
-            M[k] = (int)q;
-        }
-    }
-    return ok;
-}
-
 __global__ __launch_bounds__(RDF_BLOCK) void rdf_counts_kernel(const RdfArgs a, int types_per_chunk) {
     extern __shared__ unsigned hist[];  // [types_per_chunk][n_bins]
     __shared__ double xj[RDF_TILE][3];
@@ -83,7 +55,7 @@ __global__ __launch_bounds__(RDF_BLOCK) void rdf_counts_kernel(const RdfArgs a, 
     double C[9], Ci[9];
     int M[3];
     load_cell(a, b, frame, C);
-    if (!image_range(C, a.r_max, M)) {
+    if (!image_range(C, a.r_max, ALIGNN_TRAJ_MAX_IMAGE_RANGE, M)) {
         if (threadIdx.x == 0) atomicOr(a.status, ALIGNN_TRAJ_STATUS_IMAGES);
         return;
     }

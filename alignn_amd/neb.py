@@ -27,7 +27,6 @@ from __future__ import annotations
 
 import ctypes as C
 import numbers
-import os
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
@@ -40,31 +39,16 @@ from .relax import relax
 
 __all__ = ["neb", "neb_interpolate", "NEBResult", "METHODS", "MAX_IMAGES"]
 
-HEADER = os.path.join(os.path.dirname(_abi.HEADER), "alignn_neb.h")
-with open(HEADER) as _f:
-    STRUCTS, SIGNATURES = _abi.parse(_f.read())  # the argument block alignn_neb_args; entry point -> (restype, argtypes)
+H = _abi.header("alignn_neb.h")
+HEADER, STRUCTS, SIGNATURES = H.path, H.structs, H.signatures  # the argument block alignn_neb_args; entry point -> (restype, argtypes)
 NebArgs = STRUCTS["alignn_neb_args"]
 METHODS = {"aseneb": 0, "improvedtangent": 1}
-MAX_IMAGES = 64  # ALIGNN_NEB_MAX_IMAGES: images per band, the endpoints included
+MAX_IMAGES = H.defines["ALIGNN_NEB_MAX_IMAGES"]  # images per band, the endpoints included
 _FIRE = ("dt", "maxstep", "dtmax", "Nmin", "finc", "fdec", "astart", "fa", "a")
-
-_bound = None
 
 
 def _load():
-    """The library of ``_lib.load()`` with the entry points of alignn_neb.h typed (once)."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.alignn_neb_args_size() != C.sizeof(NebArgs):  # (a library built from another alignn_neb.h than the one read here)
-            raise RuntimeError(f"argument block alignn_neb_args: library says {lib.alignn_neb_args_size()} bytes, the header "
-                               f"gives {C.sizeof(NebArgs)}")
-        _bound = lib
-    return lib
+    return _lib.bind(H)
 
 
 @dataclass

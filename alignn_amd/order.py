@@ -29,7 +29,6 @@ from __future__ import annotations
 
 import ctypes as C
 import numbers
-import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -42,38 +41,24 @@ from .trajectory import _frames, _groups, _positive, _traj, pair_row  # noqa: F4
 __all__ = ["adf", "steinhardt", "structure_factor", "ADFResult", "SteinhardtResult", "SQResult", "MAX_NEIGHBORS", "MAX_L",
            "MAX_HKL", "MAX_BINS", "MAX_IMAGE_RANGE"]
 
-HEADER = os.path.join(os.path.dirname(_abi.HEADER), "alignn_order.h")
-with open(HEADER) as _f:
-    STRUCTS, SIGNATURES = _abi.parse(_f.read())  # the argument blocks; entry point -> (restype, argtypes)
+H = _abi.header("alignn_order.h")
+HEADER, STRUCTS, SIGNATURES = H.path, H.structs, H.signatures  # the argument blocks; entry point -> (restype, argtypes)
 AngleArgs, SqArgs = STRUCTS["alignn_order_angle_args"], STRUCTS["alignn_order_sq_args"]
-MAX_SPECIES = 8  # ALIGNN_ORDER_MAX_SPECIES
-MAX_IMAGE_RANGE = 8  # ALIGNN_ORDER_MAX_IMAGE_RANGE
-MAX_NEIGHBORS = 64  # ALIGNN_ORDER_MAX_NEIGHBORS
-MAX_BINS = 1024  # ALIGNN_ORDER_MAX_BINS
-MAX_L = 12  # ALIGNN_ORDER_MAX_L
-MAX_LS = 4  # ALIGNN_ORDER_MAX_LS
-MAX_HKL = 32  # ALIGNN_ORDER_MAX_HKL
-SQ_FRAME_CHUNK = 64  # ALIGNN_ORDER_SQ_FRAME_CHUNK
-STATUS_IMAGES, STATUS_NEIGHBORS, STATUS_HKL = 1, 2, 4  # ALIGNN_ORDER_STATUS_*
-
-_bound = None
+MAX_SPECIES = H.defines["ALIGNN_ORDER_MAX_SPECIES"]
+MAX_IMAGE_RANGE = H.defines["ALIGNN_ORDER_MAX_IMAGE_RANGE"]
+MAX_NEIGHBORS = H.defines["ALIGNN_ORDER_MAX_NEIGHBORS"]
+MAX_BINS = H.defines["ALIGNN_ORDER_MAX_BINS"]
+MAX_L = H.defines["ALIGNN_ORDER_MAX_L"]
+MAX_LS = H.defines["ALIGNN_ORDER_MAX_LS"]
+MAX_HKL = H.defines["ALIGNN_ORDER_MAX_HKL"]
+SQ_FRAME_CHUNK = H.defines["ALIGNN_ORDER_SQ_FRAME_CHUNK"]
+STATUS_IMAGES = H.defines["ALIGNN_ORDER_STATUS_IMAGES"]
+STATUS_NEIGHBORS = H.defines["ALIGNN_ORDER_STATUS_NEIGHBORS"]
+STATUS_HKL = H.defines["ALIGNN_ORDER_STATUS_HKL"]
 
 
 def _load():
-    """The library of ``_lib.load()`` with the entry points of alignn_order.h typed (once)."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        for query, block in ((lib.alignn_order_angle_args_size, AngleArgs), (lib.alignn_order_sq_args_size, SqArgs)):
-            if query() != C.sizeof(block):  # (a library built from another alignn_order.h than the one read here)
-                raise RuntimeError(f"argument block {block.__name__}: library says {query()} bytes, the header gives "
-                                   f"{C.sizeof(block)}")
-        _bound = lib
-    return lib
+    return _lib.bind(H)
 
 
 # --- results -----------------------------------------------------------------------------------------------------------------------

@@ -28,7 +28,6 @@ from __future__ import annotations
 
 import ctypes as C
 import numbers
-import os
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence
 
@@ -55,33 +54,16 @@ MAX_ATOMS_PER_EVAL = 32768
 DISPLACEMENTS = ("all", "symmetry")
 
 # the entry points of the symmetry-reduced path: include/alignn_phsym.h
-PHSYM_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "alignn_phsym.h")
-with open(PHSYM_HEADER) as _f:
-    PHSYM_STRUCTS, PHSYM_SIGNATURES = _abi.parse(_f.read())  # the argument blocks; entry point -> (restype, argtypes)
+PHSYM = _abi.header("alignn_phsym.h")
+PHSYM_HEADER, PHSYM_STRUCTS, PHSYM_SIGNATURES = PHSYM.path, PHSYM.structs, PHSYM.signatures
 PlanArgs, DisplaceArgs = PHSYM_STRUCTS["alignn_phsym_plan_args"], PHSYM_STRUCTS["alignn_phsym_displace_args"]
 RowsArgs, FcArgs = PHSYM_STRUCTS["alignn_phsym_rows_args"], PHSYM_STRUCTS["alignn_phsym_fc_args"]
-PHSYM_MAX_ATOMS = 32  # ALIGNN_PHSYM_MAX_ATOMS
-PHSYM_MAX_SITE_OPS = 48  # ALIGNN_PHSYM_MAX_SITE_OPS
-
-_phsym_bound = None
+PHSYM_MAX_ATOMS = PHSYM.defines["ALIGNN_PHSYM_MAX_ATOMS"]
+PHSYM_MAX_SITE_OPS = PHSYM.defines["ALIGNN_PHSYM_MAX_SITE_OPS"]
 
 
 def _load_phsym():
-    """The library of ``_lib.load()`` with the entry points of alignn_phsym.h typed (once)."""
-    global _phsym_bound
-    lib = _lib.load()
-    if _phsym_bound is not lib:
-        for name, (res, args) in PHSYM_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        for query, block in ((lib.alignn_phsym_plan_args_size, PlanArgs), (lib.alignn_phsym_displace_args_size, DisplaceArgs),
-                             (lib.alignn_phsym_rows_args_size, RowsArgs), (lib.alignn_phsym_fc_args_size, FcArgs)):
-            if query() != C.sizeof(block):  # (a library built from another alignn_phsym.h than the one read here)
-                raise RuntimeError(f"argument block {block.__name__}: library says {query()} bytes, the header gives "
-                                   f"{C.sizeof(block)}")
-        _phsym_bound = lib
-    return lib
+    return _lib.bind(PHSYM)
 
 
 def monkhorst_pack(kpts) -> np.ndarray:

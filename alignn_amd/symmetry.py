@@ -28,7 +28,6 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import numbers
-import os
 from dataclasses import dataclass, field
 from math import gcd
 from typing import List, Optional, Sequence, Tuple
@@ -42,36 +41,22 @@ from ._structures import host, shape_of
 __all__ = ["find_symmetry", "symmetrize_forces", "symmetrize_stress", "symmetrize_positions", "distinct_miller_indices",
            "SymmetryResult", "CRYSTAL_SYSTEMS", "MAX_ATOMS", "MAX_IMAGE_RANGE"]
 
-HEADER = os.path.join(os.path.dirname(_abi.HEADER), "alignn_sym.h")
-with open(HEADER) as _f:
-    STRUCTS, SIGNATURES = _abi.parse(_f.read())  # the argument blocks; entry point -> (restype, argtypes)
+H = _abi.header("alignn_sym.h")
+HEADER, STRUCTS, SIGNATURES = H.path, H.structs, H.signatures  # the argument blocks; entry point -> (restype, argtypes)
 FindArgs, ApplyArgs = STRUCTS["alignn_sym_find_args"], STRUCTS["alignn_sym_apply_args"]
-MAX_ATOMS = 1024  # ALIGNN_SYM_MAX_ATOMS
-MAX_IMAGE_RANGE = 8  # ALIGNN_SYM_MAX_IMAGE_RANGE
-MAX_CANDIDATES = 256  # ALIGNN_SYM_MAX_CANDIDATES
-MAX_LATTICE_OPS = 48  # ALIGNN_SYM_MAX_LATTICE_OPS
-INFO = 8  # ALIGNN_SYM_INFO
-STATUS_IMAGES, STATUS_OVERFLOW, STATUS_INPUT = 1, 2, 4  # ALIGNN_SYM_STATUS_*
+MAX_ATOMS = H.defines["ALIGNN_SYM_MAX_ATOMS"]
+MAX_IMAGE_RANGE = H.defines["ALIGNN_SYM_MAX_IMAGE_RANGE"]
+MAX_CANDIDATES = H.defines["ALIGNN_SYM_MAX_CANDIDATES"]
+MAX_LATTICE_OPS = H.defines["ALIGNN_SYM_MAX_LATTICE_OPS"]
+INFO = H.defines["ALIGNN_SYM_INFO"]
+STATUS_IMAGES = H.defines["ALIGNN_SYM_STATUS_IMAGES"]
+STATUS_OVERFLOW = H.defines["ALIGNN_SYM_STATUS_OVERFLOW"]
+STATUS_INPUT = H.defines["ALIGNN_SYM_STATUS_INPUT"]
 CRYSTAL_SYSTEMS = ("triclinic", "monoclinic", "orthorhombic", "tetragonal", "trigonal", "hexagonal", "cubic")
-
-_bound = None
 
 
 def _load():
-    """The library of ``_lib.load()`` with the entry points of alignn_sym.h typed (once)."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        for query, block in ((lib.alignn_sym_find_args_size, FindArgs), (lib.alignn_sym_apply_args_size, ApplyArgs)):
-            if query() != C.sizeof(block):  # (a library built from another alignn_sym.h than the one read here)
-                raise RuntimeError(f"argument block {block.__name__}: library says {query()} bytes, the header gives "
-                                   f"{C.sizeof(block)}")
-        _bound = lib
-    return lib
+    return _lib.bind(H)
 
 
 @dataclass

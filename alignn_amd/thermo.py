@@ -24,7 +24,6 @@ read here with the reader of alignn_amd/_abi.py.
 from __future__ import annotations
 
 import numbers
-import os
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -41,29 +40,17 @@ from .phonons import DISPLACEMENTS, MAX_DIM, PhononResult, _supercells, monkhors
 __all__ = ["thermal_sums", "thermal_properties", "qha", "ThermalResult", "QHAResult", "KB"]
 
 KB = 1.38064852e-23 / 1.6021766208e-19  # eV/K, CODATA 2014: the unit set of alignn_amd/phonons.py (and the kernel's constant)
-HEADER = os.path.join(os.path.dirname(_abi.HEADER), "alignn_thermo.h")
-with open(HEADER) as _f:
-    _, SIGNATURES = _abi.parse(_f.read())  # entry point -> (restype, argtypes); the header declares no structs
+H = _abi.header("alignn_thermo.h")  # (it declares no structs)
+HEADER, SIGNATURES = H.path, H.signatures
 DEFAULT_TEMPERATURES = np.arange(0, 1001, 10)  # K: the reference's ``phonons3`` asks for these
 DEFAULT_DX = np.arange(-0.05, 0.05, 0.01)  # the reference's ``ev_curve`` strains
 # ``qha`` has a ``cutoff`` of its own (the mode cutoff, eV), so the neighbour cutoff of the evaluations cannot be passed through it
 _EVALUATION = tuple(k for k in EVALUATION if k != "cutoff")
 _ION_RELAXATION = ("steps", "fmax")
 
-_bound = None
-
 
 def _load():
-    """The library of ``_lib.load()`` with the entry points of alignn_thermo.h typed (once)."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bound = lib
-    return lib
+    return _lib.bind(H)
 
 
 @dataclass

@@ -33,7 +33,6 @@ from __future__ import annotations
 
 import ctypes as C
 import numbers
-import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -48,35 +47,19 @@ __all__ = ["rdf", "msd", "vacf", "vdos", "diffusion", "green_kubo", "analyze_md"
            "VACFResult", "VDOSResult", "DiffusionResult", "TrajectoryAnalysis", "A2_FS_TO_CM2_S", "MAX_SPECIES", "MAX_BINS",
            "MAX_IMAGE_RANGE"]
 
-HEADER = os.path.join(os.path.dirname(_abi.HEADER), "alignn_traj.h")
-with open(HEADER) as _f:
-    STRUCTS, SIGNATURES = _abi.parse(_f.read())  # the argument blocks; entry point -> (restype, argtypes)
+H = _abi.header("alignn_traj.h")
+HEADER, STRUCTS, SIGNATURES = H.path, H.structs, H.signatures  # the argument blocks; entry point -> (restype, argtypes)
 RdfArgs, CorrArgs = STRUCTS["alignn_traj_rdf_args"], STRUCTS["alignn_traj_corr_args"]
-MAX_SPECIES = 8  # ALIGNN_TRAJ_MAX_SPECIES
-MAX_BINS = 4096  # ALIGNN_TRAJ_MAX_BINS
-MAX_IMAGE_RANGE = 8  # ALIGNN_TRAJ_MAX_IMAGE_RANGE
-STATUS_IMAGES = 1  # ALIGNN_TRAJ_STATUS_IMAGES
+MAX_SPECIES = H.defines["ALIGNN_TRAJ_MAX_SPECIES"]
+MAX_BINS = H.defines["ALIGNN_TRAJ_MAX_BINS"]
+MAX_IMAGE_RANGE = H.defines["ALIGNN_TRAJ_MAX_IMAGE_RANGE"]
+STATUS_IMAGES = H.defines["ALIGNN_TRAJ_STATUS_IMAGES"]
 A2_FS_TO_CM2_S = 0.1  # 1 A^2/fs = 1e-16 cm^2 / 1e-15 s
 WINDOWS = {"none": 0, "hann": 1}
 
-_bound = None
-
 
 def _load():
-    """The library of ``_lib.load()`` with the entry points of alignn_traj.h typed (once)."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        for query, block in ((lib.alignn_traj_rdf_args_size, RdfArgs), (lib.alignn_traj_corr_args_size, CorrArgs)):
-            if query() != C.sizeof(block):  # (a library built from another alignn_traj.h than the one read here)
-                raise RuntimeError(f"argument block {block.__name__}: library says {query()} bytes, the header gives "
-                                   f"{C.sizeof(block)}")
-        _bound = lib
-    return lib
+    return _lib.bind(H)
 
 
 def pair_row(a: int, b: int) -> int:

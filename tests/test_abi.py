@@ -2,26 +2,23 @@
 include/alignn_hip.h declares (no compute calls - there is no GPU here), and the ctypes table in
 alignn_amd/_lib.py covers exactly that set.  The table and the argument structs are read from the header
 (alignn_amd/_abi.py): the reader is checked on literal snippets, its struct layouts against a C compiler's
-sizeof / offsetof of the real header, and their sizes against the library's."""
+sizeof / offsetof of the real header, and their sizes against the library's.  The headers of the batched workflows
+(``_abi.WORKFLOW_HEADERS``) have a test module each (test_*_abi.py); what spans them is here: their limits as ``_abi.defines``
+reads them, ``_lib.bind``, and that no two headers declare the same name."""
 
 import ctypes as C
-import keyword
-import os
+import itertools
 import re
-import shutil
-import subprocess
+import types
 
 import pytest
 
 from alignn_amd import _abi, _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import abi_checks
 
 
 def _declared():
-    text = open(os.path.join(ROOT, "include", "alignn_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(alignn_[a-z0-9_]+)\s*\(", text))
+    return abi_checks.declared(_abi.HEADER)
 
 
 def test_library_exports_every_declared_symbol():
@@ -129,33 +126,8 @@ def test_derived_tables_of_the_real_header():
 
 
 # ---- layout against the compiler: sizeof / offsetof of every struct of the real header --------------------------------------
-def _host_compiler():
-    for cc in ("/opt/rocm/lib/llvm/bin/clang", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib/llvm/bin/clang")):
-        if os.path.exists(cc):
-            return cc
-    return shutil.which("clang") or shutil.which("cc") or shutil.which("gcc")
-
-
 def test_struct_layouts_match_the_compiler(tmp_path):
-    cc = _host_compiler()
-    if cc is None:
-        pytest.skip("no host C compiler")
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "alignn_hip.h"', "int main(void) {"]
-    for name, st in _abi.STRUCTS.items():
-        lines.append(f'    printf("{name} sizeof %zu\\n", sizeof({name}));')
-        for field, _ in st._fields_:
-            c_field = field[:-1] if field.endswith("_") and keyword.iskeyword(field[:-1]) else field  # in_ -> in
-            lines.append(f'    printf("{name} {field} %zu\\n", offsetof({name}, {c_field}));')
-    lines += ["    return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    seen = [tuple(ln.split()) for ln in out if ln]
-    want = []
-    for name, st in _abi.STRUCTS.items():
-        want.append((name, "sizeof", str(C.sizeof(st))))
-        want += [(name, field, str(getattr(st, field).offset)) for field, _ in st._fields_]
+    seen, want = abi_checks.layouts("alignn_hip.h", _abi.STRUCTS, tmp_path)
     assert len(want) == 12 + sum(len(st._fields_) for st in _abi.STRUCTS.values()) > 300
     assert seen == want
 
@@ -175,3 +147,133 @@ def test_struct_sizes_match_the_library():
     for name, query in queries.items():
         assert query() == C.sizeof(_abi.STRUCTS[name]), name
     assert [C.sizeof(st) for st in _abi.STRUCTS.values()] == [352, 424, 152, 104, 192, 104, 248, 728, 56, 312, 296, 336]
+
+
+# ---- the limits of the headers: #define NAME literal ------------------------------------------------------------------------
+def test_defines_on_literals():
+    assert _abi.defines("""
+        #ifndef GUARD_H
+        #define GUARD_H
+        #include <stdint.h>
+        #define LIMIT 4096 /* a comment after the value */
+        #  define MASK 0x10
+        #define TAU 1e-4   /* a comment
+                              over two lines */
+        #define HALF -.5
+        /* #define INSIDE_A_COMMENT 3 */
+        int f(void);
+        #endif
+    """) == {"LIMIT": 4096, "MASK": 16, "TAU": 1e-4, "HALF": -0.5}
+    found = _abi.defines("#define A 2\n#define B 2.0\n")
+    assert (type(found["A"]), type(found["B"])) == (int, float)
+
+
+LIMITS = {
+    "alignn_hip.h": {},
+    "alignn_thermo.h": {},
+    "alignn_neb.h": {"ALIGNN_NEB_MAX_IMAGES": 64},
+    "alignn_traj.h": {"ALIGNN_TRAJ_MAX_SPECIES": 8, "ALIGNN_TRAJ_MAX_BINS": 4096, "ALIGNN_TRAJ_MAX_IMAGE_RANGE": 8,
+                      "ALIGNN_TRAJ_STATUS_IMAGES": 1},
+    "alignn_sym.h": {"ALIGNN_SYM_MAX_ATOMS": 1024, "ALIGNN_SYM_MAX_IMAGE_RANGE": 8, "ALIGNN_SYM_MAX_CANDIDATES": 256,
+                     "ALIGNN_SYM_MAX_LATTICE_OPS": 48, "ALIGNN_SYM_INFO": 8, "ALIGNN_SYM_STATUS_IMAGES": 1,
+                     "ALIGNN_SYM_STATUS_OVERFLOW": 2, "ALIGNN_SYM_STATUS_INPUT": 4},
+    "alignn_order.h": {"ALIGNN_ORDER_MAX_SPECIES": 8, "ALIGNN_ORDER_MAX_IMAGE_RANGE": 8, "ALIGNN_ORDER_MAX_NEIGHBORS": 64,
+                       "ALIGNN_ORDER_MAX_BINS": 1024, "ALIGNN_ORDER_MAX_L": 12, "ALIGNN_ORDER_MAX_LS": 4, "ALIGNN_ORDER_MAX_HKL": 32,
+                       "ALIGNN_ORDER_SQ_FRAME_CHUNK": 64, "ALIGNN_ORDER_STATUS_IMAGES": 1, "ALIGNN_ORDER_STATUS_NEIGHBORS": 2,
+                       "ALIGNN_ORDER_STATUS_HKL": 4},
+    "alignn_phsym.h": {"ALIGNN_PHSYM_MAX_ATOMS": 32, "ALIGNN_PHSYM_MAX_SITE_OPS": 48, "ALIGNN_PHSYM_N_CANDIDATES": 13,
+                       "ALIGNN_PHSYM_TAU": 1e-4},
+}
+
+
+def _read(name):
+    with open(abi_checks.INCLUDE + "/" + name) as f:
+        return f.read()
+
+
+def test_defines_of_the_real_headers():
+    assert tuple(LIMITS) == ("alignn_hip.h",) + _abi.WORKFLOW_HEADERS
+    for name, want in LIMITS.items():
+        found = _abi.defines(_read(name))
+        assert found == want and [type(found[k]) for k in want] == [type(v) for v in want.values()], name
+        if name in _abi.WORKFLOW_HEADERS:
+            assert _abi.header(name).defines == want and _abi.header(name) is _abi.header(name), name
+
+
+@pytest.mark.parametrize("text,where", [
+    ("#define A 1\n#define F(x) x", "line 2"),                                   # a function-like macro
+    ("\n\n#define A (1)", "line 3"),                                             # not a literal: parentheses
+    ("#define A 1 + 2", "'#define A 1 + 2'"),                                    # ... an expression
+    ("#define A B", "line 1"),                                                   # ... another name
+    ("#define A 1u", "line 1"),                                                  # ... a suffix
+    ("#define A 010", "line 1"),                                                 # ... an octal literal
+    ("#define A 1 \\\n 2", "line 1"),                                            # ... a continued line
+    ("/* two\nlines */ #define A \"s\"", "line 2"),                              # ... a string, after a comment
+    ("#define", "line 1"),                                                       # no name
+])
+def test_defines_is_strict(text, where):
+    with pytest.raises(ValueError, match=re.escape(where)):
+        _abi.defines(text)
+
+
+# ---- one binder for the workflow headers (_lib.bind) -------------------------------------------------------------------------
+def test_no_name_in_two_headers():
+    read = {"alignn_hip.h": (_abi.STRUCTS, _abi.SIGNATURES)}
+    for name in _abi.WORKFLOW_HEADERS:
+        read[name] = (_abi.header(name).structs, _abi.header(name).signatures)
+    assert len(read) == 7 and sum(len(sigs) for _, sigs in read.values()) == 162 + 3 + 3 + 9 + 7 + 8 + 9
+    for (a, (structs_a, sigs_a)), (b, (structs_b, sigs_b)) in itertools.combinations(read.items(), 2):
+        assert not set(sigs_a) & set(sigs_b), (a, b)
+        assert not set(structs_a) & set(structs_b), (a, b)
+        assert not (set(structs_a) | set(structs_b)) & (set(sigs_a) | set(sigs_b)), (a, b)
+
+
+def test_every_argument_block_of_a_workflow_header_has_its_size_query(tmp_path):
+    blocks = [s for name in _abi.WORKFLOW_HEADERS for s in _abi.header(name).structs]
+    assert len(blocks) == 11
+    odd = tmp_path / "alignn_odd.h"
+    odd.write_text("typedef struct alignn_odd_args { int n; } alignn_odd_args;\nint alignn_odd(void);\n")
+    with pytest.raises(ValueError, match="alignn_odd_args_size"):
+        _abi.header(str(odd))
+    odd.write_text("typedef struct alignn_odd_args { int n; } alignn_odd_args;\nint alignn_odd_args_size(void);\n")
+    with pytest.raises(ValueError, match="alignn_odd_args_size"):  # (the query answers a size_t)
+        _abi.header(str(odd))
+
+
+def _stub(H, sizes):
+    """An object with every entry point of ``H`` as a plain function, which takes ``restype`` / ``argtypes`` as attributes like
+    a ctypes one; the size queries answer ``sizes``."""
+    stub = types.SimpleNamespace()
+    for name in H.signatures:
+        setattr(stub, name, (lambda size: lambda *args: size)(sizes.get(name, 0)))
+    return stub
+
+
+def test_bind_refuses_a_library_of_another_header():
+    H = _abi.header("alignn_traj.h")
+    assert [C.sizeof(st) for st in H.structs.values()] == [136, 96]
+    stub = _stub(H, {"alignn_traj_rdf_args_size": 136, "alignn_traj_corr_args_size": 104})
+    with pytest.raises(RuntimeError, match="argument block alignn_traj_corr_args: library says 104 bytes, the header gives 96"):
+        _lib.bind(H, stub)
+    assert stub.alignn_traj_vdos.restype is C.c_int and stub.alignn_traj_rdf_args_size.restype is C.c_size_t
+    with pytest.raises(RuntimeError, match="alignn_traj_corr_args"):  # (not remembered as bound: every call checks again)
+        _lib.bind(H, stub)
+    assert _lib.bind(H) is _lib.load()
+
+
+def test_bind_returns_the_library_and_types_a_header_once(monkeypatch):
+    lib = _lib.load()
+    for name in _abi.WORKFLOW_HEADERS:
+        H = _abi.header(name)
+        assert _lib.bind(H) is lib and _lib._bound[H.path] is lib
+        abi_checks.assert_typed(lib, H.signatures)
+    typed = []
+    monkeypatch.setattr(_lib, "_type", lambda lib, sigs: typed.append((lib, sigs)))
+    for name in _abi.WORKFLOW_HEADERS:
+        assert _lib.bind(_abi.header(name)) is lib
+    assert typed == []
+    neb = _abi.header("alignn_neb.h")
+    monkeypatch.setitem(_lib._bound, neb.path, lib)  # (put back afterwards)
+    other = _stub(neb, {"alignn_neb_args_size": C.sizeof(neb.structs["alignn_neb_args"])})
+    assert _lib.bind(neb, other) is other and _lib.bind(neb, other) is other  # another library object: typed again, once
+    assert typed == [(other, neb.signatures)]

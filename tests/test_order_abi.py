@@ -1,46 +1,21 @@
 """CPU-side checks of the sixth header, include/alignn_order.h: it reads with the reader of alignn_amd/_abi.py, the built library
-exports exactly the names it declares (no compute calls - there is no GPU here), no name collides with the other headers, the
+exports exactly the names it declares (no compute calls - there is no GPU here), the
 ctypes layout of its argument blocks agrees with a C compiler's sizeof / offsetof and with the library's size queries, and
 every range check answers hipErrorInvalidValue before anything touches a device."""
 
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
-
-import pytest
 
 import alignn_amd
 from alignn_amd import _abi, _lib
-from alignn_amd.neb import SIGNATURES as NEB_SIGNATURES
-from alignn_amd.neb import STRUCTS as NEB_STRUCTS
 from alignn_amd.order import (HEADER, MAX_BINS, MAX_HKL, MAX_IMAGE_RANGE, MAX_L, MAX_LS, MAX_NEIGHBORS, MAX_SPECIES, SIGNATURES,
                               SQ_FRAME_CHUNK, STATUS_HKL, STATUS_IMAGES, STATUS_NEIGHBORS, STRUCTS, AngleArgs, SqArgs, _load)
-from alignn_amd.symmetry import SIGNATURES as SYM_SIGNATURES
-from alignn_amd.symmetry import STRUCTS as SYM_STRUCTS
-from alignn_amd.thermo import SIGNATURES as THERMO_SIGNATURES
-from alignn_amd.trajectory import SIGNATURES as TRAJ_SIGNATURES
-from alignn_amd.trajectory import STRUCTS as TRAJ_STRUCTS
+from tests import abi_checks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ANGLE_CALLS = {"alignn_order_angles", "alignn_order_adf_finish", "alignn_order_steinhardt_mean"}
 SQ_CALLS = {"alignn_order_sq_vectors", "alignn_order_sq_accumulate", "alignn_order_sq_bin"}
 SIZES = {"alignn_order_angle_args_size", "alignn_order_sq_args_size"}
 NAMES = ANGLE_CALLS | SQ_CALLS | SIZES
-
-
-def _declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return set(re.findall(r"\b(alignn_[a-z0-9_]+)\s*\(", text))
-
-
-def _exported(lib_path):
-    nm = "/opt/rocm/lib/llvm/bin/llvm-nm" if os.path.exists("/opt/rocm/lib/llvm/bin/llvm-nm") else shutil.which("nm")
-    if nm is None:
-        pytest.skip("no nm")
-    out = subprocess.run([nm, "-D", "--defined-only", lib_path], check=True, capture_output=True, text=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("alignn_order_")}
 
 
 def test_header_reads_and_the_library_exports_exactly_its_names():
@@ -50,28 +25,18 @@ def test_header_reads_and_the_library_exports_exactly_its_names():
     lib_path = build()
     structs, sigs = _abi.parse(open(HEADER).read())
     assert list(structs) == ["alignn_order_angle_args", "alignn_order_sq_args"] == list(STRUCTS)
-    assert set(sigs) == _declared(HEADER) == set(SIGNATURES) == NAMES
-    assert _exported(lib_path) == NAMES  # nothing of the prefix beside what the header declares
+    assert set(sigs) == abi_checks.declared(HEADER) == set(SIGNATURES) == NAMES
+    assert abi_checks.exported(lib_path, "alignn_order_") == NAMES  # nothing of the prefix beside what the header declares
     assert not any(name.startswith("alignn_traj_") for name in NAMES)
-    others = set(_abi.SIGNATURES) | set(THERMO_SIGNATURES) | set(NEB_SIGNATURES) | set(TRAJ_SIGNATURES) | set(SYM_SIGNATURES)
-    assert not set(sigs) & others  # no name in two headers
-    assert not set(structs) & (set(_abi.STRUCTS) | set(NEB_STRUCTS) | set(TRAJ_STRUCTS) | set(SYM_STRUCTS))
     lib = _load()
     assert lib is _lib.load()
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
+    abi_checks.assert_typed(lib, sigs)
     for name in NAMES - SIZES:
         assert sigs[name] == (C.c_int, [C.c_void_p, C.c_void_p]), name
     for name in SIZES:
         assert sigs[name] == (C.c_size_t, []), name
-    text = open(HEADER).read()
-    for macro, value in (("MAX_SPECIES", MAX_SPECIES), ("MAX_IMAGE_RANGE", MAX_IMAGE_RANGE), ("MAX_NEIGHBORS", MAX_NEIGHBORS),
-                         ("MAX_BINS", MAX_BINS), ("MAX_L", MAX_L), ("MAX_LS", MAX_LS), ("MAX_HKL", MAX_HKL),
-                         ("SQ_FRAME_CHUNK", SQ_FRAME_CHUNK), ("STATUS_IMAGES", STATUS_IMAGES),
-                         ("STATUS_NEIGHBORS", STATUS_NEIGHBORS), ("STATUS_HKL", STATUS_HKL)):
-        assert re.search(rf"#define\s+ALIGNN_ORDER_{macro}\s+(\d+)", text).group(1) == str(value), macro
-    assert (MAX_IMAGE_RANGE, MAX_NEIGHBORS, MAX_BINS, MAX_L, MAX_HKL, SQ_FRAME_CHUNK) == (8, 64, 1024, 12, 32, 64)
+    assert (MAX_SPECIES, MAX_IMAGE_RANGE, MAX_NEIGHBORS, MAX_BINS, MAX_L, MAX_LS, MAX_HKL, SQ_FRAME_CHUNK) == (8, 8, 64, 1024, 12, 4, 32, 64)
+    assert (STATUS_IMAGES, STATUS_NEIGHBORS, STATUS_HKL) == (1, 2, 4)
     for name in ("adf", "steinhardt", "structure_factor", "ADFResult", "SteinhardtResult", "SQResult"):
         assert getattr(alignn_amd, name) is getattr(alignn_amd.order, name), name
     assert (alignn_amd.MAX_NEIGHBORS, alignn_amd.MAX_L, alignn_amd.MAX_HKL) == (MAX_NEIGHBORS, MAX_L, MAX_HKL)
@@ -131,30 +96,6 @@ def test_entry_points_refuse_arguments_out_of_range():
     assert lib.alignn_order_sq_accumulate(C.byref(SqArgs(**{**SQ_OK, "n_vectors": 0, "max_vectors": 0})), None) == 0
 
 
-def _host_compiler():
-    for cc in ("/opt/rocm/lib/llvm/bin/clang", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib/llvm/bin/clang")):
-        if os.path.exists(cc):
-            return cc
-    return shutil.which("clang") or shutil.which("cc") or shutil.which("gcc")
-
-
 def test_argument_block_layouts_match_the_compiler(tmp_path):
-    cc = _host_compiler()
-    if cc is None:
-        pytest.skip("no host C compiler")
-    blocks = (("alignn_order_angle_args", AngleArgs), ("alignn_order_sq_args", SqArgs))
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "alignn_order.h"', "int main(void) {"]
-    want = []
-    for name, block in blocks:
-        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
-        want.append((name, str(C.sizeof(block))))
-        for field, _ in block._fields_:
-            lines.append(f'    printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
-            want.append((f"{name}.{field}", str(getattr(block, field).offset)))
-    lines += ["    return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    seen = [tuple(ln.split()) for ln in out if ln]
+    seen, want = abi_checks.layouts("alignn_order.h", STRUCTS, tmp_path)
     assert len(want) == 2 + 28 + 27 and seen == want

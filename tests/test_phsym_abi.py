@@ -1,46 +1,20 @@
 """CPU-side checks of the seventh header, include/alignn_phsym.h: it reads with the reader of alignn_amd/_abi.py, the built
-library exports exactly the names it declares (no compute calls - there is no GPU here), no name collides with the other
-headers, the ctypes layout of its argument blocks agrees with a C compiler's sizeof / offsetof and with the library's size
+library exports exactly the names it declares (no compute calls - there is no GPU here), the ctypes layout of its argument blocks agrees with a C compiler's sizeof / offsetof and with the library's size
 queries, and every range check answers hipErrorInvalidValue before anything touches a device."""
 
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
-
-import pytest
 
 import alignn_amd  # noqa: F401  (the package exports the function ``phonons``: the module is taken from sys.modules)
 from alignn_amd import _abi, _lib
-from alignn_amd.neb import SIGNATURES as NEB_SIGNATURES
-from alignn_amd.neb import STRUCTS as NEB_STRUCTS
-from alignn_amd.symmetry import SIGNATURES as SYM_SIGNATURES
-from alignn_amd.symmetry import STRUCTS as SYM_STRUCTS
-from alignn_amd.thermo import SIGNATURES as THERMO_SIGNATURES
-from alignn_amd.trajectory import SIGNATURES as TRAJ_SIGNATURES
-from alignn_amd.trajectory import STRUCTS as TRAJ_STRUCTS
+from tests import abi_checks
 
 PH = sys.modules["alignn_amd.phonons"]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = {"alignn_phsym_plan_args_size", "alignn_phsym_displace_args_size", "alignn_phsym_rows_args_size", "alignn_phsym_fc_args_size"}
 ENTRIES = {"alignn_phsym_plan", "alignn_phsym_displace", "alignn_phsym_rows", "alignn_phsym_solve", "alignn_phsym_distribute"}
 NAMES = SIZES | ENTRIES
 BLOCKS = ["alignn_phsym_plan_args", "alignn_phsym_displace_args", "alignn_phsym_rows_args", "alignn_phsym_fc_args"]
-
-
-def _declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return set(re.findall(r"\b(alignn_[a-z0-9_]+)\s*\(", text))
-
-
-def _exported(lib_path):
-    nm = "/opt/rocm/lib/llvm/bin/llvm-nm" if os.path.exists("/opt/rocm/lib/llvm/bin/llvm-nm") else shutil.which("nm")
-    if nm is None:
-        pytest.skip("no nm")
-    out = subprocess.run([nm, "-D", "--defined-only", lib_path], check=True, capture_output=True, text=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("alignn_phsym_")}
 
 
 def test_header_reads_and_the_library_exports_exactly_its_names():
@@ -50,23 +24,16 @@ def test_header_reads_and_the_library_exports_exactly_its_names():
     lib_path = build()
     structs, sigs = _abi.parse(open(PH.PHSYM_HEADER).read())
     assert list(structs) == BLOCKS == list(PH.PHSYM_STRUCTS)
-    assert set(sigs) == _declared(PH.PHSYM_HEADER) == set(PH.PHSYM_SIGNATURES) == NAMES
-    assert _exported(lib_path) == NAMES  # nothing of the prefix beside what the header declares
-    others = set(_abi.SIGNATURES) | set(THERMO_SIGNATURES) | set(NEB_SIGNATURES) | set(TRAJ_SIGNATURES) | set(SYM_SIGNATURES)
-    assert not set(sigs) & others  # no name in two headers
-    assert not set(structs) & (set(_abi.STRUCTS) | set(NEB_STRUCTS) | set(TRAJ_STRUCTS) | set(SYM_STRUCTS))
+    assert set(sigs) == abi_checks.declared(PH.PHSYM_HEADER) == set(PH.PHSYM_SIGNATURES) == NAMES
+    assert abi_checks.exported(lib_path, "alignn_phsym_") == NAMES  # nothing of the prefix beside what the header declares
     lib = PH._load_phsym()
     assert lib is _lib.load()
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
+    abi_checks.assert_typed(lib, sigs)
     for name in ENTRIES:
         assert sigs[name] == (C.c_int, [C.c_void_p, C.c_void_p]), name
     for name in SIZES:
         assert sigs[name] == (C.c_size_t, []), name
-    text = open(PH.PHSYM_HEADER).read()
-    for macro, value in (("MAX_ATOMS", PH.PHSYM_MAX_ATOMS), ("MAX_SITE_OPS", PH.PHSYM_MAX_SITE_OPS), ("N_CANDIDATES", 13)):
-        assert re.search(rf"#define\s+ALIGNN_PHSYM_{macro}\s+(\d+)", text).group(1) == str(value), macro
+    assert (PH.PHSYM_MAX_ATOMS, PH.PHSYM_MAX_SITE_OPS, PH.PHSYM.defines["ALIGNN_PHSYM_N_CANDIDATES"]) == (32, 48, 13)
     assert PH.PHSYM_MAX_ATOMS * 3 == PH.MAX_DIM
 
 
@@ -115,30 +82,6 @@ def test_entry_points_refuse_arguments_out_of_range():
         assert fn(C.byref(PH.FcArgs(**{**FC_OK, "n_items": 0})), None) == 0
 
 
-def _host_compiler():
-    for cc in ("/opt/rocm/lib/llvm/bin/clang", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib/llvm/bin/clang")):
-        if os.path.exists(cc):
-            return cc
-    return shutil.which("clang") or shutil.which("cc") or shutil.which("gcc")
-
-
 def test_argument_block_layouts_match_the_compiler(tmp_path):
-    cc = _host_compiler()
-    if cc is None:
-        pytest.skip("no host C compiler")
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "alignn_phsym.h"', "int main(void) {"]
-    want = []
-    for name in BLOCKS:
-        block = PH.PHSYM_STRUCTS[name]
-        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
-        want.append((name, str(C.sizeof(block))))
-        for field, _ in block._fields_:
-            lines.append(f'    printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
-            want.append((f"{name}.{field}", str(getattr(block, field).offset)))
-    lines += ["    return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    seen = [tuple(ln.split()) for ln in out if ln]
+    seen, want = abi_checks.layouts("alignn_phsym.h", PH.PHSYM_STRUCTS, tmp_path)
     assert len(want) == 4 + 20 + 13 + 11 + 25 and seen == want

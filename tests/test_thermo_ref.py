@@ -4,15 +4,13 @@ identities and limits; (2) the restated quasi-harmonic pipeline on an Einstein s
 the second header, include/alignn_thermo.h, through the reader of alignn_amd/_abi.py and against the built library; (4) the
 input checks of the drivers, which raise before any device work."""
 
-import re
-
 import numpy as np
 import pytest
 import torch
 
 from alignn_amd import _abi, _lib, thermo
 from alignn_amd.phonons import PhononResult
-from tests import pair_ref
+from tests import abi_checks, pair_ref
 from tests import thermo_ref as ref
 
 KB = ref.KB
@@ -124,24 +122,16 @@ def test_derive_step_edges():
 
 
 # --- (3) the second header -----------------------------------------------------------------------------------------------------------
-def _declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return set(re.findall(r"\b(alignn_[a-z0-9_]+)\s*\(", text))
-
-
 def test_second_header_reads_and_the_library_exports_it():
     from alignn_amd.build import build
 
     build()
     structs, sigs = _abi.parse(open(thermo.HEADER).read())
-    assert structs == {} and set(sigs) == _declared(thermo.HEADER) == set(thermo.SIGNATURES)
+    assert structs == {} and set(sigs) == abi_checks.declared(thermo.HEADER) == set(thermo.SIGNATURES)
     assert set(sigs) == {"alignn_phonon_thermal_workspace", "alignn_phonon_thermal", "alignn_qha_derive"}
-    assert not set(sigs) & set(_abi.SIGNATURES)  # no name in both headers; the first header's table is untouched
     lib = thermo._load()
     assert lib is _lib.load()
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
+    abi_checks.assert_typed(lib, sigs)
     chunk = ref.CHUNK
     assert lib.alignn_phonon_thermal_workspace(1, chunk, 3) == (4 * 3 + 2) * 8
     assert lib.alignn_phonon_thermal_workspace(2, 2 * chunk + 1, 5) == 2 * 3 * (4 * 5 + 2) * 8

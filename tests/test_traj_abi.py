@@ -1,39 +1,17 @@
 """CPU-side checks of the fourth header, include/alignn_traj.h: it reads with the reader of alignn_amd/_abi.py, the built library
-exports exactly the names it declares (no compute calls - there is no GPU here), no name collides with the other headers, the
+exports exactly the names it declares (no compute calls - there is no GPU here), the
 ctypes layout of its argument blocks agrees with a C compiler's sizeof / offsetof and with the library's size queries, and
 every range check answers hipErrorInvalidValue before anything touches a device."""
 
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
 
 from alignn_amd import _abi, _lib
-from alignn_amd.neb import SIGNATURES as NEB_SIGNATURES
-from alignn_amd.neb import STRUCTS as NEB_STRUCTS
-from alignn_amd.thermo import SIGNATURES as THERMO_SIGNATURES
 from alignn_amd.trajectory import (HEADER, MAX_BINS, MAX_IMAGE_RANGE, MAX_SPECIES, SIGNATURES, STATUS_IMAGES, STRUCTS, CorrArgs,
                                    RdfArgs, _load)
+from tests import abi_checks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"alignn_traj_rdf_counts", "alignn_traj_rdf_normalise", "alignn_traj_rdf_args_size", "alignn_traj_com",
          "alignn_traj_corr", "alignn_traj_corr_args_size", "alignn_traj_vdos", "alignn_traj_fit", "alignn_traj_green_kubo"}
-
-
-def _declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return set(re.findall(r"\b(alignn_[a-z0-9_]+)\s*\(", text))
-
-
-def _exported(lib_path):
-    nm = "/opt/rocm/lib/llvm/bin/llvm-nm" if os.path.exists("/opt/rocm/lib/llvm/bin/llvm-nm") else shutil.which("nm")
-    if nm is None:
-        pytest.skip("no nm")
-    out = subprocess.run([nm, "-D", "--defined-only", lib_path], check=True, capture_output=True, text=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("alignn_traj_")}
 
 
 def test_header_reads_and_the_library_exports_exactly_its_names():
@@ -43,16 +21,11 @@ def test_header_reads_and_the_library_exports_exactly_its_names():
     lib_path = build()
     structs, sigs = _abi.parse(open(HEADER).read())
     assert list(structs) == ["alignn_traj_rdf_args", "alignn_traj_corr_args"] == list(STRUCTS)
-    assert set(sigs) == _declared(HEADER) == set(SIGNATURES) == NAMES
-    assert _exported(lib_path) == NAMES  # nothing of the prefix beside what the header declares
-    others = set(_abi.SIGNATURES) | set(THERMO_SIGNATURES) | set(NEB_SIGNATURES)
-    assert not set(sigs) & others  # no name in two headers
-    assert not set(structs) & (set(_abi.STRUCTS) | set(NEB_STRUCTS))
+    assert set(sigs) == abi_checks.declared(HEADER) == set(SIGNATURES) == NAMES
+    assert abi_checks.exported(lib_path, "alignn_traj_") == NAMES  # nothing of the prefix beside what the header declares
     lib = _load()
     assert lib is _lib.load()
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
+    abi_checks.assert_typed(lib, sigs)
     for name in ("alignn_traj_rdf_counts", "alignn_traj_rdf_normalise", "alignn_traj_com", "alignn_traj_corr"):
         assert sigs[name] == (C.c_int, [C.c_void_p, C.c_void_p]), name
     assert sigs["alignn_traj_rdf_args_size"] == sigs["alignn_traj_corr_args_size"] == (C.c_size_t, [])
@@ -60,10 +33,7 @@ def test_header_reads_and_the_library_exports_exactly_its_names():
                                                   C.c_void_p, C.c_void_p])
     assert sigs["alignn_traj_fit"] == (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p])
     assert sigs["alignn_traj_green_kubo"] == (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p])
-    text = open(HEADER).read()
-    for macro, value in (("MAX_SPECIES", MAX_SPECIES), ("MAX_BINS", MAX_BINS), ("MAX_IMAGE_RANGE", MAX_IMAGE_RANGE),
-                         ("STATUS_IMAGES", STATUS_IMAGES)):
-        assert re.search(rf"#define\s+ALIGNN_TRAJ_{macro}\s+(\d+)", text).group(1) == str(value), macro
+    assert (MAX_SPECIES, MAX_BINS, MAX_IMAGE_RANGE, STATUS_IMAGES) == (8, 4096, 8, 1)
 
 
 def test_argument_block_sizes_match_the_library():
@@ -129,30 +99,6 @@ def test_entry_points_refuse_arguments_out_of_range():
     assert gk(rows=0) == 0
 
 
-def _host_compiler():
-    for cc in ("/opt/rocm/lib/llvm/bin/clang", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib/llvm/bin/clang")):
-        if os.path.exists(cc):
-            return cc
-    return shutil.which("clang") or shutil.which("cc") or shutil.which("gcc")
-
-
 def test_argument_block_layouts_match_the_compiler(tmp_path):
-    cc = _host_compiler()
-    if cc is None:
-        pytest.skip("no host C compiler")
-    blocks = (("alignn_traj_rdf_args", RdfArgs), ("alignn_traj_corr_args", CorrArgs))
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "alignn_traj.h"', "int main(void) {"]
-    want = []
-    for name, block in blocks:
-        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
-        want.append((name, str(C.sizeof(block))))
-        for field, _ in block._fields_:
-            lines.append(f'    printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
-            want.append((f"{name}.{field}", str(getattr(block, field).offset)))
-    lines += ["    return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    seen = [tuple(ln.split()) for ln in out if ln]
+    seen, want = abi_checks.layouts("alignn_traj.h", STRUCTS, tmp_path)
     assert len(want) == 2 + 22 + 17 and seen == want
