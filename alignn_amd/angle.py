@@ -1,5 +1,5 @@
 """The bond-angle embedding as ONE pair of C calls (csrc/angle.hip): ``alignn_angle_embed_fwd`` / ``alignn_angle_embed_bwd``
-for callers outside the whole-model path (tests, tools).  ``z = MLPLayer(64 -> 256)(MLPLayer(bins -> 64)(RBFExpansion(h)))``
+(and ``alignn_angle_embed_infer`` for evaluation mode) for callers outside the whole-model path (tests, tools).  ``z = MLPLayer(64 -> 256)(MLPLayer(bins -> 64)(RBFExpansion(h)))``
 (alignn/models/alignn.py:215-222) in training mode, without the [T, bins] / [T, 64] / [T, 256] intermediates.  No fallback:
 the library is required."""
 
@@ -24,7 +24,9 @@ def _mlp(lin, bn, grads):
 
 
 class AngleEmbedding:
-    """Holds the buffers one forward + backward of the embedding needs.  ``layers`` = the two MLPLayer modules."""
+    """Holds the buffers one forward + backward of the embedding needs.  ``layers`` = the two MLPLayer modules.  ``stat1`` /
+    ``stat2`` / ``scal`` / ``grads`` may be replaced, and ``z`` / ``amax`` / ``out`` handed to the calls, by a caller that wants
+    the outputs in buffers of its own (contiguous float32 of the same sizes)."""
 
     def __init__(self, centers: torch.Tensor, gamma: float, layers, eps=1e-5, momentum=0.1):
         self.lib = _lib.load()
@@ -49,11 +51,11 @@ class AngleEmbedding:
         a.stat1, a.stat2, a.scal = self.stat1.data_ptr(), self.stat2.data_ptr(), self.scal.data_ptr()
         return a
 
-    def forward(self, h: torch.Tensor):
+    def forward(self, h: torch.Tensor, z=None, amax=None):
         h = h.contiguous()
         a = self._args(h)
-        z = torch.empty(h.numel(), 256, device=h.device)
-        amax = torch.zeros(1, device=h.device)
+        z = torch.empty(h.numel(), 256, device=h.device) if z is None else z
+        amax = torch.zeros(1, device=h.device) if amax is None else amax
         nbytes = self.lib.alignn_angle_embed_workspace(h.numel(), a.bins, 0)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=h.device)
         a.z, a.z_amax, a.workspace, a.workspace_bytes = z.data_ptr(), amax.data_ptr(), ws.data_ptr(), nbytes
@@ -62,9 +64,22 @@ class AngleEmbedding:
         self._h = h
         return z, amax
 
-    def backward(self, gz: torch.Tensor):
-        """-> ((gW1, gb1, red1), (gW2, gb2, red2)), red = [dbeta | dgamma]"""
+    def infer(self, h: torch.Tensor, z=None, amax=None):
+        """evaluation mode: z from the layers' running statistics, which stay as they are; stat1 / stat2 / scal are scratch"""
+        h = h.contiguous()
+        a = self._args(h)
+        z = torch.empty(h.numel(), 256, device=h.device) if z is None else z
+        amax = torch.zeros(1, device=h.device) if amax is None else amax
+        a.z, a.z_amax = z.data_ptr(), amax.data_ptr()
+        with _lib.device_guard(h):
+            _lib.check(self.lib.alignn_angle_embed_infer(C.byref(a), _lib.stream()), "angle_embed_infer")
+        return z, amax
+
+    def backward(self, gz: torch.Tensor, out=None):
+        """-> ((gW1, gb1, red1), (gW2, gb2, red2)), red = [dbeta | dgamma]; ``out``: such a pair of triples to write into"""
         h, gz = self._h, gz.contiguous()
+        if out is not None:
+            self.grads = out
         a = self._args(h)
         nbytes = self.lib.alignn_angle_embed_workspace(h.numel(), a.bins, 1)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=h.device)

@@ -17,6 +17,9 @@
 //             pass 7  dW1 = dx1^T rbf (and db1)                            reads h, da1
 // BatchNorm's global statistics are what forces the passes apart (each is a grid-wide dependency).
 //
+// Statistics: a sum behind a variance is taken about a pivot inside the data where it would otherwise cancel against the square
+// of its mean - x1 of the pivot cosine (h[0], or the median of the first 64 when h[0] is an outlier), a1 and W2 a1 about
+// pivot_a1 (tests/test_gpu_angle_f64.py: row0_outlier, beta_heavy, constant).
 // Arithmetic: products as f16x3 split products (hi * hi + hi * lo + lo * hi, fp32 accumulation: v_mfma_f32_32x32x16_f16) of
 // operands scaled by powers of two from tracked / bounded maxima, like the projections of csrc/gemm_x6.hip; everything
 // else fp32, column sums in float64.  Register tiles change orientation (rows <-> features across lanes) by a product
@@ -52,7 +55,8 @@ constexpr int kAmaxW1 = 0, kAmaxW2 = 1, kBoundA1 = 2, kBoundDx2 = 3, kBoundDx1 =
               kScalHead = 128,             // what the forward zeroes (scalars that kernels raise atomically)
               kMeanA1 = 128,               // [64] mean of a1 (layer-1 activations), written by the forward
               kCovA1 = 192,                // [64][64] sum over rows of (a1 - mean)(a1 - mean)^T, written by the forward
-              kScalFloats = 192 + 64 * 64; // 4288
+              kPivotA1 = 192 + 64 * 64,    // [64] pivot of a1 for the layer-2 statistics (pivot_a1), written by the forward
+              kScalFloats = kPivotA1 + 64; // 4352
 constexpr float kRbfScale = 16384.0f;     // rbf values lie in (0, 1]
 
 __device__ __forceinline__ f32x16 mfma(const f16x8& a, const f16x8& b, const f32x16& c) {
@@ -108,6 +112,14 @@ __device__ __forceinline__ float dsilu_fast(float z) {
     const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -kLog2e));
     return s * fmaf(z, 1.0f - s, 1.0f);
 }
+
+// The pivot of the layer-2 statistics and of a1's moments, per layer-1 feature: a1 of the pivot cosine (whose x1 is the layer-1
+// shift scal[kShift..]) where the feature's mean dwarfs its spread, else 0 (angle_stat_finalize_kernel<false> decides and files
+// it in scal[kPivotA1..]).  Sums of a1 - pivot, and of W2 (a1 - pivot) = x2 - b2 - W2 pivot, are then sums about a value
+// inside the data: their second moments do not cancel against the squares of their means when mean(a1) >> std(a1).  A
+// feature whose sums are well conditioned keeps pivot 0, and its sums are the plain ones, bit for bit.
+constexpr float kPivotRatio = 16.0f;  // |a1 of the pivot cosine| > 16 std(z1): the plain sums would lose 8 of their 24 bits
+__device__ __forceinline__ float pivot_a1(const float* __restrict__ scal, int f) { return scal[kPivotA1 + f]; }
 
 struct P {  // kernel parameters (by value)
     const float* h;
@@ -174,9 +186,10 @@ __device__ __forceinline__ void l1_setup(const P& p, L1Shared& sh, L1Mode mode, 
             sh.c[1][f] = b1 - p.scal[kShift + f];
         } else {
             const float mean = p.stat1[f], rstd = p.stat1[kE + f], sc = p.stat1[2 * kE + f], be = p.stat1[3 * kE + f];
-            if (mode == kL1Act) {  // sa z1 = acc * c0 + c1
+            if (mode == kL1Act) {  // sa z1 = acc * c0 + c1;  c2 = sa * pivot of a1 (the statistics pass centres a1 on it)
                 sh.c[0][f] = sc * inv * sa;
                 sh.c[1][f] = fmaf(b1 - mean, sc, be) * sa;
+                sh.c[2][f] = pivot_a1(p.scal, f) * sa;
             } else {  // xhat = acc * c0 + c1;  z1 = xhat * c2 + c3;  dx1 = c4 gz1 + xhat c5 + c6  (c5, c6 carry -1/n sums)
                 const float inv_n = 1.0f / (float)p.rows;
                 sh.c[0][f] = rstd * inv;
@@ -245,7 +258,10 @@ __device__ __forceinline__ void atomic_max_pos(float* p, float v) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// prep: max|W1|, max|W2| and the shift of the layer-1 statistics (x1 of row 0 - any value near the column means will do)
+// prep: max|W1|, max|W2| and the shift of the layer-1 statistics: x1 of the pivot cosine - any value near the column means will
+// do.  That is h[0], unless h[0] lies more than four interquartile ranges of the first (up to) 64 cosines from their median:
+// then the median (with h[0] = -1 and every other cosine within 1e-3 of 0.5 the sums shifted by x1(h[0]) cancelled in
+// q / n - dm^2 by a factor of `rows`).  Four such ranges = 5.4 sigma: up to there the shifted sums lose 5 of their 24 bits.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void angle_prep_kernel(P p) {
     // blocks 0 .. gridDim.x - 2: a slice of W2 each; the last block: W1 and the shift.  scal[] was zeroed before.
@@ -266,8 +282,28 @@ __global__ __launch_bounds__(kThreads) void angle_prep_kernel(P p) {
         __syncthreads();
     }
     if (t == 0) atomic_max_pos(p.scal + (last ? kAmaxW1 : kAmaxW2), sh[0]);
+    if (last) {  // (uniform) median and quartiles: the elements of rank (m - 1) / 2, m / 4, (3 m) / 4 among the first m
+        __shared__ float pivot_h, quart[2];
+        const int m = p.rows < 64 ? (int)p.rows : 64;
+        if (t == 0) pivot_h = quart[0] = quart[1] = m > 0 ? p.h[0] : 0.0f;  // (what stays if no rank matches: NaN among the cosines)
+        __syncthreads();
+        if (t < 64) {  // (the first wave: every lane ranks its own cosine against the others', passed lane to lane)
+            const float mine = t < m ? p.h[t] : 0.0f;
+            int rank = 0;
+            for (int j = 0; j < m; ++j) {
+                const float o = __shfl(mine, j, 64);
+                rank += (o < mine || (o == mine && j < t)) ? 1 : 0;
+            }
+            if (t < m && rank == (m - 1) / 2) pivot_h = mine;
+            if (t < m && rank == m / 4) quart[0] = mine;
+            if (t < m && rank == (3 * m) / 4) quart[1] = mine;
+        }
+        __syncthreads();
+        const float h0 = m > 0 ? p.h[0] : 0.0f;
+        if (t < kE) sh[t] = fabsf(h0 - pivot_h) > 4.0f * (quart[1] - quart[0]) ? pivot_h : h0;
+    }
     if (last && t < kE) {
-        const float hv = p.rows > 0 ? p.h[0] : 0.0f;
+        const float hv = sh[t];
         float acc = p.b1[t];
         for (int k = 0; k < p.bins; ++k) {
             const float d = hv - p.centers[k];
@@ -353,20 +389,23 @@ __global__ __launch_bounds__(kThreads, 2) void angle_l1_stats_kernel(P p) {
 
 // statistics of a layer from slabs.  LAYER2 = false: float slabs [slabs][2][F] = shifted sum | shifted sum of squares
 // (shift in scal[kShift..], max |x - c| in scal[kDall]) (layer 1: also writes the bound of |a1|); true: double slabs [slabs][2][F] of the RAW
-// accumulator sums: x2 = acc * unit + bias with unit = 1 / (a1 scale * W2 scale) - the variance does not see the bias.
+// accumulator sums of W2 (a1 - pivot_a1): x2 = acc * unit + bias + W2 pivot_a1 with unit = 1 / (a1 scale * W2 scale) - the variance
+// sees neither the bias nor the pivot.
 // 4 columns x 64 slab lanes per workgroup (csrc/norm.hip bn_finalize_kernel).
 template <bool LAYER2>
 __global__ __launch_bounds__(256) void angle_stat_finalize_kernel(const void* __restrict__ partial, int slabs, int64_t rows, int F,
                                                                   const float* __restrict__ bias, const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float eps, float momentum,
                                                                   float* __restrict__ rm, float* __restrict__ rv,
-                                                                  float* __restrict__ stat, float* __restrict__ scal) {
-    __shared__ double shs[64][4], shq[64][4];
+                                                                  float* __restrict__ stat, float* __restrict__ scal,
+                                                                  const float* __restrict__ W2) {
+    __shared__ double shs[64][4], shq[64][4], shp[LAYER2 ? 64 : 1][4];
     __shared__ float shm[64][4];
     const int c = threadIdx.x & 3, y = threadIdx.x >> 2;
     const int f = blockIdx.x * 4 + c;
     double s = 0.0, q = 0.0;
     float dmax = 0.0f;
+    if constexpr (LAYER2) shp[y][c] = (double)W2[f * kE + y] * (double)pivot_a1(scal, y);  // term y of (W2 pivot_a1)[f]
     for (int k = y; k < slabs; k += 64) {
         if constexpr (LAYER2) {
             const double* pp = static_cast<const double*>(partial) + (size_t)k * 2 * F;
@@ -390,6 +429,7 @@ __global__ __launch_bounds__(256) void angle_stat_finalize_kernel(const void* __
     if constexpr (LAYER2) {
         unit = 1.0 / ((double)f16_scale(scal[kBoundA1]) * (double)f16_scale(scal[kAmaxW2]));
         shift = (double)bias[f];
+        for (int j = 0; j < kE; ++j) shift += shp[j][c];
     } else
         shift = (double)scal[kShift + f];
     const double dm = s / n * unit;
@@ -410,6 +450,10 @@ __global__ __launch_bounds__(256) void angle_stat_finalize_kernel(const void* __
     if constexpr (!LAYER2) {  // |a1| = |silu(z)| <= |z| <= |gamma rstd| (max|x - c| + |c - mean|) + |beta|
         const float bound = fabsf(g * rstd) * (scal[kDall] + fabsf((float)dm)) + fabsf(b);
         atomic_max_pos(scal + kBoundA1, bound);
+        // pivot_a1: a1 of the pivot cosine where it dwarfs the spread of z1 = xhat gamma + beta (std |gamma rstd| sqrt(var)), else 0
+        const float zp = fmaf((float)(shift - (double)mean), g * rstd, b);
+        const float ap = zp * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(zp * -kLog2e));
+        scal[kPivotA1 + f] = fabsf(ap) > kPivotRatio * fabsf(g * rstd) * sqrtf(var) ? ap : 0.0f;
     }
 }
 
@@ -502,7 +546,7 @@ __global__ __launch_bounds__(256) void angle_red_finalize_kernel(const double* _
     atomic_max_pos(scal + bound, b);
 }
 
-// moments of a1 from their reduced sums [64 + 64 x 64] (scaled by sa, sa^2) -> scal[kMeanA1] = mean,
+// moments of a1 from the reduced sums [64 + 64 x 64] of a1 - pivot_a1 (scaled by sa, sa^2) -> scal[kMeanA1] = mean,
 // scal[kCovA1] = sum_rows (a1 - mean)(a1 - mean)^T
 __global__ __launch_bounds__(256) void angle_moments_finalize_kernel(const float* __restrict__ sums, int64_t rows,
                                                                      float* __restrict__ scal) {
@@ -512,7 +556,7 @@ __global__ __launch_bounds__(256) void angle_moments_finalize_kernel(const float
     const double sa = (double)f16_scale(scal[kBoundA1]), n = (double)rows;
     const double mk = (double)sums[k] / (n * sa), mj = (double)sums[j] / (n * sa);
     scal[kCovA1 + i] = (float)((double)sums[kE + i] / (sa * sa) - n * mk * mj);
-    if (k == 0) scal[kMeanA1 + j] = (float)mj;
+    if (k == 0) scal[kMeanA1 + j] = (float)((double)pivot_a1(scal, j) + mj);
 }
 
 // identity fragments for changing the orientation of a register tile: B[k][n] = 1 where slot k of step s names feature n
@@ -553,10 +597,13 @@ struct Dx2Const {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
-// pass 5: dW2[f][j] = sum_rows dx2[row][f] a1[row][j],  dx2 = gamma rstd (gz - (c0 + xhat c1) / n): the recomputed tile
-// D[row][feature] (lane = feature, registers = rows) IS the A operand [m = feature][k = rows] of that product; its B operand,
-// a1 as (lane = j, registers = rows), is a1's fragment turned by an identity product in phase A and filed in LDS.
-// partial[workgroup][256][64], partial_b[workgroup][256] (column sums of dx2 = db2) floats.
+// pass 4: G[f][j] = sum_rows gz[row][f] (a1[row][j] - mean_j), gz = g_z silu'(.), and the BatchNorm-backward sums c0 = sum gz,
+// c1 = sum gz xhat (see below how dW2 comes out of them): the recomputed tile D[row][feature] (lane = feature, registers =
+// rows) IS the A operand [m = feature][k = rows] of that product; its B operand, a1 - mean as (lane = j, registers = rows), is
+// a1's fragment turned by an identity product in phase A and filed in LDS.
+// Writes partial[workgroup][256][64] floats (G) and partial_d[workgroup][2][256] doubles (c0 | c1); gb2 is written by
+// angle_dw2_fixup_kernel, as exact zeros.  Nothing writes the partial_b[workgroup][256] slabs of the earlier form (column sums
+// of dx2): the backward's workspace keeps their place (tests/test_gpu_angle_f64.py).
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int bfrag_idx(int rb, int jb, int s, int hl, int lane) { return (((rb * 2 + jb) * 2 + s) * 2 + hl) * 64 + lane; }
 
@@ -749,7 +796,7 @@ __global__ __launch_bounds__(kE) void angle_dw2_fixup_kernel(P p, float* __restr
 // fragments in LDS (64 KiB per orientation) - so a wave keeps its rows' layer-1 activations in REGISTERS (they are its own
 // MFMA output), shares nothing with the other waves and meets them at no barrier after the set-up.  Per feature block fb of
 // 32: 12 products recompute x2, then
-//   MODE 0  column sums of the raw accumulators and their squares    -> partial[wave][2][256] double
+//   MODE 0  column sums of the accumulators of W2 (a1 - pivot_a1), squares -> partial[wave][2][256] double
 //   MODE 1  z = silu((x2 - mean) gamma rstd + beta), max|z|           -> z
 //   MODE 2  sums of gz = g_z silu'(.) and gz xhat, maxima             -> partial[wave][2][256] double
 //   MODE 3  da1 += dx2 W2 (x2 recomputed with the operands swapped: lane = row, registers = features, which IS the A
@@ -828,7 +875,7 @@ __global__ __launch_bounds__(rb_threads(MODE), 1) void angle_rb_kernel(P p) {
     float am0 = 0.0f;
     if constexpr (MODE == 0)
         for (int i = lane; i < 2 * kH; i += 64) col_sums[w][i] = 0.0;  // (a wave's own block: no barrier needed)
-    f32x16 m2[2][2];       // MODE 0: sum over rows of (sa a1)[j] (sa a1)[j'] - D[m = j][n = j']: lane = j' 32 jb2 + il, registers = j of block jb
+    f32x16 m2[2][2];       // MODE 0, a1 = a1 - pivot_a1: sum over rows of (sa a1)[j] (sa a1)[j'] - D[m = j][n = j']: lane = j' 32 jb2 + il, registers = j of block jb
     float m1[2] = {0.0f, 0.0f};  // MODE 0: sum over rows of (sa a1)[j], j = 32 jb + il
     f16x8 idp0, idp1;
     if constexpr (MODE == 0) {
@@ -868,10 +915,16 @@ __global__ __launch_bounds__(rb_threads(MODE), 1) void angle_rb_kernel(P p) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) a[4 * q + e] = silu_scaled(fmaf(acc1[cb][8 * s + 4 * q + e], u[e], v[e]), neg_k);
                     }
-                    if constexpr (MODE == 0) {  // rows past the end must not reach the moments (their x2 is masked anyway)
+                    if constexpr (MODE == 0) {  // a1 - pivot_a1 (header of pivot_a1); rows past the end must not reach the sums
+                        // (fp16 range: silu(u) - silu(v) <= 1.22 max(|u|, |v|), so |a1 - pivot| sa < 1.22 x 2^15 < 65504)
                         const float okf = row0 + il < p.rows ? 1.0f : 0.0f;
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) a[i] *= okf;
+                        for (int q = 0; q < 2; ++q) {
+                            float c[4];
+                            l1_const4(sh, 2, cb, 2 * s + q, hh, c);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) a[4 * q + e] = (a[4 * q + e] - c[e]) * okf;
+                        }
                     }
                     split8s(a, a_hi[2 * cb + s], a_lo[2 * cb + s]);
                 }
@@ -1072,7 +1125,7 @@ __global__ __launch_bounds__(rb_threads(MODE), 1) void angle_rb_kernel(P p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// passes 7, 8 (one wave per block of 32 rows, nothing shared): gz1 = da1 silu'(z1), then
+// passes 6, 7 (one wave per block of 32 rows, nothing shared): gz1 = da1 silu'(z1), then
 //   MODE 0  sums of gz1 and gz1 xhat1, maxima                        -> partial[wave][2][64] double
 //   MODE 1  dx1 = gamma rstd (gz1 - (c0 + xhat c1) / n);  dW1[c][k] = sum_rows dx1[row][c] rbf[row][k]: both operands turned to
 //           (registers = rows) by identity products; the expansion carries a column of ones in slot `bins`, so column `bins`
@@ -1302,7 +1355,7 @@ size_t alignn_angle_embed_workspace(int64_t rows, int bins, int backward) {
     size_t total = al256((size_t)rows * kE * sizeof(float));                       // da1
     total += sums;                                                                  // sums (layer 2, then layer 1: waves * 2 * 64)
     total += al256((size_t)kGrid * kH * kE * sizeof(float));                        // dW2 slabs
-    total += al256((size_t)kGrid * kH * sizeof(float));                             // db2 slabs
+    total += al256((size_t)kGrid * kH * sizeof(float));                             // (db2 slabs of the earlier form: unused)
     total += al256((size_t)alignn_slab_fold_slabs() * kH * kE * sizeof(float));     // folded dW2 slabs
     total += al256(waves * kE * (size_t)(bins + 1) * sizeof(float));                // dW1 | db1 slabs
     total += 2 * al256((size_t)alignn_slab_fold_slabs() * kE * (size_t)(bins + 1) * sizeof(float));
@@ -1328,7 +1381,8 @@ int alignn_angle_embed_fwd(const alignn_angle_args* a, alignn_stream_t stream) {
     const int g1 = grid_for(a->rows, 32 * (kThreads / 64)), g2 = grid_for(a->rows, kTile);
     hipLaunchKernelGGL(angle_l1_stats_kernel, dim3(g1), dim3(kThreads), 0, st, p);
     hipLaunchKernelGGL(angle_stat_finalize_kernel<false>, dim3(kE / 4), dim3(256), 0, st, (const void*)p.partial, g1 * (kThreads / 64),
-                       a->rows, kE, a->l1.b, a->l1.gamma, a->l1.beta, a->eps, a->momentum, a->l1.rm, a->l1.rv, a->stat1, a->scal);
+                       a->rows, kE, a->l1.b, a->l1.gamma, a->l1.beta, a->eps, a->momentum, a->l1.rm, a->l1.rv, a->stat1, a->scal,
+                       (const float*)nullptr);
     const int grb = rb_grid(a->rows, 0);
     const int rb_slabs = grb * (rb_threads(0) / 64);
     (void)g2;
@@ -1340,7 +1394,7 @@ int alignn_angle_embed_fwd(const alignn_angle_args* a, alignn_stream_t stream) {
         hipLaunchKernelGGL(angle_moments_finalize_kernel, dim3(kE * kE / 256), dim3(256), 0, st, (const float*)msum, a->rows, a->scal);
     }
     hipLaunchKernelGGL(angle_stat_finalize_kernel<true>, dim3(kH / 4), dim3(256), 0, st, (const void*)p.partial, rb_slabs, a->rows, kH,
-                       a->l2.b, a->l2.gamma, a->l2.beta, a->eps, a->momentum, a->l2.rm, a->l2.rv, a->stat2, a->scal);
+                       a->l2.b, a->l2.gamma, a->l2.beta, a->eps, a->momentum, a->l2.rm, a->l2.rv, a->stat2, a->scal, a->l2.W);
     hipLaunchKernelGGL(angle_rb_kernel<1>, dim3(rb_grid(a->rows, 1)), dim3(rb_threads(1)), 0, st, p);
     ALIGNN_CHECK_LAUNCH();
     return 0;
@@ -1396,6 +1450,11 @@ int alignn_angle_embed_bwd(const alignn_angle_args* a, alignn_stream_t stream) {
     P p = make_params(*a);
     p.da1 = da1;
     const int g1 = grid_for(a->rows, 32 * waves_per);
+    // the backward's own scalars (kBoundDx2 .. kAmaxXh1, contiguous) are only ever RAISED by its passes: without this a second
+    // backward on the same forward state kept the first one's maxima, and a g_z 2^-30 of the first was sliced with the first
+    // one's operand scales - into fp16 subnormals.  (A kernel, not a memset: see angle_zero_kernel.)
+    static_assert(kBoundDx2 == 3 && kAmaxXh1 == 8 && kBoundDx1 == 4 && kAmaxGz2 == 5 && kAmaxXh2 == 6 && kAmaxGz1 == 7, "one range");
+    hipLaunchKernelGGL(angle_zero_kernel, dim3(1), dim3(64), 0, st, a->scal + kBoundDx2, kAmaxXh1 - kBoundDx2 + 1);
     // layer 2: BatchNorm-backward sums and G = sum gz (a1 - mean) in one pass over g_z, then dW2 from G once c1 is known
     p.partial = dw2;
     p.partial_d = sums;

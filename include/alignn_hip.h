@@ -855,7 +855,9 @@ int alignn_add3(const float* a, const float* b, const float* c, float* out, int6
  * hidden features (alignn_angle_embed_supported).  BatchNorm in training mode: batch statistics, running statistics
  * updated (momentum), statistics kept in stat1 / stat2 for the backward; l1 / l2: the two layers' parameters, running
  * statistics and gradient destinations (img / img_t / w_amax unused).  scal: 128 floats the forward zeroes and both
- * directions use (operand scales, bounds).  Backward writes l?.gW, l?.gb, l?.red (= dbeta | dgamma); h gets no gradient. */
+ * directions use (operand scales, bounds).  Backward writes l?.gW, l?.gb, l?.red (= dbeta | dgamma); h gets no gradient.
+ * The backward resets the maxima and bounds it raises itself: any number of backwards on the state of one forward, each
+ * sliced at the scales of its own g_z. */
 typedef struct alignn_angle_args {
     const float* h;                /* [rows] cosines */
     int64_t rows;
