@@ -14,6 +14,7 @@ from .ealignn_atomwise import eALIGNNAtomWise, eALIGNNAtomWiseConfig  # noqa: F4
 from .interface import InterfaceResult, MatchResult, interface_energy, match_lattices  # noqa: F401
 from .graph import CSRGraph, GraphBatch, build_csr  # noqa: F401
 from .neb import NEBResult, neb, neb_interpolate  # noqa: F401
+from .idpp import IDPPResult, idpp_forces, idpp_interpolate  # noqa: F401
 from .order import (MAX_HKL, MAX_L, MAX_NEIGHBORS, ADFResult, SQResult, SteinhardtResult, adf, steinhardt,  # noqa: F401
                     structure_factor)
 from .relax import RelaxResult, relax  # noqa: F401

@@ -19,8 +19,11 @@ rows, and ``relax`` keeps a structure's bits independent of its batch, so a band
 call.  tests/neb_ref.py restates the formulas in numpy.  The entry points are declared in include/alignn_neb.h, read here with
 the reader of alignn_amd/_abi.py.
 
-Not here: IDPP interpolation, the ``eb`` / ``spline`` / ``string`` methods, a list of spring constants along a band, variable-
-cell NEB, dynamic relaxation of images, and the relaxation of the endpoints (relax them with ``relax`` first).
+A band starts from the straight line, from the IDPP path (``interpolation="idpp"``: alignn_amd/idpp.py runs the same evaluator
+on the image dependent pair potential, csrc/idpp.hip, in place of the model) or from images handed in (``start``).
+
+Not here: the ``eb`` / ``spline`` / ``string`` methods, a list of spring constants along a band, variable-cell NEB, dynamic
+relaxation of images, and the relaxation of the endpoints (relax them with ``relax`` first).
 """
 
 from __future__ import annotations
@@ -247,6 +250,14 @@ class _BandEvaluator:
         e, _ = self.images(which, lat_v * 2, ends.rows(ends.frac), ends.rows(ends.pos))
         self.end_energy.copy_(e.view(2, self.B).t())
 
+    def interior(self, which, lattices, frac, cart):
+        """(energy, forces) of the interior images of the active bands ``which``, in evaluation order: the one place the band
+        meets what it is relaxed on (alignn_amd/idpp.py puts the IDPP objective here)."""
+        ns, M = self.ns, self.M
+        split = lambda ts: [t[j * ns[b]:(j + 1) * ns[b]] for b, t in zip(which, ts) for j in range(int(M[b]) - 2)]
+        lat_img = [lat for b, lat in zip(which, lattices) for _ in range(int(M[b]) - 2)]
+        return self.images(self._structures, lat_img, split(frac), split(cart))
+
     def __call__(self, which, lattices, frac, cart):
         ns, M, dev = self.ns, self.M, self.dev
         if list(which) != self._which:  # (bands have retired: the launch's index arrays)
@@ -267,9 +278,7 @@ class _BandEvaluator:
         if any(t.data_ptr() != base + 24 * int(self.row0[b]) or not t.is_contiguous() for b, t in zip(which, cart)):
             raise RuntimeError("neb: the bands' rows are not views of one packed position array")
         self.args.positions = base
-        split = lambda ts: [t[j * ns[b]:(j + 1) * ns[b]] for b, t in zip(which, ts) for j in range(int(M[b]) - 2)]
-        lat_img = [lat for b, lat in zip(which, lattices) for _ in range(int(M[b]) - 2)]
-        energy, forces = self.images(self._structures, lat_img, split(frac), split(cart))
+        energy, forces = self.interior(which, lattices, frac, cart)
         out = torch.empty_like(forces)
         self.args.forces, self.args.energy, self.args.forces_out = forces.data_ptr(), energy.data_ptr(), out.data_ptr()
         _lib.check(_load().alignn_neb_forces(C.byref(self.args), _lib.stream()), "neb_forces")
@@ -277,11 +286,68 @@ class _BandEvaluator:
 
 
 # --- the driver --------------------------------------------------------------------------------------------------------------------
+INTERPOLATIONS = ("linear", "idpp")
+
+
+def _check_start(who, interpolation, idpp_fmax, idpp_steps, start, ns, M):
+    """The ``ValueError`` checks of where a band starts: ``interpolation``, the IDPP pass's limits and the shapes of ``start``."""
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"{who}: interpolation must be one of {list(INTERPOLATIONS)}, got {interpolation!r}")
+    if not (isinstance(idpp_steps, numbers.Integral) and idpp_steps >= 0 and isinstance(idpp_fmax, numbers.Real) and idpp_fmax >= 0):
+        raise ValueError(f"{who}: need idpp_steps >= 0 and idpp_fmax >= 0")
+    if start is None:
+        return
+    if interpolation == "idpp":
+        raise ValueError(f"{who}: start gives the interior images as they are; it cannot be combined with interpolation='idpp'")
+    if isinstance(start, (torch.Tensor, np.ndarray)) and start.ndim != 4 or len(start) != len(ns):
+        raise ValueError(f"{who}: start needs one [n_images, n, 3] array of interior images per band, {len(ns)} of them")
+    for i, s in enumerate(start):
+        want = (int(M[i]) - 2, ns[i], 3)
+        if shape_of(s) != want:
+            raise ValueError(f"{who}: start[{i}] is {shape_of(s)}, need {list(want)}: the interior images of band {i}")
+        if not np.isfinite(host(s).astype(np.float64)).all():
+            raise ValueError(f"{who}: start[{i}] must be finite")
+
+
+def _linear_path(lattices, initial, final, ns, M, tiled, dev):
+    """The bands on the device -> (the 2 B endpoints as one packed batch, the initial structures and then the final ones; the
+    cells [B, 3, 3]; the interior rows of the straight path and the inverse cells, as ``neb_interpolate`` gives them; the fixed
+    flags per interior row, or None)."""
+    B = len(ns)
+    ends = pack(list(lattices) * 2, list(initial) + list(final), ns * 2, dev)
+    lat = ends.lat[:B].contiguous()
+    rows, inv = neb_interpolate(lat, ends.pos[:ends.ptr[B]], ends.pos[ends.ptr[B]:], ns, M)
+    fixed_t = None
+    if tiled is not None and any(t.any() for t in tiled):
+        fixed_t = torch.tensor(np.concatenate(tiled).astype(np.uint8), device=dev)
+    return ends, lat, rows, inv, fixed_t
+
+
+def _run_band(evaluate, lat_v, rows, ns, M, tiled, fmax, steps, dev, fire):
+    """FIRE on every band as one structure of its interior rows ``rows``, through ``relax`` and the band evaluator."""
+    counts = [(int(M[b]) - 2) * ns[b] for b in range(len(ns))]
+    bands = list(torch.split(rows, counts))
+    return relax(None, lat_v, bands, None, evaluator=evaluate, fixed=tiled, optimize_lattice=False, fmax=fmax,
+                 steps=steps, device=dev, **fire)
+
+
+def _band_results(energies, r, ends, ns, M):
+    """Per band: the M energies of the last evaluation and the band [M, n, 3], endpoints included."""
+    B = len(ns)
+    ptr = np.concatenate([[0], np.cumsum(M)])
+    E = [energies[ptr[b]:ptr[b + 1]].copy() for b in range(B)]
+    positions = [torch.cat([ends.rows(ends.pos)[b][None], r.positions[b].view(int(M[b]) - 2, ns[b], 3),
+                            ends.rows(ends.pos)[B + b][None]]) for b in range(B)]
+    return E, positions
+
+
 def neb(model, lattices: Sequence, initial: Sequence, final: Sequence, atom_features: Optional[Sequence] = None, *,
         n_images=3, k=0.1, climb: bool = False, method: str = "aseneb", fmax: float = 0.05, steps: int = 100,
         fixed: Optional[Sequence] = None, forces_fn: Optional[Callable] = None, device=None,
         max_atoms_per_eval: Optional[int] = None, cutoff: float = 8.0, max_neighbors: int = 12,
-        neighbor_strategy: str = "k-nearest", intensive: bool = True, force_multiplier: float = 1.0, **fire) -> NEBResult:
+        neighbor_strategy: str = "k-nearest", intensive: bool = True, force_multiplier: float = 1.0,
+        interpolation: str = "linear", idpp_fmax: float = 0.1, idpp_steps: int = 100, start: Optional[Sequence] = None,
+        **fire) -> NEBResult:
     """Nudged elastic band between ``initial[b]`` and ``final[b]`` ([n_b, 3] Cartesian, the same atoms in the same order) in the
     cell ``lattices[b]``, for B bands together: ASE's ``NEB(images, k=k, climb=climb, method=method)`` with
     ``interpolate(mic=True)`` and ``FIRE(neb).run(fmax, steps)``.
@@ -298,41 +364,45 @@ def neb(model, lattices: Sequence, initial: Sequence, final: Sequence, atom_feat
     of whole images of at most this many atoms (an image larger than it goes alone); the results are the same bits.  ``**fire``:
     FIRE's ``dt``, ``maxstep``, ``dtmax``, ``Nmin``, ``finc``, ``fdec``, ``astart``, ``fa``, ``a`` with ``relax``'s defaults.
 
+    Where the bands start.  ``interpolation="linear"`` (the default): the straight line between the endpoints,
+    ``interpolate(mic=True)``.  ``"idpp"``: ASE's ``interpolate(method="idpp")`` - from the straight line, the band's own NEB
+    (its ``k``, its ``method``, no climbing image, the same ``fixed`` rows, the same ``**fire``) is first run on the image
+    dependent pair potential of alignn_amd/idpp.py instead of the model, until its largest force is below ``idpp_fmax`` or for
+    ``idpp_steps`` steps (ASE's defaults), with FIRE where ASE's default is ``MDMin``; the model then starts from that path.
+    ``start``: B arrays [n_images_b, n_b, 3], the interior images as they are to be used, instead of an interpolation (not
+    together with ``"idpp"``); ``idpp_interpolate`` gives such images.
+
     The endpoints are used as given: relax them with ``relax`` first.  Displacements between neighbouring images take the
     minimum image convention of the plain wrap (``f -= rint(f)`` on the fractional difference), not ASE's Minkowski-reduced
     ``find_mic``: for strongly skewed cells the two can differ.  A band whose endpoints coincide is refused.
 
-    Not supported: IDPP interpolation, the ``eb`` / ``spline`` / ``string`` methods, a list of spring constants along a band,
-    variable-cell NEB, dynamic relaxation of images, endpoint relaxation inside the call."""
+    Not supported: the ``eb`` / ``spline`` / ``string`` methods, a list of spring constants along a band, variable-cell NEB,
+    dynamic relaxation of images, endpoint relaxation inside the call."""
     who = "neb"
     ns, M, ks, tiled = _check(who, model, lattices, initial, final, atom_features, n_images, k, climb, method, fmax, steps, fixed,
                               forces_fn, max_atoms_per_eval, fire)
+    _check_start(who, interpolation, idpp_fmax, idpp_steps, start, ns, M)
     dev = gpu_device(who, model, forces_fn, device)
     B = len(ns)
     evaluation = dict(cutoff=cutoff, max_neighbors=max_neighbors, neighbor_strategy=neighbor_strategy, intensive=intensive,
                       force_multiplier=force_multiplier)
 
     with _lib.device_guard(torch.empty(0, device=dev)):
-        # the 2 B endpoints as one packed batch: the initial structures, then the final ones
-        ends = pack(list(lattices) * 2, list(initial) + list(final), ns * 2, dev)
-        lat = ends.lat[:B].contiguous()
-        rows, inv = neb_interpolate(lat, ends.pos[:ends.ptr[B]], ends.pos[ends.ptr[B]:], ns, M)
-        fixed_t = None
-        if tiled is not None and any(t.any() for t in tiled):
-            fixed_t = torch.tensor(np.concatenate(tiled).astype(np.uint8), device=dev)
+        ends, lat, rows, inv, fixed_t = _linear_path(lattices, initial, final, ns, M, tiled, dev)
+        if start is not None:
+            rows = torch.cat([torch.as_tensor(s).to(dev, torch.float64).reshape(-1, 3) for s in start]).contiguous()
+        elif interpolation == "idpp":
+            from .idpp import idpp_pass
+
+            rows = torch.cat(idpp_pass(who, ns, M, ks, tiled, lat, inv, ends, fixed_t, method, rows, idpp_fmax, idpp_steps, dev,
+                                       fire)[0].positions)
         evaluate = _BandEvaluator(who, model, forces_fn, atom_features, ns, M, ks, lat, inv, ends, fixed_t, method, climb,
                                   max_atoms_per_eval, dev, evaluation)
         lat_v = [lat[b] for b in range(B)]
         evaluate.endpoints(lat_v)
-        counts = [(int(M[b]) - 2) * ns[b] for b in range(B)]
-        bands = list(torch.split(rows, counts))
-        r = relax(None, lat_v, bands, None, evaluator=evaluate, fixed=tiled, optimize_lattice=False, fmax=fmax,
-                  steps=steps, device=dev, **fire)
+        r = _run_band(evaluate, lat_v, rows, ns, M, tiled, fmax, steps, dev, fire)
         energies = evaluate.energies_all.cpu().numpy()
-    ptr = np.concatenate([[0], np.cumsum(M)])
-    E = [energies[ptr[b]:ptr[b + 1]].copy() for b in range(B)]
-    positions = [torch.cat([ends.rows(ends.pos)[b][None], r.positions[b].view(int(M[b]) - 2, ns[b], 3),
-                            ends.rows(ends.pos)[B + b][None]]) for b in range(B)]
+    E, positions = _band_results(energies, r, ends, ns, M)
     return NEBResult(positions=positions, energies=E, forces=[f.view(int(M[b]) - 2, ns[b], 3) for b, f in enumerate(r.forces)],
                      imax=np.array([1 + int(np.argmax(e[1:-1])) for e in E]), barrier=np.array([e.max() - e[0] for e in E]),
                      delta_e=np.array([e[-1] - e[0] for e in E]), fmax=r.fmax, converged=r.converged, n_steps=r.n_steps,

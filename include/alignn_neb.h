@@ -14,6 +14,9 @@
  *     f = (d0 Cinv[0] + d1 Cinv[1]) + d2 Cinv[2];  f -= rint(f);  mic(d) = (f0 C[0] + f1 C[1]) + f2 C[2]
  * with Cinv the inverse of C by cofactors (csrc/cell3.h) - not ASE's Minkowski-reduced find_mic: in a strongly skewed cell the
  * two can differ.
+ *
+ * Not here: the image dependent pair potential that a band can be started on (IDPP) has a header of its own, alignn_idpp.h; its
+ * results are laid out as _neb_forces reads an evaluation.
  */
 #ifndef ALIGNN_NEB_H
 #define ALIGNN_NEB_H
