@@ -191,7 +191,10 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     const float sg = f16_scale(*g.g_amax), sy = f16_scale(*g.y_amax);
     const float inv_sg = 1.0f / sg, inv_sw = 1.0f / f16_scale(*g.w_amax);
-    const float inv_dw = (1.0f / sg) * (1.0f / sy);
+    // the weight gradient's two inverse scales: their product wherever fp32 holds it (then dw_i1 = 1: the bits of one multiply),
+    // one after the other where it does not - sg sy >= 2^150, both maxima tiny, the product would be 0 and dW with it
+    const float inv_sy = 1.0f / sy, inv_gy = inv_sg * inv_sy;
+    const float dw_i0 = inv_gy != 0.0f ? inv_gy : inv_sg, dw_i1 = inv_gy != 0.0f ? 1.0f : inv_sy;
 
     if constexpr (BNRED) {  // BatchNorm constants -> LDS (read per epilogue round; visible after the first barrier)
         for (int i = t; i < 4 * H / 4; i += NTH) *reinterpret_cast<float4*>(smem + NSTAT + i * 16) = f4_ld(g.nstat + i * 4);
@@ -515,7 +518,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int f = 64 * wf + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * half, c = 128 * wc + 32 * b + il;
-                    out[f * H + c] = acc_dw[a][b][r] * inv_dw;
+                    out[f * H + c] = acc_dw[a][b][r] * dw_i0 * dw_i1;
                 }
     }
     if constexpr (BNRED) {
@@ -599,11 +602,14 @@ int alignn_gemm_dgrad_wgrad_f16x3(const float* G, int64_t ldg, const float* g_am
     if (!alignn_gemm_dgrad_wgrad_supported(M, H, H) || G == nullptr || Y == nullptr || Wt_split == nullptr || C == nullptr ||
         dW == nullptr || g_amax == nullptr || y_amax == nullptr || w_amax == nullptr)
         return (int)hipErrorInvalidValue;
-    if ((ldg & 3) || (ldy & 3) || (ldc & 3) || (lddw & 3) || !aligned16(G) || !aligned16(Y) || !aligned16(C) || !aligned16(dW) || !aligned16(Wt_split) ||
-        (addend && ((ldadd & 3) || !aligned16(addend))))
+    // leading dimensions: 16-byte aligned rows of 256 floats that do not overlap, and 32-bit row offsets inside a 64-row tile
+    // (as launch_nt_p of gemm_x6.hip)
+    auto ld_ok = [](int64_t ld) { return ld >= H && ld < ((int64_t)1 << 20) && !(ld & 3); };
+    if (!ld_ok(ldg) || !ld_ok(ldy) || !ld_ok(ldc) || !ld_ok(lddw) || !aligned16(G) || !aligned16(Y) || !aligned16(C) || !aligned16(dW) ||
+        !aligned16(Wt_split) || (addend && (!ld_ok(ldadd) || !aligned16(addend))))
         return (int)hipErrorInvalidValue;
     const bool bnred = Xn != nullptr;
-    if (bnred && (nstat == nullptr || red_partial == nullptr || (ldxn & 3) || !aligned16(Xn) || !aligned16(nstat) || !aligned16(red_partial)))
+    if (bnred && (nstat == nullptr || red_partial == nullptr || !ld_ok(ldxn) || !aligned16(Xn) || !aligned16(nstat) || !aligned16(red_partial)))
         return (int)hipErrorInvalidValue;
     if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < alignn_gemm_dgrad_wgrad_workspace(M))
         return (int)hipErrorInvalidValue;

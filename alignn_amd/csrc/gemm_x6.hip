@@ -885,11 +885,15 @@ __global__ __launch_bounds__(TNT) void gemm_tn_x6_kernel(TnArgs g) {
     const int col = t & 255;
     const float* src = is_x ? g.X + k0 + col : g.G + n0 + col;
     const int64_t ld = is_x ? g.ldx : g.ldg;
-    float scale = 1.0f, inv_scale = 1.0f;
+    float scale = 1.0f, inv_s0 = 1.0f, inv_s1 = 1.0f;
     if constexpr (F16) {
         const float sg = f16_scale(*g.g_amax), sx = f16_scale(*g.x_amax);
         scale = is_x ? sx : sg;
-        inv_scale = (1.0f / sg) * (1.0f / sx);
+        // the product of the two inverse scales wherever fp32 holds it (then inv_s1 = 1: the bits of one multiply), one after the
+        // other where it does not - sg sx >= 2^150, both maxima tiny, the product would be 0 and the slab with it
+        const float inv_sg = 1.0f / sg, inv_sx = 1.0f / sx, inv_gx = inv_sg * inv_sx;
+        inv_s0 = inv_gx != 0.0f ? inv_gx : inv_sg;
+        inv_s1 = inv_gx != 0.0f ? 1.0f : inv_sx;
     }
     // sliced-stage LDS image, per operand: [plane][column 256][chunk 2, swizzled][8 x 16 bit]
     const int w_off = (is_x ? NPL * TPLANE : 0) + col * (TSTEP * 2);
@@ -1046,7 +1050,7 @@ __global__ __launch_bounds__(TNT) void gemm_tn_x6_kernel(TnArgs g) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             float4 v = ov[i];
-            if constexpr (F16) v = f4_scale(v, inv_scale);
+            if constexpr (F16) v = f4_scale(f4_scale(v, inv_s0), inv_s1);
             f4_st(out + (int64_t)(row0 + i * 4) * g.K + ocol, v);
         }
     }

@@ -93,7 +93,12 @@ int alignn_gemm_nt_x6(const float* A, int64_t lda, const void* Wsplit, const flo
 
 /* Weight gradient on the split product (both operands sliced in registers): slab partials ws[z][N][K] for
  * z < alignn_gemm_tn_x6_splits(M,N,K); needs N % 256 == 0, K % 256 == 0, M >= 4096.  alignn_gemm_tn uses it
- * automatically for such shapes and sums the slabs. */
+ * automatically for such shapes and sums the slabs.
+ * Range of the maxima (f16x3, here and in alignn_gemm_tn): the accumulators are divided by the two operand scales.  Where
+ * the product of the two inverse scales is an fp32 number - scales multiplying to less than 2^150, about
+ * max|G| max|X| >= 2^-121 - it is applied as one factor; below, where that product is 0 in fp32, the two inverse scales
+ * are applied one after the other, so a weight gradient of ordinary fp32 size (max|G| = max|X| = 2^-62, 4096 rows: entries
+ * around 1e-37) is returned as such and not as 0.  Results on every other input keep their bits. */
 int alignn_gemm_tn_x6_supported(int64_t M, int N, int K);
 size_t alignn_gemm_tn_x6_workspace(int64_t M, int N, int K);
 int alignn_gemm_tn_x6_splits(int64_t M, int N, int K);
@@ -209,7 +214,16 @@ int alignn_gemm_nt_f16x3_bnred(const float* A, int64_t lda, const float* a_amax,
  * red_partial - the BatchNorm-backward column sums of C against the pre-activation Xn, left as
  * alignn_gemm_dgrad_wgrad_slabs(M) * 2 slabs of [2][256] for alignn_bn_bwd_finalize.  `workspace`:
  * alignn_gemm_dgrad_wgrad_workspace(M) bytes (one 256 x 256 partial of dW per workgroup, summed in fp64 in slab order:
- * bit-reproducible).  Shapes: N = K = 256, M >= 4096 (alignn_gemm_dgrad_wgrad_supported). */
+ * bit-reproducible).  Shapes: N = K = 256, M >= 4096 (alignn_gemm_dgrad_wgrad_supported).
+ * - Leading dimensions.  ldg, ldy, ldc, lddw - and ldadd, ldxn where their pointer is given - are multiples of 4 in
+ *   [256, 2^20): rows must not overlap, and the kernel addresses the rows of a 64-row tile with 32-bit offsets (as the
+ *   persistent kernel of alignn_gemm_nt_f16x3).  Anything else is refused (invalid value) before any launch.
+ * - Range of the maxima.  C: as alignn_gemm_nt_f16x3.  dW: as alignn_gemm_tn_x6_partials - the two inverse scales are one
+ *   factor where their product is an fp32 number and are applied one after the other where it is not (scales multiplying to
+ *   2^150 or more, about g_amax y_amax < 2^-121), so dW is not flushed to 0 there.
+ * - Rows past M.  The last tile re-reads row M - 1 of G, addend and Xn for its missing rows and multiplies those of Y by 0
+ *   (an infinity in row M - 1 of Y therefore gives NaN in its column of dW); no row behind the M given is read.
+ * - Extents.  Exactly alignn_gemm_dgrad_wgrad_slabs(M) slabs of `workspace` and twice as many of `red_partial` are written. */
 int alignn_gemm_dgrad_wgrad_supported(int64_t M, int N, int K);
 int alignn_gemm_dgrad_wgrad_slabs(int64_t M);
 size_t alignn_gemm_dgrad_wgrad_workspace(int64_t M);

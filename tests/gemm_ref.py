@@ -252,3 +252,47 @@ def operands(M, N, K, data, seed=0):
     elif data == "zero_rows":
         a[::4] = 0.0
     return a.contiguous(), w.contiguous(), bias.contiguous(), addend.contiguous()
+
+
+# ---- operands of the fused input-gradient + weight-gradient pass (csrc/gemm_dw.hip): C = G W (+ addend), dW = G^T Y, and the
+# BatchNorm-backward sums of C against Xn
+
+DW_H = 256
+DW_PLAIN = ("normal", "row_blocks", "tiny", "huge", "outlier", "zero_rows")
+DW_DATA = DW_PLAIN + ("y_row_blocks", "y_outlier", "cancelling", "dw_cancelling", "small_maxima", "integers", "bn_normal",
+                      "bn_mean_over_spread", "bn_scale_zero_negative", "bn_saturated")
+
+
+def dw_operands(M, data, seed=0):
+    """float32 CPU (G [M, 256], Y [M, 256], W [256, 256], addend [M, 256], xn [M, 256], nstat [4, 256]) on one of DW_DATA.
+    W = w.t() of ``operands``' w, so that G W = G w^T and the NT bound functions apply with (a, w) = (G, W.t()); for the weight
+    gradient (a, w) = (G.t(), Y.t()).  nstat = [mean, rstd, gamma rstd, beta] from xn's own column statistics."""
+    H = DW_H
+    g = torch.Generator().manual_seed(1000 * seed + 31 * DW_DATA.index(data) + M)
+    rn = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+    ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, generator=g).float()  # noqa: E731
+    G, w, _, addend = operands(M, H, H, data if data in DW_PLAIN + ("cancelling",) else "normal", seed)
+    Y = rn(M, H)
+    if data in ("y_row_blocks", "y_outlier"):  # the structure on Y (another seed than G's: the two are independent)
+        Y = operands(M, H, H, data[2:], seed + 1)[0]
+    elif data == "dw_cancelling":  # row pairs (g, g + 2^-12 noise) against (y, -y): dW lies far below |G|^T |Y|
+        G[1::2] = G[0:2 * (M // 2):2] + 2.0 ** -12 * rn(M // 2, H)
+        Y[1::2] = -Y[0:2 * (M // 2):2]
+        if M % 2:
+            G[M - 1], Y[M - 1] = G[M - 1] * 2.0 ** -12, Y[M - 1] * 2.0 ** -12
+    elif data == "small_maxima":  # both maxima near 2^-62: the product of the two inverse scales is 2^-152
+        G, Y, addend = G * 2.0 ** -64, Y * 2.0 ** -64, addend * 2.0 ** -64
+    elif data == "integers":  # every slice product and every partial sum is representable: any order gives float64's bits
+        G, Y, addend, w = ri(-4, 4, M, H), ri(-4, 4, M, H), ri(-4, 4, M, H), ri(-8, 8, H, H) / 16
+    xn = rn(M, H) * 2 + 0.5
+    gamma, beta = rn(H).double(), rn(H).double()
+    if data == "bn_mean_over_spread":  # column means up to 100 spreads
+        xn = rn(M, H) * 0.5 + torch.linspace(-50.0, 50.0, H)
+    elif data == "bn_scale_zero_negative":  # a third of gamma rstd zero, the rest of either sign
+        gamma[0::3] = 0.0
+        gamma[1::3], gamma[2::3] = gamma[1::3].abs() + 0.1, -gamma[2::3].abs() - 0.1
+    elif data == "bn_saturated":  # exp overflows on one side: silu' is 0 or 1 to rounding
+        beta = torch.where(torch.arange(H) % 2 == 0, 60.0, -60.0).double()
+    mean, var = xn.double().mean(0), xn.double().var(0, unbiased=False) + 1e-5
+    nstat = torch.stack([mean, var.rsqrt(), gamma * var.rsqrt(), beta]).float()
+    return tuple(t.contiguous() for t in (G, Y, w.t(), addend, xn, nstat))

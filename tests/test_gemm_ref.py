@@ -121,6 +121,77 @@ def test_image_index_map_element_by_element():
     assert not bool(rows[:, 1, :, 4:].any())  # rows 260 .. 511
 
 
+# ---- dw_operands: what tests/test_gpu_gemm_dw_f64.py relies on
+
+DW_M_MAX = 64 * (3 * 256 - 1) - 7  # the largest row count that module can reach: three tiles per workgroup on the largest grid
+
+
+@pytest.mark.parametrize("data", ref.DW_DATA)
+def test_dw_operands_shapes_and_statistics(data):
+    M = 4096 + 33
+    G, Y, W, addend, xn, nstat = ref.dw_operands(M, data)
+    for t, shape in ((G, (M, 256)), (Y, (M, 256)), (W, (256, 256)), (addend, (M, 256)), (xn, (M, 256)), (nstat, (4, 256))):
+        assert t.shape == shape and t.dtype == torch.float32 and t.is_contiguous() and bool(torch.isfinite(t).all()), data
+    assert all(torch.equal(a, b) for a, b in zip(ref.dw_operands(M, data), (G, Y, W, addend, xn, nstat)))  # (a function of its arguments)
+    mean, var = d(xn).mean(0), d(xn).var(0, unbiased=False) + 1e-5
+    assert torch.allclose(d(nstat[0]), mean, rtol=1e-6, atol=1e-6) and torch.allclose(d(nstat[1]), var.rsqrt(), rtol=1e-6, atol=0)
+    if data in ref.DW_PLAIN + ("cancelling",):  # G W = a w^T of ``operands``
+        a, w, _, add = ref.operands(M, 256, 256, data)
+        assert torch.equal(G, a) and torch.equal(W, w.t()) and torch.equal(addend, add)
+    if data == "bn_mean_over_spread":
+        assert float((mean.abs() * var.rsqrt()).max()) > 90
+    if data == "bn_scale_zero_negative":
+        s = nstat[2]
+        assert int((s == 0).sum()) == 86 and int((s > 0).sum()) == 85 and int((s < 0).sum()) == 85
+    if data == "bn_saturated":
+        z = (d(xn) - mean) * d(nstat[2]) + d(nstat[3])
+        assert float(z[:, 0::2].min()) > 30 and float(z[:, 1::2].max()) < -30
+
+
+def test_dw_integers_are_exact_in_every_order():
+    """at the largest M: every fp16 low slice is zero with the true maxima and with maxima 16 x (and 5.5: no power of two) too
+    large, and a float32 product - one summation order among many, all of representable partial sums - has float64's bits"""
+    G, Y, W, addend, _, _ = ref.dw_operands(DW_M_MAX, "integers")
+    assert float(G.abs().max()) == 4 and float(Y.abs().max()) == 4 and float(W.abs().max()) == 0.5
+    for x, maxima in ((G, (4.0, 5.5, 64.0)), (Y, (4.0, 5.5, 64.0)), (W, (0.5, 8.0))):
+        for amax in maxima:
+            h, l = ref.slices_f16x2(x, amax)
+            assert not bool(l.any()) and torch.equal(d(h), d(x) * ref.f16_scale(amax)), amax
+    assert torch.equal(d(G.t() @ Y), d(G).t() @ d(Y))
+    assert torch.equal(d(G @ W + addend), d(G) @ d(W) + d(addend)) and torch.equal(d(G @ W), d(G) @ d(W))
+    assert float((d(G).abs().t() @ d(Y).abs()).max()) < 2.0 ** 24  # (the sum of magnitudes itself is an exact float32)
+
+
+@pytest.mark.parametrize("M", (4096 + 33, 64 * 224 + 1, 128 * 224 + 33))
+def test_dw_small_maxima_references_are_float32_numbers(M):
+    """both maxima in [2^-63, 2^-61): the two operand scales multiply to at least 2^150, so the product of their inverses is below
+    float32's smallest subnormal - while the weight gradient itself is an ordinary float32 tensor: its largest entry is a normal
+    number of 2^-123 or more, and so are nine in ten of the others.  (A sum of M products of independent N(0, 1) 2^-64 values is
+    N(0, M) 2^-128: one entry in twenty at 4129 rows falls below 2^-126 by chance.  float32 holds those to 2^-150 absolute, which
+    is below a thousandth of the bound the kernel is held to at every entry - asserted here, so the bound asks nothing of an
+    entry that float32 cannot give.)"""
+    G, Y, _, _, _, _ = ref.dw_operands(M, "small_maxima")
+    ga, ya = float(G.abs().max()), float(Y.abs().max())
+    assert 2.0 ** -63 <= ga < 2.0 ** -61 and 2.0 ** -63 <= ya < 2.0 ** -61
+    assert ref.f16_scale(ga) * ref.f16_scale(ya) >= 2.0 ** 150
+    inv = torch.tensor(1.0 / ref.f16_scale(ga)) * torch.tensor(1.0 / ref.f16_scale(ya))  # (float32 arithmetic)
+    assert inv.dtype == torch.float32 and float(inv) == 0.0
+    dw = (d(G).t() @ d(Y)).abs()
+    normal = dw >= 2.0 ** -126
+    assert float(dw.max()) >= 2.0 ** -123 and float(normal.double().mean()) > 0.9 and float(dw.median()) >= 2.0 ** -126
+    bound = ref.f16x3_scheme_bound_at(G.t(), Y.t(), ga, ya) + (M + 3) * ref.U * (d(G).abs().t() @ d(Y).abs())
+    assert float(bound.min()) > 2.0 ** 10 * 2.0 ** -150
+    assert float((dw / bound).median()) > 2.0  # (a zero in its place is outside the bound at most entries, and by far at the largest)
+    assert float((dw / bound).max()) > 8.0
+
+
+@pytest.mark.parametrize("M", (4096 + 33, 64 * 224 + 1))
+def test_dw_cancelling_lies_far_below_the_sum_of_magnitudes(M):
+    G, Y, _, _, _, _ = ref.dw_operands(M, "dw_cancelling")
+    dw, mag = (d(G).t() @ d(Y)).abs(), d(G).abs().t() @ d(Y).abs()
+    assert float((dw / mag).median()) <= 2.0 ** -8
+
+
 @pytest.mark.parametrize("rows,R", ((1, 64), (64, 64), (65, 64), (300, 128), (257, 64)))
 def test_slab_helpers_sum_to_the_whole_tensor(rows, R):
     g = torch.Generator().manual_seed(rows)

@@ -594,13 +594,18 @@ def _tn_x6_chunk(M, N, K):
     return max(cdiv(cdiv(M, want), 16) * 16, 128)
 
 
-# (8200, 1024, 256): 57 slabs of 144 rows, the last one 136 rows - no multiple of 16
-@pytest.mark.parametrize("data", ("normal", "row_blocks"))
-@pytest.mark.parametrize("M,N,K", ((4096, 256, 256), (4113, 256, 512), (4113, 512, 256), (8200, 1024, 256)))
+# (8200, 1024, 256): 57 slabs of 144 rows, the last one 136 rows - no multiple of 16.  ``small_maxima`` (gemm_ref.dw_operands: both
+# maxima near 2^-62, the two operand scales multiply to 2^152): the product of the two inverse scales is 0 in float32, the kernel
+# applies them one after the other there - the same bound form, for both entry points (the bf16x6 form has no scales)
+X6_TN = tuple((M, N, K, data) for M, N, K in ((4096, 256, 256), (4113, 256, 512), (4113, 512, 256), (8200, 1024, 256))
+              for data in ("normal", "row_blocks")) + ((4096, 256, 256, "small_maxima"),)
+
+
+@pytest.mark.parametrize("M,N,K,data", X6_TN)
 def test_x6_tn(M, N, K, data):
     lib = _lib.load()
     rep = Report(f"x6 tn ({M}, {N}, {K}) {data}", TAG)
-    g, x = _tn_operands(M, N, K, data)
+    g, x = ref.dw_operands(M, data)[:2] if data == "small_maxima" else _tn_operands(M, N, K, data)
     g, x = _wide(g, 4), _wide(x, 4 if M % 2 else 12)
     g_amax, x_amax = _scalar(g), _scalar(x)
     chunk, splits = _tn_x6_chunk(M, N, K), lib.alignn_gemm_tn_x6_splits(M, N, K)
