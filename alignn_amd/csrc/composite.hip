@@ -33,7 +33,10 @@ FwdScratch fwd_scratch(int64_t n, int64_t m, int H, int Kin, int edge_kind) {
     s.n_slabs = alignn_egc_slabs(n);
     s.e_slabs = edge_kind >= 1 ? alignn_gemm_nt_x6_row_tiles(m, H, Kin) : s.n_slabs;
     size_t off = 0;
-    s.e_part = off, off += al((size_t)(s.e_slabs + 1) * (3 * H + 1));  // (the gate pass writes pivot slabs [3][H] + counts)
+    // e_part, one of two layouts, each sized as its writer's header entry states: the projection epilogue's row_tiles + 1 slabs
+    // of [2][H] (the last one the persistent kernel's scratch slab), or the gate pass's alignn_egc_slabs(n) pivot slabs [3][H]
+    // followed by their counts - exactly slabs * (3 H + 1) floats, nothing behind them
+    s.e_part = off, off += al(edge_kind >= 1 ? (size_t)(s.e_slabs + 1) * 2 * H : (size_t)s.e_slabs * (3 * H + 1));
     s.e_fold = off, off += al((size_t)alignn_slab_fold_slabs() * 2 * H);
     s.n_part = off, off += al((size_t)s.n_slabs * (3 * H + 1));
     s.bd2 = off, off += edge_kind == 2 ? al((size_t)n * H) : 0;

@@ -43,6 +43,12 @@ def _empty(*shape, like):
     return torch.empty(*shape, dtype=torch.float32, device=like.device)
 
 
+def _scratch(nbytes, like):
+    """the scratch block of a composite call (alignn_egc_conv_{fwd,bwd,wgrad}_scratch bytes), as float32; one allocator of its
+    own, as _empty is for activations, so that tests/test_gpu_conv_extents.py can put guard bands round it"""
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=like.device)
+
+
 # ---------------------------------------------------------------------------------------------
 # side stream for weight gradients
 #
@@ -1777,7 +1783,7 @@ class EdgeGatedConvFn(torch.autograd.Function):
         xo_amax = new_amax(x) if _track(n) else None
         yo_amax = new_amax(x) if (need_y and _track(m)) else None
         nbytes = lib.alignn_egc_conv_fwd_scratch(n, m, H, Kin, edge_kind)
-        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        scratch = _scratch(nbytes, like=x)
         args = _lib.EgcFwdArgs(
             seg_ptr=ptr(graph.seg_ptr), seg_node=ptr(graph.seg_node), src=ptr(graph.src), dst=ptr(graph.dst),
             seg_rank=ptr(graph.seg_rank), n=n, m=m,
@@ -1865,7 +1871,7 @@ class EdgeGatedConvFn(torch.autograd.Function):
         g_x = _empty(n, Kin, like=x)
         g_y = _empty(m, Kin, like=x)
         nbytes = lib.alignn_egc_conv_bwd_scratch(n, m, H, Kin, dx_kind, dy_kind)
-        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        scratch = _scratch(nbytes, like=x)
         args = _lib.EgcBwdArgs(
             seg_ptr=ptr(graph.seg_ptr), seg_node=ptr(graph.seg_node), src=ptr(graph.src), dst=ptr(graph.dst),
             out_ptr=ptr(graph.out_ptr), out_slot=ptr(graph.out_slot),
@@ -1902,7 +1908,7 @@ class EdgeGatedConvFn(torch.autograd.Function):
             g_weg, g_beg = _empty(H, Kin, like=x), _empty(H, like=x)
             g_wcat, g_bcat = _empty(4 * H, Kin, like=x), _empty(4 * H, like=x)
             wb = lib.alignn_egc_conv_wgrad_scratch(n, m, H, Kin)
-            ws = torch.empty(wb // 4, dtype=torch.float32, device=x.device)
+            ws = _scratch(wb, like=x)
             wargs = _lib.EgcWgradArgs(
                 n=n, m=m, H=H, Kin=Kin, gb_slabs=gslabs, GM=ptr(GM), GP=ptr(GP), x=ptr(x), y=ptr(y), gb_part=ptr(gb_part),
                 gm_amax=ptr(tn_gm[0]), gp_amax=ptr(tn_gp[0]), x_amax=ptr(tn_gp[1]), y_amax=ptr(tn_gm[1]),

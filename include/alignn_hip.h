@@ -342,7 +342,10 @@ int alignn_bn_silu_bwd_apply_sum(const float* GY, int64_t ldgy, const float* X, 
  * ------------------------------------------------------------------------------------------ */
 
 /* number of stat slabs the gate kernel writes for a graph with n segments (pivot-slab layout: slabs*(3*H+1) floats, see
- * alignn_col_stats_welford) */
+ * alignn_col_stats_welford).  Extents: e_partial and n_partial of alignn_egc_gate_fwd / _pre / _pre_norm are written in full and
+ * hold exactly alignn_egc_slabs(n_seg) * (3 * H + 1) floats each - no slab behind them is scratch, unlike the projection
+ * epilogues' [row_tiles + 1][2][N]; gb_partial of the reverse passes exactly [slabs][H] (tests/test_gpu_conv_bn.py hands
+ * every one of them at that size inside guard bands). */
 int alignn_egc_slabs(int64_t n_seg);
 
 /* In : P[n,4H]; M[m,H] holds C = y*W_eg^T + b on entry.
@@ -650,6 +653,8 @@ typedef struct alignn_egc_fwd_args {
     float* scratch;
     size_t scratch_bytes;
 } alignn_egc_fwd_args;
+/* bytes of `scratch`: the call touches nothing outside them (the edge-statistics block inside is sized as its writer's entry
+ * above states: [row_tiles + 1][2][H] for edge_kind >= 1, alignn_egc_slabs(n) * (3 * H + 1) floats for edge_kind 0) */
 size_t alignn_egc_conv_fwd_scratch(int64_t n, int64_t m, int H, int Kin, int edge_kind);
 int alignn_egc_conv_fwd(const alignn_egc_fwd_args* args, alignn_stream_t stream);
 

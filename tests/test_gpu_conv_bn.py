@@ -39,9 +39,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from alignn_amd import _lib  # noqa: E402
-from alignn_amd._lib import ptr, stream  # noqa: E402
+from alignn_amd._lib import stream  # noqa: E402
 from tests import conv_bn_ref as ref  # noqa: E402
-from tests.gate_parity import Report, graph, is_line_graph  # noqa: E402
+from tests.gate_parity import Report, gptr, graph, guard_graph, guard_input, guarded, is_line_graph  # noqa: E402
 
 DEV = "cuda"
 INVALID = 1  # hipErrorInvalidValue
@@ -72,23 +72,26 @@ def _stat_asserts(rep, ent, side, stat, rm, rv, want, beta, x):
 
 
 def _run_case(H, gname, data):
-    lib = _lib.load()
-    g = graph(gname)
+    rep = Report(f"H={H} {gname} {data}", "conv-bn-parity")
+    lib = rep.launcher(_lib.load())
+    # every buffer a launch is handed lies between guard bands (tests/gate_parity.Guards; rep.finish() checks them first), the
+    # graph's tables and the operands as guarded copies, and every pointer goes through gptr, which refuses any other tensor
+    g = guard_graph(graph(gname))
     n, m = g.n_nodes, g.n_edges
     u, v = g.src.long(), g.dst.long()
-    o = ref.operands(H, u, v, n, data, gname, DEV)
+    o = {k: guard_input(t, k) for k, t in ref.operands(H, u, v, n, data, gname, DEV).items()}
     st = stream()
-    rep = Report(f"H={H} {gname} {data}", "conv-bn-parity")
     other = data != "normal"
-    E = lambda *s: torch.full(s, NAN, device=DEV)  # noqa: E731  (an output: whatever is not written fails)
-    EM = lambda: torch.full((max(m, 1), H), NAN, device=DEV)  # noqa: E731  (an edge-row output: never a NULL pointer)
-    Z = lambda *s: torch.zeros(*s, device=DEV)  # noqa: E731
+    E = lambda *s: guarded(s, fill=NAN, row=H)  # noqa: E731  (an output: whatever is not written fails)
+    EM = lambda: guarded((max(m, 1), H), fill=NAN)  # noqa: E731  (an edge-row output: never a NULL pointer)
+    Z = lambda *s: guarded(s, fill=0.0, row=H)  # noqa: E731
+    G = lambda t: guard_input(t.contiguous())  # noqa: E731  (a tensor made here, handed to a launch)
     pad = Z(1, H)
-    pin = lambda t: ptr(t if t.numel() else pad)  # noqa: E731  (an edge-row input of a graph without edges: not NULL either)
+    pin = lambda t: gptr(t if t.numel() else pad)  # noqa: E731  (an edge-row input of a graph without edges: not NULL either)
     P, C, M, Y, GY, Q1, Q0 = (o[k] for k in ("P", "C", "M", "Y", "GY", "Q1", "Q0"))
     eg, eb, ng, nb = o["e_gamma"], o["e_beta"], o["n_gamma"], o["n_beta"]
     slabs = lib.alignn_egc_slabs(n)
-    seg = (ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src))
+    seg = (gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src))
 
     def forward_ref(dt, second, pre, e_eval=False):
         c = {k: t.to(dt) for k, t in o.items()}
@@ -96,7 +99,7 @@ def _run_case(H, gname, data):
         return ref.values(c["P"], c[second], pre, c["e_gamma"], c["e_beta"], fixed, u, v, n, H, n_gamma=c["n_gamma"],
                           n_beta=c["n_beta"], running=c)
 
-    def slab_buffers():
+    def slab_buffers():  # exactly what include/alignn_hip.h states at alignn_egc_slabs: slabs * (3 H + 1) floats, nothing behind
         return E(slabs * (3 * H + 1)), E(slabs * (3 * H + 1))
 
     def node_side(ent, r64, r32, xpre, s0, hh, n_part):
@@ -107,9 +110,9 @@ def _run_case(H, gname, data):
         if n_part is not None:
             if float(n_part[slabs * 3 * H:].sum()) != n:
                 rep.failed.append((ent, "node slab counts", n_part[slabs * 3 * H:].tolist(), n))
-            stat, rm, rv = E(4, H), o["n_rm"].clone(), o["n_rv"].clone()
-            assert lib.alignn_bn_finalize_welford(ptr(n_part), slabs, n, H, ptr(ng), ptr(nb), ref.EPS_BN, ref.MOMENTUM, ptr(rm), ptr(rv),
-                                                  ptr(stat), st) == 0
+            stat, rm, rv = E(4, H), G(o["n_rm"]), G(o["n_rv"])
+            assert lib.alignn_bn_finalize_welford(gptr(n_part), slabs, n, H, gptr(ng), gptr(nb), ref.EPS_BN, ref.MOMENTUM, gptr(rm), gptr(rv),
+                                                  gptr(stat), st) == 0
             torch.cuda.synchronize()
             _stat_asserts(rep, ent, "n", stat, rm, rv, r64, nb, r64["xpre"])
 
@@ -119,9 +122,9 @@ def _run_case(H, gname, data):
             rep.failed.append((ent, "edge slab counts", counts.tolist(), m))
         if m == 0:  # (no finaliser is called with zero rows)
             return
-        stat, rm, rv = E(4, H), o["e_rm"].clone(), o["e_rv"].clone()
-        assert lib.alignn_bn_finalize_welford(ptr(e_part), slabs, m, H, ptr(eg), ptr(eb), ref.EPS_BN, ref.MOMENTUM, ptr(rm), ptr(rv),
-                                              ptr(stat), st) == 0
+        stat, rm, rv = E(4, H), G(o["e_rm"]), G(o["e_rv"])
+        assert lib.alignn_bn_finalize_welford(gptr(e_part), slabs, m, H, gptr(eg), gptr(eb), ref.EPS_BN, ref.MOMENTUM, gptr(rm), gptr(rv),
+                                              gptr(stat), st) == 0
         torch.cuda.synchronize()
         _stat_asserts(rep, ent, "e", stat, rm, rv, r64, eb, r64["m"])
 
@@ -131,7 +134,7 @@ def _run_case(H, gname, data):
     Mio, xpre, s0, hh = EM(), E(n, H), E(n, H), E(n, H)
     Mio[:m] = C
     e_part, n_part = slab_buffers()
-    assert lib.alignn_egc_gate_fwd(ptr(P), ptr(Mio), *seg, n, m, H, ptr(xpre), ptr(s0), ptr(hh), ptr(e_part), ptr(n_part), st) == 0
+    assert lib.alignn_egc_gate_fwd(gptr(P), gptr(Mio), *seg, n, m, H, gptr(xpre), gptr(s0), gptr(hh), gptr(e_part), gptr(n_part), st) == 0
     torch.cuda.synchronize()
     rep.close("gate_fwd", "M", Mio[:m], f64["m"], f32.get("m"), B_GATE_FWD)
     node_side("gate_fwd", f64, f32, xpre, s0, hh, n_part)
@@ -140,17 +143,17 @@ def _run_case(H, gname, data):
     # ---- inference form: C only read, fixed affine map from running statistics that are not the batch's
     i64 = forward_ref(torch.float64, "C", False, e_eval=True)
     i32 = forward_ref(torch.float32, "C", False, e_eval=True) if other else {}
-    ev_stat = i64["e_stat"].float().contiguous()
+    ev_stat = G(i64["e_stat"].float())
     c_before = C.clone()
     xpre, am = E(n, H), Z(1)
-    assert lib.alignn_egc_gate_infer(ptr(P), pin(C), *seg, n, m, H, ptr(xpre), None, None, None, ptr(am), st) == 0
+    assert lib.alignn_egc_gate_infer(gptr(P), pin(C), *seg, n, m, H, gptr(xpre), None, None, None, gptr(am), st) == 0
     torch.cuda.synchronize()
     node_side("gate_infer -YOUT", i64, i32, xpre, None, None, None)
     rep.amax("gate_infer -YOUT", "y_amax", am[0], torch.zeros(0))  # (the YOUT = NULL form writes XPRE only)
     for res in (False, True):
         xpre, yout, am = E(n, H), EM(), Z(1)
-        assert lib.alignn_egc_gate_infer(ptr(P), pin(C), *seg, n, m, H, ptr(xpre), ptr(ev_stat), pin(Y) if res else None, ptr(yout),
-                                         ptr(am), st) == 0
+        assert lib.alignn_egc_gate_infer(gptr(P), pin(C), *seg, n, m, H, gptr(xpre), gptr(ev_stat), pin(Y) if res else None, gptr(yout),
+                                         gptr(am), st) == 0
         torch.cuda.synchronize()
         ent = "gate_infer" + (" +Y" if res else "")
         y32 = i32.get("y")
@@ -163,20 +166,20 @@ def _run_case(H, gname, data):
     # ---- gate forward on a given m (`pre`): M only read
     p64 = forward_ref(torch.float64, "M", True)
     p32 = forward_ref(torch.float32, "M", True) if other else {}
-    Mio, xpre, s0, hh = M.clone(), E(n, H), E(n, H), E(n, H)
+    Mio, xpre, s0, hh = G(M), E(n, H), E(n, H), E(n, H)
     e_part, n_part = slab_buffers()
-    assert lib.alignn_egc_gate_fwd_pre(ptr(P), pin(Mio), *seg, n, m, H, ptr(xpre), ptr(s0), ptr(hh), ptr(e_part), ptr(n_part), st) == 0
+    assert lib.alignn_egc_gate_fwd_pre(gptr(P), pin(Mio), *seg, n, m, H, gptr(xpre), gptr(s0), gptr(hh), gptr(e_part), gptr(n_part), st) == 0
     torch.cuda.synchronize()
     assert torch.equal(Mio, M)
     node_side("gate_fwd_pre", p64, p32, xpre, s0, hh, n_part)
     edge_side("gate_fwd_pre", p64, e_part)
     # (what the later passes are handed: the float64 statistics and node sums, rounded once)
-    e_stat = p64["e_stat"].float().contiguous()
+    e_stat = G(p64["e_stat"].float())
     for res in (False, True):
         xpre, s0, hh, yout, am = E(n, H), E(n, H), E(n, H), EM(), Z(1)
         _, n_part = slab_buffers()
-        assert lib.alignn_egc_gate_fwd_pre_norm(ptr(P), pin(M), *seg, n, m, H, ptr(xpre), ptr(s0), ptr(hh), ptr(n_part), ptr(e_stat),
-                                                pin(Y) if res else None, ptr(yout), ptr(am), st) == 0
+        assert lib.alignn_egc_gate_fwd_pre_norm(gptr(P), pin(M), *seg, n, m, H, gptr(xpre), gptr(s0), gptr(hh), gptr(n_part), gptr(e_stat),
+                                                pin(Y) if res else None, gptr(yout), gptr(am), st) == 0
         torch.cuda.synchronize()
         ent = "gate_fwd_pre_norm" + (" +Y" if res else "")
         y32 = p32.get("y")
@@ -185,13 +188,14 @@ def _run_case(H, gname, data):
         rep.amax(ent, "y_amax", am[0], yout[:m])
 
     # ---- node quotient reverse; every seventh row of S0 is zero (the epsilon alone in the denominator)
-    s0_in, hh_in = p64["s0"].float(), p64["hh"].float().contiguous()
+    s0_in, hh_in = p64["s0"].float(), G(p64["hh"].float())
     s0_in[::7] = 0.0
+    s0_in = G(s0_in)
     del p64, p32
     for wide in (False, True):  # ldg = 4H: the Ux block of a [n, 4H] buffer, as ops calls it
         gx = o["GXW"][:, 3 * H:] if wide else o["GX"]
         gs1, gs0 = E(n, H), E(n, H)
-        assert lib.alignn_egc_node_bwd(gx.data_ptr(), gx.stride(0), ptr(s0_in), ptr(hh_in), ptr(gs1), ptr(gs0), n, H, st) == 0
+        assert lib.alignn_egc_node_bwd(gptr(gx), gx.stride(0), gptr(s0_in), gptr(hh_in), gptr(gs1), gptr(gs0), n, H, st) == 0
         torch.cuda.synchronize()
         ent = "node_bwd" + (" ldg=4H" if wide else "")
         w64 = ref.node_reverse(gx.double(), s0_in.double(), hh_in.double())
@@ -212,14 +216,14 @@ def _run_case(H, gname, data):
             # BatchNorm parameter sums by the column-reduction pass; the gate reverse then takes the float64 ones rounded once
             rslabs = lib.alignn_col_stats_slabs(m)
             part, red = E(rslabs, 2, H), E(2, H)
-            assert lib.alignn_bn_silu_bwd_reduce(ptr(GY), H, ptr(M), H, ptr(stat_in), m, H, ptr(part), st) == 0
-            assert lib.alignn_bn_bwd_finalize(ptr(part), rslabs, H, ptr(red), st) == 0
+            assert lib.alignn_bn_silu_bwd_reduce(gptr(GY), H, gptr(M), H, gptr(stat_in), m, H, gptr(part), st) == 0
+            assert lib.alignn_bn_bwd_finalize(gptr(part), rslabs, H, gptr(red), st) == 0
             torch.cuda.synchronize()
             rep.close("bn_silu_bwd_reduce" + tag, "e_red", red, r64["e_red"], r32.get("e_red"), B_LN_PARAM)
         if mode == 1:
-            e_red = r64["e_red"].float().contiguous()
+            e_red = G(r64["e_red"].float())
         a_gy = pin(GY) if mode else None
-        a_stat = ptr(stat_in) if mode == 1 else None
+        a_stat = gptr(stat_in) if mode == 1 else None
 
         def reverse_asserts(ent, GM, GP, gb, gma, gpa, blocks):
             rep.close(ent, "GM", GM[:m], r64["GM"], r32.get("GM"), B_REVERSE, fl)
@@ -237,12 +241,12 @@ def _run_case(H, gname, data):
             rep.amax(ent, "gm_amax", gma[0], GM[:m])
 
         GM, GP, gb, gma, gpa = EM(), Z(n, 4 * H), E(slabs, H), Z(1), Z(1)
-        assert lib.alignn_egc_bwd_dst(a_gy, pin(M), ptr(P), ptr(Q1), ptr(Q0), a_stat, ptr(eg), ptr(e_red), e_eval, m, *seg, n, H, ptr(GM),
-                                      ptr(GP), ptr(gb), ptr(gma), ptr(gpa), st) == 0
+        assert lib.alignn_egc_bwd_dst(a_gy, pin(M), gptr(P), gptr(Q1), gptr(Q0), a_stat, gptr(eg), gptr(e_red), e_eval, m, *seg, n, H, gptr(GM),
+                                      gptr(GP), gptr(gb), gptr(gma), gptr(gpa), st) == 0
         torch.cuda.synchronize()
         reverse_asserts("bwd_dst" + tag, GM, GP, gb, gma, gpa, 1)
         bd, gpa = GP[:, H:2 * H].clone(), Z(1)
-        assert lib.alignn_egc_bwd_src(ptr(GM), pin(M), ptr(Q1), ptr(g.out_ptr), ptr(g.out_slot), ptr(g.dst), n, H, ptr(GP), ptr(gpa), st) == 0
+        assert lib.alignn_egc_bwd_src(gptr(GM), pin(M), gptr(Q1), gptr(g.out_ptr), gptr(g.out_slot), gptr(g.dst), n, H, gptr(GP), gptr(gpa), st) == 0
         torch.cuda.synchronize()
         ent = "bwd_dst+bwd_src" + tag
         rep.close(ent, "GP", GP[:, :3 * H], r64["GP"], r32.get("GP"), B_REVERSE, fl)
@@ -253,15 +257,15 @@ def _run_case(H, gname, data):
         if is_line_graph(g):
             groups = g.grp_seg_ptr.numel() - 1
             GM, GP, gb, gma, gpa = EM(), Z(n, 4 * H), E(groups, H), Z(1), Z(1)
-            assert lib.alignn_egc_bwd_lg_fused(a_gy, ptr(M), ptr(P), ptr(Q1), ptr(Q0), a_stat, ptr(e_red), e_eval, m, ptr(g.grp_seg_ptr),
-                                               ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.dst), ptr(g.out_ptr),
-                                               ptr(g.out_slot), H, ptr(GM), ptr(GP), ptr(gb), ptr(gma), ptr(gpa), st) == 0
+            assert lib.alignn_egc_bwd_lg_fused(a_gy, gptr(M), gptr(P), gptr(Q1), gptr(Q0), a_stat, gptr(e_red), e_eval, m, gptr(g.grp_seg_ptr),
+                                               gptr(g.grp_src_ptr), groups, gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.dst), gptr(g.out_ptr),
+                                               gptr(g.out_slot), H, gptr(GM), gptr(GP), gptr(gb), gptr(gma), gptr(gpa), st) == 0
             torch.cuda.synchronize()
             reverse_asserts("bwd_lg_fused" + tag, GM, GP, gb, gma, gpa, 3)
             GM, GP, gb, gma, gpa = EM(), Z(n, 4 * H), E(groups, H), Z(1), Z(1)
-            assert lib.alignn_egc_bwd_lg_dense(a_gy, ptr(M), ptr(P), ptr(Q1), ptr(Q0), a_stat, ptr(e_red), e_eval, m, ptr(g.grp_seg_ptr),
-                                               ptr(g.grp_src_ptr), groups, g.dense_max_src, ptr(g.seg_ptr), ptr(g.seg_node), H, ptr(GM),
-                                               ptr(GP), ptr(gb), ptr(gma), ptr(gpa), st) == 0
+            assert lib.alignn_egc_bwd_lg_dense(a_gy, gptr(M), gptr(P), gptr(Q1), gptr(Q0), a_stat, gptr(e_red), e_eval, m, gptr(g.grp_seg_ptr),
+                                               gptr(g.grp_src_ptr), groups, g.dense_max_src, gptr(g.seg_ptr), gptr(g.seg_node), H, gptr(GM),
+                                               gptr(GP), gptr(gb), gptr(gma), gptr(gpa), st) == 0
             torch.cuda.synchronize()
             reverse_asserts("bwd_lg_dense" + tag, GM, GP, gb, gma, gpa, 3)
         del r64, r32
@@ -293,53 +297,55 @@ def test_entry_points_against_float64(H, gname, data):
 def test_unsupported_calls_are_refused(H):
     """hipErrorInvalidValue and no launch (every output buffer keeps its fill) at widths outside H % 4 == 0, 4 <= H <= 1024,
     from every entry point; at a supported width (64) from the calls that miss a required argument."""
-    lib = _lib.load()
-    g = graph("lg_small")
+    rep = Report(f"refusals H={H}", "conv-bn-parity")
+    lib = rep.launcher(_lib.load())
+    g = guard_graph(graph("lg_small"))
     n, m, W = g.n_nodes, g.n_edges, 1032
     groups = g.grp_seg_ptr.numel() - 1
     slabs = lib.alignn_egc_slabs(n)
     st = stream()
-    I = lambda *s: torch.randn(*s, device=DEV)  # noqa: E731, E741
-    P, M, Y, Q1, Q0, S0, stat, red = I(n, 4 * W), I(m, W), I(m, W), I(n, W), I(n, W), I(n, W).abs(), I(4, W), I(2, W)
+    I = lambda *s: guard_input(torch.randn(*s, device=DEV))  # noqa: E731, E741
+    P, M, Y, Q1, Q0, S0, stat, red = I(n, 4 * W), I(m, W), I(m, W), I(n, W), I(n, W), guard_input(I(n, W).abs()), I(4, W), I(2, W)
     m_before = M.clone()
-    outs = [torch.full(s, 7.0, device=DEV) for s in ((m, W), (n, 4 * W), (n, W), (n, W), (n, W), (max(slabs, groups) * (3 * W + 1),),
+    outs = [guarded(s, fill=7.0, row=W) for s in ((m, W), (n, 4 * W), (n, W), (n, W), (n, W), (max(slabs, groups) * (3 * W + 1),),
                                                        (slabs * (3 * W + 1),), (2,), (2,))]
     em, gp, na, nb, nc, part_a, part_b, am, am_b = outs
-    seg = (ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src))
-    lg = (ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr))
+    seg = (gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src))
+    lg = (gptr(g.grp_seg_ptr), gptr(g.grp_src_ptr))
 
     def fused(h, n_groups):
-        return lib.alignn_egc_bwd_lg_fused(ptr(Y), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(stat), ptr(red), 0, m, *lg, n_groups,
-                                           ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.dst), ptr(g.out_ptr), ptr(g.out_slot), h, ptr(em),
-                                           ptr(gp), ptr(part_a), ptr(am), ptr(am_b), st)
+        return lib.alignn_egc_bwd_lg_fused(gptr(Y), gptr(M), gptr(P), gptr(Q1), gptr(Q0), gptr(stat), gptr(red), 0, m, *lg, n_groups,
+                                           gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.dst), gptr(g.out_ptr), gptr(g.out_slot), h, gptr(em),
+                                           gptr(gp), gptr(part_a), gptr(am), gptr(am_b), st)
 
     def dense(h, n_groups, max_src):
-        return lib.alignn_egc_bwd_lg_dense(ptr(Y), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(stat), ptr(red), 0, m, *lg, n_groups, max_src,
-                                           ptr(g.seg_ptr), ptr(g.seg_node), h, ptr(em), ptr(gp), ptr(part_a), ptr(am), ptr(am_b), st)
+        return lib.alignn_egc_bwd_lg_dense(gptr(Y), gptr(M), gptr(P), gptr(Q1), gptr(Q0), gptr(stat), gptr(red), 0, m, *lg, n_groups, max_src,
+                                           gptr(g.seg_ptr), gptr(g.seg_node), h, gptr(em), gptr(gp), gptr(part_a), gptr(am), gptr(am_b), st)
 
     def pre_norm(h, e_stat, yout):
-        return lib.alignn_egc_gate_fwd_pre_norm(ptr(P), ptr(M), *seg, n, m, h, ptr(na), ptr(nb), ptr(nc), ptr(part_b), ptr(e_stat), ptr(Y),
-                                                ptr(yout), ptr(am), st)
+        return lib.alignn_egc_gate_fwd_pre_norm(gptr(P), gptr(M), *seg, n, m, h, gptr(na), gptr(nb), gptr(nc), gptr(part_b), gptr(e_stat), gptr(Y),
+                                                gptr(yout), gptr(am), st)
 
     def infer(h, e_stat, yout):
-        return lib.alignn_egc_gate_infer(ptr(P), ptr(M), *seg, n, m, h, ptr(na), ptr(e_stat), ptr(Y), ptr(yout), ptr(am), st)
+        return lib.alignn_egc_gate_infer(gptr(P), gptr(M), *seg, n, m, h, gptr(na), gptr(e_stat), gptr(Y), gptr(yout), gptr(am), st)
 
     if H == 64:
         rc = [fused(H, 0), dense(H, 0, g.dense_max_src), dense(H, groups, 0), pre_norm(H, None, em), pre_norm(H, stat, None),
               infer(H, None, em)]
     else:
         rc = [
-            lib.alignn_egc_gate_fwd(ptr(P), ptr(M), *seg, n, m, H, ptr(na), ptr(nb), ptr(nc), ptr(part_a), ptr(part_b), st),
-            lib.alignn_egc_gate_fwd_pre(ptr(P), ptr(M), *seg, n, m, H, ptr(na), ptr(nb), ptr(nc), ptr(part_a), ptr(part_b), st),
+            lib.alignn_egc_gate_fwd(gptr(P), gptr(M), *seg, n, m, H, gptr(na), gptr(nb), gptr(nc), gptr(part_a), gptr(part_b), st),
+            lib.alignn_egc_gate_fwd_pre(gptr(P), gptr(M), *seg, n, m, H, gptr(na), gptr(nb), gptr(nc), gptr(part_a), gptr(part_b), st),
             pre_norm(H, stat, em), infer(H, stat, em), infer(H, None, None),
-            lib.alignn_egc_node_bwd(ptr(Q1), W, ptr(S0), ptr(Q0), ptr(na), ptr(nb), n, H, st),
-            lib.alignn_egc_bwd_dst(ptr(Y), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(stat), None, ptr(red), 0, m, *seg, n, H, ptr(em), ptr(gp),
-                                   ptr(part_a), ptr(am), ptr(am_b), st),
-            lib.alignn_egc_bwd_dst(None, ptr(M), ptr(P), ptr(Q1), ptr(Q0), None, None, None, 0, m, *seg, n, H, ptr(em), ptr(gp),
-                                   ptr(part_a), ptr(am), ptr(am_b), st),
-            lib.alignn_egc_bwd_src(ptr(Y), ptr(M), ptr(Q1), ptr(g.out_ptr), ptr(g.out_slot), ptr(g.dst), n, H, ptr(gp), ptr(am), st),
+            lib.alignn_egc_node_bwd(gptr(Q1), W, gptr(S0), gptr(Q0), gptr(na), gptr(nb), n, H, st),
+            lib.alignn_egc_bwd_dst(gptr(Y), gptr(M), gptr(P), gptr(Q1), gptr(Q0), gptr(stat), None, gptr(red), 0, m, *seg, n, H, gptr(em), gptr(gp),
+                                   gptr(part_a), gptr(am), gptr(am_b), st),
+            lib.alignn_egc_bwd_dst(None, gptr(M), gptr(P), gptr(Q1), gptr(Q0), None, None, None, 0, m, *seg, n, H, gptr(em), gptr(gp),
+                                   gptr(part_a), gptr(am), gptr(am_b), st),
+            lib.alignn_egc_bwd_src(gptr(Y), gptr(M), gptr(Q1), gptr(g.out_ptr), gptr(g.out_slot), gptr(g.dst), n, H, gptr(gp), gptr(am), st),
             fused(H, groups), dense(H, groups, g.dense_max_src),
         ]
     torch.cuda.synchronize()
     assert rc == [INVALID] * len(rc), rc
     assert all(bool((t == 7.0).all()) for t in outs) and torch.equal(M, m_before)
+    rep.finish()  # (and nothing beside them either)

@@ -23,10 +23,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from alignn_amd import _lib  # noqa: E402
-from alignn_amd._lib import ptr, stream  # noqa: E402
+from alignn_amd._lib import stream  # noqa: E402
 from tests.dual_ref import _blocks, _duals, _values  # noqa: E402  (the restatements, any dtype)
 from tests.gate_parity import Report as _Report  # noqa: E402
 from tests.gate_parity import err as _err  # noqa: E402
+from tests.gate_parity import gptr, guard_graph, guard_input, guarded  # noqa: E402
 from tests.gate_parity import graph as _graph  # noqa: E402
 from tests.gate_parity import is_line_graph as _is_line_graph  # noqa: E402
 
@@ -105,14 +106,18 @@ def _reverse_ref(dt, g, o, H, dual):
 
 
 def _run_case(H, gname, data):
-    lib = _lib.load()
+    rep = _Report(f"H={H} {gname} {data}")
+    lib = rep.launcher(_lib.load())
+    # every buffer a launch is handed lies between guard bands (tests/gate_parity.Guards; rep.finish() checks them first), the
+    # graph's tables and the operands as guarded copies, and every pointer goes through gptr, which refuses any other tensor
     g, o = _operands(H, gname, data)
+    g, o = guard_graph(g), {k: guard_input(t, k) for k, t in o.items()}
     n, m = g.n_nodes, g.n_edges
     st = stream()
-    rep = _Report(f"H={H} {gname} {data}")
     other = data != "normal"
-    E = lambda *s: torch.empty(*s, device=DEV)  # noqa: E731
-    Z = lambda *s: torch.zeros(*s, device=DEV)  # noqa: E731
+    E = lambda *s: guarded(s, row=H)  # noqa: E731  (an output: a NaN in whatever is not written)
+    Z = lambda *s: guarded(s, fill=0.0, row=H)  # noqa: E731
+    G = lambda t: guard_input(t.contiguous())  # noqa: E731  (a tensor made here, handed to a launch)
     P, Pt, M, gamma, beta = o["P"], o["Pt"], o["M"], o["gamma"], o["beta"]
 
     # ---- forward values and tangents
@@ -121,9 +126,9 @@ def _run_case(H, gname, data):
     f32 = lambda k: r32.get(k)  # noqa: E731
     for res in (False, True):
         xpre, s0, hh, yout, stat, am = E(n, H), E(n, H), E(n, H), E(m, H), E(m, 2), Z(1)
-        assert lib.alignn_egc_gate_fwd_pre_ln(ptr(P), ptr(M), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H, ptr(xpre), ptr(s0),
-                                              ptr(hh), ptr(gamma), ptr(beta), EPS, ptr(o["Y"]) if res else None, ptr(yout), ptr(stat),
-                                              ptr(am), st) == 0
+        assert lib.alignn_egc_gate_fwd_pre_ln(gptr(P), gptr(M), gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src), n, m, H, gptr(xpre), gptr(s0),
+                                              gptr(hh), gptr(gamma), gptr(beta), EPS, gptr(o["Y"]) if res else None, gptr(yout), gptr(stat),
+                                              gptr(am), st) == 0
         torch.cuda.synchronize()
         ent = "gate_fwd_pre_ln" + (" +Y" if res else "")
         k = "y_res" if res else "y"
@@ -135,13 +140,13 @@ def _run_case(H, gname, data):
         rep.close(ent, "HH", hh, r64["hh"], f32("hh"), B_GATE_FWD)
         rep.amax(ent, "y_amax", am[0], yout)
     # (what the later passes are handed: the float64 statistics and node sums, rounded once)
-    e_stat = torch.stack([r64["mean"], r64["rstd"]], 1).float().contiguous()
-    s0_in, hh_in = r64["s0"].float().contiguous(), r64["hh"].float().contiguous()
+    e_stat = G(torch.stack([r64["mean"], r64["rstd"]], 1).float())
+    s0_in, hh_in = G(r64["s0"].float()), G(r64["hh"].float())
     for res in (False, True):
-        mt, xpre_t, s0t, hht, yt, am2 = o["Ct"].clone(), E(n, H), E(n, H), E(n, H), E(m, H), Z(2)
-        assert lib.alignn_egc_gate_dual_tan_ln(ptr(P), ptr(Pt), ptr(M), ptr(mt), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H,
-                                               ptr(xpre_t), ptr(s0_in), ptr(hh_in), ptr(s0t), ptr(hht), ptr(gamma), ptr(beta), ptr(e_stat),
-                                               ptr(o["Rt"]) if res else None, ptr(yt), ptr(am2), st) == 0
+        mt, xpre_t, s0t, hht, yt, am2 = G(o["Ct"]), E(n, H), E(n, H), E(n, H), E(m, H), Z(2)
+        assert lib.alignn_egc_gate_dual_tan_ln(gptr(P), gptr(Pt), gptr(M), gptr(mt), gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src), n, m, H,
+                                               gptr(xpre_t), gptr(s0_in), gptr(hh_in), gptr(s0t), gptr(hht), gptr(gamma), gptr(beta), gptr(e_stat),
+                                               gptr(o["Rt"]) if res else None, gptr(yt), gptr(am2), st) == 0
         torch.cuda.synchronize()
         ent = "gate_dual_tan_ln" + (" +Rt" if res else "")
         k = "yt_res" if res else "yt"
@@ -177,31 +182,31 @@ def _run_case(H, gname, data):
     # destination-ordered halves (any CSR), then the unchanged source-ordered halves
     slabs = lib.alignn_egc_ln_dst_slabs(n)
     GM, GP, gb, lnp, red, gma, gpa = E(m, H), Z(n, 4 * H), E(slabs, H), E(slabs, 2, H), E(2, H), Z(1), Z(1)
-    assert lib.alignn_egc_bwd_dst_ln(ptr(GY), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(gamma), ptr(beta), ptr(e_stat), ptr(g.seg_ptr),
-                                     ptr(g.seg_node), ptr(g.src), n, H, ptr(GM), ptr(GP), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
-    assert lib.alignn_bn_bwd_finalize(ptr(lnp), slabs, H, ptr(red), st) == 0
+    assert lib.alignn_egc_bwd_dst_ln(gptr(GY), gptr(M), gptr(P), gptr(Q1), gptr(Q0), gptr(gamma), gptr(beta), gptr(e_stat), gptr(g.seg_ptr),
+                                     gptr(g.seg_node), gptr(g.src), n, H, gptr(GM), gptr(GP), gptr(gb), gptr(lnp), gptr(gma), gptr(gpa), st) == 0
+    assert lib.alignn_bn_bwd_finalize(gptr(lnp), slabs, H, gptr(red), st) == 0
     torch.cuda.synchronize()
     assert float(GP[:, :H].abs().max()) == 0.0 and float(GP[:, 2 * H:].abs().max()) == 0.0  # (this half writes the Bd block only)
     reverse_asserts("bwd_dst_ln", v64, v32, GM, GP[:, H:2 * H], gb, red, "GP_bd")
     rep.amax("bwd_dst_ln", "gm_amax", gma[0], GM)
     rep.amax("bwd_dst_ln", "gp_amax", gpa[0], GP[:, H:2 * H])
-    assert lib.alignn_egc_bwd_src(ptr(GM), ptr(M), ptr(Q1), ptr(g.out_ptr), ptr(g.out_slot), ptr(g.dst), n, H, ptr(GP), None, st) == 0
+    assert lib.alignn_egc_bwd_src(gptr(GM), gptr(M), gptr(Q1), gptr(g.out_ptr), gptr(g.out_slot), gptr(g.dst), n, H, gptr(GP), None, st) == 0
     torch.cuda.synchronize()
     fl = 1e-2 * float(v64["GP"].abs().max())
     rep.close("bwd_dst_ln + bwd_src", "GP", GP[:, :3 * H], v64["GP"], v32.get("GP"), B_REVERSE, fl)
 
     GM, GMt, GP, GPt, gma, gpa = E(m, H), E(m, H), Z(n, 4 * H), Z(n, 4 * H), Z(2), Z(2)
-    assert lib.alignn_egc_dual_bwd_dst_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(Q1), ptr(Q0), ptr(Q1t), ptr(Q0t),
-                                          ptr(gamma), ptr(beta), ptr(e_stat), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, H, ptr(GM),
-                                          ptr(GMt), ptr(GP), ptr(GPt), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
-    assert lib.alignn_bn_bwd_finalize(ptr(lnp), slabs, H, ptr(red), st) == 0
+    assert lib.alignn_egc_dual_bwd_dst_ln(gptr(GY), gptr(GYt), gptr(M), gptr(Mt), gptr(P), gptr(Pt), gptr(Q1), gptr(Q0), gptr(Q1t), gptr(Q0t),
+                                          gptr(gamma), gptr(beta), gptr(e_stat), gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src), n, H, gptr(GM),
+                                          gptr(GMt), gptr(GP), gptr(GPt), gptr(gb), gptr(lnp), gptr(gma), gptr(gpa), st) == 0
+    assert lib.alignn_bn_bwd_finalize(gptr(lnp), slabs, H, gptr(red), st) == 0
     torch.cuda.synchronize()
     reverse_asserts("dual_bwd_dst_ln", d64, d32, GM, GP[:, H:2 * H], gb, red, "GP_bd", GMt, GPt[:, H:2 * H])
     for w, (a, b) in enumerate(((GM, GP), (GMt, GPt))):
         rep.amax("dual_bwd_dst_ln", f"gm_amax2[{w}]", gma[w], a)
         rep.amax("dual_bwd_dst_ln", f"gp_amax2[{w}]", gpa[w], b[:, H:2 * H])
-    assert lib.alignn_egc_dual_bwd_src(ptr(GM), ptr(GMt), ptr(M), ptr(Mt), ptr(Q1), ptr(Q1t), ptr(g.out_ptr), ptr(g.out_slot), ptr(g.dst),
-                                       n, H, ptr(GP), ptr(GPt), None, st) == 0
+    assert lib.alignn_egc_dual_bwd_src(gptr(GM), gptr(GMt), gptr(M), gptr(Mt), gptr(Q1), gptr(Q1t), gptr(g.out_ptr), gptr(g.out_slot), gptr(g.dst),
+                                       n, H, gptr(GP), gptr(GPt), None, st) == 0
     torch.cuda.synchronize()
     rep.close("dual_bwd_dst_ln + dual_bwd_src", "GP", GP[:, :3 * H], d64["GP"], d32.get("GP"), B_REVERSE, fl)
     rep.close("dual_bwd_dst_ln + dual_bwd_src", "GPt", GPt[:, :3 * H], d64["GPt"], d32.get("GPt"), B_REVERSE,
@@ -211,10 +216,10 @@ def _run_case(H, gname, data):
     if _is_line_graph(g):
         groups = g.grp_seg_ptr.numel() - 1
         GM, GP, gb, lnp, gma, gpa = E(m, H), Z(n, 4 * H), E(groups, H), E(groups, 2, H), Z(1), Z(1)
-        assert lib.alignn_egc_bwd_lg_dense_ln(ptr(GY), ptr(M), ptr(P), ptr(Q1), ptr(Q0), ptr(gamma), ptr(beta), ptr(e_stat), m,
-                                              ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, g.dense_max_src, ptr(g.seg_ptr),
-                                              ptr(g.seg_node), H, ptr(GM), ptr(GP), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
-        assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
+        assert lib.alignn_egc_bwd_lg_dense_ln(gptr(GY), gptr(M), gptr(P), gptr(Q1), gptr(Q0), gptr(gamma), gptr(beta), gptr(e_stat), m,
+                                              gptr(g.grp_seg_ptr), gptr(g.grp_src_ptr), groups, g.dense_max_src, gptr(g.seg_ptr),
+                                              gptr(g.seg_node), H, gptr(GM), gptr(GP), gptr(gb), gptr(lnp), gptr(gma), gptr(gpa), st) == 0
+        assert lib.alignn_bn_bwd_finalize(gptr(lnp), groups, H, gptr(red), st) == 0
         torch.cuda.synchronize()
         ent = "bwd_lg_dense_ln"
         reverse_asserts(ent, v64, v32, GM, GP[:, :3 * H], gb, red, "GP")
@@ -222,11 +227,11 @@ def _run_case(H, gname, data):
         rep.amax(ent, "gm_amax", gma[0], GM)
         rep.amax(ent, "gp_amax", gpa[0], GP)
         GM, GMt, GP, GPt, gma, gpa = E(m, H), E(m, H), Z(n, 4 * H), Z(n, 4 * H), Z(2), Z(2)
-        assert lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(GY), ptr(GYt), ptr(M), ptr(Mt), ptr(P), ptr(Pt), ptr(Q1), ptr(Q0), ptr(Q1t),
-                                                   ptr(Q0t), ptr(gamma), ptr(beta), ptr(e_stat), m, ptr(g.grp_seg_ptr),
-                                                   ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr), ptr(g.seg_node), H, ptr(GM), ptr(GMt),
-                                                   ptr(GP), ptr(GPt), ptr(gb), ptr(lnp), ptr(gma), ptr(gpa), st) == 0
-        assert lib.alignn_bn_bwd_finalize(ptr(lnp), groups, H, ptr(red), st) == 0
+        assert lib.alignn_egc_dual_bwd_lg_dense_ln(gptr(GY), gptr(GYt), gptr(M), gptr(Mt), gptr(P), gptr(Pt), gptr(Q1), gptr(Q0), gptr(Q1t),
+                                                   gptr(Q0t), gptr(gamma), gptr(beta), gptr(e_stat), m, gptr(g.grp_seg_ptr),
+                                                   gptr(g.grp_src_ptr), groups, gptr(g.seg_ptr), gptr(g.seg_node), H, gptr(GM), gptr(GMt),
+                                                   gptr(GP), gptr(GPt), gptr(gb), gptr(lnp), gptr(gma), gptr(gpa), st) == 0
+        assert lib.alignn_bn_bwd_finalize(gptr(lnp), groups, H, gptr(red), st) == 0
         torch.cuda.synchronize()
         ent = "dual_bwd_lg_dense_ln"
         reverse_asserts(ent, d64, d32, GM, GP[:, :3 * H], gb, red, "GP", GMt, GPt[:, :3 * H])
@@ -272,39 +277,41 @@ def test_the_restatements_are_consistent(H, gname):
 @pytest.mark.parametrize("H", [0, 2, 6, 260])
 def test_unsupported_widths_are_refused(H):
     """hipErrorInvalidValue and no launch (every output buffer keeps its fill) at widths outside H % 4 == 0, 4 <= H <= 256."""
-    lib = _lib.load()
-    g = _graph("lg_small")
+    rep = _Report(f"refusals H={H}")
+    lib = rep.launcher(_lib.load())
+    g = guard_graph(_graph("lg_small"))
     n, m, W = g.n_nodes, g.n_edges, 264
     groups = g.grp_seg_ptr.numel() - 1
     st = stream()
-    I = lambda *s: torch.randn(*s, device=DEV)  # noqa: E731, E741
+    I = lambda *s: guard_input(torch.randn(*s, device=DEV))  # noqa: E731, E741
     P, Pt, M, Mt, Y = I(n, 4 * W), I(n, 4 * W), I(m, W), I(m, W), I(m, W)
     q = [I(n, W) for _ in range(4)]
     gamma, beta, e_stat = I(W), I(W), I(m, 2)
     mt_before = Mt.clone()
-    outs = [torch.full(s, 7.0, device=DEV) for s in ((m, W), (m, W), (n, 4 * W), (n, 4 * W), (n, W), (n, W), (n, W), (1024, W),
+    outs = [guarded(s, fill=7.0, row=W) for s in ((m, W), (m, W), (n, 4 * W), (n, 4 * W), (n, W), (n, W), (n, W), (1024, W),
                                                        (1024, 2, W), (m, 2), (2,), (2,))]
     em, emt, gp, gpt, na, nb, nc, gb, lnp, stat, am, am_b = outs
     rc = [
-        lib.alignn_egc_gate_fwd_pre_ln(ptr(P), ptr(M), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H, ptr(na), ptr(nb), ptr(nc),
-                                       ptr(gamma), ptr(beta), EPS, ptr(Y), ptr(em), ptr(stat), ptr(am), st),
-        lib.alignn_egc_gate_dual_tan_ln(ptr(P), ptr(Pt), ptr(M), ptr(Mt), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, m, H, ptr(na),
-                                        ptr(q[0]), ptr(q[1]), ptr(nb), ptr(nc), ptr(gamma), ptr(beta), ptr(e_stat), ptr(Y), ptr(em),
-                                        ptr(am), st),
-        lib.alignn_egc_bwd_lg_dense_ln(ptr(Y), ptr(M), ptr(P), ptr(q[0]), ptr(q[1]), ptr(gamma), ptr(beta), ptr(e_stat), m,
-                                       ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, g.dense_max_src, ptr(g.seg_ptr), ptr(g.seg_node), H,
-                                       ptr(em), ptr(gp), ptr(gb), ptr(lnp), ptr(am), ptr(am_b), st),
-        lib.alignn_egc_dual_bwd_lg_dense_ln(ptr(Y), ptr(Y), ptr(M), ptr(Mt), ptr(P), ptr(Pt), *(ptr(t) for t in q), ptr(gamma),
-                                            ptr(beta), ptr(e_stat), m, ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr),
-                                            ptr(g.seg_node), H, ptr(em), ptr(emt), ptr(gp), ptr(gpt), ptr(gb), ptr(lnp), ptr(am),
-                                            ptr(am_b), st),
-        lib.alignn_egc_bwd_dst_ln(ptr(Y), ptr(M), ptr(P), ptr(q[0]), ptr(q[1]), ptr(gamma), ptr(beta), ptr(e_stat), ptr(g.seg_ptr),
-                                  ptr(g.seg_node), ptr(g.src), n, H, ptr(em), ptr(gp), ptr(gb), ptr(lnp), ptr(am), ptr(am_b), st),
-        lib.alignn_egc_dual_bwd_dst_ln(ptr(Y), ptr(Y), ptr(M), ptr(Mt), ptr(P), ptr(Pt), *(ptr(t) for t in q), ptr(gamma), ptr(beta),
-                                       ptr(e_stat), ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src), n, H, ptr(em), ptr(emt), ptr(gp),
-                                       ptr(gpt), ptr(gb), ptr(lnp), ptr(am), ptr(am_b), st),
+        lib.alignn_egc_gate_fwd_pre_ln(gptr(P), gptr(M), gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src), n, m, H, gptr(na), gptr(nb), gptr(nc),
+                                       gptr(gamma), gptr(beta), EPS, gptr(Y), gptr(em), gptr(stat), gptr(am), st),
+        lib.alignn_egc_gate_dual_tan_ln(gptr(P), gptr(Pt), gptr(M), gptr(Mt), gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src), n, m, H, gptr(na),
+                                        gptr(q[0]), gptr(q[1]), gptr(nb), gptr(nc), gptr(gamma), gptr(beta), gptr(e_stat), gptr(Y), gptr(em),
+                                        gptr(am), st),
+        lib.alignn_egc_bwd_lg_dense_ln(gptr(Y), gptr(M), gptr(P), gptr(q[0]), gptr(q[1]), gptr(gamma), gptr(beta), gptr(e_stat), m,
+                                       gptr(g.grp_seg_ptr), gptr(g.grp_src_ptr), groups, g.dense_max_src, gptr(g.seg_ptr), gptr(g.seg_node), H,
+                                       gptr(em), gptr(gp), gptr(gb), gptr(lnp), gptr(am), gptr(am_b), st),
+        lib.alignn_egc_dual_bwd_lg_dense_ln(gptr(Y), gptr(Y), gptr(M), gptr(Mt), gptr(P), gptr(Pt), *(gptr(t) for t in q), gptr(gamma),
+                                            gptr(beta), gptr(e_stat), m, gptr(g.grp_seg_ptr), gptr(g.grp_src_ptr), groups, gptr(g.seg_ptr),
+                                            gptr(g.seg_node), H, gptr(em), gptr(emt), gptr(gp), gptr(gpt), gptr(gb), gptr(lnp), gptr(am),
+                                            gptr(am_b), st),
+        lib.alignn_egc_bwd_dst_ln(gptr(Y), gptr(M), gptr(P), gptr(q[0]), gptr(q[1]), gptr(gamma), gptr(beta), gptr(e_stat), gptr(g.seg_ptr),
+                                  gptr(g.seg_node), gptr(g.src), n, H, gptr(em), gptr(gp), gptr(gb), gptr(lnp), gptr(am), gptr(am_b), st),
+        lib.alignn_egc_dual_bwd_dst_ln(gptr(Y), gptr(Y), gptr(M), gptr(Mt), gptr(P), gptr(Pt), *(gptr(t) for t in q), gptr(gamma), gptr(beta),
+                                       gptr(e_stat), gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src), n, H, gptr(em), gptr(emt), gptr(gp),
+                                       gptr(gpt), gptr(gb), gptr(lnp), gptr(am), gptr(am_b), st),
     ]
     torch.cuda.synchronize()
     assert rc == [INVALID] * 6, rc
     assert all(bool((t == 7.0).all()) for t in outs) and torch.equal(Mt, mt_before)
     assert lib.alignn_egc_ln_fused_supported(H, 1 << 30) == 0 and lib.alignn_egc_ln_dst_supported(H) == 0
+    rep.finish()  # (and nothing beside the outputs either)

@@ -24,9 +24,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from alignn_amd import _lib  # noqa: E402
-from alignn_amd._lib import ptr, stream  # noqa: E402
+from alignn_amd._lib import stream  # noqa: E402
 from tests import dual_ref as D  # noqa: E402
-from tests.gate_parity import Report, graph, is_line_graph  # noqa: E402
+from tests.gate_parity import Report, gptr, graph, guard_graph, guard_input, guarded, is_line_graph  # noqa: E402
 
 DEV = "cuda"
 INVALID = 1  # hipErrorInvalidValue
@@ -36,12 +36,22 @@ B_LN_FWD, B_GATE_FWD, B_LN_PARAM, B_LN_INPUT, B_REVERSE = 2e-6, 2e-5, 2e-5, 2e-5
 F64, F32 = torch.float64, torch.float32
 
 
+# Every buffer a launch is handed lies between guard bands (tests/gate_parity.Guards; Report.finish checks them first) - the
+# graph's tables and the operands as guarded copies (``_G``) - and every pointer goes through gptr, which refuses any other tensor.
 def _full(*s):
-    return torch.full(s, FILL, device=DEV)
+    return guarded(s, fill=FILL)
 
 
 def _zeros(*s):
-    return torch.zeros(*s, device=DEV)
+    return guarded(s, fill=0.0)
+
+
+def _G(t, name="?"):
+    return guard_input(t.contiguous(), name)
+
+
+def _guard_all(o):
+    return {k: _G(t, k) for k, t in o.items()}
 
 
 def _strided(t, ld):
@@ -59,7 +69,7 @@ def _same_bits(rep, entry, name, got, other, what):
 
 def _finalize(lib, partial, slabs, Fw):
     red = _full(2, Fw)
-    assert lib.alignn_bn_bwd_finalize(ptr(partial), slabs, Fw, ptr(red), stream()) == 0
+    assert lib.alignn_bn_bwd_finalize(gptr(partial), slabs, Fw, gptr(red), stream()) == 0
     return red
 
 
@@ -73,11 +83,11 @@ def test_layernorm_row_kernels_against_float64(rows, Fw, data):
     operands of leading dimension F + 8; the node variant writes the last column block of a [rows, 4F] buffer.  Up to one row per
     wave (rows <= 5) and two or three (4097, 9001: the grid is capped at 1024 workgroups of 4 waves, the dbeta / dgamma registers
     and the slab write then accumulate over a wave's rows)."""
-    lib = _lib.load()
-    st = stream()
-    o = D.row_operands(rows, Fw, data, DEV)
-    other = data != "normal"
     rep = Report(f"rows={rows} F={Fw} {data}", "dual-f64")
+    lib = rep.launcher(_lib.load())
+    st = stream()
+    o = _guard_all(D.row_operands(rows, Fw, data, DEV))
+    other = data != "normal"
     slabs = lib.alignn_dual_slabs(rows)
     assert slabs == min((rows + 3) // 4, 1024)
     ref = {}
@@ -90,9 +100,9 @@ def test_layernorm_row_kernels_against_float64(rows, Fw, data):
             X, Xt, R, Rt = (_strided(o[k], ld) for k in ("X", "Xt", "R", "Rt"))
             for have_y in (True, False):
                 Y, Yt, stat, am = _full(rows, ld), _full(rows, ld), _full(rows, 2), _zeros(2)
-                assert lib.alignn_ln_silu_dual_fwd(ptr(X), ptr(Xt), ld, ptr(R) if res else None, ptr(Rt) if res else None, ld,
-                                                   ptr(o["gamma"]), ptr(o["beta"]), D.EPS, ptr(Y) if have_y else None, ptr(Yt), ld,
-                                                   ptr(stat), rows, Fw, ptr(am), st) == 0
+                assert lib.alignn_ln_silu_dual_fwd(gptr(X), gptr(Xt), ld, gptr(R) if res else None, gptr(Rt) if res else None, ld,
+                                                   gptr(o["gamma"]), gptr(o["beta"]), D.EPS, gptr(Y) if have_y else None, gptr(Yt), ld,
+                                                   gptr(stat), rows, Fw, gptr(am), st) == 0
                 torch.cuda.synchronize()
                 ent = "ln_silu_dual_fwd" + (" +R" if res else "") + ("" if have_y else " Y=NULL") + f" ld={ld}"
                 if have_y:
@@ -110,13 +120,13 @@ def test_layernorm_row_kernels_against_float64(rows, Fw, data):
     # ---- reverse (the residual does not enter); the statistics handed over are float64's, rounded once
     r64, r32 = ref[False]
     f32 = lambda k: None if r32 is None else r32[k]  # noqa: E731
-    stat = torch.stack([r64["mean"], r64["rstd"]], 1).float().contiguous()
+    stat = _G(torch.stack([r64["mean"], r64["rstd"]], 1).float())
     node_in = [o[k] for k in ("S0", "HH", "S0t", "HHt")]
     for ld in (Fw, Fw + 8):
         X, Xt, GY, GYt = (_strided(o[k], ld) for k in ("X", "Xt", "GY", "GYt"))
         GX, GXt, partial, am = _full(rows, ld), _full(rows, ld), _full(slabs, 2, Fw), _zeros(2)
-        assert lib.alignn_ln_silu_dual_bwd(ptr(GY), ptr(GYt), ld, ptr(X), ptr(Xt), ld, ptr(o["gamma"]), ptr(o["beta"]), ptr(stat),
-                                           ptr(GX), ptr(GXt), ld, ptr(partial), rows, Fw, ptr(am), st) == 0
+        assert lib.alignn_ln_silu_dual_bwd(gptr(GY), gptr(GYt), ld, gptr(X), gptr(Xt), ld, gptr(o["gamma"]), gptr(o["beta"]), gptr(stat),
+                                           gptr(GX), gptr(GXt), ld, gptr(partial), rows, Fw, gptr(am), st) == 0
         red = _finalize(lib, partial, slabs, Fw)
         torch.cuda.synchronize()
         ent = f"ln_silu_dual_bwd ld={ld}"
@@ -128,15 +138,15 @@ def test_layernorm_row_kernels_against_float64(rows, Fw, data):
         rep.amax(ent, "amax2[1]", am[1], GXt[:, :Fw])
         assert bool((GX[:, Fw:] == FILL).all()) and bool((GXt[:, Fw:] == FILL).all())
         # the node variant: (gx, gxt) into the Ux column block of [rows, 4F] buffers, Q1 .. Q0t beside them
-        GP, GPt, partial, am = _full(rows, 4 * Fw), _full(rows, 4 * Fw), _full(slabs, 2, Fw), torch.tensor([0.0, ABOVE], device=DEV)
+        GP, GPt, partial, am = _full(rows, 4 * Fw), _full(rows, 4 * Fw), _full(slabs, 2, Fw), _G(torch.tensor([0.0, ABOVE], device=DEV))
         ux, uxt = GP[:, 3 * Fw:], GPt[:, 3 * Fw:]
         q = [_full(rows, Fw) for _ in range(4)]
-        assert lib.alignn_ln_silu_dual_bwd_node(ptr(GY), ptr(GYt), ld, ptr(X), ptr(Xt), ld, ptr(o["gamma"]), ptr(o["beta"]), ptr(stat),
-                                                ptr(ux), ptr(uxt), 4 * Fw, ptr(partial), rows, Fw, ptr(am), *(ptr(t) for t in node_in),
-                                                *(ptr(t) for t in q), st) == 0
+        assert lib.alignn_ln_silu_dual_bwd_node(gptr(GY), gptr(GYt), ld, gptr(X), gptr(Xt), ld, gptr(o["gamma"]), gptr(o["beta"]), gptr(stat),
+                                                gptr(ux), gptr(uxt), 4 * Fw, gptr(partial), rows, Fw, gptr(am), *(gptr(t) for t in node_in),
+                                                *(gptr(t) for t in q), st) == 0
         red = _finalize(lib, partial, slabs, Fw)
         q_own = [_full(rows, Fw) for _ in range(4)]
-        assert lib.alignn_egc_node_dual_bwd(ptr(ux), ptr(uxt), 4 * Fw, *(ptr(t) for t in node_in), *(ptr(t) for t in q_own), rows, Fw,
+        assert lib.alignn_egc_node_dual_bwd(gptr(ux), gptr(uxt), 4 * Fw, *(gptr(t) for t in node_in), *(gptr(t) for t in q_own), rows, Fw,
                                             st) == 0
         torch.cuda.synchronize()
         ent = f"ln_silu_dual_bwd_node ld={ld}"
@@ -159,67 +169,70 @@ def test_layernorm_row_kernels_against_float64(rows, Fw, data):
 def test_layernorm_row_kernels_without_rows(Fw):
     """rows == 0: the forward returns 0 and touches nothing; both reverse entries return 0 and leave a zero slab, so that the
     finalised [2, F] is exactly 0 over a workspace that held 7.0."""
-    lib = _lib.load()
+    rep = Report(f"rows=0 F={Fw}", "dual-f64")
+    lib = rep.launcher(_lib.load())
     st = stream()
-    o = D.row_operands(4, Fw, "normal", DEV)
+    o = _guard_all(D.row_operands(4, Fw, "normal", DEV))
     stat = _full(4, 2)
     outs = [_full(4, Fw) for _ in range(8)]
     am = _zeros(2)
     assert lib.alignn_dual_slabs(0) == 1
-    assert lib.alignn_ln_silu_dual_fwd(ptr(o["X"]), ptr(o["Xt"]), Fw, ptr(o["R"]), ptr(o["Rt"]), Fw, ptr(o["gamma"]), ptr(o["beta"]), D.EPS,
-                                       ptr(outs[0]), ptr(outs[1]), Fw, ptr(stat), 0, Fw, ptr(am), st) == 0
+    assert lib.alignn_ln_silu_dual_fwd(gptr(o["X"]), gptr(o["Xt"]), Fw, gptr(o["R"]), gptr(o["Rt"]), Fw, gptr(o["gamma"]), gptr(o["beta"]), D.EPS,
+                                       gptr(outs[0]), gptr(outs[1]), Fw, gptr(stat), 0, Fw, gptr(am), st) == 0
     torch.cuda.synchronize()
     assert bool((stat == FILL).all()) and float(am.abs().max()) == 0.0
     for node in (False, True):
         partial = _full(4, 2, Fw)
         if node:
-            rc = lib.alignn_ln_silu_dual_bwd_node(ptr(o["GY"]), ptr(o["GYt"]), Fw, ptr(o["X"]), ptr(o["Xt"]), Fw, ptr(o["gamma"]),
-                                                  ptr(o["beta"]), ptr(stat), ptr(outs[0]), ptr(outs[1]), Fw, ptr(partial), 0, Fw, ptr(am),
-                                                  *(ptr(o[k]) for k in ("S0", "HH", "S0t", "HHt")), *(ptr(t) for t in outs[2:6]), st)
+            rc = lib.alignn_ln_silu_dual_bwd_node(gptr(o["GY"]), gptr(o["GYt"]), Fw, gptr(o["X"]), gptr(o["Xt"]), Fw, gptr(o["gamma"]),
+                                                  gptr(o["beta"]), gptr(stat), gptr(outs[0]), gptr(outs[1]), Fw, gptr(partial), 0, Fw, gptr(am),
+                                                  *(gptr(o[k]) for k in ("S0", "HH", "S0t", "HHt")), *(gptr(t) for t in outs[2:6]), st)
         else:
-            rc = lib.alignn_ln_silu_dual_bwd(ptr(o["GY"]), ptr(o["GYt"]), Fw, ptr(o["X"]), ptr(o["Xt"]), Fw, ptr(o["gamma"]), ptr(o["beta"]),
-                                             ptr(stat), ptr(outs[0]), ptr(outs[1]), Fw, ptr(partial), 0, Fw, ptr(am), st)
+            rc = lib.alignn_ln_silu_dual_bwd(gptr(o["GY"]), gptr(o["GYt"]), Fw, gptr(o["X"]), gptr(o["Xt"]), Fw, gptr(o["gamma"]), gptr(o["beta"]),
+                                             gptr(stat), gptr(outs[0]), gptr(outs[1]), Fw, gptr(partial), 0, Fw, gptr(am), st)
         assert rc == 0
         red = _finalize(lib, partial, 1, Fw)
         torch.cuda.synchronize()
         assert float(red.abs().max()) == 0.0 and bool((partial[1:] == FILL).all())
         assert all(bool((t == FILL).all()) for t in outs) and float(am.abs().max()) == 0.0
+    rep.finish()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # gate kernels
 # ----------------------------------------------------------------------------------------------------------------------
 def _run_gate_case(H, gname, data, stream_rows=False):
-    lib = _lib.load()
+    rep = Report(f"H={H} {gname} {data}", "dual-f64")
+    lib = rep.launcher(_lib.load())
     st = stream()
     g = graph(gname)
+    o = _guard_all(D.operands(H, g, data, DEV))
+    g = guard_graph(g)
     n, m = g.n_nodes, g.n_edges
     u, v = g.src.long(), g.dst.long()
-    o = D.operands(H, g, data, DEV)
     other = data != "normal"
-    rep = Report(f"H={H} {gname} {data}", "dual-f64")
     r64 = D.gate_case(F64, o, u, v, n, H)
-    hd = r64["handed"]
+    hd = r64["handed"] = _guard_all(r64["handed"])
     r32 = D.gate_case(F32, o, u, v, n, H, hd) if other else {}
     f32 = lambda k: r32.get(k)  # noqa: E731
     P, Pt = o["P"], o["Pt"]
-    csr = (ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src))
+    csr = (gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src))
     parts = D.reverse_parts(data, n, v)
 
     # ---- forward: values and tangents from C, Ct
-    M, Mt = o["C"].clone(), o["Ct"].clone()
+    M, Mt = _G(o["C"]), _G(o["Ct"])
     xpre, xpre_t, s0, hh, s0t, hht = (_full(n, H) for _ in range(6))
-    assert lib.alignn_egc_gate_dual_fwd(ptr(P), ptr(Pt), ptr(M), ptr(Mt), *csr, n, m, H, ptr(xpre), ptr(xpre_t), ptr(s0), ptr(hh),
-                                        ptr(s0t), ptr(hht), st) == 0
+    assert lib.alignn_egc_gate_dual_fwd(gptr(P), gptr(Pt), gptr(M), gptr(Mt), *csr, n, m, H, gptr(xpre), gptr(xpre_t), gptr(s0), gptr(hh),
+                                        gptr(s0t), gptr(hht), st) == 0
     torch.cuda.synchronize()
     fwd = dict(m=M, mt=Mt, xpre=xpre, xpre_t=xpre_t, s0=s0, hh=hh, s0t=s0t, hht=hht)
     for k, t in fwd.items():
         rep.close("gate_dual_fwd", k, t, r64[k], f32(k), B_LN_FWD if k in ("m", "mt") else B_GATE_FWD)
     # the tangent half alone, handed the values the full pass wrote: the same bits, and M untouched
-    M_before, Mt2 = M.clone(), o["Ct"].clone()
+    M_before, Mt2 = M.clone(), _G(o["Ct"])
     xpre_t2, s0t2, hht2 = (_full(n, H) for _ in range(3))
-    assert lib.alignn_egc_gate_dual_fwd_tangent(ptr(P), ptr(Pt), ptr(M), ptr(Mt2), *csr, n, m, H, ptr(xpre_t2), ptr(s0), ptr(hh), ptr(s0t2),
-                                                ptr(hht2), st) == 0
+    assert lib.alignn_egc_gate_dual_fwd_tangent(gptr(P), gptr(Pt), gptr(M), gptr(Mt2), *csr, n, m, H, gptr(xpre_t2), gptr(s0), gptr(hh), gptr(s0t2),
+                                                gptr(hht2), st) == 0
     torch.cuda.synchronize()
     assert torch.equal(M, M_before), "alignn_egc_gate_dual_fwd_tangent wrote to M"
     for k, t in (("mt", Mt2), ("xpre_t", xpre_t2), ("s0t", s0t2), ("hht", hht2)):
@@ -233,13 +246,13 @@ def _run_gate_case(H, gname, data, stream_rows=False):
     partial, gp_amax = _full(slabs, 2, H), _zeros(2)
     node_in = [hd[k] for k in ("s0", "hh", "s0t", "hht")]
     q = [_full(n, H) for _ in range(4)]
-    assert lib.alignn_ln_silu_dual_bwd_node(ptr(o["GX"]), ptr(o["GXt"]), H, ptr(hd["xpre"]), ptr(hd["xpre_t"]), H, ptr(o["n_gamma"]),
-                                            ptr(o["n_beta"]), ptr(hd["n_stat"]), ptr(ux), ptr(uxt), 4 * H, ptr(partial), n, H, ptr(gp_amax),
-                                            *(ptr(t) for t in node_in), *(ptr(t) for t in q), st) == 0
+    assert lib.alignn_ln_silu_dual_bwd_node(gptr(o["GX"]), gptr(o["GXt"]), H, gptr(hd["xpre"]), gptr(hd["xpre_t"]), H, gptr(o["n_gamma"]),
+                                            gptr(o["n_beta"]), gptr(hd["n_stat"]), gptr(ux), gptr(uxt), 4 * H, gptr(partial), n, H, gptr(gp_amax),
+                                            *(gptr(t) for t in node_in), *(gptr(t) for t in q), st) == 0
     red = _finalize(lib, partial, slabs, H)
     q_own, q_handed = [_full(n, H) for _ in range(4)], [_full(n, H) for _ in range(4)]
-    assert lib.alignn_egc_node_dual_bwd(ptr(ux), ptr(uxt), 4 * H, *(ptr(t) for t in node_in), *(ptr(t) for t in q_own), n, H, st) == 0
-    assert lib.alignn_egc_node_dual_bwd(ptr(hd["gx"]), ptr(hd["gxt"]), H, *(ptr(t) for t in node_in), *(ptr(t) for t in q_handed), n, H,
+    assert lib.alignn_egc_node_dual_bwd(gptr(ux), gptr(uxt), 4 * H, *(gptr(t) for t in node_in), *(gptr(t) for t in q_own), n, H, st) == 0
+    assert lib.alignn_egc_node_dual_bwd(gptr(hd["gx"]), gptr(hd["gxt"]), H, *(gptr(t) for t in node_in), *(gptr(t) for t in q_handed), n, H,
                                         st) == 0
     torch.cuda.synchronize()
     ent = "ln_silu_dual_bwd_node"
@@ -288,7 +301,7 @@ def _run_gate_case(H, gname, data, stream_rows=False):
     first = True
     for has_gl in (True, False):
         tag = "gl_" if has_gl else "nogl_"
-        gl, glt = (ptr(hd["GL"]), ptr(hd["GLt"])) if has_gl else (None, None)
+        gl, glt = (gptr(hd["GL"]), gptr(hd["GLt"])) if has_gl else (None, None)
         variant = " GL" if has_gl else " GL=NULL"
         # destination-ordered and source-ordered halves
         GP[:, :3 * H] = FILL
@@ -298,15 +311,15 @@ def _run_gate_case(H, gname, data, stream_rows=False):
         GM, GMt, gb, gm_amax, src_amax = _full(m, H), _full(m, H), _full(slabs, H), _zeros(2), _zeros(2)
         if not has_gl:
             gm_amax[1] = ABOVE
-        assert lib.alignn_egc_dual_bwd_dst(gl, glt, ptr(Mo), ptr(Mto), ptr(P), ptr(Pt), *(ptr(t) for t in qs), *csr, n, H, ptr(GM), ptr(GMt),
-                                           ptr(GP), ptr(GPt), ptr(gb), ptr(gm_amax), ptr(gp_amax), st) == 0
+        assert lib.alignn_egc_dual_bwd_dst(gl, glt, gptr(Mo), gptr(Mto), gptr(P), gptr(Pt), *(gptr(t) for t in qs), *csr, n, H, gptr(GM), gptr(GMt),
+                                           gptr(GP), gptr(GPt), gptr(gb), gptr(gm_amax), gptr(gp_amax), st) == 0
         torch.cuda.synchronize()
         assert bool((GP[:, :H] == FILL).all()) and bool((GP[:, 2 * H:3 * H] == FILL).all())  # (this half writes the Bd block only)
         if not first:
             for w, t in enumerate((GP, GPt)):
                 rep.amax("dual_bwd_dst" + variant, f"gp_amax2[{w}]", gp_amax[w], t[:, H:2 * H])
-        assert lib.alignn_egc_dual_bwd_src(ptr(GM), ptr(GMt), ptr(Mo), ptr(Mto), ptr(qs[0]), ptr(qs[2]), ptr(g.out_ptr), ptr(g.out_slot),
-                                           ptr(g.dst), n, H, ptr(GP), ptr(GPt), ptr(src_amax), st) == 0
+        assert lib.alignn_egc_dual_bwd_src(gptr(GM), gptr(GMt), gptr(Mo), gptr(Mto), gptr(qs[0]), gptr(qs[2]), gptr(g.out_ptr), gptr(g.out_slot),
+                                           gptr(g.dst), n, H, gptr(GP), gptr(GPt), gptr(src_amax), st) == 0
         torch.cuda.synchronize()
         for w, t in enumerate((GP, GPt)):
             rep.amax("dual_bwd_src" + variant, f"gp_amax2[{w}]", src_amax[w], torch.cat([t[:, :H], t[:, 2 * H:3 * H]], 1))
@@ -323,9 +336,9 @@ def _run_gate_case(H, gname, data, stream_rows=False):
                 GM, GMt, gb, gm_amax = _full(m, H), _full(m, H), _full(groups, H), _zeros(2)
                 if not has_gl:
                     gm_amax[1] = ABOVE
-                assert lib.alignn_egc_dual_bwd_lg_dense(gl, glt, ptr(Mo), ptr(Mto), ptr(P), ptr(Pt), *(ptr(t) for t in qs), m_rows,
-                                                        ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr), ptr(g.seg_node), H,
-                                                        ptr(GM), ptr(GMt), ptr(GP), ptr(GPt), ptr(gb), ptr(gm_amax), ptr(gp_amax), st) == 0
+                assert lib.alignn_egc_dual_bwd_lg_dense(gl, glt, gptr(Mo), gptr(Mto), gptr(P), gptr(Pt), *(gptr(t) for t in qs), m_rows,
+                                                        gptr(g.grp_seg_ptr), gptr(g.grp_src_ptr), groups, gptr(g.seg_ptr), gptr(g.seg_node), H,
+                                                        gptr(GM), gptr(GMt), gptr(GP), gptr(GPt), gptr(gb), gptr(gm_amax), gptr(gp_amax), st) == 0
                 torch.cuda.synchronize()
                 check("dual_bwd_lg_dense" + variant + ("" if m_rows == m else " m_rows=threshold"), tag, GM, GMt, gb, gm_amax, False,
                       preset=not has_gl)
@@ -351,27 +364,28 @@ def test_dense_kernel_streaming_instantiations_on_a_small_graph():
 def test_dense_kernel_on_a_line_graph_that_streams():
     """a real streaming launch: >= 128 MiB per [rows, 256] tensor.  The dense kernel only, with GL given, on N(0,1) operands and
     adjoints."""
-    lib = _lib.load()
+    rep = Report("H=256 lg_stream normal", "dual-f64")
+    lib = rep.launcher(_lib.load())
     st = stream()
     H, g = 256, graph("lg_stream")
     n, m = g.n_nodes, g.n_edges
     assert m * H * 4 >= 128 << 20
     u, v = g.src.long(), g.dst.long()
-    o = D.operands(H, g, "normal", DEV)
+    o = _guard_all(D.operands(H, g, "normal", DEV))
+    g = guard_graph(g)
     gen = torch.Generator(device=DEV).manual_seed(11)
-    o.update({k: torch.randn(n, H, device=DEV, generator=gen) for k in ("Q1", "Q0", "Q1t", "Q0t")})
+    o.update({k: _G(torch.randn(n, H, device=DEV, generator=gen), k) for k in ("Q1", "Q0", "Q1t", "Q0t")})
     rev = D.ln_reverse(F64, o["M"], o["Mt"], o["gamma"], o["beta"], o["GY"], o["GYt"])
-    GL, GLt = rev["gx"].float().contiguous(), rev["gxt"].float().contiguous()
+    GL, GLt = _G(rev["gx"].float(), "GL"), _G(rev["gxt"].float(), "GLt")
     del rev
     r64 = D.reverse(F64, o, u, v, n, H, True)
     groups = g.grp_seg_ptr.numel() - 1
     GM, GMt, GP, GPt, gb, gm_amax, gp_amax = _full(m, H), _full(m, H), _full(n, 4 * H), _full(n, 4 * H), _full(groups, H), _zeros(2), _zeros(2)
-    assert lib.alignn_egc_dual_bwd_lg_dense(ptr(GL), ptr(GLt), ptr(o["M"]), ptr(o["Mt"]), ptr(o["P"]), ptr(o["Pt"]),
-                                            *(ptr(o[k]) for k in ("Q1", "Q0", "Q1t", "Q0t")), m, ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr),
-                                            groups, ptr(g.seg_ptr), ptr(g.seg_node), H, ptr(GM), ptr(GMt), ptr(GP), ptr(GPt), ptr(gb),
-                                            ptr(gm_amax), ptr(gp_amax), st) == 0
+    assert lib.alignn_egc_dual_bwd_lg_dense(gptr(GL), gptr(GLt), gptr(o["M"]), gptr(o["Mt"]), gptr(o["P"]), gptr(o["Pt"]),
+                                            *(gptr(o[k]) for k in ("Q1", "Q0", "Q1t", "Q0t")), m, gptr(g.grp_seg_ptr), gptr(g.grp_src_ptr),
+                                            groups, gptr(g.seg_ptr), gptr(g.seg_node), H, gptr(GM), gptr(GMt), gptr(GP), gptr(GPt), gptr(gb),
+                                            gptr(gm_amax), gptr(gp_amax), st) == 0
     torch.cuda.synchronize()
-    rep = Report("H=256 lg_stream normal", "dual-f64")
     fl, flt = 1e-2 * float(r64["GP"].abs().max()), 1e-2 * float(r64["GPt"].abs().max())
     ent = "dual_bwd_lg_dense GL streaming"
     rep.close(ent, "GM", GM, r64["GM"], None, B_REVERSE, fl)
@@ -395,8 +409,8 @@ def _refusal_calls(lib, g, W, H, t, drop=None):
     ``drop``: an argument to pass as NULL"""
     n, m, st = g.n_nodes, g.n_edges, stream()
     groups = g.grp_seg_ptr.numel() - 1
-    p = lambda k: None if k == drop else ptr(t[k])  # noqa: E731
-    csr = (ptr(g.seg_ptr), ptr(g.seg_node), ptr(g.src))
+    p = lambda k: None if k == drop else gptr(t[k])  # noqa: E731
+    csr = (gptr(g.seg_ptr), gptr(g.seg_node), gptr(g.src))
     node_in = [p(k) for k in ("s0", "hh", "s0t", "hht")]
     q_out = [p(k) for k in ("o_q1", "o_q0", "o_q1t", "o_q0t")]
     q_in = [p(k) for k in ("s0", "hh", "s0t", "hht")]
@@ -415,20 +429,20 @@ def _refusal_calls(lib, g, W, H, t, drop=None):
         "node_dual_bwd": lambda: lib.alignn_egc_node_dual_bwd(p("hh"), p("hht"), W, *q_in, *q_out, n, H, st),
         "dual_bwd_dst": lambda: lib.alignn_egc_dual_bwd_dst(p("R"), p("Rt"), p("M"), p("Mt"), p("P"), p("Pt"), *q_in, *csr, n, H, p("o_em"),
                                                             p("o_emt"), p("o_gp"), p("o_gpt"), p("o_gb"), p("o_am"), p("o_am2"), st),
-        "dual_bwd_src": lambda: lib.alignn_egc_dual_bwd_src(p("R"), p("Rt"), p("M"), p("Mt"), p("s0"), p("hh"), ptr(g.out_ptr), ptr(g.out_slot),
-                                                            ptr(g.dst), n, H, p("o_gp"), p("o_gpt"), p("o_am2"), st),
+        "dual_bwd_src": lambda: lib.alignn_egc_dual_bwd_src(p("R"), p("Rt"), p("M"), p("Mt"), p("s0"), p("hh"), gptr(g.out_ptr), gptr(g.out_slot),
+                                                            gptr(g.dst), n, H, p("o_gp"), p("o_gpt"), p("o_am2"), st),
         "dual_bwd_lg_dense": lambda: lib.alignn_egc_dual_bwd_lg_dense(p("R"), p("Rt"), p("M"), p("Mt"), p("P"), p("Pt"), *q_in, m,
-                                                                      ptr(g.grp_seg_ptr), ptr(g.grp_src_ptr), groups, ptr(g.seg_ptr),
-                                                                      ptr(g.seg_node), H, p("o_em"), p("o_emt"), p("o_gp"), p("o_gpt"), p("o_gb"),
+                                                                      gptr(g.grp_seg_ptr), gptr(g.grp_src_ptr), groups, gptr(g.seg_ptr),
+                                                                      gptr(g.seg_node), H, p("o_em"), p("o_emt"), p("o_gp"), p("o_gpt"), p("o_gb"),
                                                                       p("o_am"), p("o_am2"), st),
     }
 
 
 def _refusal_buffers(g, W):
     n, m = g.n_nodes, g.n_edges
-    I = lambda *s: torch.randn(*s, device=DEV)  # noqa: E731, E741
+    I = lambda *s: _G(torch.randn(*s, device=DEV))  # noqa: E731, E741
     t = dict(P=I(n, 4 * W), Pt=I(n, 4 * W), M=I(m, W), Mt=I(m, W), R=I(m, W), Rt=I(m, W), gamma=I(W), beta=I(W), stat=I(max(n, m), 2),
-             s0=I(n, W).abs(), hh=I(n, W), s0t=I(n, W), hht=I(n, W))
+             s0=_G(torch.randn(n, W, device=DEV).abs()), hh=I(n, W), s0t=I(n, W), hht=I(n, W))
     t.update(o_em=_full(m, W), o_emt=_full(m, W), o_gp=_full(n, 4 * W), o_gpt=_full(n, 4 * W), o_gb=_full(1024, W), o_part=_full(1024, 2, W),
              o_stat=_full(m, 2), o_am=_full(2), o_am2=_full(2), o_q1=_full(n, W), o_q0=_full(n, W), o_q1t=_full(n, W), o_q0t=_full(n, W),
              o_n4=_full(n, W), o_n5=_full(n, W), o_gx=_full(n, W), o_gxt=_full(n, W))
@@ -443,20 +457,23 @@ def _unchanged(t, before):
 def test_unsupported_widths_are_refused(H):
     """hipErrorInvalidValue and no launch (every output keeps its fill, M and Mt their contents) at widths outside
     F % 4 == 0, 4 <= F <= 1024, from every entry point."""
-    g = graph("lg_small")
+    rep = Report(f"refusals H={H}", "dual-f64")
+    g = guard_graph(graph("lg_small"))
     t = _refusal_buffers(g, 1032)
     before = {k: t[k].clone() for k in ("M", "Mt")}
-    rc = {k: f() for k, f in _refusal_calls(_lib.load(), g, 1032, H, t).items()}
+    rc = {k: f() for k, f in _refusal_calls(rep.launcher(_lib.load()), g, 1032, H, t).items()}
     torch.cuda.synchronize()
     assert all(r == INVALID for r in rc.values()), rc
     assert _unchanged(t, before)
+    rep.finish()  # (and nothing beside the outputs either)
 
 
 def test_half_given_pairs_and_null_node_pointers_are_refused():
     """R without Rt (and Rt without R), GL without GLt (and the reverse) and any null node pointer of alignn_ln_silu_dual_bwd_node:
     hipErrorInvalidValue and no launch, at a supported width."""
-    lib = _lib.load()
-    g = graph("lg_small")
+    rep = Report("refusals of half-given pairs", "dual-f64")
+    lib = rep.launcher(_lib.load())
+    g = guard_graph(graph("lg_small"))
     W = H = 64
     t = _refusal_buffers(g, W)
     before = {k: t[k].clone() for k in ("M", "Mt")}
@@ -470,3 +487,4 @@ def test_half_given_pairs_and_null_node_pointers_are_refused():
         assert _refusal_calls(lib, g, W, H, t, drop)["ln_silu_dual_bwd_node"]() == INVALID, drop
         torch.cuda.synchronize()
         assert _unchanged(t, before)
+    rep.finish()  # (and nothing beside the outputs either)
