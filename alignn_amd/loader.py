@@ -180,9 +180,10 @@ def _stage_hip(packed: PackedBatch, dev, d, view, feature_table, cosines):
     out = torch.empty(off + ws_bytes, dtype=torch.uint8, device=dev)
     base = out.data_ptr()
     a = {name: (out[offs[name]:offs[name] + n * (8 if dt is _I64 else 4)].view(dt) if n else None) for name, dt, n in want}
-    if T == 0:  # (no bond pair shares an atom: empty arrays, as graph.csr_and_line_graph gives - never None inside a CSRGraph)
+    if T == 0:  # (no bond pair shares an atom: empty arrays, as the torch builders give - never None inside a CSRGraph, and
+        # with ``cosines`` an empty ``h``, not None)
         for name, dt, _n in want:
-            if a[name] is None and name != "h":
+            if a[name] is None and (name != "h" or cosines):
                 a[name] = torch.empty(0, dtype=dt, device=dev)
     with _lib.device_guard(out):  # (_lib.stream() is the CURRENT device's stream: stage(packed, "cuda:1") while cuda:0 is current)
         rc = lib.alignn_stage_batch(

@@ -914,7 +914,7 @@ int alignn_angle_embed_infer(const alignn_angle_args* args, alignn_stream_t stre
  * also L(g)'s seg_node), perm / inv [E] int64 (slot k holds caller edge perm[k]), r_canon [E,3]; lg_seg_ptr / lg_out_ptr
  * [E+1], lg_src / lg_dst / lg_out_slot / lg_seg_rank [T], lg_ident [T] int64 = 0..T-1 (optional), h [T] (optional; needs
  * r).  workspace: alignn_stage_batch_workspace(N, E) bytes.  ~15 launches, no atomics, bit-identical to alignn_amd.graph's
- * build_csr + line_graph_of (tests).
+ * build_csr + line_graph_of and to a line graph built from this definition alone (tests/test_gpu_stage_ref.py).
  * ------------------------------------------------------------------------------------------ */
 size_t alignn_stage_batch_workspace(int64_t n_nodes, int64_t n_edges);
 int alignn_stage_batch(const int32_t* u, const int32_t* v, const float* r, int64_t n_nodes, int64_t n_edges, int64_t n_triplets,

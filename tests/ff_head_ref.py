@@ -14,6 +14,10 @@ import math
 import torch
 
 STRESS_UNIT = -160.21766208  # eV / A^3 -> GPa with the sign of the virial (alignn_atomwise.py:621-622)
+# what a GPU test allows a kernel on top of 4 x this file's float32 error: 2e-6 absolute for an RBF value, 1e-6 of the largest
+# element for lengths, cosines and means, 2e-5 of the largest element for gradients and tangents (tests/test_gpu_ff_head.py;
+# tests/test_gpu_stage_ref.py takes the cosine bound for the h of alignn_stage_batch)
+B_RBF, B_VALUE, B_GRAD = 2e-6, 1e-6, 2e-5
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 csrc/convln.hip; tests/test_gpu_conv_bn.py: the BatchNorm flavour, csrc/conv.hip): the hard graphs, the error measure and the
 report that collects every failure of a case before it asserts and prints the worst error per (entry point, output) - which
 tests/test_gpu_norm.py (csrc/norm.hip) uses too - and the guard bands (``guarded``, ``guard_input``, ``gptr``) that the pins of
-conv.hip, convln.hip and dual.hip put round every buffer they hand to a launch."""
+conv.hip, convln.hip, dual.hip and stage.hip (tests/test_gpu_stage_ref.py: integer tables with ``pattern=``) put round every
+buffer they hand to a launch."""
 
 import functools
 import os
@@ -82,6 +83,8 @@ NAN_BITS = 0x7FF8A5A5  # a quiet NaN with a payload: torch.full(.., nan) has non
 # dtype -> (integer view of the same width, guard pattern); integer tensors are index operands: guards of zeros (a valid row)
 _PATTERN = {torch.float32: (torch.int32, NAN_BITS), torch.float64: (torch.int64, 0x7FF8A5A5A5A5A5A5),
             torch.float16: (torch.int16, 0x7FA5), torch.bfloat16: (torch.int16, 0x7FA5)}
+# ``pattern=`` for index tables: negative (no index, count or offset is) and non-zero in every byte; uint8 is raw scratch
+INT_PATTERN = {torch.int32: -0x5A5A5A5B, torch.int64: -0x5A5A5A5A5A5A5A5B, torch.uint8: 0xA5}
 
 
 def guard_elements(row, itemsize=4):
@@ -91,11 +94,12 @@ def guard_elements(row, itemsize=4):
 
 
 class _Guarded:
-    def __init__(self, name, base, before, numel, row):
+    def __init__(self, name, base, before, numel, row, pattern=0):
         self.name, self.base, self.before, self.numel, self.row, self.entry = name, base, before, numel, row, None
+        self.pattern = pattern  # (integer dtypes only: what their guards hold)
 
     def sides(self):
-        view, pat = _PATTERN.get(self.base.dtype, (self.base.dtype, 0))
+        view, pat = _PATTERN.get(self.base.dtype, (self.base.dtype, self.pattern))
         end = self.before + self.numel
         return (("before", self.base[:self.before].view(view), pat), ("after", self.base[end:].view(view), pat))
 
@@ -103,14 +107,19 @@ class _Guarded:
 class Guards:
     """Registry of guarded buffers, each one flat allocation [before | payload | after].  Float guards hold NAN_BITS: a launch
     that writes there changes the bits (``check``), one that reads there and uses the value poisons an output, which
-    Report.record rejects.  Integer guards hold zeros and only "unwritten" is checked.  Blind spots: an access farther from
-    the payload than the guard (GUARD_MIN elements or two rows) lands in another buffer's payload or outside the registry
-    and is not seen; neither is a read that is fetched and never used."""
+    Report.record rejects.  Integer guards hold zeros and only "unwritten" is checked - a stray zero is not seen - unless the
+    buffer is made with ``pattern=``: an integer of the dtype's range that no table can hold (INT_PATTERN), kept in the guards
+    and, without ``fill``, in the payload too, so that a stray write of ANY valid value, zero included, and an element of an
+    output that was never written both show.  Blind spots: an access farther from the payload than the guard (GUARD_MIN
+    elements or two rows) lands in another buffer's payload or outside the registry and is not seen; neither is a read that
+    is fetched and never used."""
 
     def __init__(self):
         self.bufs, self.pending, self.last_entry, self.launches = {}, [], None, {}
 
-    def guarded(self, shape, dtype=torch.float32, fill=None, name="?", device=DEV, row=None):
+    def guarded(self, shape, dtype=torch.float32, fill=None, name="?", device=DEV, row=None, pattern=None):
+        if pattern is not None and dtype in _PATTERN:
+            raise ValueError(f"pattern= is for integer dtypes: {dtype} guards always hold the NaN pattern")
         shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
         numel = 1
         for s in shape:
@@ -118,7 +127,7 @@ class Guards:
         row = int(row) if row else (shape[-1] if len(shape) >= 2 else 1)
         g = guard_elements(max(row, 1), torch.empty(0, dtype=dtype).element_size())
         base = torch.empty(2 * g + numel, dtype=dtype, device=device)  # a fresh allocation: the payload keeps its alignment
-        rec = _Guarded(name, base, g, numel, max(row, 1))
+        rec = _Guarded(name, base, g, numel, max(row, 1), 0 if pattern is None else int(pattern))
         for _, side, pat in rec.sides():
             side.fill_(pat)
         # (a tensor of its own on the same storage, not a view of ``base``: autograd and version counters see a fresh tensor)
@@ -127,13 +136,15 @@ class Guards:
             payload.fill_(fill)
         elif dtype in _PATTERN:
             payload.view(_PATTERN[dtype][0]).fill_(_PATTERN[dtype][1])  # (never torch.empty's leftovers: a run is repeatable)
+        elif pattern is not None:
+            payload.fill_(rec.pattern)
         self.bufs[base.untyped_storage().data_ptr()] = rec
         return payload
 
-    def guard_input(self, t, name="?"):
+    def guard_input(self, t, name="?", pattern=None):
         if t is None:
             return None
-        out = self.guarded(t.shape, t.dtype, None, name, t.device)
+        out = self.guarded(t.shape, t.dtype, None, name, t.device, pattern=pattern)
         out.copy_(t)
         return out
 
@@ -238,18 +249,19 @@ def _argument_names():
 _ACTIVE = Guards()  # the registry of the Report made last
 
 
-def guarded(shape, dtype=torch.float32, fill=None, name="?", device=DEV, row=None):
+def guarded(shape, dtype=torch.float32, fill=None, name="?", device=DEV, row=None, pattern=None):
     """A contiguous tensor of ``shape`` in the middle of one flat allocation [before | payload | after], registered with the
     current Report.  before == after == guard_elements(row) (``row``: the last dimension unless given), so the payload sits
-    where a fresh allocation's would, 512-byte aligned.  ``fill`` None leaves the guard pattern in the payload too.  A stray
+    where a fresh allocation's would, 512-byte aligned.  ``fill`` None leaves the guard pattern in the payload too
+    (``pattern``: what the guards of an INTEGER buffer hold instead of zeros, see Guards).  A stray
     access farther away than the guard lands in another buffer's payload or outside the registry: the helper does not see it
     (see Guards)."""
-    return _ACTIVE.guarded(shape, dtype, fill, name, device, row)
+    return _ACTIVE.guarded(shape, dtype, fill, name, device, row, pattern)
 
 
-def guard_input(t, name="?"):
+def guard_input(t, name="?", pattern=None):
     """a copy of the operand ``t`` (contiguous, same dtype) inside a guarded buffer; None stays None"""
-    return _ACTIVE.guard_input(t, name)
+    return _ACTIVE.guard_input(t, name, pattern)
 
 
 def gptr(t):

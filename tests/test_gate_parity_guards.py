@@ -63,6 +63,64 @@ def test_integer_operands_get_guards_of_zeros():
         rep.finish()
 
 
+def test_a_zero_written_into_a_default_integer_guard_is_not_seen():
+    """the blind spot ``pattern=`` closes, and the unchanged default: guards of zeros, the payload left as allocated"""
+    rep = gp.Report("indices, default")
+    ptr = gp.guarded((7,), I32, name="ptr", device=CPU)
+    rec = _base(rep, ptr)
+    assert rec.pattern == 0 and all(bool((side == 0).all()) and pat == 0 for _, side, pat in rec.sides())
+    rec.base[rec.before - 1] = 0
+    rec.base[rec.before + 7] = 0
+    assert rep.guards.check() == []
+    rep.finish()
+
+
+@pytest.mark.parametrize("dtype", [I32, torch.int64, torch.uint8])
+def test_a_patterned_integer_guard_reports_a_stray_zero(dtype):
+    """``pattern=``: guards and the unfilled payload hold a value no table can hold (negative, no zero byte), so a zero written
+    beside the payload - ptr[0], the closing zero of a count - is reported, and so is any other valid value; an element of the
+    payload nobody wrote still holds the pattern"""
+    pat = gp.INT_PATTERN[dtype]
+    nbytes = torch.empty(0, dtype=dtype).element_size()
+    assert (pat < 0 or dtype == torch.uint8) and all((pat >> (8 * b)) & 0xFF for b in range(nbytes))
+    rep = gp.Report("indices, patterned")
+    out = gp.guarded((9,), dtype, name="lg_seg_ptr", device=CPU, pattern=pat)
+    rec = _base(rep, out)
+    assert rec.pattern == pat and bool((out == pat).all()) and bool((rec.base == pat).all())
+    assert rep.guards.check() == []
+    out[:8] = torch.arange(8, dtype=dtype)  # (the launch's own writes; element 8 is "left out")
+    assert rep.guards.check() == [] and int((out == pat).nonzero()) == 8
+    rec.base[rec.before + 9] = 0
+    assert [f[:3] for f in rep.guards.check()] == [("lg_seg_ptr", "after", 0)]
+    rec.base[rec.before + 9] = pat
+    rec.base[rec.before - 2] = 0
+    rec.base[rec.before - 1] = 5
+    assert [f[:3] for f in rep.guards.check()] == [("lg_seg_ptr", "before", -1)]
+    rec.base[rec.before - 1] = pat
+    assert [f[:3] for f in rep.guards.check()] == [("lg_seg_ptr", "before", -2)]
+    with pytest.raises(AssertionError, match="lg_seg_ptr: the guard before the payload changed at offset -2 elements"):
+        rep.finish()
+
+
+def test_pattern_goes_with_guard_input_and_fill_and_is_refused_for_floats():
+    rep = gp.Report("indices, patterned inputs")
+    pat = gp.INT_PATTERN[I32]
+    idx = gp.guard_input(torch.arange(7, dtype=I32), "src", pattern=pat)
+    rec = _base(rep, idx)
+    assert torch.equal(idx, torch.arange(7, dtype=I32))
+    assert all(bool((side == pat).all()) for _, side, _p in rec.sides())
+    z = gp.guarded((3,), I32, fill=0, name="bad", device=CPU, pattern=pat)
+    assert bool((z == 0).all()) and bool((_base(rep, z).base[:4] == pat).all())
+    plain = gp.guard_input(torch.arange(7, dtype=I32), "plain")  # (beside patterned buffers: still guards of zeros)
+    assert int(_base(rep, plain).base.abs().sum()) == 21
+    rep.finish()
+    with pytest.raises(ValueError, match="integer dtypes"):
+        gp.guarded((3,), torch.float32, device=CPU, pattern=1)
+    rec.base[rec.before + 7] = 0
+    with pytest.raises(AssertionError, match="src: the guard after the payload changed at offset 0 elements"):
+        rep.finish()
+
+
 @pytest.mark.parametrize("where,side,offset,rows", [("before", "before", -1, -1 / 36), ("after", "after", 0, 0.0),
                                                      ("row_after", "after", 36, 1.0)])
 def test_a_stray_write_is_reported_with_buffer_side_and_offset(where, side, offset, rows):

@@ -41,7 +41,7 @@ DEV = "cuda"
 F32, F64 = torch.float32, torch.float64
 U = 2.0 ** -24  # unit roundoff of float32
 INVALID = 1  # hipErrorInvalidValue
-B_RBF, B_VALUE, B_GRAD = 2e-6, 1e-6, 2e-5  # the existing suite's bounds (module docstring)
+B_RBF, B_VALUE, B_GRAD = R.B_RBF, R.B_VALUE, R.B_GRAD  # the existing suite's bounds (module docstring): 2e-6, 1e-6, 2e-5
 SENTINEL = 777.0
 
 
