@@ -5,6 +5,7 @@ Public surface mirrors ``alignn.models.alignn`` of the reference; see ``alignn_a
 
 from .alignn import ALIGNN, ALIGNNConfig, ALIGNNConv, EdgeGatedGraphConv, MLPLayer, RBFExpansion  # noqa: F401
 from .alignn_atomwise import ALIGNNAtomWise, ALIGNNAtomWiseConfig  # noqa: F401
+from .cells import CellResult, conventional_cell, primitive_cell  # noqa: F401
 from .defects import EV_A2_TO_J_M2, SurfaceResult, VacancyResult, miller_basis, surface_energy, vacancy_formation  # noqa: F401
 from .elastic import ElasticResult, elastic_fit, elastic_tensor  # noqa: F401
 from .eos import EOS_FORMS, EV_A3_TO_GPA, EVResult, eos_fit, ev_curve  # noqa: F401

@@ -169,11 +169,47 @@ def _supercell_dims(who, supercell, lattices, enforce_c_size, extend, B) -> List
     return out
 
 
+def _on_conventional_cell(who, flag, model, lattices, positions, atom_features, forces_fn, stress, species, symprec, device,
+                          site_labels=None):
+    """``on_conventional_cell``: False leaves the parents as given; True replaces them by ``conventional_cell`` of them, with
+    ``atom_features``, ``species`` and the ``site_labels`` arrays taken through ``source_atom``.
+    -> (lattices, positions, atom_features, species, site_labels)."""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError(f"{who}: on_conventional_cell is one bool, got {type(flag).__name__}")
+    if not flag:
+        return lattices, positions, atom_features, species, site_labels
+    from .cells import conventional_cell
+
+    ns = check_inputs(who, model, lattices, positions, atom_features, forces_fn=forces_fn, stress=stress)
+    arrays = site_labels is not None and not isinstance(site_labels, str)
+    for name, rows in (("species", species), ("site_labels", site_labels if arrays else None)):
+        if rows is None:
+            continue
+        if len(rows) != len(ns):
+            raise ValueError(f"{who}: {name} needs one integer [n_i] array per structure, {len(ns)} of them")
+        for s, r in enumerate(rows):
+            if host(r).shape != (ns[s],):
+                raise ValueError(f"{who}: {name}[{s}] is {host(r).shape}, need [{ns[s]}]")
+    cell = conventional_cell(lattices, positions, species, symprec=symprec, device=gpu_device(who, model, forces_fn, device))
+    src = host(cell.packed["source_atom"]).astype(np.int64)  # (one copy: the rows of every host array are taken through it)
+    ptr = np.concatenate([[0], np.cumsum(cell.ns)])
+    src = [src[ptr[s]:ptr[s + 1]] for s in range(len(ns))]
+
+    def through(rows):
+        if rows is None:
+            return None
+        return [r[torch.as_tensor(i, device=r.device)] if isinstance(r, torch.Tensor) else np.asarray(r)[i] for r, i in zip(rows, src)]
+
+    return ([cell.lattices[s] for s in range(len(ns))], cell.positions, through(atom_features), through(species),
+            through(site_labels) if arrays else site_labels)
+
+
 def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_features: Optional[Sequence] = None, *,
                       site_labels: Optional[Sequence] = None, supercell=None, enforce_c_size: float = 15.0, extend: int = 1,
                       chemical_potentials: Optional[Sequence] = None, relax_structures: bool = True,
                       max_atoms_per_call: int = MAX_ATOMS_PER_CALL, forces_fn: Optional[Callable] = None, device=None,
-                      species: Optional[Sequence] = None, symprec: float = 1e-3, **relax_kwargs) -> VacancyResult:
+                      species: Optional[Sequence] = None, symprec: float = 1e-3, on_conventional_cell: bool = False,
+                      **relax_kwargs) -> VacancyResult:
     """Vacancy formation energies of B crystals, the reference's ``vacancy_formation`` (ff.py:808) for each: per parent one
     pristine supercell and one supercell with an atom removed per class of sites, all relaxed together.
 
@@ -182,9 +218,13 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
     ``site_labels``: B integer arrays [n_s], one class per distinct label (e.g. the Wyckoff classes of spglib, the reference's
     ``using_wyckoffs``); default: every atom its own class; ``"auto"``: the orbits of ``find_symmetry(lattices, positions,
     species, symprec=symprec)``, the atoms the crystal's own symmetry makes equivalent (``species``: B integer arrays, None: all
-    atoms alike; both are used by ``"auto"`` only).  The atom removed is the class's lowest-index atom, in image 0.
+    atoms alike; both are used by ``"auto"`` and ``on_conventional_cell`` only).  The atom removed is the class's lowest-index atom, in image 0.
     ``chemical_potentials``: B arrays with one value (eV) per class in ascending label order, added to the formation energy;
-    default 0 (the reference reads jarvis' unary-energy table).
+    default 0 (the reference reads jarvis' unary-energy table).  ``on_conventional_cell=True`` (the reference's default; here
+    False, the parents as given) first replaces the parents by ``conventional_cell(lattices, positions, species,
+    symprec=symprec)`` of them (alignn_amd/cells.py): the rows of ``atom_features``, ``species`` and the ``site_labels`` arrays
+    are taken through its ``source_atom``, ``"auto"`` is evaluated on the new cell, and ``supercell`` / ``enforce_c_size`` refer
+    to it.
 
     ``relax_structures=False`` evaluates the structures as built (``steps=0``).  ``relax_kwargs`` go to ``relax`` as whole-call
     options; ``steps=100``, ``fmax=0.1`` and ``optimize_lattice=True`` are the defaults here, as in the reference's
@@ -192,6 +232,9 @@ def vacancy_formation(model, lattices: Sequence, positions: Sequence, atom_featu
     call (whole jobs).  The reference relaxes the same pristine supercell once per defect; here once per parent."""
     who = "vacancy_formation"
     optimize_lattice = bool(relax_kwargs.get("optimize_lattice", True))
+    lattices, positions, atom_features, species, site_labels = _on_conventional_cell(
+        who, on_conventional_cell, model, lattices, positions, atom_features, forces_fn, optimize_lattice, species, symprec, device,
+        site_labels)
     ns = check_inputs(who, model, lattices, positions, atom_features, forces_fn=forces_fn, stress=optimize_lattice)
     B = len(ns)
     check_job_options(who, max_atoms_per_call, relax_kwargs)
@@ -286,6 +329,7 @@ def _miller_lists(who, miller_indices, B) -> List[np.ndarray]:
 def surface_energy(model, lattices: Sequence, positions: Sequence, atom_features: Optional[Sequence] = None, *,
                    miller_indices, thickness: float = 25.0, vacuum: float = 18.0, relax_structures: bool = True,
                    max_atoms_per_call: int = MAX_ATOMS_PER_CALL, forces_fn: Optional[Callable] = None, device=None,
+                   on_conventional_cell: bool = False, species: Optional[Sequence] = None, symprec: float = 1e-3,
                    **relax_kwargs) -> SurfaceResult:
     """Surface energies of B crystals, the reference's ``surface_energy`` (ff.py:900) for each: per parent the parent itself
     (its energy per atom) and one slab per Miller index, all relaxed together.
@@ -293,7 +337,10 @@ def surface_energy(model, lattices: Sequence, positions: Sequence, atom_features
     The structures, the model (or ``forces_fn``) and the device: alignn_amd/_structures.py.  ``miller_indices``: one list of
     (h, k, l) for all parents, or B lists.  A slab is ASE's general surface construction on ``miller_basis``: ``layers = max(1,
     int(thickness / h3))`` repeats of the parent in the oriented cell, h3 the spacing of its (hkl) planes, ``vacuum`` (A) added
-    above the slab.  The parents are taken as given (conventional-cell standardisation is the caller's).
+    above the slab.  ``on_conventional_cell=True`` (the reference's default; here False, the parents as given) first replaces the
+    parents by ``conventional_cell(lattices, positions, species, symprec=symprec)`` of them (alignn_amd/cells.py), the rows of
+    ``atom_features`` taken through its ``source_atom``: Miller indices and thickness then refer to the conventional cell.
+    ``species`` (B integer arrays, None: all atoms alike) and ``symprec`` are used by that option only.
 
     ``surf_en = (E_slab - epa n_slab) / (2 area)`` in eV/A^2; ``surf_en_J_m2`` is that times ``EV_A2_TO_J_M2`` = 16.02176634.
     The reference multiplies by 16 instead, so its figures are 0.14 % lower.
@@ -303,6 +350,8 @@ def surface_energy(model, lattices: Sequence, positions: Sequence, atom_features
     vacuum axis stays (with every component free the filter shrinks the vacuum)."""
     who = "surface_energy"
     optimize_lattice = bool(relax_kwargs.get("optimize_lattice", True))
+    lattices, positions, atom_features, _, _ = _on_conventional_cell(
+        who, on_conventional_cell, model, lattices, positions, atom_features, forces_fn, optimize_lattice, species, symprec, device)
     ns = check_inputs(who, model, lattices, positions, atom_features, forces_fn=forces_fn, stress=optimize_lattice)
     B = len(ns)
     check_job_options(who, max_atoms_per_call, relax_kwargs)

@@ -10,7 +10,8 @@ The reference gets its symmetry from spglib through jarvis' ``Spacegroup3D``, on
   ``vacancy_formation(site_labels="auto")`` uses the orbits as its classes of sites.
 
 An operation acts on fractional column coordinates as x' = W x + t (the cell's rows are the lattice vectors), W an integer
-matrix with det +-1 in the basis of the cell AS GIVEN - no cell is reduced or standardised, entries of W may exceed +-1 - and t in
+matrix with det +-1 in the basis of the cell AS GIVEN - the search reduces or standardises no cell, entries of W may exceed +-1;
+``primitive_cell`` and ``conventional_cell`` of alignn_amd/cells.py take the step from these operations to cells - and t in
 [0, 1).  ``symprec`` is a length in A: lattice vectors keep their lengths and the lengths of their differences within it, and
 every atom's image lies within it of an atom of its species.  The definitions are stated in include/alignn_sym.h (read here with
 the reader of alignn_amd/_abi.py) and restated in numpy by tests/sym_ref.py.  The kernels (csrc/symmetry.hip) are float64 without
@@ -18,8 +19,8 @@ contraction and without floating-point atomics, every sum in a fixed order: a st
 batch and at any place of it.  One array of B x 8 integers (counts, crystal system, status) is read back between the search and
 the launch that fills the results; nothing else.
 
-Not here: space-group numbers and symbols, Wyckoff letters, standardised / conventional / primitive cells, symmetrising the
-lattice itself, symmetry-reduced strains and q-meshes, a symmetry constraint inside ``relax``, magnetic or site-property-aware
+Not here: space-group numbers and symbols, Wyckoff letters, symmetrising the lattice itself (primitive and conventional cells:
+alignn_amd/cells.py; rotations of a supercell's crystal that do not keep the supercell are not among its operations), symmetry-reduced strains and q-meshes, a symmetry constraint inside ``relax``, magnetic or site-property-aware
 symmetry.  (Symmetry-reduced displacements: ``phonons(displacements="symmetry", symmetry=...)``, alignn_amd/phonons.py.)
 """
 
