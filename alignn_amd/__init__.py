@@ -16,6 +16,7 @@ from .interface import InterfaceResult, MatchResult, interface_energy, match_lat
 from .graph import CSRGraph, GraphBatch, build_csr  # noqa: F401
 from .neb import NEBResult, neb, neb_interpolate  # noqa: F401
 from .idpp import IDPPResult, idpp_forces, idpp_interpolate  # noqa: F401
+from .local_order import BondOrderResult, CNAResult, bond_order, cna  # noqa: F401
 from .order import (MAX_HKL, MAX_L, MAX_NEIGHBORS, ADFResult, SQResult, SteinhardtResult, adf, steinhardt,  # noqa: F401
                     structure_factor)
 from .relax import RelaxResult, relax  # noqa: F401

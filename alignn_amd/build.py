@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libalignn_hip.so")
-SOURCES = ["norm.hip", "conv.hip", "gemm_f32.hip", "gemm_x6.hip", "embed.hip", "dual.hip", "knn.hip", "composite.hip", "model.hip", "stage.hip", "radius.hip", "angle.hip", "ff.hip", "convln.hip", "gemm_dw.hip", "relax.hip", "dynamics.hip", "phonon.hip", "defects.hip", "eos.hip", "elastic.hip", "interface.hip", "thermo.hip", "neb.hip", "trajectory.hip", "symmetry.hip", "order.hip", "phonon_sym.hip", "idpp.hip", "cells.hip"]
+SOURCES = ["norm.hip", "conv.hip", "gemm_f32.hip", "gemm_x6.hip", "embed.hip", "dual.hip", "knn.hip", "composite.hip", "model.hip", "stage.hip", "radius.hip", "angle.hip", "ff.hip", "convln.hip", "gemm_dw.hip", "relax.hip", "dynamics.hip", "phonon.hip", "defects.hip", "eos.hip", "elastic.hip", "interface.hip", "thermo.hip", "neb.hip", "trajectory.hip", "symmetry.hip", "order.hip", "phonon_sym.hip", "idpp.hip", "cells.hip", "local_order.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 DEVICE_FLAGS: list = []
 # Per-file additions: no SLP vectorisation where hipcc 7.2 would otherwise emit the packed-fp32 form that MI355X gets wrong:

@@ -21,8 +21,8 @@ alone, in a batch and at any place of it.  Read back from the device: the status
 ``structure_factor``, the number of reciprocal vectors of every structure (it sizes the lists).  tests/order_ref.py restates the
 formulas in numpy; the entry points are declared in include/alignn_order.h, read here with the reader of alignn_amd/_abi.py.
 
-Not here: per-frame cells for S(q), cutoffs per species pair, the averaged q_l of Lechner and Dellago and the w_l invariants,
-common-neighbour analysis, form-factor weighting.
+Not here: per-frame cells for S(q), cutoffs per species pair, form-factor weighting.  (The averaged q_l of Lechner and Dellago,
+the w_l invariants and common-neighbour analysis are in ``alignn_amd.local_order``.)
 """
 
 from __future__ import annotations
