@@ -1,8 +1,10 @@
 // What the builders of derived structures share (defects.hip, interface.hip, eos.hip): the inverse of a 3 x 3 cell by cofactors and
-// the product of a row vector with a cell; for symmetry.hip and phonon_sym.hip, the Cartesian rotation of an operation; and, for
-// trajectory.hip, order.hip and symmetry.hip, the determinant, the heights and the range of periodic images of a cell.  float64
-// without contraction, every sum in a fixed order; tests/defects_ref.py restates the first two operation for operation (inv3_cof,
-// row_dot), tests/traj_ref.py the image range.
+// the product of a row vector with a cell; for symmetry.hip and phonon_sym.hip, the Cartesian rotation of an operation; for
+// trajectory.hip, order.hip and symmetry.hip, the determinant, the heights and the range of periodic images of a cell; and, for
+// every kernel that takes a minimum image in Cartesian space (trajectory.hip, neb.hip, idpp.hip and, through neighbor_list.h,
+// order.hip and local_order.hip), the wrapped difference and the shift to a periodic image.  float64 without contraction, every sum
+// in a fixed order; tests/defects_ref.py restates the first two operation for operation (inv3_cof, row_dot), tests/traj_ref.py the
+// image range, the wrap and the shift.
 #pragma once
 #include <stdint.h>
 
@@ -64,6 +66,24 @@ __device__ __forceinline__ bool image_range(const double (&C)[9], double r, int 
 // x M for a row vector x and a row-major M: (x0 M0k + x1 M1k) + x2 M2k
 __device__ __forceinline__ double row_dot(const double* x, const double (&m)[9], int k) {
     return (x[0] * m[k] + x[1] * m[3 + k]) + x[2] * m[6 + k];
+}
+
+// the plain wrap of the row difference d in the cell C with inverse Ci: f = d Ci, f - rint(f) (half to even), then that row x C
+__device__ __forceinline__ void wrap_difference(const double (&d)[3], const double (&C)[9], const double (&Ci)[9],
+                                                double (&d0)[3]) {
+    double f[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        f[c] = row_dot(d, Ci, c);
+        f[c] -= rint(f[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d0[c] = row_dot(f, C, c);
+}
+
+// component c of d0 moved to the periodic image (m0, m1, m2): d0[c] + ((m0 C[0][c] + m1 C[1][c]) + m2 C[2][c])
+__device__ __forceinline__ double image_offset(const double (&d0)[3], int m0, int m1, int m2, const double (&C)[9], int c) {
+    return d0[c] + (((double)m0 * C[c] + (double)m1 * C[3 + c]) + (double)m2 * C[6 + c]);
 }
 
 __device__ __forceinline__ void load9(const double* p, double (&A)[9]) {

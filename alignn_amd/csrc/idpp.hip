@@ -39,19 +39,11 @@ __device__ __forceinline__ bool band_fits(const IdppArgs& a, int k, Band& g) {
     return g.M <= a.max_images && a.force_ptr[k + 1] - g.fbeg == rows && a.energy_ptr[k + 1] - g.gbeg == g.M - 2;
 }
 
-// |mic(x - y)| in the cell C with inverse Ci (neb.hip's wrap), the wrapped difference in D
+// |mic(x - y)| in the cell C with inverse Ci (cell3.h's wrap_difference, as in neb.hip), the wrapped difference in D
 __device__ __forceinline__ double wrapped(const double (&x)[3], const double* y, const double (&C)[9], const double (&Ci)[9],
                                           double (&D)[3]) {
-    double d[3], f[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) d[j] = x[j] - y[j];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        f[j] = row_dot(d, Ci, j);
-        f[j] -= rint(f[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) D[j] = row_dot(f, C, j);
+    const double d[3] = {x[0] - y[0], x[1] - y[1], x[2] - y[2]};
+    wrap_difference(d, C, Ci, D);
     return sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
 }
 

@@ -4,17 +4,16 @@
 // of the argument blocks.
 //
 //   cna_kernel             one wavefront per (frame, centre atom), four per workgroup: the neighbour list by ballot and prefix into
-//                          LDS (the pair geometry of order.hip's angles_kernel, entry for entry), the adaptive sort as a rank count,
-//                          lane a the 64-bit mask of the entries bonded to entry a, the signature from popcounts and a flood fill
-//                          over the masks in LDS, the class from ballots;
+//                          LDS (neighbor_list.h's build_list, the list of order.hip's angles_kernel), the adaptive sort as a
+//                          rank count, lane a the 64-bit mask of the entries bonded to entry a, the signature from popcounts and a
+//                          flood fill over the masks in LDS, the class from ballots;
 //   cna_counts_kernel      one wavefront per (frame, structure): atoms per group and class by LDS integer atomics, the fractions;
 //   bond_qlm_kernel        pass 1, one wavefront per (frame, atom): lane a the harmonics of entry a, an xor butterfly per (l, m);
 //   bond_finish_kernel     pass 2: the same list again, the gather of q_lm(j), then s, t, q, w of q_lm and of the averaged q_lm.
 // float64, no contraction, no atomics on floating-point values, every sum in a fixed order over the atom's own list: a structure's
 // bits are the same alone, in a batch and at any place of the batch.
 #include "../../include/alignn_local.h"
-#include "common.h"
-#include "cell3.h"
+#include "neighbor_list.h"
 
 #pragma clang fp contract(off)
 
@@ -31,97 +30,8 @@ constexpr double SQRT2 = 1.4142135623730951, SQRT3 = 1.7320508075688772;  // (th
 using CnaArgs = alignn_local_cna_args;
 using BondArgs = alignn_local_bond_args;
 
-static_assert(NBR == ALIGNN_WAVE, "a lane per list entry");
+static_assert(NBR == NEIGHBOR_LIST_CAP, "the list of neighbor_list.h");
 static_assert(MS == MAX_L + 1 && W3J == (2 * MAX_L + 1) * (2 * MAX_L + 1), "the strides of qlm and w3j");
-
-__device__ __forceinline__ void wave_sync() {  // the wavefront's LDS writes are seen by its lanes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the species of structure b that have members: groups 1 .. Sb
-__device__ __forceinline__ int species_of(const int32_t* group_count, int b, int S) {
-    int Sb = 0;
-    for (int g = 1; g <= S; ++g)
-        if (group_count[b * (S + 1) + g] > 0) Sb = g;
-    return Sb;
-}
-
-// The neighbour list of atom il of one frame, in the order j ascending, then (m0, m1, m2) lexicographic: (dx, dy, dz, r) of
-// entry a into list[a] and its j into lj[a] (when not NULL), a < NBR; returns the number found (uniform), which may exceed NBR.
-// Operation for operation the list of order.hip's angles_kernel.
-__device__ __forceinline__ int build_list(const double* X, const int32_t* GR, int n, int il, int Sb, const double (&C)[9],
-                                          const double (&Ci)[9], const int (&M)[3], double r_cut, int lane, double (*list)[4], int* lj) {
-    const double xi[3] = {X[3 * il], X[3 * il + 1], X[3 * il + 2]};
-    const int w1 = 2 * M[1] + 1, w2 = 2 * M[2] + 1, nimg = (2 * M[0] + 1) * w1 * w2;
-    const int64_t total = (int64_t)n * nimg;
-    const bool narrow = total < ((int64_t)1 << 31);
-    int count = 0;  // (uniform)
-    for (int64_t c0 = 0; c0 < total; c0 += ALIGNN_WAVE) {
-        const int64_t cand = c0 + lane;
-        bool hit = false;
-        double dx = 0.0, dy = 0.0, dz = 0.0, r = 0.0;
-        int j = 0;
-        if (cand < total) {
-            int img;
-            if (narrow) {
-                j = (int)((unsigned)cand / (unsigned)nimg);
-                img = (int)((unsigned)cand - (unsigned)j * (unsigned)nimg);
-            } else {
-                j = (int)(cand / nimg);
-                img = (int)(cand - (int64_t)j * nimg);
-            }
-            const int q2 = img / w2, m2 = img - q2 * w2 - M[2];
-            const int q1 = q2 / w1, m1 = q2 - q1 * w1 - M[1], m0 = q1 - M[0];
-            const int gj = GR[j];
-            double dp[3], df[3], d0[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dp[c] = X[3 * j + c] - xi[c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                df[c] = row_dot(dp, Ci, c);
-                df[c] -= rint(df[c]);
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) d0[c] = row_dot(df, C, c);
-            const double a0 = (double)m0, a1 = (double)m1, a2 = (double)m2;
-            const double s0 = a0 * C[0] + a1 * C[3], s1 = a0 * C[1] + a1 * C[4], s2 = a0 * C[2] + a1 * C[5];
-            dx = d0[0] + (s0 + a2 * C[6]);
-            dy = d0[1] + (s1 + a2 * C[7]);
-            dz = d0[2] + (s2 + a2 * C[8]);
-            r = sqrt((dx * dx + dy * dy) + dz * dz);
-            const bool self = j == il && m0 == 0 && m1 == 0 && m2 == 0;
-            hit = !self && r < r_cut && gj >= 1 && gj <= Sb;
-        }
-        const unsigned long long mask = __ballot(hit);
-        const int at = count + __popcll(mask & ((1ull << lane) - 1ull));
-        if (hit && at < NBR) {
-            list[at][0] = dx;
-            list[at][1] = dy;
-            list[at][2] = dz;
-            list[at][3] = r;
-            if (lj) lj[at] = j;
-        }
-        count += __popcll(mask);
-    }
-    return count;
-}
-
-// what the three kernels share of a (frame, structure): the cell, its inverse and the image range; false (and the status bit)
-// when the frame is skipped
-template <class Args>
-__device__ __forceinline__ bool frame_cell(const Args& a, int frame, int b, double r_cut, int lane, bool flag, double (&C)[9],
-                                           double (&Ci)[9], int (&M)[3]) {
-    const int64_t cell_at = a.lattice_per_frame ? (int64_t)frame * a.n_structs + b : b;
-    load9(a.lattice + 9 * cell_at, C);
-    if (!image_range(C, r_cut, ALIGNN_LOCAL_MAX_IMAGE_RANGE, M) || !(r_cut > 0.0)) {  // (or r_cut is not a number > 0)
-        if (flag && lane == 0) atomicOr(a.status, ALIGNN_LOCAL_STATUS_IMAGES);
-        return false;
-    }
-    inv3_cof(C, Ci);
-    return true;
-}
 
 // ---- common-neighbour analysis ----
 
@@ -202,10 +112,14 @@ __global__ __launch_bounds__(BLOCK) void cna_kernel(const CnaArgs a) {
         const int frame = a.frame0 + f * a.frame_step;
         double C[9], Ci[9];
         int M[3];
-        if (!frame_cell(a, frame, b, r_cut, lane, true, C, Ci, M)) continue;
+        if (!frame_cell(a.lattice, a.lattice_per_frame, a.n_structs, frame, b, r_cut, ALIGNN_LOCAL_MAX_IMAGE_RANGE, C, Ci, M) ||
+            !(r_cut > 0.0)) {  // (or r_cut is not a number > 0)
+            if (lane == 0) atomicOr(a.status, ALIGNN_LOCAL_STATUS_IMAGES);
+            continue;
+        }
         const double* X = a.traj + 3 * ((int64_t)frame * a.n_atoms + beg);
         wave_sync();  // (the list of the frame before has been read)
-        const int count = build_list(X, GR, n, il, Sb, C, Ci, M, r_cut, lane, list, nullptr);
+        const int count = build_list<false, false>(X, GR, n, il, Sb, C, Ci, M, r_cut, lane, list, nullptr, nullptr);
         const int64_t row = (int64_t)f * a.n_atoms + beg + il;
         int cls = 0, sig[NSIG] = {0, 0, 0, 0, 0};
         if (count > NBR) {
@@ -308,10 +222,14 @@ __global__ __launch_bounds__(BLOCK) void bond_qlm_kernel(const BondArgs a) {
         const int f = a.chunk0 + fk, frame = a.frame0 + f * a.frame_step;
         double C[9], Ci[9];
         int M[3];
-        if (!frame_cell(a, frame, b, r_cut, lane, true, C, Ci, M)) continue;
+        if (!frame_cell(a.lattice, a.lattice_per_frame, a.n_structs, frame, b, r_cut, ALIGNN_LOCAL_MAX_IMAGE_RANGE, C, Ci, M) ||
+            !(r_cut > 0.0)) {  // (or r_cut is not a number > 0)
+            if (lane == 0) atomicOr(a.status, ALIGNN_LOCAL_STATUS_IMAGES);
+            continue;
+        }
         const double* X = a.traj + 3 * ((int64_t)frame * a.n_atoms + beg);
         wave_sync();  // (the list of the frame before has been read)
-        const int count = build_list(X, GR, n, il, Sb, C, Ci, M, r_cut, lane, list, nullptr);
+        const int count = build_list<false, false>(X, GR, n, il, Sb, C, Ci, M, r_cut, lane, list, nullptr, nullptr);
         double* out = a.qlm + ((int64_t)fk * a.n_atoms + beg + il) * L * MS * 2;
         if (lane == 0) a.n_neighbors[(int64_t)f * a.n_atoms + beg + il] = count;
         if (count > NBR || count == 0) {
@@ -425,14 +343,16 @@ __global__ __launch_bounds__(BLOCK) void bond_finish_kernel(const BondArgs a) {
         const int f = a.chunk0 + fk, frame = a.frame0 + f * a.frame_step;
         double C[9], Ci[9];
         int M[3];
-        if (!frame_cell(a, frame, b, r_cut, lane, false, C, Ci, M)) continue;  // (pass 1 has set the bit)
+        if (!frame_cell(a.lattice, a.lattice_per_frame, a.n_structs, frame, b, r_cut, ALIGNN_LOCAL_MAX_IMAGE_RANGE, C, Ci, M) ||
+            !(r_cut > 0.0))
+            continue;  // (pass 1 has set the bit)
         const int64_t row = (int64_t)f * a.n_atoms + beg + il;
         const double* Qf = a.qlm + ((int64_t)fk * a.n_atoms + beg) * L * MS * 2;  // the q_lm of this structure in this frame
         int count = 0;
         if (a.average) {
             const double* X = a.traj + 3 * ((int64_t)frame * a.n_atoms + beg);
             wave_sync();  // (the list of the frame before has been read)
-            count = build_list(X, GR, n, il, Sb, C, Ci, M, r_cut, lane, list, lj);
+            count = build_list<true, false>(X, GR, n, il, Sb, C, Ci, M, r_cut, lane, list, lj, nullptr);
             wave_sync();
         }
         const bool over = count > NBR;  // (pass 1 has written zeros for q_lm and set the bit)

@@ -10,7 +10,7 @@
 //                            writes F.
 // float64, no contraction, no atomics, every sum in a fixed order that depends on the image's own rows only: a band's bits are the
 // same alone, in a batch and at any place of the batch.  The minimum image convention is the plain wrap of the fractional
-// difference (rint: half to even), not a Minkowski-reduced search.
+// difference (cell3.h's wrap_difference; rint: half to even), not a Minkowski-reduced search.
 #include "../../include/alignn_neb.h"
 #include "common.h"
 #include "cell3.h"
@@ -21,18 +21,6 @@ namespace {
 
 constexpr int NEB_BLOCK = 256, NEB_WAVES = NEB_BLOCK / ALIGNN_WAVE;
 constexpr int NEB_INTERP_BLOCK = 256, NEB_INTERP_MAX_BLOCKS = 4096;
-
-// the plain wrap of the row difference d in the cell C with inverse Ci
-__device__ __forceinline__ void mic(const double (&d)[3], const double (&C)[9], const double (&Ci)[9], double (&out)[3]) {
-    double f[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        f[j] = row_dot(d, Ci, j);
-        f[j] -= rint(f[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) out[j] = row_dot(f, C, j);
-}
 
 // the band of output row r: the last b with row_ptr[b] <= r (empty bands are stepped over)
 __device__ __forceinline__ int band_of(const int32_t* __restrict__ row_ptr, int n_bands, int64_t r) {
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(NEB_INTERP_BLOCK) void neb_interpolate_kernel(
             x0[j] = initial[3 * (e0 + atom) + j];
             d[j] = final[3 * (e0 + atom) + j] - x0[j];
         }
-        mic(d, C, Ci, step);
+        wrap_difference(d, C, Ci, step);
         const double jd = (double)(img + 1);
 #pragma unroll
         for (int j = 0; j < 3; ++j) positions[3 * r + j] = x0[j] + jd * (step[j] / images);
@@ -145,8 +133,8 @@ __global__ __launch_bounds__(NEB_BLOCK) void neb_forces_kernel(const NebArgs a) 
             d2[j] = Rp[3 * r + j] - x;
             f[j] = Fo[3 * r + j];
         }
-        mic(d1, C, Ci, t1);
-        mic(d2, C, Ci, t2);
+        wrap_difference(d1, C, Ci, t1);
+        wrap_difference(d2, C, Ci, t2);
         if (FIX && FIX[r]) f[0] = f[1] = f[2] = 0.0;
     };
 

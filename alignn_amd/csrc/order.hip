@@ -3,10 +3,11 @@
 // restatement, include/alignn_order.h states the formulas, the layouts and every field of the argument blocks.
 //
 //   angles_kernel          one workgroup of four wavefronts per (chunk of 64 frames, centre atom, structure), a wavefront per
-//                          frame: the neighbour list by ballot and prefix into LDS (the pair geometry of trajectory.hip's
-//                          rdf_counts_kernel), then the pairs of the list lane-strided: the angle into an LDS histogram of 32-bit
-//                          counts (LDS integer atomics, flushed with integer atomic adds; rows that do not fit go in chunks) and
-//                          the Legendre sums of the Steinhardt parameters (lane-strided, then the xor butterfly);
+//                          frame: the neighbour list by ballot and prefix into LDS (neighbor_list.h's build_list, the pair
+//                          geometry of trajectory.hip's rdf_counts_kernel), then the pairs of the list lane-strided: the angle
+//                          into an LDS histogram of 32-bit counts (LDS integer atomics, flushed with integer atomic adds; rows
+//                          that do not fit go in chunks) and the Legendre sums of the Steinhardt parameters (lane-strided, then
+//                          the xor butterfly);
 //   adf_marginal_kernel, adf_normalise_kernel     the rows of group 0 by integer sums; adf and the bin centres;
 //   steinhardt_mean_kernel one wavefront per (frame, structure): the group means in the row order of trajectory.hip's corr_kernel;
 //   sq_vectors_kernel      one wavefront per structure: the half space of reciprocal vectors inside q_max, counted or listed in
@@ -18,8 +19,7 @@
 // sum has a fixed order over the structure's own rows, frames and vectors, so a structure's bits are the same alone, in a batch
 // and at any place of the batch.
 #include "../../include/alignn_order.h"
-#include "common.h"
-#include "cell3.h"
+#include "neighbor_list.h"
 
 #pragma clang fp contract(off)
 
@@ -28,6 +28,7 @@ namespace {
 constexpr int ANG_WAVES = 4, ANG_BLOCK = ANG_WAVES * ALIGNN_WAVE, ANG_FRAMES = 64;
 constexpr int ANG_HIST_CAP = 4096;  // 32-bit counts of the LDS histogram at the most (16 KiB beside the 9 KiB of the lists)
 constexpr int NBR = ALIGNN_ORDER_MAX_NEIGHBORS;
+static_assert(NBR == NEIGHBOR_LIST_CAP, "the list of neighbor_list.h");
 constexpr int MAX_LS = ALIGNN_ORDER_MAX_LS, MAX_L = ALIGNN_ORDER_MAX_L;
 constexpr int MEAN_ROWS = 4;  // rows per lane in a chunk of 256 (corr_kernel's CORR_WAVES)
 constexpr int SQ_BLOCK = 256, SQ_ATOMS = 16;
@@ -58,9 +59,7 @@ __global__ __launch_bounds__(ANG_BLOCK) void angles_kernel(const AngleArgs a, in
     if (n < 1 || beg < 0 || (int64_t)beg + n > a.n_atoms || il >= n) return;  // (uniform over the workgroup)
     const int lane = threadIdx.x & (ALIGNN_WAVE - 1), wave = threadIdx.x / ALIGNN_WAVE;
     const int S = a.n_species, G = S + 1, nb = a.n_bins, P = 1 + S * (S + 1) / 2;
-    int Sb = 0;
-    for (int g = 1; g <= S; ++g)
-        if (a.group_count[b * G + g] > 0) Sb = g;
+    const int Sb = species_of(a.group_count, b, S);
     const int rows = Sb * (Sb + 1) / 2;
     const int32_t* GR = a.group + beg;
     const int gi = GR[il];
@@ -88,69 +87,13 @@ __global__ __launch_bounds__(ANG_BLOCK) void angles_kernel(const AngleArgs a, in
             const int frame = a.frame0 + f * a.frame_step;
             double C[9], Ci[9];
             int M[3];
-            const int64_t cell_at = a.lattice_per_frame ? (int64_t)frame * a.n_structs + b : b;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) C[j] = a.lattice[9 * cell_at + j];
-            if (!image_range(C, r_cut, ALIGNN_ORDER_MAX_IMAGE_RANGE, M) || !(r_cut > 0.0)) {  // (or r_cut is not a number > 0)
+            if (!frame_cell(a.lattice, a.lattice_per_frame, a.n_structs, frame, b, r_cut, ALIGNN_ORDER_MAX_IMAGE_RANGE, C, Ci, M) ||
+                !(r_cut > 0.0)) {  // (or r_cut is not a number > 0)
                 if (lane == 0) atomicOr(a.status, ALIGNN_ORDER_STATUS_IMAGES);
                 continue;
             }
-            inv3_cof(C, Ci);
             const double* X = a.traj + 3 * ((int64_t)frame * a.n_atoms + beg);
-            const double xi[3] = {X[3 * il], X[3 * il + 1], X[3 * il + 2]};
-            const int w1 = 2 * M[1] + 1, w2 = 2 * M[2] + 1, nimg = (2 * M[0] + 1) * w1 * w2;
-            const int64_t total = (int64_t)n * nimg;
-            const bool narrow = total < ((int64_t)1 << 31);
-
-            // the neighbour list, in the order j ascending, then (m0, m1, m2) lexicographic
-            int count = 0;  // (uniform)
-            for (int64_t c0 = 0; c0 < total; c0 += ALIGNN_WAVE) {
-                const int64_t cand = c0 + lane;
-                bool hit = false;
-                double dx = 0.0, dy = 0.0, dz = 0.0, r = 0.0;
-                int gj = 0;
-                if (cand < total) {
-                    int j, img;
-                    if (narrow) {
-                        j = (int)((unsigned)cand / (unsigned)nimg);
-                        img = (int)((unsigned)cand - (unsigned)j * (unsigned)nimg);
-                    } else {
-                        j = (int)(cand / nimg);
-                        img = (int)(cand - (int64_t)j * nimg);
-                    }
-                    const int q2 = img / w2, m2 = img - q2 * w2 - M[2];
-                    const int q1 = q2 / w1, m1 = q2 - q1 * w1 - M[1], m0 = q1 - M[0];
-                    gj = GR[j];
-                    double dp[3], df[3], d0[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) dp[c] = X[3 * j + c] - xi[c];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        df[c] = row_dot(dp, Ci, c);
-                        df[c] -= rint(df[c]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) d0[c] = row_dot(df, C, c);
-                    const double a0 = (double)m0, a1 = (double)m1, a2 = (double)m2;
-                    const double s0 = a0 * C[0] + a1 * C[3], s1 = a0 * C[1] + a1 * C[4], s2 = a0 * C[2] + a1 * C[5];
-                    dx = d0[0] + (s0 + a2 * C[6]);
-                    dy = d0[1] + (s1 + a2 * C[7]);
-                    dz = d0[2] + (s2 + a2 * C[8]);
-                    r = sqrt((dx * dx + dy * dy) + dz * dz);
-                    const bool self = j == il && m0 == 0 && m1 == 0 && m2 == 0;
-                    hit = !self && r < r_cut && gj >= 1 && gj <= Sb;
-                }
-                const unsigned long long mask = __ballot(hit);
-                const int at = count + __popcll(mask & ((1ull << lane) - 1ull));
-                if (hit && at < NBR) {
-                    list[at][0] = dx;
-                    list[at][1] = dy;
-                    list[at][2] = dz;
-                    list[at][3] = r;
-                    lgrp[at] = gj;
-                }
-                count += __popcll(mask);
-            }
+            const int count = build_list<false, true>(X, GR, n, il, Sb, C, Ci, M, r_cut, lane, list, nullptr, lgrp);
             const int64_t row = (int64_t)f * a.n_atoms + beg + il;
             if (count > NBR) {
                 if (lane == 0) {
@@ -162,9 +105,7 @@ __global__ __launch_bounds__(ANG_BLOCK) void angles_kernel(const AngleArgs a, in
                 }
                 continue;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
 
             const int npairs = count * (count - 1) / 2;
             double sl[MAX_LS] = {0.0, 0.0, 0.0, 0.0};

@@ -15,8 +15,7 @@
 // sum has a fixed order over the structure's own rows and frames, so a structure's bits are the same alone, in a batch and at any
 // place of the batch.
 #include "../../include/alignn_traj.h"
-#include "common.h"
-#include "cell3.h"
+#include "neighbor_list.h"
 
 #pragma clang fp contract(off)
 
@@ -32,13 +31,6 @@ constexpr double PI = 3.14159265358979323846;
 using RdfArgs = alignn_traj_rdf_args;
 using CorrArgs = alignn_traj_corr_args;
 
-// the cell of structure b in the frame `frame` (an index into the whole trajectory)
-__device__ __forceinline__ void load_cell(const RdfArgs& a, int b, int frame, double (&C)[9]) {
-    const int64_t at = a.lattice_per_frame ? (int64_t)frame * a.n_structs + b : b;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) C[j] = a.lattice[9 * at + j];
-}
-
 __global__ __launch_bounds__(RDF_BLOCK) void rdf_counts_kernel(const RdfArgs a, int types_per_chunk) {
     extern __shared__ unsigned hist[];  // [types_per_chunk][n_bins]
     __shared__ double xj[RDF_TILE][3];
@@ -46,20 +38,16 @@ __global__ __launch_bounds__(RDF_BLOCK) void rdf_counts_kernel(const RdfArgs a, 
     const int f = blockIdx.x, tile = blockIdx.y, b = blockIdx.z;
     const int beg = a.atom_ptr[b], n = a.atom_ptr[b + 1] - beg;
     if (n < 1 || beg < 0 || (int64_t)beg + n > a.n_atoms || tile * RDF_TILE >= n) return;  // (uniform over the workgroup)
-    const int S = a.n_species, G = S + 1;
-    int Sb = 0;
-    for (int g = 1; g <= S; ++g)
-        if (a.group_count[b * G + g] > 0) Sb = g;
+    const int S = a.n_species;
+    const int Sb = species_of(a.group_count, b, S);
     const int types = Sb * (Sb + 1) / 2;
     const int frame = a.frame0 + f * a.frame_step;
     double C[9], Ci[9];
     int M[3];
-    load_cell(a, b, frame, C);
-    if (!image_range(C, a.r_max, ALIGNN_TRAJ_MAX_IMAGE_RANGE, M)) {
+    if (!frame_cell(a.lattice, a.lattice_per_frame, a.n_structs, frame, b, a.r_max, ALIGNN_TRAJ_MAX_IMAGE_RANGE, C, Ci, M)) {
         if (threadIdx.x == 0) atomicOr(a.status, ALIGNN_TRAJ_STATUS_IMAGES);
         return;
     }
-    inv3_cof(C, Ci);
     const double* X = a.traj + 3 * ((int64_t)frame * a.n_atoms + beg);
     const int32_t* GR = a.group + beg;
     const int nb = a.n_bins, P = 1 + S * (S + 1) / 2;
@@ -97,25 +85,16 @@ __global__ __launch_bounds__(RDF_BLOCK) void rdf_counts_kernel(const RdfArgs a, 
                 const int t = hi * (hi - 1) / 2 + (lo - 1);
                 if (t < t0 || t >= t1) continue;
                 unsigned* H = hist + (t - t0) * nb;
-                double dp[3], df[3], d0[3];
+                double dp[3], d0[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) dp[c] = xj[jl][c] - xi[c];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    df[c] = row_dot(dp, Ci, c);
-                    df[c] -= rint(df[c]);
-                }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) d0[c] = row_dot(df, C, c);
+                wrap_difference(dp, C, Ci, d0);
                 for (int m0 = -M[0]; m0 <= M[0]; ++m0) {
-                    const double a0 = (double)m0;
                     for (int m1 = -M[1]; m1 <= M[1]; ++m1) {
-                        const double a1 = (double)m1;
-                        const double s0 = a0 * C[0] + a1 * C[3], s1 = a0 * C[1] + a1 * C[4], s2 = a0 * C[2] + a1 * C[5];
                         for (int m2 = -M[2]; m2 <= M[2]; ++m2) {
                             if (i == j && m0 == 0 && m1 == 0 && m2 == 0) continue;
-                            const double a2 = (double)m2;
-                            const double dx = d0[0] + (s0 + a2 * C[6]), dy = d0[1] + (s1 + a2 * C[7]), dz = d0[2] + (s2 + a2 * C[8]);
+                            const double dx = image_offset(d0, m0, m1, m2, C, 0), dy = image_offset(d0, m0, m1, m2, C, 1),
+                                         dz = image_offset(d0, m0, m1, m2, C, 2);
                             const double r = sqrt((dx * dx + dy * dy) + dz * dz);
                             if (!(r < r_max)) continue;
                             const double kb = floor(r * scale);
@@ -145,7 +124,7 @@ __global__ void rdf_volume_kernel(const RdfArgs a) {
     double sum = 0.0;
     for (int f = 0; f < a.n_frames; ++f) {
         double C[9];
-        load_cell(a, b, a.frame0 + f * a.frame_step, C);
+        load9(frame_lattice(a.lattice, a.lattice_per_frame, a.n_structs, a.frame0 + f * a.frame_step, b), C);
         sum = sum + fabs(det3_cof(C));
     }
     a.volume[b] = a.n_frames > 0 ? sum / (double)a.n_frames : 0.0;

@@ -14,8 +14,9 @@ tensors (``MDResult.traj_positions`` [n_frames, sum n_i, 3], ``traj_lattices`` u
 Conventions.  Frames (``start`` / ``stop`` / ``step``), groups (0 every atom, 1 .. S the species in ascending atomic number, at
 most 8), ``lattices`` ([B, 3, 3] or [F, B, 3, 3]) and the neighbour list of an atom - the (j, image) with r < ``r_cut``, (i, 0)
 left out, its own images included, at most 64, in the order j ascending, then the image lexicographic - are those of
-``alignn_amd.order``.  All geometry is in the centre atom's frame, on the displacements of its list entries, so a cell smaller
-than the cutoff is analysed through its own images.  The kernels (csrc/local_order.hip) are float64 without contraction, without
+``alignn_amd.order``: the inputs are checked by alignn_amd/_trajectory_inputs.py and the list is built by csrc/neighbor_list.h,
+for both.  All geometry is in the centre atom's frame, on the displacements of its list entries, so a cell smaller than the
+cutoff is analysed through its own images.  The kernels (csrc/local_order.hip) are float64 without contraction, without
 floating-point atomics, every sum in a fixed order over the atom's own list: a structure's numbers are the same bits alone, in a
 batch and at any place of it.  Read back from the device: the status word of each call.  tests/local_ref.py restates the rules
 in numpy; the entry points and every formula are in include/alignn_local.h, read here with the reader of alignn_amd/_abi.py.
@@ -28,7 +29,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
 from dataclasses import dataclass
 from fractions import Fraction
 from functools import lru_cache
@@ -38,8 +38,7 @@ import numpy as np
 import torch
 
 from . import _abi, _lib, order
-from .order import _cells, _cutoffs, _raise_status
-from .trajectory import _frames, _groups, _traj
+from ._trajectory_inputs import _cutoffs, _raise_status, degrees, inputs
 
 __all__ = ["cna", "bond_order", "CNAResult", "BondOrderResult", "CLASSES", "SIGNATURES_COUNTED", "wigner_3j_table", "ylm_norms"]
 
@@ -158,15 +157,6 @@ def ylm_norms() -> np.ndarray:
 
 
 # --- the functions -----------------------------------------------------------------------------------------------------------------
-def _inputs(who, traj, lattices, ns, start, stop, step):
-    traj, ns = _traj(who, "traj", traj, ns)
-    B, F = len(ns), traj.shape[0]
-    if max(ns) > 65535:
-        raise ValueError(f"{who}: a structure of {max(ns)} atoms; a call takes at most 65535 per structure")
-    lattices = _cells(who, lattices, traj, ((B, 3, 3), (F, B, 3, 3)))
-    return traj, ns, lattices, _frames(who, F, start, stop, step)
-
-
 def cna(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], species: Optional[Sequence] = None, *, r_cut,
         adaptive: bool = False, start: Optional[int] = None, stop: Optional[int] = None, step: Optional[int] = None) -> CNAResult:
     """Common-neighbour analysis of B structures over the frames ``start:stop:step`` of ``traj`` [F, sum ns, 3] (float64 on the
@@ -190,25 +180,21 @@ def cna(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], species: 
     who = "cna"
     if not isinstance(adaptive, (bool, np.bool_)):
         raise ValueError(f"{who}: adaptive is one bool, got {adaptive!r}")
-    traj, ns, lattices, (frame0, fstep, used) = _inputs(who, traj, lattices, ns, start, stop, step)
-    B, N, F = len(ns), sum(ns), traj.shape[0]
-    dev = traj.device
+    sel = inputs(who, traj, lattices, ns, start, stop, step)
+    B, N, used, dev = len(sel.ns), sum(sel.ns), sel.n_frames, sel.traj.device
     lib = _load()
-    with _lib.device_guard(traj):
+    with _lib.device_guard(sel.traj):
         cut = _cutoffs(who, r_cut, B, dev)
-        ptr, group, count, S, lists = _groups(who, ns, species, dev)
+        S, lists = sel.groups(species)
         structure = torch.zeros(used, N, dtype=torch.int32, device=dev)
         signatures = torch.zeros(used, N, N_SIGNATURES, dtype=torch.int32, device=dev)
         n_neighbors = torch.zeros(used, N, dtype=torch.int32, device=dev)
         counts = torch.zeros(B, S + 1, used, N_CLASSES, dtype=torch.int64, device=dev)
         fraction = torch.zeros(B, S + 1, used, N_CLASSES, dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        args = CnaArgs(traj=traj.data_ptr(), lattice=lattices.data_ptr(), atom_ptr=ptr.data_ptr(), group=group.data_ptr(),
-                       group_count=count.data_ptr(), r_cut=cut.data_ptr(), structure=structure.data_ptr(),
-                       signature_counts=signatures.data_ptr(), n_neighbors=n_neighbors.data_ptr(), counts=counts.data_ptr(),
-                       fraction=fraction.data_ptr(), status=status.data_ptr(), n_structs=B, n_atoms=N, max_atoms=max(ns), n_species=S,
-                       n_total_frames=F, frame0=frame0, frame_step=fstep, n_frames=used, lattice_per_frame=int(lattices.ndim == 4),
-                       adaptive=int(adaptive))
+        args = CnaArgs(r_cut=cut.data_ptr(), structure=structure.data_ptr(), signature_counts=signatures.data_ptr(),
+                       n_neighbors=n_neighbors.data_ptr(), counts=counts.data_ptr(), fraction=fraction.data_ptr(),
+                       adaptive=int(adaptive), **sel.fields(CnaArgs, status))
         _lib.check(lib.alignn_local_cna(C.byref(args), _lib.stream()), "local_cna")
         _lib.check(lib.alignn_local_cna_counts(C.byref(args), _lib.stream()), "local_cna_counts")
         _raise_status(who, int(status.item()))
@@ -229,20 +215,15 @@ def bond_order(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], sp
     Two passes over chunks of frames: the first writes the q_lm of the chunk, the second builds the same lists again and gathers
     them; no list is stored, and the q_lm of at most ``QLM_SCRATCH_BYTES`` (a whole frame at the least) at a time."""
     who = "bond_order"
-    ok = isinstance(ls, (tuple, list)) and 1 <= len(ls) <= MAX_LS and all(
-        isinstance(l, numbers.Integral) and not isinstance(l, (bool, np.bool_)) and 1 <= l <= MAX_L for l in ls)
-    if not ok or len(set(int(l) for l in ls)) != len(ls):
-        raise ValueError(f"{who}: ls must be 1 to {MAX_LS} distinct integers in 1 .. {MAX_L}, got {ls!r}")
-    ls = tuple(int(l) for l in ls)
+    ls = degrees(who, ls, MAX_LS, MAX_L)
     if not isinstance(average, (bool, np.bool_)):
         raise ValueError(f"{who}: average is one bool, got {average!r}")
-    traj, ns, lattices, (frame0, fstep, used) = _inputs(who, traj, lattices, ns, start, stop, step)
-    B, N, F, L = len(ns), sum(ns), traj.shape[0], len(ls)
-    dev = traj.device
+    sel = inputs(who, traj, lattices, ns, start, stop, step)
+    B, N, used, dev, L = len(sel.ns), sum(sel.ns), sel.n_frames, sel.traj.device, len(ls)
     lib = _load()
-    with _lib.device_guard(traj):
+    with _lib.device_guard(sel.traj):
         cut = _cutoffs(who, r_cut, B, dev)
-        ptr, group, count, S, lists = _groups(who, ns, species, dev)
+        S, lists = sel.groups(species)
         f64 = lambda: torch.zeros(used, N, L, dtype=torch.float64, device=dev)
         out = {k: f64() for k in ("s", "t", "q", "w")}
         if average:
@@ -256,12 +237,10 @@ def bond_order(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], sp
         per_frame = N * L * M_STRIDE * 16  # the bytes of a frame's q_lm
         chunk = max(1, min(used, QLM_SCRATCH_BYTES // per_frame))
         qlm = torch.empty(chunk, N, L, M_STRIDE, 2, dtype=torch.float64, device=dev)
-        args = BondArgs(traj=traj.data_ptr(), lattice=lattices.data_ptr(), atom_ptr=ptr.data_ptr(), group=group.data_ptr(),
-                        group_count=count.data_ptr(), r_cut=cut.data_ptr(), ynorm=ynorm.data_ptr(), w3j=w3j.data_ptr(),
-                        qlm=qlm.data_ptr(), n_neighbors=n_neighbors.data_ptr(), status=status.data_ptr(), n_structs=B, n_atoms=N,
-                        max_atoms=max(ns), n_species=S, n_total_frames=F, frame0=frame0, frame_step=fstep, n_frames=used,
-                        lattice_per_frame=int(lattices.ndim == 4), average=int(average), n_ls=L,
-                        **{k: v.data_ptr() for k, v in out.items()}, **{f"l{u}": l for u, l in enumerate(ls)})
+        degree = {f"l{u}": l for u, l in enumerate(ls)}
+        args = BondArgs(r_cut=cut.data_ptr(), ynorm=ynorm.data_ptr(), w3j=w3j.data_ptr(), qlm=qlm.data_ptr(),
+                        n_neighbors=n_neighbors.data_ptr(), average=int(average), n_ls=L, **{k: v.data_ptr() for k, v in out.items()},
+                        **degree, **sel.fields(BondArgs, status))
         for chunk0 in range(0, used, chunk):
             args.chunk0, args.chunk_frames = chunk0, min(chunk, used - chunk0)
             _lib.check(lib.alignn_local_bond_qlm(C.byref(args), _lib.stream()), "local_bond_qlm")
@@ -273,10 +252,8 @@ def bond_order(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], sp
             if name not in out:
                 continue
             one = torch.zeros(B, S + 1, used, L, dtype=torch.float64, device=dev)
-            margs = order.AngleArgs(atom_ptr=ptr.data_ptr(), group=group.data_ptr(), group_count=count.data_ptr(),
-                                    q=out[name].data_ptr(), mean=one.data_ptr(), n_structs=B, n_atoms=N, max_atoms=max(ns), n_species=S,
-                                    n_bins=1, n_total_frames=F, frame0=frame0, frame_step=fstep, n_frames=used, n_ls=L,
-                                    **{f"l{u}": l for u, l in enumerate(ls)})
+            margs = order.AngleArgs(q=out[name].data_ptr(), mean=one.data_ptr(), n_bins=1, n_ls=L, **degree,
+                                    **sel.fields(order.AngleArgs, status))
             _lib.check(olib.alignn_order_steinhardt_mean(C.byref(margs), _lib.stream()), "order_steinhardt_mean")
             mean[:, :, :, k] = one
         _raise_status(who, int(status.item()))

@@ -12,10 +12,10 @@ tensors (``MDResult.traj_positions`` [n_frames, sum n_i, 3], ``traj_lattices`` u
   Ashcroft-Langreth partials, per vector and in shells of |q|.
 
 Conventions.  Frames (``start`` / ``stop`` / ``step``), groups (0 every atom, 1 .. S the species in ascending atomic number, at
-most 8), ``lattices`` ([B, 3, 3] or [F, B, 3, 3]) and the pair rows (``pair_row``) are those of ``alignn_amd.trajectory``; so is
-the pair geometry: the fractional difference wrapped by ``rint``, the images |m_k| <= floor(r_cut / h_k + 1/2) of each frame's
-own cell, an atom's own images included.  The neighbours of an atom are the (j, image) with r < ``r_cut``, at most 64.  The
-kernels (csrc/order.hip) are float64 without contraction, the angle histogram is summed with integer atomics (exact), every
+most 8), ``lattices`` ([B, 3, 3] or [F, B, 3, 3]) and the pair rows (``pair_row``) are those of ``alignn_amd.trajectory``, checked
+by the functions of alignn_amd/_trajectory_inputs.py that all three modules share; so is the pair geometry: the fractional
+difference wrapped by ``rint``, the images |m_k| <= floor(r_cut / h_k + 1/2) of each frame's own cell, an atom's own images
+included.  The neighbours of an atom are the (j, image) with r < ``r_cut``, at most 64.  The kernels (csrc/order.hip) are float64 without contraction, the angle histogram is summed with integer atomics (exact), every
 floating-point sum has a fixed order over the structure's own rows, frames and vectors: a structure's numbers are the same bits
 alone, in a batch and at any place of it.  Read back from the device: the status word of each call and, for
 ``structure_factor``, the number of reciprocal vectors of every structure (it sizes the lists).  tests/order_ref.py restates the
@@ -28,7 +28,6 @@ the w_l invariants and common-neighbour analysis are in ``alignn_amd.local_order
 from __future__ import annotations
 
 import ctypes as C
-import numbers
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -36,7 +35,8 @@ import numpy as np
 import torch
 
 from . import _abi, _lib
-from .trajectory import _frames, _groups, _positive, _traj, pair_row  # noqa: F401  (pair_row numbers the rows of the results)
+from ._trajectory_inputs import _cutoffs, _positive, _raise_status, bins, degrees, inputs
+from .trajectory import pair_row  # noqa: F401  (pair_row numbers the rows of the results)
 
 __all__ = ["adf", "steinhardt", "structure_factor", "ADFResult", "SteinhardtResult", "SQResult", "MAX_NEIGHBORS", "MAX_L",
            "MAX_HKL", "MAX_BINS", "MAX_IMAGE_RANGE"]
@@ -118,66 +118,19 @@ class SQResult:
     q_max: float
 
 
-# --- checks (host) -----------------------------------------------------------------------------------------------------------------
-def _bins(who: str, n_bins) -> int:
-    if not isinstance(n_bins, numbers.Integral) or isinstance(n_bins, (bool, np.bool_)) or not 1 <= n_bins <= MAX_BINS:
-        raise ValueError(f"{who}: n_bins must be 1 .. {MAX_BINS}, got {n_bins!r}")
-    return int(n_bins)
-
-
-def _cutoffs(who: str, r_cut, B: int, dev) -> torch.Tensor:
-    """One number, B numbers, or a float64 tensor [B] on the device -> [B] on the device."""
-    if isinstance(r_cut, torch.Tensor):
-        if r_cut.dtype != torch.float64 or r_cut.device != dev or tuple(r_cut.shape) != (B,):
-            raise ValueError(f"{who}: r_cut as a tensor must be float64 [{B}] on the trajectory's device, got {r_cut.dtype} "
-                             f"{tuple(r_cut.shape)} on {r_cut.device}")
-        return r_cut.contiguous()
-    if isinstance(r_cut, (list, tuple, np.ndarray)):
-        if len(r_cut) != B:
-            raise ValueError(f"{who}: r_cut needs one number or one per structure ({B}), got {len(r_cut)}")
-        values = [_positive(who, f"r_cut[{b}]", v) for b, v in enumerate(r_cut)]
-    else:
-        values = [_positive(who, "r_cut", r_cut)] * B
-    return torch.tensor(values, dtype=torch.float64, device=dev)
-
-
-def _cells(who: str, lattices, traj, shapes) -> torch.Tensor:
-    if not isinstance(lattices, torch.Tensor) or lattices.dtype != torch.float64 or lattices.device != traj.device:
-        raise TypeError(f"{who}: lattices must be a float64 tensor on the trajectory's device")
-    if tuple(lattices.shape) not in shapes:
-        raise ValueError(f"{who}: lattices must be " + " or ".join(str(list(s)) for s in shapes) + f", got {tuple(lattices.shape)}")
-    return lattices.contiguous()
-
-
-def _raise_status(who: str, word: int):
-    if word & STATUS_IMAGES:
-        raise ValueError(f"{who}: r_cut needs periodic images beyond +-{MAX_IMAGE_RANGE} cells along an axis of some frame's cell "
-                         "(or a cell is singular, or an r_cut is not a finite number > 0): lower r_cut or analyse a supercell")
-    if word & STATUS_NEIGHBORS:
-        raise ValueError(f"{who}: an atom has more than {MAX_NEIGHBORS} neighbours inside r_cut: lower r_cut (it is meant to end "
-                         "between the first and the second shell)")
-
-
+# --- the call of the angle functions  ----------------------------------------------------------------------------------------------
 def _angles(who, traj, lattices, ns, species, r_cut, n_bins, ls, start, stop, step):
     """The call of ``alignn_order_angles`` both public functions share: ``n_bins`` given -> the histogram, ``ls`` given -> q."""
-    traj, ns = _traj(who, "traj", traj, ns)
-    B, N, F = len(ns), sum(ns), traj.shape[0]
-    if max(ns) > 65535:
-        raise ValueError(f"{who}: a structure of {max(ns)} atoms; a call takes at most 65535 per structure")
-    lattices = _cells(who, lattices, traj, ((B, 3, 3), (F, B, 3, 3)))
-    frame0, fstep, used = _frames(who, F, start, stop, step)
-    dev = traj.device
+    sel = inputs(who, traj, lattices, ns, start, stop, step)
+    B, N, used, dev = len(sel.ns), sum(sel.ns), sel.n_frames, sel.traj.device
     lib = _load()
     out = {}
-    with _lib.device_guard(traj):
+    with _lib.device_guard(sel.traj):
         cut = _cutoffs(who, r_cut, B, dev)
-        ptr, group, count, S, lists = _groups(who, ns, species, dev)
+        S, lists = sel.groups(species)
         P = 1 + S * (S + 1) // 2
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        args = AngleArgs(traj=traj.data_ptr(), lattice=lattices.data_ptr(), atom_ptr=ptr.data_ptr(), group=group.data_ptr(),
-                         group_count=count.data_ptr(), r_cut=cut.data_ptr(), status=status.data_ptr(), n_structs=B, n_atoms=N,
-                         max_atoms=max(ns), n_species=S, n_bins=1, n_total_frames=F, frame0=frame0, frame_step=fstep,
-                         n_frames=used, lattice_per_frame=int(lattices.ndim == 4))
+        args = AngleArgs(r_cut=cut.data_ptr(), n_bins=1, **sel.fields(AngleArgs, status))
         if n_bins is not None:
             out["counts"] = torch.zeros(B, S + 1, P, n_bins, dtype=torch.int64, device=dev)
             out["adf"] = torch.empty(B, S + 1, P, n_bins, dtype=torch.float64, device=dev)
@@ -213,7 +166,7 @@ def adf(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], species: 
     ``min(floor(theta n_bins / pi), n_bins - 1)``.  ``n_bins``: 1 .. 1024.  A ``ValueError`` when r_cut needs more than 8 images
     along an axis of some cell, or gives some atom more than 64 neighbours."""
     who = "adf"
-    n_bins = _bins(who, n_bins)
+    n_bins = bins(who, n_bins, MAX_BINS)
     out, lists, cut, used = _angles(who, traj, lattices, ns, species, r_cut, n_bins, None, start, stop, step)
     return ADFResult(theta=out["theta"], counts=out["counts"], adf=out["adf"], species=lists, r_cut=cut, n_frames=used)
 
@@ -228,11 +181,7 @@ def steinhardt(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], sp
     before the square root.  Perfect first shells: fcc q4 0.19094 q6 0.57452, hcp 0.09722 0.48476, bcc (8 neighbours) 0.50918
     0.62854, simple cubic 0.76376 0.35355."""
     who = "steinhardt"
-    ok = isinstance(ls, (tuple, list)) and 1 <= len(ls) <= MAX_LS and all(
-        isinstance(l, numbers.Integral) and not isinstance(l, (bool, np.bool_)) and 1 <= l <= MAX_L for l in ls)
-    if not ok or len(set(int(l) for l in ls)) != len(ls):
-        raise ValueError(f"{who}: ls must be 1 to {MAX_LS} distinct integers in 1 .. {MAX_L}, got {ls!r}")
-    ls = tuple(int(l) for l in ls)
+    ls = degrees(who, ls, MAX_LS, MAX_L)
     out, lists, cut, used = _angles(who, traj, lattices, ns, species, r_cut, None, ls, start, stop, step)
     return SteinhardtResult(q=out["q"], n_neighbors=out["n_neighbors"], mean=out["mean"], ls=ls, species=lists, r_cut=cut,
                             n_frames=used)
@@ -248,25 +197,17 @@ def structure_factor(traj: torch.Tensor, lattice: torch.Tensor, ns: Sequence[int
     frames are summed in chunks of 64 and the chunks in order, so the bits do not depend on the launch.  ``n_bins``: 1 .. 1024
     shells over [0, q_max).  A per-frame lattice [F, B, 3, 3] is a ``ValueError``: the vectors would move with the frame."""
     who = "structure_factor"
-    traj, ns = _traj(who, "traj", traj, ns)
-    B, N, F = len(ns), sum(ns), traj.shape[0]
-    q_max, n_bins = _positive(who, "q_max", q_max), _bins(who, n_bins)
-    if isinstance(lattice, torch.Tensor) and lattice.ndim == 4:
-        raise ValueError(f"{who}: a per-frame lattice {tuple(lattice.shape)} is not supported: S(q) is taken on the reciprocal "
-                         f"lattice of one fixed cell per structure, [{B}, 3, 3]")
-    lattice = _cells(who, lattice, traj, ((B, 3, 3),))
-    frame0, fstep, used = _frames(who, F, start, stop, step)
-    dev = traj.device
+    q_max, n_bins = _positive(who, "q_max", q_max), bins(who, n_bins, MAX_BINS)
+    sel = inputs(who, traj, lattice, ns, start, stop, step, per_frame=False, atom_limit=False)
+    B, used, dev = len(sel.ns), sel.n_frames, sel.traj.device
     lib = _load()
     i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
-    with _lib.device_guard(traj):
-        ptr, group, count, S, lists = _groups(who, ns, species, dev)
+    with _lib.device_guard(sel.traj):
+        S, lists = sel.groups(species)
         P = 1 + S * (S + 1) // 2
         words = i32(B + 1)  # the vectors of every structure, then the status word: one copy back
-        args = SqArgs(traj=traj.data_ptr(), lattice=lattice.data_ptr(), atom_ptr=ptr.data_ptr(), group=group.data_ptr(),
-                      group_count=count.data_ptr(), n_vec=words.data_ptr(), status=words[B:].data_ptr(), q_max=q_max, n_structs=B,
-                      n_atoms=N, n_species=S, n_bins=n_bins, n_total_frames=F, frame0=frame0, frame_step=fstep, n_frames=used)
+        args = SqArgs(n_vec=words.data_ptr(), q_max=q_max, n_bins=n_bins, **sel.fields(SqArgs, words[B:]))
         _lib.check(lib.alignn_order_sq_vectors(C.byref(args), _lib.stream()), "order_sq_vectors")
         host = words.cpu().numpy()
         if int(host[B]) & STATUS_HKL:

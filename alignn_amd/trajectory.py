@@ -19,7 +19,8 @@ count the selected frames.  The kernels (csrc/trajectory.hip) are float64 withou
 integer atomics (exact), every floating-point sum has a fixed order over the structure's own rows and frames: a structure's
 numbers are the same bits alone, in a batch and at any place of it.  Nothing is read back from the device but the status word of
 ``rdf``.  tests/traj_ref.py restates the formulas in numpy; the entry points are declared in include/alignn_traj.h, read here
-with the reader of alignn_amd/_abi.py.
+with the reader of alignn_amd/_abi.py.  The checks of these conventions - frames, the trajectory tensor, cells, groups - are in
+alignn_amd/_trajectory_inputs.py, which ``alignn_amd.order`` and ``alignn_amd.local_order`` use as well.
 
 Units.  Positions in A, momenta in amu A per ASE time unit (what ``run_md`` records), so the VACF is in A^2 per ASE time unit
 squared.  ``dtau_fs`` is the time between two selected frames in fs: ``timestep * interval * step``.  Diffusion coefficients are
@@ -41,6 +42,7 @@ import torch
 
 from . import _abi, _lib
 from ._structures import host
+from ._trajectory_inputs import _frames, _groups, _masses, _positive, _traj, bins, inputs
 from .dynamics import FS
 
 __all__ = ["rdf", "msd", "vacf", "vdos", "diffusion", "green_kubo", "analyze_md", "pair_row", "RDFResult", "MSDResult",
@@ -153,80 +155,6 @@ class TrajectoryAnalysis:
     diffusion: DiffusionResult
 
 
-# --- checks (host) -----------------------------------------------------------------------------------------------------------------
-def _frames(who: str, F: int, start, stop, step) -> Tuple[int, int, int]:
-    """The slice ``start:stop:step`` of F frames -> (first frame, step, frames used)."""
-    for name, v in (("start", start), ("stop", stop), ("step", step)):
-        if v is not None and (not isinstance(v, numbers.Integral) or isinstance(v, (bool, np.bool_))):
-            raise ValueError(f"{who}: {name} must be an int or None, got {v!r}")
-    if step is not None and step < 1:
-        raise ValueError(f"{who}: step must be >= 1, got {step}")
-    r = range(F)[slice(start, stop, step)]
-    return (r.start if len(r) else 0), r.step, len(r)
-
-
-def _traj(who: str, name: str, traj, ns) -> Tuple[torch.Tensor, List[int]]:
-    ns = [int(n) for n in ns]
-    if not ns or min(ns) < 1:
-        raise ValueError(f"{who}: ns needs the atom count (>= 1) of at least one structure, got {ns}")
-    if len(ns) > 65535:
-        raise ValueError(f"{who}: {len(ns)} structures; a call takes at most 65535")
-    if not isinstance(traj, torch.Tensor) or traj.dtype != torch.float64 or not traj.is_cuda:
-        raise TypeError(f"{who}: {name} must be a float64 tensor on the GPU (what run_md records)")
-    if traj.ndim != 3 or tuple(traj.shape[1:]) != (sum(ns), 3):
-        raise ValueError(f"{who}: {name} must be [n_frames, {sum(ns)}, 3], got {tuple(traj.shape)}")
-    if traj.shape[0] >= 2 ** 31 or traj.shape[1] >= 2 ** 31 // 3:
-        raise ValueError(f"{who}: {name} has {traj.shape[0]} frames of {traj.shape[1]} rows; a call takes fewer than 2^31 of each")
-    return traj.contiguous(), ns
-
-
-def _groups(who: str, ns: List[int], species, dev):
-    """-> (atom_ptr [B + 1], group [N] 1-based rank of the row's species in its structure, group_count [B, S + 1], S, the
-    species lists)."""
-    B = len(ns)
-    if species is None:
-        ranks, lists = [np.ones(n, dtype=np.int32) for n in ns], [[0]] * B
-    else:
-        if len(species) != B:
-            raise ValueError(f"{who}: species needs one array of atomic numbers per structure ({B}) or None, got {len(species)}")
-        ranks, lists = [], []
-        for b, z in enumerate(species):
-            z = host(z)
-            if z.shape != (ns[b],) or z.dtype.kind not in "iu":
-                raise ValueError(f"{who}: species[{b}] is {z.dtype} {z.shape}, need integers [{ns[b]}]")
-            uniq, inverse = np.unique(z, return_inverse=True)
-            if len(uniq) > MAX_SPECIES:
-                raise ValueError(f"{who}: structure {b} has {len(uniq)} species; at most {MAX_SPECIES} are supported")
-            ranks.append((inverse.reshape(-1) + 1).astype(np.int32))
-            lists.append([int(u) for u in uniq])
-    S = max(len(l) for l in lists)
-    count = np.zeros((B, S + 1), dtype=np.int32)
-    for b in range(B):
-        count[b, 0] = ns[b]
-        count[b, 1:1 + len(lists[b])] = np.bincount(ranks[b], minlength=len(lists[b]) + 1)[1:]
-    ptr = np.concatenate([[0], np.cumsum(ns)]).astype(np.int32)
-    dev_i32 = lambda x: torch.tensor(np.ascontiguousarray(x), dtype=torch.int32, device=dev)
-    return dev_i32(ptr), dev_i32(np.concatenate(ranks)), dev_i32(count), S, [list(l) for l in lists]
-
-
-def _masses(who: str, masses, ns, dev) -> torch.Tensor:
-    if len(masses) != len(ns):
-        raise ValueError(f"{who}: masses needs one array per structure ({len(ns)}), got {len(masses)}")
-    for b, x in enumerate(masses):
-        if host(x).shape != (ns[b],):
-            raise ValueError(f"{who}: masses[{b}] is {host(x).shape}, need [{ns[b]}]")
-    m = torch.cat([torch.as_tensor(host(x)).to(torch.float64) for x in masses])
-    if not bool(torch.isfinite(m).all() and (m > 0).all()):
-        raise ValueError(f"{who}: masses must be finite and > 0")
-    return m.to(dev)
-
-
-def _positive(who: str, name: str, v) -> float:
-    if not isinstance(v, numbers.Real) or isinstance(v, (bool, np.bool_)) or not np.isfinite(v) or v <= 0:
-        raise ValueError(f"{who}: {name} must be a finite number > 0, got {v!r}")
-    return float(v)
-
-
 # --- the functions -----------------------------------------------------------------------------------------------------------------
 def rdf(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], species: Optional[Sequence] = None, *, r_max: float = 8.0,
         n_bins: int = 200, start: Optional[int] = None, stop: Optional[int] = None, step: Optional[int] = None) -> RDFResult:
@@ -240,31 +168,19 @@ def rdf(traj: torch.Tensor, lattices: torch.Tensor, ns: Sequence[int], species: 
     back).  r = sqrt((dx dx + dy dy) + dz dz) falls into bin floor(r (n_bins / r_max)); r >= r_max is dropped.  ``n_bins``: 1 ..
     4096."""
     who = "rdf"
-    traj, ns = _traj(who, "traj", traj, ns)
-    B, N, F = len(ns), sum(ns), traj.shape[0]
-    r_max = _positive(who, "r_max", r_max)
-    if not isinstance(n_bins, numbers.Integral) or not 1 <= n_bins <= MAX_BINS:
-        raise ValueError(f"{who}: n_bins must be 1 .. {MAX_BINS}, got {n_bins!r}")
-    if not isinstance(lattices, torch.Tensor) or lattices.dtype != torch.float64 or lattices.device != traj.device:
-        raise TypeError(f"{who}: lattices must be a float64 tensor on the trajectory's device")
-    if tuple(lattices.shape) not in ((B, 3, 3), (F, B, 3, 3)):
-        raise ValueError(f"{who}: lattices must be [{B}, 3, 3] or [{F}, {B}, 3, 3], got {tuple(lattices.shape)}")
-    frame0, fstep, used = _frames(who, F, start, stop, step)
-    dev = traj.device
+    r_max, n_bins = _positive(who, "r_max", r_max), bins(who, n_bins, MAX_BINS, bool_ok=True)
+    sel = inputs(who, traj, lattices, ns, start, stop, step, atom_limit=False)
+    B, used, dev = len(sel.ns), sel.n_frames, sel.traj.device
     lib = _load()
-    with _lib.device_guard(traj):
-        ptr, group, count, S, lists = _groups(who, ns, species, dev)
+    with _lib.device_guard(sel.traj):
+        S, lists = sel.groups(species)
         P = 1 + S * (S + 1) // 2
-        lattices = lattices.contiguous()
         counts = torch.zeros(B, P, n_bins, dtype=torch.int64, device=dev)
         g, coord = torch.empty(B, P, n_bins, dtype=torch.float64, device=dev), torch.empty(B, P, n_bins, dtype=torch.float64, device=dev)
         volume, centres = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(n_bins, dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        args = RdfArgs(traj=traj.data_ptr(), lattice=lattices.data_ptr(), atom_ptr=ptr.data_ptr(), group=group.data_ptr(),
-                       group_count=count.data_ptr(), counts=counts.data_ptr(), g=g.data_ptr(), coord=coord.data_ptr(),
-                       volume=volume.data_ptr(), centres=centres.data_ptr(), status=status.data_ptr(), r_max=r_max, n_structs=B,
-                       n_atoms=N, max_atoms=max(ns), n_species=S, n_bins=int(n_bins), n_total_frames=F, frame0=frame0,
-                       frame_step=fstep, n_frames=used, lattice_per_frame=int(lattices.ndim == 4))
+        args = RdfArgs(counts=counts.data_ptr(), g=g.data_ptr(), coord=coord.data_ptr(), volume=volume.data_ptr(),
+                       centres=centres.data_ptr(), r_max=r_max, n_bins=int(n_bins), **sel.fields(RdfArgs, status))
         _lib.check(lib.alignn_traj_rdf_counts(C.byref(args), _lib.stream()), "traj_rdf_counts")
         _lib.check(lib.alignn_traj_rdf_normalise(C.byref(args), _lib.stream()), "traj_rdf_normalise")
         if int(status.item()) & STATUS_IMAGES:

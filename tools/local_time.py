@@ -88,7 +88,7 @@ line("bond_order l = 4, 6, average=False (pass 2 builds no list)", lambda: bond_
 bo = bond_order(pos, cells, ns, species, r_cut=args.rcut, ls=(4, 6))
 L, N = 2, B * n
 lib = local_order._load()
-from alignn_amd.trajectory import _groups
+from alignn_amd._trajectory_inputs import _groups
 ptr, group, count, S, _ = _groups("local_time", ns, species, pos.device)
 cut = torch.full((B,), args.rcut, dtype=torch.float64, device=dev)
 table = np.zeros((L, local_order.W3J_STRIDE))
