@@ -67,16 +67,17 @@ extern "C" {
  * sums; fraction = counts / N_a (a group without members: 0).
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_local_cna_args {
-    const double* traj;         /* [n_total_frames][n_atoms][3] */
-    const double* lattice;      /* [B][3][3] (lattice_per_frame 0) or [n_total_frames][B][3][3] (1), row-major */
+    const double* traj;         /* [n_total_frames][n_atoms][3]   (_local_cna) */
+    const double* lattice;      /* [B][3][3] (lattice_per_frame 0) or [n_total_frames][B][3][3] (1), row-major   (_local_cna) */
     const int32_t* atom_ptr;    /* [B + 1], 0 first */
     const int32_t* group;       /* [n_atoms] */
     const int32_t* group_count; /* [B][S + 1] */
-    const double* r_cut;        /* [B] */
-    int32_t* structure;         /* [n_frames][n_atoms] */
+    const double* r_cut;        /* [B]   (_local_cna) */
+    int32_t* structure;         /* [n_frames][n_atoms]   (these three: _local_cna writes every element of a frame without
+                                 * ALIGNN_LOCAL_STATUS_IMAGES - a skipped frame is left to the caller's zeros; _local_cna_counts reads structure) */
     int32_t* signature_counts;  /* [n_frames][n_atoms][ALIGNN_LOCAL_SIGNATURES] */
     int32_t* n_neighbors;       /* [n_frames][n_atoms] */
-    int64_t* counts;            /* [B][S + 1][n_frames][ALIGNN_LOCAL_CLASSES]   (_local_cna_counts) */
+    int64_t* counts;            /* [B][S + 1][n_frames][ALIGNN_LOCAL_CLASSES]   (_local_cna_counts writes every element of these two) */
     double* fraction;           /* [B][S + 1][n_frames][ALIGNN_LOCAL_CLASSES]   (_local_cna_counts) */
     int32_t* status;            /* [1], bits are ORed in (_local_cna) */
     int n_structs;              /* B >= 0 */
@@ -124,10 +125,11 @@ typedef struct alignn_local_bond_args {
     const int32_t* group;       /* [n_atoms] */
     const int32_t* group_count; /* [B][S + 1] */
     const double* r_cut;        /* [B] */
-    const double* ynorm;        /* [ALIGNN_LOCAL_MAX_L + 1][ALIGNN_LOCAL_M_STRIDE] */
+    const double* ynorm;        /* [ALIGNN_LOCAL_MAX_L + 1][ALIGNN_LOCAL_M_STRIDE]   (_local_bond_qlm) */
     const double* w3j;          /* [n_ls][ALIGNN_LOCAL_W3J_STRIDE]   (_local_bond_finish) */
     double* qlm;                /* [chunk_frames][n_atoms][n_ls][ALIGNN_LOCAL_M_STRIDE][2] */
-    double* s;                  /* [n_frames][n_atoms][n_ls]   (these eight: _local_bond_finish) */
+    double* s;                  /* [n_frames][n_atoms][n_ls]   (these eight: _local_bond_finish writes the frames of the chunk that have no
+                                 * ALIGNN_LOCAL_STATUS_IMAGES; a skipped frame is left to the caller's zeros) */
     double* t;
     double* q;
     double* w;
@@ -135,7 +137,7 @@ typedef struct alignn_local_bond_args {
     double* t_avg;
     double* q_avg;
     double* w_avg;
-    int32_t* n_neighbors;       /* [n_frames][n_atoms]   (_local_bond_qlm) */
+    int32_t* n_neighbors;       /* [n_frames][n_atoms]   (_local_bond_qlm writes the frames of the chunk that are not skipped) */
     int32_t* status;            /* [1], bits are ORed in (_local_bond_qlm) */
     int n_structs;              /* B >= 0 */
     int n_atoms;                /* atom_ptr[B] >= 0 */

@@ -65,17 +65,18 @@ extern "C" {
  * non-zero bins to counts with integer atomic adds.
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_order_angle_args {
-    const double* traj;         /* [n_total_frames][n_atoms][3] */
-    const double* lattice;      /* [B][3][3] (lattice_per_frame 0) or [n_total_frames][B][3][3] (1), row-major */
-    const int32_t* atom_ptr;    /* [B + 1], 0 first */
+    const double* traj;         /* [n_total_frames][n_atoms][3]   (_order_angles) */
+    const double* lattice;      /* [B][3][3] (lattice_per_frame 0) or [n_total_frames][B][3][3] (1), row-major   (_order_angles) */
+    const int32_t* atom_ptr;    /* [B + 1], 0 first   (these three: _order_angles, _order_steinhardt_mean) */
     const int32_t* group;       /* [n_atoms] */
     const int32_t* group_count; /* [B][S + 1] */
-    const double* r_cut;        /* [B] */
-    int64_t* counts;            /* [B][S + 1][P][n_bins], or NULL */
+    const double* r_cut;        /* [B]   (_order_angles) */
+    int64_t* counts;            /* [B][S + 1][P][n_bins], or NULL   (_order_angles adds; _order_adf_finish writes the marginal rows) */
     double* adf;                /* [B][S + 1][P][n_bins]   (_order_adf_finish) */
     double* theta;              /* [n_bins]                (_order_adf_finish) */
-    double* q;                  /* [n_frames][n_atoms][n_ls], or NULL */
-    int32_t* n_neighbors;       /* [n_frames][n_atoms]     (with q) */
+    double* q;                  /* [n_frames][n_atoms][n_ls], or NULL   (_order_angles writes every element of a frame without
+                                 * ALIGNN_ORDER_STATUS_IMAGES - a frame that is not counted is left to the caller's zeros; _order_steinhardt_mean reads) */
+    int32_t* n_neighbors;       /* [n_frames][n_atoms]     (with q: _order_angles writes it where it writes q) */
     double* mean;               /* [B][S + 1][n_frames][n_ls]   (_order_steinhardt_mean) */
     int32_t* status;            /* [1], bits are ORed in (_order_angles) */
     int n_structs;              /* B >= 0 */
@@ -131,17 +132,18 @@ size_t alignn_order_angle_args_size(void); /* a binding checks its own packing a
  * n_vectors[b][k] their number, centres[k] = (k + 1/2) (q_max / n_bins).
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_order_sq_args {
-    const double* traj;         /* [n_total_frames][n_atoms][3] */
-    const double* lattice;      /* [B][3][3], row-major */
-    const int32_t* atom_ptr;    /* [B + 1] */
-    const int32_t* group;       /* [n_atoms] */
-    const int32_t* group_count; /* [B][S + 1] */
+    const double* traj;         /* [n_total_frames][n_atoms][3]   (_order_sq_accumulate) */
+    const double* lattice;      /* [B][3][3], row-major   (_order_sq_vectors, _order_sq_accumulate) */
+    const int32_t* atom_ptr;    /* [B + 1]   (_order_sq_accumulate) */
+    const int32_t* group;       /* [n_atoms]   (_order_sq_accumulate) */
+    const int32_t* group_count; /* [B][S + 1]   (_order_sq_bin) */
     const int32_t* vec_ptr;     /* [B + 1], 0 first (not read by the counting call of _order_sq_vectors) */
     int32_t* n_vec;             /* [B]                     (_order_sq_vectors with hkl = NULL) */
-    int32_t* hkl;               /* [n_vectors][3], or NULL */
+    int32_t* hkl;               /* [n_vectors][3], or NULL (these three: _order_sq_vectors with hkl given writes every element;
+                                 * _order_sq_accumulate reads hkl, _order_sq_bin reads vbin) */
     double* qnorm;              /* [n_vectors] */
     int32_t* vbin;              /* [n_vectors] */
-    double* partial;            /* [n_chunks][P][n_vectors] */
+    double* partial;            /* [n_chunks][P][n_vectors] (_order_sq_accumulate writes every element, _order_sq_bin reads) */
     double* s_vec;              /* [P][n_vectors]          (_order_sq_bin) */
     double* s;                  /* [B][P][n_bins]          (_order_sq_bin) */
     int64_t* n_vectors_bin;     /* [B][n_bins]             (_order_sq_bin) */

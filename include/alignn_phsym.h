@@ -73,7 +73,7 @@ extern "C" {
  * n_dir is the one array a driver reads back: the directions of a representative (1 .. 3), 0 for a non-representative, -1 for
  * every atom of a structure that cannot be planned (more than ALIGNN_PHSYM_MAX_ATOMS atoms, no operations, an atom_map entry
  * outside the structure, a site group without the identity's place or beyond ALIGNN_PHSYM_MAX_SITE_OPS, offsets that do not fit
- * the arrays). */
+ * the arrays).  Every element of the nine outputs is written; of a structure that cannot be planned, n_dir alone. */
 typedef struct alignn_phsym_plan_args {
     const double* lattice;      /* [B][3][3] */
     const int32_t* supercell;   /* [B][3] */
@@ -104,7 +104,7 @@ size_t alignn_phsym_plan_args_size(void); /* a binding checks its own packing ag
  * cart_k = cart_k + (sg ? delta : -delta) d_k with d = dirs[atom_ptr[s] + atom][m]; frac_c = wrap01((x S0c + y S1c) + z S2c)
  * with S the inverse supercell.  The rows of job q start at row_off[q] of frac (and of cart when it is given). */
 typedef struct alignn_phsym_displace_args {
-    const double* positions;      /* [N][3] Cartesian */
+    const double* positions;      /* [N][3] Cartesian, N = atom_ptr[B] */
     const int32_t* atom_ptr;      /* [B + 1] */
     const double* lattice;        /* [B][3][3] */
     const double* inv_supercell;  /* [B][3][3] */
@@ -112,8 +112,8 @@ typedef struct alignn_phsym_displace_args {
     const double* dirs;           /* [N][3][3] (_phsym_plan) */
     const int32_t* jobs;          /* [n_jobs][4]: structure, atom, direction m, sign (0: -, 1: +) */
     const int64_t* row_off;       /* [n_jobs] */
-    double* frac;                 /* wrapped fractional rows */
-    double* cart;                 /* unwrapped Cartesian rows, or NULL */
+    double* frac;                 /* [rows][3] wrapped fractional rows, rows = the sum over the jobs of their supercell atoms n_sc; every row is written */
+    double* cart;                 /* [rows][3] unwrapped Cartesian rows, every one written; or NULL: only frac is written */
     double delta;                 /* finite, > 0 */
     int n_jobs;                   /* >= 0 */
     int n_structs;                /* B >= 1: the range of a job's structure */
@@ -126,13 +126,13 @@ size_t alignn_phsym_displace_args_size(void);
  * 0 none, 1 Frederiksen: the supercell's force sum off the displaced atom's row, 2 mean: sum / n_sc off every row; the kernels
  * share csrc/phonon_rows.h), written to the rows from out_rows[p] of g. */
 typedef struct alignn_phsym_rows_args {
-    const double* forces;       /* rows of the chunk's supercells */
+    const double* forces;       /* [force_rows][3], the rows of the chunk's supercells: twice the sum over the pairs of n_sc */
     const int32_t* pairs;       /* [n_pairs][2]: structure, displaced atom */
     const int64_t* pair_rows;   /* [n_pairs] */
     const int64_t* out_rows;    /* [n_pairs] */
     const int32_t* atom_ptr;    /* [B + 1] */
     const int32_t* supercell;   /* [B][3] */
-    double* g;                  /* [rows][3] */
+    double* g;                  /* [g_rows][3], g_rows = the sum over every direction of every representative of n_sc; a pair's n_sc rows are written */
     double delta;               /* finite, > 0 */
     int drift;                  /* 0, 1, 2 */
     int n_pairs;                /* >= 0 */
@@ -148,8 +148,10 @@ size_t alignn_phsym_rows_args_size(void);
 typedef struct alignn_phsym_fc_args {
     const int32_t* items;       /* [n_items][2] */
     const int64_t* g_rows;      /* [n_items]                      (_solve) */
-    const double* g;            /* [rows][3]                      (_solve) */
-    double* fc;                 /* the packed force constants */
+    const double* g;            /* [g_rows][3]                    (_solve) */
+    double* fc;                 /* [fc_total], fc_total = the sum over the structures of (N0 N1 N2) (3 n_b)^2: the packed force constants.
+                                 * _solve writes every block Phi(i; .) of its items, _distribute reads those and writes every block of its
+                                 * items: the caller need not zero it */
     const int64_t* fc_off;      /* [B] */
     const int32_t* atom_ptr;    /* [B + 1] */
     const int32_t* supercell;   /* [B][3] */
@@ -159,7 +161,7 @@ typedef struct alignn_phsym_fc_args {
     const int32_t* atom_map;    /* [map_ptr[B]] */
     const int32_t* shifts;      /* [map_ptr[B]][3] */
     const double* rot;          /* [G][3][3]  (_phsym_plan) */
-    const int32_t* rep;         /* [N]        (_distribute) */
+    const int32_t* rep;         /* [N]        (_distribute), N = atom_ptr[B] */
     const int32_t* n_site;      /* [N]        (_solve) */
     const int32_t* site_ops;    /* [N][48]    (_solve) */
     const int32_t* n_dir;       /* [N]        (_solve) */

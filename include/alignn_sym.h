@@ -81,14 +81,14 @@ typedef struct alignn_sym_find_args {
     const int32_t* seg_hi;    /* [N] */
     const int32_t* pivot_lo;  /* [B] */
     const int32_t* pivot_hi;  /* [B] */
-    double* frac;             /* [N][3]             (_sym_search writes, _sym_fill reads) */
-    int32_t* lattice_ops;     /* [B][48][9]         (_sym_search writes, _sym_fill reads) */
-    uint8_t* accepted;        /* [48 N]             (_sym_search writes, _sym_fill reads) */
-    int32_t* op_count;        /* [B][48]            (_sym_search writes, _sym_fill reads) */
-    int32_t* info;            /* [B][8]             (_sym_search writes, _sym_fill reads the status and the counts) */
+    double* frac;             /* [N][3]             (these four: scratch of the pair, the caller need not zero them.  _sym_search */
+    int32_t* lattice_ops;     /* [B][48][9]          writes what _sym_fill reads and nothing else: the frac rows of a structure */
+    uint8_t* accepted;        /* [48 N]              without a status bit, its first info[5] lattice operations, the flag of every */
+    int32_t* op_count;        /* [B][48]             candidate of those, and every count, zeroed first) */
+    int32_t* info;            /* [B][8]             (_sym_search writes every word, _sym_fill reads the status and the counts) */
     const int64_t* op_ptr;    /* [B + 1]            (_sym_fill) */
     const int64_t* map_ptr;   /* [B + 1]            (_sym_fill) */
-    int32_t* rotations;       /* [G][3][3]          (_sym_fill), G = op_ptr[B] */
+    int32_t* rotations;       /* [G][3][3]          (_sym_fill writes every element of these five), G = op_ptr[B] */
     double* translations;     /* [G][3]             (_sym_fill) */
     int32_t* atom_map;        /* [map_ptr[B]]       (_sym_fill) */
     int32_t* shifts;          /* [map_ptr[B]][3]    (_sym_fill) */
@@ -118,8 +118,8 @@ size_t alignn_sym_find_args_size(void); /* a binding checks its own packing agai
 typedef struct alignn_sym_apply_args {
     const double* lattice;      /* [B][3][3] */
     const double* in;           /* [N][3] forces or Cartesian positions; [B][3][3] stresses */
-    double* out;                /* as in */
-    const int32_t* atom_ptr;    /* [B + 1] */
+    double* out;                /* as in: every element is written */
+    const int32_t* atom_ptr;    /* [B + 1]         (_sym_forces, _sym_positions) */
     const int64_t* op_ptr;      /* [B + 1] */
     const int64_t* map_ptr;     /* [B + 1] */
     const int32_t* rotations;   /* [G][3][3] */

@@ -56,12 +56,12 @@ extern "C" {
  *     centres[k] = (k + 1/2) (r_max / n_bins)
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_traj_rdf_args {
-    const double* traj;         /* [n_total_frames][n_atoms][3] */
+    const double* traj;         /* [n_total_frames][n_atoms][3]   (_rdf_counts) */
     const double* lattice;      /* [B][3][3] (lattice_per_frame 0) or [n_total_frames][B][3][3] (1), row-major */
-    const int32_t* atom_ptr;    /* [B + 1], 0 first */
-    const int32_t* group;       /* [n_atoms] */
+    const int32_t* atom_ptr;    /* [B + 1], 0 first   (_rdf_counts) */
+    const int32_t* group;       /* [n_atoms]   (_rdf_counts) */
     const int32_t* group_count; /* [B][S + 1] */
-    int64_t* counts;            /* [B][P][n_bins] */
+    int64_t* counts;            /* [B][P][n_bins]   (_rdf_counts adds, _rdf_normalise reads) */
     double* g;                  /* [B][P][n_bins]   (_rdf_normalise) */
     double* coord;              /* [B][P][n_bins]   (_rdf_normalise) */
     double* volume;             /* [B] <V>          (_rdf_normalise) */
@@ -100,9 +100,9 @@ typedef struct alignn_traj_corr_args {
     const double* traj;         /* [n_total_frames][n_atoms][3]: positions (mode 0) or momenta (mode 1) */
     const double* masses;       /* [n_atoms], > 0 (_traj_com and mode 1) */
     const int32_t* atom_ptr;    /* [B + 1] */
-    const int32_t* group;       /* [n_atoms] */
-    const int32_t* group_count; /* [B][S + 1] */
-    double* com;                /* [n_frames][B][3], or NULL (mode 0: no centre of mass is removed) */
+    const int32_t* group;       /* [n_atoms]   (_traj_corr) */
+    const int32_t* group_count; /* [B][S + 1]   (_traj_corr) */
+    double* com;                /* [n_frames][B][3], or NULL (mode 0: no centre of mass is removed); _traj_com writes every element, _traj_corr reads */
     double* out;                /* [B][S + 1][max_lag + 1][3] (mode 0) or [B][S + 1][max_lag + 1] (mode 1) */
     int n_structs;              /* B >= 0 */
     int n_atoms;                /* atom_ptr[B] */
