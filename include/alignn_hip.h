@@ -964,7 +964,10 @@ int alignn_radius_emit(const float* lat, const float* cart, const int32_t* graph
  * the [B] / [B][3][3] (row-major) ones; the evaluation is that of the active batch.  A structure is recorded (forces_out,
  * energy_out, fmax_out, stress_out), then either retired (status[1+k] = 1: converged, 2: `steps` steps taken; -1: force rows
  * of another count than its atoms, nothing written) or stepped (status[1+k] = 0): |dr| over the structure clipped to maxstep.
- * Fixed-order reductions: a structure's step is bit-identical whatever else shares the launch.
+ * Fixed-order reductions: a structure's step is bit-identical whatever else shares the launch.  B is the number of structures
+ * of the batch (atom_ptr has B + 1 entries), N = atom_ptr[B].  Only a stepped structure's state is rewritten - its rows of
+ * positions, velocities, frac (xa), its state and istate (xc, cell_velocities, defgrad, lattice) - and nothing of a structure
+ * that is not in `active` is read or written.
  *
  * At fixed cell (xc == NULL; optimize_lattice=False) the rows are the atoms'.  With a cell-filter state (xc != NULL: every
  * field marked "filter" is then required, and ignored otherwise) the step is that of ASE's ExpCellFilter (ase/constraints.py,
@@ -984,7 +987,7 @@ int alignn_radius_emit(const float* lat, const float* cart, const int32_t* graph
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_fire_args {
     /* inputs of the step: the evaluation of the active batch */
-    const double* forces;      /* [.][3]: rows [force_ptr[k], force_ptr[k+1]) are active[k]'s */
+    const double* forces;      /* [force_ptr[n_active]][3]: rows [force_ptr[k], force_ptr[k+1]) are active[k]'s */
     const double* energy;      /* [n_active] */
     const double* stress;      /* filter: [n_active][3][3], eV/A^3, ASE's sign */
     const int32_t* force_ptr;  /* [n_active + 1] */
@@ -1004,7 +1007,7 @@ typedef struct alignn_fire_args {
     double* defgrad;         /* filter: [B][3][3] F of the evaluated cell */
     double* lattice;         /* filter: [B][3][3] the current cells C = C0 F^T */
     /* outputs */
-    double* forces_out;  /* [N][3] */
+    double* forces_out;  /* [N][3]; these five: the rows of the active structures whose force rows fit */
     double* energy_out;  /* [B] */
     double* fmax_out;    /* [B] max over the rows of |F_i| */
     double* stress_out;  /* filter: [B][3][3] symmetrised */
@@ -1051,7 +1054,7 @@ size_t alignn_fire_args_sizeof(void); /* a binding checks its own packing agains
 typedef struct alignn_md_args {
     /* inputs of the step: the evaluation at the current positions */
     const double* forces;  /* [n_rows][3] */
-    const double* energy;  /* [B] */
+    const double* energy;  /* [B] = [n_structures]; N below is atom_ptr[B] */
     const double* stress;  /* [B][3][3], eV/A^3, ASE's sign: required by 4 and by 6 with ptime > 0; 3, 6: NULL records no
                               pressure; 0-2, 5: ignored */
     int64_t n_rows;        /* must equal atom_ptr[n_structures], else status[0] = -1 and nothing is written */
@@ -1069,7 +1072,7 @@ typedef struct alignn_md_args {
     double* frac;        /* [N][3] for the next neighbour search */
     double* velocities;  /* [N][3] v between the halves: required by 1 and 3 */
     double* scratch;     /* [N][3] between the halves, 1: the velocity noise of the step, 3: the positions before the drift; required by both */
-    int32_t* status;     /* [1]; required */
+    int32_t* status;     /* [1]; required; zeroed by the caller: a launch writes it only where n_rows does not fit */
     /* outputs: frames [steps / interval + 1]; epot, ekin, temperature required, the others written unless NULL */
     double* epot;           /* [frames][B] = energy */
     double* ekin;           /* [frames][B] KE = 0.5 sum p^2 / m */
@@ -1079,9 +1082,10 @@ typedef struct alignn_md_args {
     double* traj_positions; /* [frames][N][3] */
     double* traj_momenta;   /* [frames][N][3] */
     double* traj_lattice;   /* 3, 4, 6: [frames][B][3][3] */
-    double* noise_out;      /* tests: 1: [N][18] per atom xi[3], eta[3], the 12 Philox words as doubles; 3: [N][36] per atom 4
-                               normals, 4 uniforms, 16 words, then the structure's 4 centre-of-mass normals and their 8 words
-                               (fixcm only) */
+    double* noise_out;      /* tests: 1: [N][18] per atom xi[3], eta[3], the 12 Philox words as doubles; 3: [N][36] (with and
+                               without fixcm) per atom 4 normals, 4 uniforms, 16 words, then the structure's 4 centre-of-mass
+                               normals and their 8 words (written with fixcm only: without it the last 12 of every 36 are left
+                               as they are); written by the launches that begin a step (t < steps); 0, 2, 4-6: ignored */
     /* scalars */
     int n_structures, t, interval, steps, ensemble, fixcm;
     double dt, friction, andersen_prob, taut, taup, kB; /* friction: 1; andersen_prob: 3; taut: 2, 4; taup: 4 */
@@ -1107,23 +1111,28 @@ int alignn_md_init_momenta(const int32_t* atom_ptr, int n_structures, const doub
  * atoms, m_s = 3 n_s, a supercell supercell[s] = (N0, N1, N2) of Ncell_s = N0 N1 N2 images (atom j = image n_s + b, image =
  * (m0 N1 + m1) N2 + m2), and its force constants C [Ncell_s][m_s][m_s] at fc_off[s] of the fc buffers.
  *
- * _displace: for job k < n_jobs, jobs[k] = (s, d), d = 6a + 2i + sign (0: -delta, 1: +delta) moves atom a of image 0 along
- * axis i.  Writes the supercell's n_s Ncell_s rows from row_off[k] of frac [.][3] (wrapped into [0, 1) with inv_supercell[s],
- * the inverse of the supercell lattice) and, unless NULL, of cart [.][3] (Cartesian, unwrapped: positions + image offsets of
- * the primitive lattice[s] + the displacement).
- * _fc_rows: pair k: pairs[k] = (s, x = 3a + i); the minus supercell's forces are rows [pair_rows[k], + n_s Ncell_s) of forces,
- * the plus supercell's the rows after.  Writes row x of every cell: (F- - F+) / (2 delta) after the drift correction (0 none,
- * 1 Frederiksen: the supercell's force sum off atom a's row, 2 mean: sum / (n_s Ncell_s) off every row).
+ * _displace: for job k < n_jobs, jobs [n_jobs][2] (int), jobs[k] = (s, d), d = 6a + 2i + sign (0: -delta, 1: +delta) moves atom
+ * a of image 0 along axis i; row_off [n_jobs].  Writes the supercell's n_s Ncell_s rows from row_off[k] of frac [rows][3]
+ * (wrapped into [0, 1) with inv_supercell[s], the inverse of the supercell lattice) and, unless NULL, of cart [rows][3]
+ * (Cartesian, unwrapped: positions + image offsets of the primitive lattice[s] + the displacement); rows = the largest
+ * row_off[k] + n_s Ncell_s.  positions [atom_ptr[B]][3], atom_ptr [B + 1], lattice and inv_supercell [B][3][3], supercell [B][3].
+ * _fc_rows: pair k: pairs [n_pairs][2], pairs[k] = (s, x = 3a + i); the minus supercell's forces are rows [pair_rows[k], + n_s
+ * Ncell_s) of forces, the plus supercell's the rows after (pair_rows [n_pairs]; forces [.][3] ends with the last pair's plus
+ * supercell).  Writes row x of every cell of fc (fc_off [B]; fc holds every structure's C): (F- - F+) / (2 delta) after the
+ * drift correction (0 none, 1 Frederiksen: the supercell's force sum off atom a's row, 2 mean: sum / (n_s Ncell_s) off every
+ * row).
  * _symmetrize (out of place), _acoustic (in place): one pass of ASE's Phonons.symmetrize / Phonons.acoustic (offset 0).
  * _mass_weight: dyn = fc * (m_x^-1/2 m_y^-1/2) (masses [atoms] in amu).  max_elems = max_s Ncell_s m_s^2, max_atoms = max_s n_s.
  * _eigh: one workgroup per (q < n_q, structure).  D(q) = sum_R dyn[R] exp(-2 pi i q.R) over the lattice points of rows
  * [cell_ptr[s], cell_ptr[s+1]) of lattice_points [.][3] (int) paired with the cells of dyn at dyn_off[s] (dims[s] = m_s <=
- * max_dim <= alignn_phonon_eigh_max_dim()), from its upper triangle; parallel cyclic Jacobi in LDS.  Writes per structure,
+ * max_dim <= alignn_phonon_eigh_max_dim()), from its upper triangle; parallel cyclic Jacobi in LDS.  dyn_off, dims, freq_off
+ * and mode_off are [n_structures], cell_ptr [n_structures + 1], qpoints [n_q][3].  Writes per structure,
  * ascending per q: freqs [n_q][m_s] at freq_off[s] (sign(l) scale sqrt(|l|)), eigvals (the same shape; NULL: not written),
  * modes [n_q][m_s][m_s] complex (interleaved re, im; column r = the eigenvector of eigenvalue r; NULL: not computed) at
  * mode_off[s] (in doubles).  status[0] = 1 when a (q, structure) hit the sweep cap; untouched otherwise.
- * _dos: per structure s < n_structures over freqs [freq_off[s], freq_off[s+1]): energies [s][npts] = linspace(min - 3 width,
- * max + 3 width, npts), weights [s][npts] = sum of unit Gaussians of `width` at those energies.
+ * _dos: per structure s < n_structures over freqs [freq_off[s], freq_off[s+1]) (freq_off [n_structures + 1]): energies
+ * [s][npts] = linspace(min - 3 width, max + 3 width, npts), weights [s][npts] = sum of unit Gaussians of `width` at those
+ * energies.
  * Fixed-order reductions: a structure's results are bit-identical whatever else shares the launches.
  * ------------------------------------------------------------------------------------------ */
 int alignn_phonon_displace(const double* positions, const int32_t* atom_ptr, const double* lattice, const double* inv_supercell,
@@ -1150,8 +1159,9 @@ int alignn_phonon_dos(const double* freqs, const int64_t* freq_off, int n_struct
 /* ------------------------------------------------------------------------------------------
  * Builders of the defect tasks' derived structures (csrc/defects.hip; alignn_amd/defects.py is the driver, tests/defects_ref.py
  * the numpy restatement).  positions [atoms][3] Cartesian, atom_ptr [n_structures + 1] and lattice [n_structures][3][3] (rows
- * a, b, c) are the packed parents.  Job k writes its cell to cells [k][3][3] and its rows [row_off[k], row_off[k+1]) of cart
- * [.][3] (Cartesian), frac [.][3] (wrapped into [0, 1) of its cell) and src [.] (the row of positions an atom came from).  One
+ * a, b, c) are the packed parents.  Job k writes its cell to cells [k][3][3] and its rows [row_off[k], row_off[k+1]) (row_off
+ * [n_jobs + 1]; the row arrays have row_off[n_jobs] rows) of cart [.][3] (Cartesian), frac [.][3] (wrapped into [0, 1) of its
+ * cell) and src [.] (the row of positions an atom came from).  One
  * workgroup per job, float64 without contraction, fixed-order sums: a job's bits do not depend on the launch it is in.  A job
  * whose fields or row range do not fit (structure index, removed atom, layers, |det| of the basis, row count) writes nothing.
  *
@@ -1224,7 +1234,9 @@ int alignn_elastic_fit(const double* strain, const double* stress, const int32_t
  * _zsl_match: pair p has the surface cells film_cells [p][2][2] and subs_cells [p][2][2] (rows v1, v2 in the plane, v1 x v2 > 0)
  * and the largest multiples nmax_film [p], nmax_subs [p] <= max_film, max_subs <= 256 of its two sides (n area <= max_area; the
  * host's).  hnf [.][3] = (n, a, b) lists the Hermite normal forms [[a, b], [0, n / a]] of every n <= 256 in the order (n, a, b),
- * prefix [n] (n = 1 .. 257) the first entry of multiple n.  Workspaces: film_tab [film_rows][4], film_int [film_rows][4],
+ * prefix [258]: prefix [n] (n = 1 .. 257) the first entry of multiple n ([0] is not read), so that hnf has prefix [257] rows.  film_off
+ * and subs_off are [n_pairs].  Workspaces (written and read by the launch; what they hold afterwards is not part of the
+ * result): film_tab [film_rows][4], film_int [film_rows][4],
  * subs_tab [subs_rows][6][4], subs_int [subs_rows][4] with pair p's prefix [nmax + 1] rows from film_off [p] / subs_off [p], and
  * best_score, best_tag [n_pairs][max_film].  Every super-lattice u = a v1 + b v2, w = (n / a) v2 is Lagrange-reduced keeping its
  * orientation ((u, w) <- (w, -u) while |u| > |w|, w <- w - rint(u.w / u.u) u, at most 64 rounds); a film basis is compared with
@@ -1238,8 +1250,9 @@ int alignn_elastic_fit(const double* strain, const double* stress, const int32_t
  *
  * _interface_build: the slabs are alignn_slab_build's with vacuum 0 (slab_cells [n_slabs][3][3], rows slab_off [k] ..
  * slab_off [k + 1] of slab_cart and slab_src).  jobs [n_pairs][10] = (film slab, substrate slab, film matrix [4], substrate
- * matrix [4]); pair p writes three structures in one cell, cells [3 p + (0, 1, 2)], rows out_off [3 p + k] .. out_off [3 p + k +
- * 1] of cart, frac (wrapped into [0, 1)), src (slab_src of the slab row) and part (0 substrate, 1 film): the substrate's j n_s
+ * matrix [4]); pair p writes three structures in one cell, cells [3 p + (0, 1, 2)] of cells [3 n_pairs][3][3], rows out_off [3 p +
+ * k] .. out_off [3 p + k + 1] (out_off [3 n_pairs + 1]; the row arrays have out_off [3 n_pairs] rows) of cart, frac (wrapped
+ * into [0, 1)), src (slab_src of the slab row) and part (0 substrate, 1 film): the substrate's j n_s
  * rows, the film's i n_f rows, then both (substrate first).  Cell: A0 = (|u_s|, 0, 0), A1 = (u_s.w_s, u_s x w_s, 0) / |u_s|, A2 =
  * (0, 0, Lz), u_s and w_s the substrate's super-cell vectors in the plane of its slab (x along the slab's row 0).  A slab atom
  * with fractions f, image (m0, m1), m0 < a, m1 < det / a, a = gcd(M00, M10), row (m0 det / a + m1) n + atom, sits at the

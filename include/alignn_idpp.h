@@ -58,9 +58,9 @@ typedef struct alignn_idpp_args {
     const double* final;       /* [sum n_b][3] image M_b - 1 */
     const double* positions;   /* [N][3] the bands' interior rows, a band's images one after the other, image 1 first */
     /* outputs */
-    double* forces;            /* [.][3] F_a of every interior row of the active bands */
-    double* energy;            /* [.] E_m of every interior image of the active bands */
-    double* row_energy;        /* [.] scratch, one entry per row of `forces`: e_a (the second launch reads it) */
+    double* forces;            /* [force_ptr[n_active]][3] F_a of every interior row of the active bands */
+    double* energy;            /* [energy_ptr[n_active]] E_m of every interior image of the active bands */
+    double* row_energy;        /* [force_ptr[n_active]] scratch, one entry per row of `forces`: e_a (the second launch reads it) */
     int32_t* status;           /* [n_active] 0, or -1 for a band whose row counts do not fit */
     /* scalars */
     int n_active;              /* 0 .. 65535 */

@@ -72,8 +72,10 @@ int alignn_neb_interpolate(const double* initial, const double* final, const int
  * ------------------------------------------------------------------------------------------ */
 typedef struct alignn_neb_args {
     /* the evaluation of the active bands' interior images, in evaluation order: band by band, image 1 first */
-    const double* forces;      /* [.][3] raw forces: rows [force_ptr[k], force_ptr[k+1]) are active[k]'s, (M - 2) n of them */
-    const double* energy;      /* [.] energies: entries [energy_ptr[k], energy_ptr[k+1]) are active[k]'s, M - 2 of them */
+    const double* forces;      /* [force_ptr[n_active]][3] raw forces: rows [force_ptr[k], force_ptr[k+1]) are active[k]'s,
+                                  (M - 2) n of them */
+    const double* energy;      /* [energy_ptr[n_active]] energies: entries [energy_ptr[k], energy_ptr[k+1]) are active[k]'s,
+                                  M - 2 of them */
     const int32_t* force_ptr;  /* [n_active + 1] */
     const int32_t* energy_ptr; /* [n_active + 1] */
     const int32_t* active;     /* [n_active] band indices */
@@ -90,10 +92,11 @@ typedef struct alignn_neb_args {
     const double* positions;   /* [N][3] the bands' interior rows: relax's position array */
     const uint8_t* fixed;      /* [N] non-zero: the row's raw force is zero (FixAtoms), or NULL */
     /* outputs */
-    double* forces_out;        /* [.][3] the projected forces, laid out as `forces`: alignn_fire_step takes them as its forces */
+    double* forces_out;        /* [force_ptr[n_active]][3] the projected forces, laid out as `forces` (alignn_fire_step takes them as its
+                                  forces): the rows of the active bands that fit are written */
     double* energies_out;      /* [sum M_b] every image's energy by global image index (written for the active bands) */
     int32_t* imax;             /* [n_active] */
-    double* emax;              /* [n_active] E[imax] */
+    double* emax;              /* [n_active] E[imax] (not written for a band that does not fit) */
     /* scalars */
     int n_active;              /* >= 0 */
     int max_images;            /* the largest M_b of the active bands: 3 .. ALIGNN_NEB_MAX_IMAGES (sizes the launch) */

@@ -124,7 +124,8 @@ size_t alignn_traj_corr_args_size(void);
  * structure and group), out [n_rows][n_freq] in fs; one thread per (row, frequency) sums over k in ascending order:
  *     out[j] = (2 dtau) sum_k (c_k w_k) (C(k) / C(0)) cos((2 pi (nu_j 1e-3)) (k dtau)),   nu_j = j (f_max_thz / (n_freq - 1))
  * c_0 = 1/2, else 1; window 1 (Hann): w_k = (1 + cos(pi k / K)) / 2 (K = max_lag; 1 when K = 0); window 0: w_k = 1.  dtau in fs,
- * nu in THz.  A row with C(0) = 0 gives zeros.  n_freq >= 2, f_max_thz > 0, dtau > 0.
+ * nu in THz.  A row with C(0) = 0 gives zeros.  n_freq >= 2, f_max_thz > 0, dtau > 0: anything else is refused with
+ * hipErrorInvalidValue before a launch, and out is left as it was.
  * ------------------------------------------------------------------------------------------ */
 int alignn_traj_vdos(const double* vacf, int n_rows, int max_lag, double dtau, int n_freq, double f_max_thz, int window,
                      double* out, void* stream);

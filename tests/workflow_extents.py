@@ -18,11 +18,16 @@ Payloads before a launch: ``in`` arrays are copies of the caller's tensors, ``ad
 arrays hold the guard pattern (a NaN with a payload; for integers ``gate_parity.INT_PATTERN``, which no count, index or flag can
 be), so that an element of an ``out`` array that still holds the pattern after the launch was never written.
 
+``Block`` also takes another table of the same form (``table=``): tests/step_extents.py holds the argument blocks of the step
+kernels and the flat prototypes, with a further role ``state`` (read and rewritten; allocated like an input).  A dtype that torch
+cannot fill (uint64) is held as the signed integer of the same width (``STORAGE``).
+
 Blind spots, those of the instrument: an access farther from an array than its guard (1024 elements or two rows) lands in
 another buffer or outside the registry, and a value that is fetched from beside an array but never used changes nothing."""
 
 import ast
 import ctypes as C
+import functools
 
 import torch
 
@@ -31,6 +36,7 @@ from tests import gate_parity as gp
 
 F64, I32, I64, U8 = torch.float64, torch.int32, torch.int64, torch.uint8
 ROLES = ("in", "out", "add", "scratch", "unused")
+STORAGE = {torch.uint64: torch.int64}  # what a buffer of a dtype torch cannot fill holds instead: the same width, signed
 TRAJ = "3 * n_total_frames * n_atoms"
 CELLS = "9 * B * (n_total_frames if lattice_per_frame else 1)"
 
@@ -199,17 +205,26 @@ def entry_points():
     return {e: s for s, t in TABLE.items() for e in t["entries"]}
 
 
-def header_of(struct):
-    return _abi.header(TABLE[struct]["header"])
+@functools.lru_cache(maxsize=None)
+def read_header(name):
+    """``_abi.header``; for alignn_hip.h, whose blocks come with ``S_sizeof`` queries that ``_lib.load`` checks, the same record"""
+    if name == "alignn_hip.h":
+        with open(_abi.HEADER) as f:
+            return _abi.Header(_abi.HEADER, _abi.STRUCTS, _abi.SIGNATURES, _abi.defines(f.read()))
+    return _abi.header(name)
+
+
+def header_of(struct, table=None):
+    return read_header((table or TABLE)[struct]["header"])
 
 
 def _names(expr):
     return {n.id for n in ast.walk(ast.parse(str(expr), mode="eval")) if isinstance(n, ast.Name)}
 
 
-def names_used(struct, expr):
+def names_used(struct, expr, table=None):
     """the names a count or row expression rests on, its struct's ``let`` abbreviations resolved"""
-    let, out, todo = TABLE[struct]["let"], set(), _names(expr)
+    let, out, todo = (table or TABLE)[struct]["let"], set(), _names(expr)
     while todo:
         n = todo.pop()
         if n in let:
@@ -219,16 +234,16 @@ def names_used(struct, expr):
     return out
 
 
-def count_of(struct, field, entry=None):
-    c = TABLE[struct]["fields"][field]["count"]
+def count_of(struct, field, entry=None, table=None):
+    c = (table or TABLE)[struct]["fields"][field]["count"]
     return c[entry] if isinstance(c, dict) else c
 
 
-def evaluate(struct, expr, values):
+def evaluate(struct, expr, values, table=None):
     """``expr`` with the scalars ``values`` (fields and derived names), the header's defines and the struct's abbreviations"""
-    env = dict(header_of(struct).defines)
+    env = dict(header_of(struct, table).defines)
     env.update(values)
-    for k, v in TABLE[struct]["let"].items():
+    for k, v in (table or TABLE)[struct]["let"].items():
         env[k] = eval(v, {"__builtins__": {}}, env)  # noqa: S307 (the table's own text)
     return int(eval(str(expr), {"__builtins__": {}}, env))  # noqa: S307
 
@@ -244,12 +259,15 @@ def pattern_left(t):
 class Block:
     """One argument block whose every non-NULL pointer lies in a guarded buffer of exactly the tabled extent.  ``set`` the scalars,
     ``alloc`` the arrays of an entry point (``inputs``: field -> the tensor to copy in; the other arrays by role), ``launch`` it,
-    ``unwritten`` lists the ``out`` arrays that still hold a pattern element.  The struct's field names name the buffers."""
+    ``unwritten`` lists the ``out`` arrays that still hold a pattern element.  The struct's field names name the buffers.
+    ``table``: another table of the same form (tests/step_extents.py), whose further role ``state`` - an array the launch reads and
+    rewrites - is allocated like an input: guarded, with the caller's tensor copied in."""
 
-    def __init__(self, guards, struct, device=gp.DEV, case=""):
+    def __init__(self, guards, struct, device=gp.DEV, case="", table=None):
         self.guards, self.struct, self.device, self.case = guards, struct, device, case
-        self.table = TABLE[struct]
-        self.args = header_of(struct).structs[struct]()
+        self.tables = table or TABLE
+        self.table = self.tables[struct]
+        self.args = header_of(struct, self.tables).structs[struct]()
         self.payload, self.derived = {}, {}
 
     def set(self, **scalars):
@@ -269,8 +287,8 @@ class Block:
 
     def extent(self, field, entry=None):
         spec = self.table["fields"][field]
-        n = evaluate(self.struct, count_of(self.struct, field, entry), self.values())
-        return n, max(1, evaluate(self.struct, spec["row"], self.values()))
+        n = evaluate(self.struct, count_of(self.struct, field, entry, self.tables), self.values(), self.tables)
+        return n, max(1, evaluate(self.struct, spec["row"], self.values(), self.tables))
 
     def role(self, field, entry):
         return self.table["fields"][field]["roles"][self.table["entries"].index(entry)]
@@ -282,7 +300,8 @@ class Block:
             if field in self.payload or field in null or self.role(field, entry) == "unused":
                 continue
             n, row = self.extent(field, entry)
-            dtype, pat = spec["dtype"], gp.INT_PATTERN.get(spec["dtype"])
+            dtype = STORAGE.get(spec["dtype"], spec["dtype"])
+            pat = gp.INT_PATTERN.get(dtype)
             if n == 0:
                 self.payload[field] = None
                 assert field not in inputs or inputs.pop(field).numel() == 0
@@ -296,7 +315,7 @@ class Block:
                 t = self.guards.guarded(shape, dtype, None, name, self.device, row, pat)
                 t.copy_(src.reshape(shape))
             else:
-                assert self.role(field, entry) != "in", f"{name}: an input of {entry} without a tensor"
+                assert self.role(field, entry) not in ("in", "state"), f"{name}: an input of {entry} without a tensor"
                 fill = 0 if "add" in spec["roles"] else None
                 t = self.guards.guarded(shape, dtype, fill, name, self.device, row, pat)
             self.payload[field] = t
