@@ -15,6 +15,7 @@ import torch
 from alignn_amd import conventional_cell, find_symmetry, primitive_cell, surface_energy, vacancy_formation
 from tests import cells_ref as ref
 from tests import pair_ref, sym_ref
+from tests.cells_ref import same_bits as _same_bits
 from tests.sim_gpu import DEV
 
 pytestmark = pytest.mark.gpu
@@ -41,15 +42,6 @@ def _want(fn, name):
         A, pos, z = TABLE[name][:3]
         _CACHE[key] = getattr(ref, fn.__name__)(A, pos, z, 1e-3)
     return _CACHE[key]
-
-
-FIELDS = ("positions", "source_atom", "transform_num")
-SCALARS = ("transform_den", "multiplicity", "centring", "crystal_system", "n_translations", "ns")
-
-
-def _same_bits(a, i, b, j):
-    return all(torch.equal(getattr(a, f)[i], getattr(b, f)[j]) for f in FIELDS) and torch.equal(a.lattices[i], b.lattices[j]) and \
-        all(getattr(a, f)[i] == getattr(b, f)[j] for f in SCALARS)
 
 
 @pytest.mark.parametrize("fn", [conventional_cell, primitive_cell])
