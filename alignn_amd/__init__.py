@@ -25,5 +25,7 @@ from .symmetry import (SymmetryResult, distinct_miller_indices, find_symmetry, s
 from .thermo import QHAResult, ThermalResult, qha, thermal_properties, thermal_sums  # noqa: F401
 from .trajectory import (A2_FS_TO_CM2_S, DiffusionResult, MSDResult, RDFResult, TrajectoryAnalysis, VACFResult,  # noqa: F401
                          VDOSResult, analyze_md, diffusion, green_kubo, msd, pair_row, rdf, vacf, vdos)
+from .vanhove import (FqtResult, VanHoveDistinctResult, VanHoveSelfResult, intermediate_scattering,  # noqa: F401
+                      van_hove_distinct, van_hove_self)
 
 __version__ = "0.1.0"

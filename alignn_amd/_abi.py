@@ -24,6 +24,8 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 WORKFLOW_HEADERS = ("alignn_thermo.h", "alignn_neb.h", "alignn_traj.h", "alignn_sym.h", "alignn_order.h", "alignn_phsym.h")
 # the headers added after those, in the same form and read and bound the same way (build.py compiles against them too)
 LATER_HEADERS = ("alignn_idpp.h", "alignn_cells.h", "alignn_local.h")
+# the headers of the trajectory analyses added after those, a tuple of their own (the tests of the two above walk them whole)
+ANALYSIS_HEADERS = ("alignn_vanhove.h",)
 
 # the ctypes class of a value of each type (None: there is no such value); behind a `*` every type is c_void_p
 _BASE = {"void": None, "char": C.c_char, "uint8_t": C.c_uint8, "uint64_t": C.c_uint64, "int": C.c_int, "int32_t": C.c_int32,

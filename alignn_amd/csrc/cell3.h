@@ -69,16 +69,24 @@ __device__ __forceinline__ double row_dot(const double* x, const double (&m)[9],
 }
 
 // the plain wrap of the row difference d in the cell C with inverse Ci: f = d Ci, f - rint(f) (half to even), then that row x C
+// (shift: the whole cells rint(f) that were taken off, for vanhove.hip, which has to know which image of an atom is the atom)
 __device__ __forceinline__ void wrap_difference(const double (&d)[3], const double (&C)[9], const double (&Ci)[9],
-                                                double (&d0)[3]) {
+                                                double (&d0)[3], double (&shift)[3]) {
     double f[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         f[c] = row_dot(d, Ci, c);
-        f[c] -= rint(f[c]);
+        shift[c] = rint(f[c]);
+        f[c] -= shift[c];
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) d0[c] = row_dot(f, C, c);
+}
+
+__device__ __forceinline__ void wrap_difference(const double (&d)[3], const double (&C)[9], const double (&Ci)[9],
+                                                double (&d0)[3]) {
+    double shift[3];
+    wrap_difference(d, C, Ci, d0, shift);
 }
 
 // component c of d0 moved to the periodic image (m0, m1, m2): d0[c] + ((m0 C[0][c] + m1 C[1][c]) + m2 C[2][c])

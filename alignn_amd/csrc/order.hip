@@ -20,6 +20,7 @@
 // and at any place of the batch.
 #include "../../include/alignn_order.h"
 #include "neighbor_list.h"
+#include "sq_modes.h"
 
 #pragma clang fp contract(off)
 
@@ -31,10 +32,6 @@ constexpr int NBR = ALIGNN_ORDER_MAX_NEIGHBORS;
 static_assert(NBR == NEIGHBOR_LIST_CAP, "the list of neighbor_list.h");
 constexpr int MAX_LS = ALIGNN_ORDER_MAX_LS, MAX_L = ALIGNN_ORDER_MAX_L;
 constexpr int MEAN_ROWS = 4;  // rows per lane in a chunk of 256 (corr_kernel's CORR_WAVES)
-constexpr int SQ_BLOCK = 256, SQ_ATOMS = 16;
-constexpr int sq_vectors_per_thread(int ns) { return ns <= 2 ? 8 : 4; }  // (what the registers hold beside NS sums per vector)
-constexpr int HKL = ALIGNN_ORDER_MAX_HKL;
-constexpr int SQ_SLOT1 = HKL + 1, SQ_SLOT2 = SQ_SLOT1 + 2 * HKL + 1, SQ_SLOTS = SQ_SLOT2 + 2 * HKL + 1;  // h0 >= 0 | h1 | h2
 constexpr int SQ_CHUNK = ALIGNN_ORDER_SQ_FRAME_CHUNK;
 constexpr int SMALL_BLOCK = 256;
 constexpr double PI = 3.14159265358979323846, TWO_PI = 2.0 * PI;
@@ -229,25 +226,6 @@ __global__ __launch_bounds__(ALIGNN_WAVE) void steinhardt_mean_kernel(const Angl
 
 // ---- the static structure factor ----
 
-// H_k = floor(q_max |C_k| / (2 pi)) and the inverse cell; false when an axis needs more than the range or the cell is singular
-__device__ __forceinline__ bool hkl_range(const double (&C)[9], double q_max, int (&H)[3], double (&Ci)[9]) {
-    const double det = det3_cof(C);
-    bool ok = fabs(det) > 0.0 && fabs(det) < 1e300;  // (a NaN fails)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double len = sqrt((C[3 * k] * C[3 * k] + C[3 * k + 1] * C[3 * k + 1]) + C[3 * k + 2] * C[3 * k + 2]);
-        const double h = floor((q_max * len) / TWO_PI);
-        if (!(h >= 0.0 && h <= (double)HKL)) {
-            ok = false;
-            H[k] = 0;
-        } else {
-            H[k] = (int)h;
-        }
-    }
-    inv3_cof(C, Ci);
-    return ok;
-}
-
 __global__ __launch_bounds__(ALIGNN_WAVE) void sq_vectors_kernel(const SqArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     double C[9], Ci[9];
@@ -305,9 +283,7 @@ __global__ __launch_bounds__(ALIGNN_WAVE) void sq_vectors_kernel(const SqArgs a)
 template <int NS>
 __global__ __launch_bounds__(SQ_BLOCK) void sq_accumulate_kernel(const SqArgs a) {
     constexpr int SQ_VPT = sq_vectors_per_thread(NS), SQ_SLAB = SQ_BLOCK * SQ_VPT;
-    __shared__ double2 tab[SQ_ATOMS][SQ_SLOTS];  // (cos, sin) of pi (2 (h f_k)): slots [0, 33) h0 | [33, 98) h1 | [98, 163) h2
-    __shared__ double fr[SQ_ATOMS][3];
-    __shared__ int grp[SQ_ATOMS];
+    __shared__ SqTile lds;
     const int slab = blockIdx.x, chunk = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
     const int beg = a.atom_ptr[b], n = a.atom_ptr[b + 1] - beg;
     const int off = a.vec_ptr[b], V = a.vec_ptr[b + 1] - off;
@@ -324,75 +300,13 @@ __global__ __launch_bounds__(SQ_BLOCK) void sq_accumulate_kernel(const SqArgs a)
 
     int i0[SQ_VPT], i1[SQ_VPT], i2[SQ_VPT];
     bool live[SQ_VPT];
-#pragma unroll
-    for (int j = 0; j < SQ_VPT; ++j) {
-        const int v = slab * SQ_SLAB + j * SQ_BLOCK + tid;
-        live[j] = v < V;
-        int h0 = 0, h1 = 0, h2 = 0;
-        if (live[j]) {
-            h0 = a.hkl[3 * ((int64_t)off + v)];
-            h1 = a.hkl[3 * ((int64_t)off + v) + 1];
-            h2 = a.hkl[3 * ((int64_t)off + v) + 2];
-            if (h0 < 0 || h0 > H[0] || h1 < -H[1] || h1 > H[1] || h2 < -H[2] || h2 > H[2]) {  // (not a vector of this cell)
-                live[j] = false;
-                h0 = h1 = h2 = 0;
-            }
-        }
-        i0[j] = h0;
-        i1[j] = SQ_SLOT1 + HKL + h1;
-        i2[j] = SQ_SLOT2 + HKL + h2;
-    }
+    sq_thread_vectors<SQ_VPT>(a.hkl + 3 * (int64_t)off, V, slab * SQ_SLAB, H, i0, i1, i2, live);
 
     const int f_end = min(a.n_frames, (chunk + 1) * SQ_CHUNK);
     for (int f = chunk * SQ_CHUNK; f < f_end; ++f) {
         const double* X = a.traj + 3 * ((int64_t)(a.frame0 + f * a.frame_step) * a.n_atoms + beg);
         double re[SQ_VPT][NS], im[SQ_VPT][NS];
-#pragma unroll
-        for (int j = 0; j < SQ_VPT; ++j)
-#pragma unroll
-            for (int g = 0; g < NS; ++g) re[j][g] = im[j][g] = 0.0;
-        for (int t0 = 0; t0 < n; t0 += SQ_ATOMS) {
-            const int na = min(SQ_ATOMS, n - t0);
-            __syncthreads();  // (the last tile's table has been read)
-            if (tid < SQ_ATOMS * 3) {
-                const int at = tid / 3, k = tid - 3 * at;
-                if (at < na) {
-                    const double x = row_dot(X + 3 * (t0 + at), Ci, k);
-                    fr[at][k] = x - floor(x);
-                    if (k == 0) grp[at] = a.group[beg + t0 + at];
-                }
-            }
-            __syncthreads();
-            for (int e = tid; e < SQ_ATOMS * 3 * (HKL + 1); e += SQ_BLOCK) {  // h >= 0; e_k(-h) is the conjugate
-                const int at = e / (3 * (HKL + 1)), rest = e - at * (3 * (HKL + 1));
-                const int k = rest / (HKL + 1), h = rest - k * (HKL + 1);
-                const int Hk = k == 0 ? H[0] : k == 1 ? H[1] : H[2];
-                if (at < na && h <= Hk) {
-                    const double fk = k == 0 ? fr[at][0] : k == 1 ? fr[at][1] : fr[at][2];
-                    double s, c;
-                    sincospi(2.0 * ((double)h * fk), &s, &c);
-                    const int zero = k == 0 ? 0 : k == 1 ? SQ_SLOT1 + HKL : SQ_SLOT2 + HKL;
-                    tab[at][zero + h] = make_double2(c, s);
-                    if (k > 0 && h > 0) tab[at][zero - h] = make_double2(c, -s);
-                }
-            }
-            __syncthreads();
-            for (int at = 0; at < na; ++at) {
-                const int g = grp[at];
-#pragma unroll
-                for (int j = 0; j < SQ_VPT; ++j) {
-                    const double2 e0 = tab[at][i0[j]], e1 = tab[at][i1[j]], e2 = tab[at][i2[j]];
-                    const double pr = e0.x * e1.x - e0.y * e1.y, pi = e0.x * e1.y + e0.y * e1.x;
-                    const double xr = pr * e2.x - pi * e2.y, xi = pr * e2.y + pi * e2.x;
-#pragma unroll
-                    for (int s = 0; s < NS; ++s) {
-                        const bool member = g == s + 1;
-                        re[j][s] = re[j][s] + (member ? xr : 0.0);
-                        im[j][s] = im[j][s] + (member ? xi : 0.0);
-                    }
-                }
-            }
-        }
+        sq_frame_modes<NS, SQ_VPT>(X, a.group + beg, n, Ci, H, i0, i1, i2, lds, re, im);  // (sq_modes.h)
         const bool first = f == chunk * SQ_CHUNK;
 #pragma unroll
         for (int j = 0; j < SQ_VPT; ++j) {

@@ -16,6 +16,7 @@
 // place of the batch.
 #include "../../include/alignn_traj.h"
 #include "neighbor_list.h"
+#include "group_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -23,7 +24,7 @@ namespace {
 
 constexpr int RDF_BLOCK = 256, RDF_TILE = 64, RDF_ROUNDS = RDF_TILE / (RDF_BLOCK / RDF_TILE);
 constexpr int RDF_HIST_CAP = 14336;  // 32-bit counts of the LDS histogram at the most (56 KiB beside the j tile)
-constexpr int CORR_BLOCK = 256, CORR_WAVES = CORR_BLOCK / ALIGNN_WAVE;
+constexpr int CORR_BLOCK = GROUP_ROWS_BLOCK;
 constexpr int MAX_GROUPS = ALIGNN_TRAJ_MAX_SPECIES + 1;
 constexpr int SMALL_BLOCK = 256, SMALL_MAX_BLOCKS = 4096;
 constexpr double PI = 3.14159265358979323846;
@@ -192,7 +193,6 @@ __global__ __launch_bounds__(CORR_BLOCK) void corr_kernel(const CorrArgs a) {
     if (n < 1 || beg < 0 || (int64_t)beg + n > a.n_atoms) return;  // (uniform)
     const int S = a.n_species, G = S + 1, B = a.n_structs;
     const int n_or = (a.n_frames - 1 - k) / a.origin_stride + 1;  // k <= max_lag <= n_frames - 1
-    const int lane = threadIdx.x & (ALIGNN_WAVE - 1), wave = threadIdx.x / ALIGNN_WAVE;
     if (threadIdx.x < MAX_GROUPS * NC) acc[threadIdx.x / NC][threadIdx.x % NC] = 0.0;
     const int64_t fstride = 3 * (int64_t)a.n_atoms;
 
@@ -229,21 +229,7 @@ __global__ __launch_bounds__(CORR_BLOCK) void corr_kernel(const CorrArgs a) {
         for (int c = 0; c < NC; ++c) part[threadIdx.x][c] = s[c];
         grp[threadIdx.x] = gi;
         __syncthreads();
-        // the rows of group g: a lane's rows lane, lane + 64, ... in order, then the butterfly; wave w owns the groups w, w + 4, ...
-        for (int g = wave; g <= S; g += CORR_WAVES) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                double v = 0.0;
-#pragma unroll
-                for (int q = 0; q < CORR_WAVES; ++q) {
-                    const int r = lane + ALIGNN_WAVE * q;
-                    const bool member = grp[r] >= 1 && (g == 0 || grp[r] == g);
-                    v = v + (member ? part[r][c] : 0.0);
-                }
-                v = wave_sum(v);
-                if (lane == 0) acc[g][c] = acc[g][c] + v;
-            }
-        }
+        group_rows_add<NC>(part, grp, acc, S);  // (group_rows.h: the fixed order of the rows of a group)
     }
     __syncthreads();
     if (threadIdx.x < G * NC) {

@@ -38,7 +38,7 @@ from . import _abi, _lib
 from ._trajectory_inputs import _cutoffs, _positive, _raise_status, bins, degrees, inputs
 from .trajectory import pair_row  # noqa: F401  (pair_row numbers the rows of the results)
 
-__all__ = ["adf", "steinhardt", "structure_factor", "ADFResult", "SteinhardtResult", "SQResult", "MAX_NEIGHBORS", "MAX_L",
+__all__ = ["adf", "steinhardt", "structure_factor", "reciprocal_vectors", "ReciprocalVectors", "ADFResult", "SteinhardtResult", "SQResult", "MAX_NEIGHBORS", "MAX_L",
            "MAX_HKL", "MAX_BINS", "MAX_IMAGE_RANGE"]
 
 H = _abi.header("alignn_order.h")
@@ -116,6 +116,55 @@ class SQResult:
     species: List[List[int]]
     n_frames: int
     q_max: float
+
+
+# --- the reciprocal vectors of fixed cells ---------------------------------------------------------------------------------------------
+@dataclass
+class ReciprocalVectors:
+    """The reciprocal-lattice vectors of B fixed cells inside ``q_max``, as ``alignn_order_sq_vectors`` lists them: ``hkl``
+    [V, 3] int32, ``qnorm`` [V] and ``vbin`` [V] int32 (the shell of ``n_bins`` over [0, q_max)) on the device, structure b's at
+    ``offsets[b] .. offsets[b + 1]`` (``vec_ptr`` [B + 1] int32: the same on the device); ``n_vectors`` = V, ``max_vectors`` the
+    most of one structure.  With V = 0 the three arrays hold one unused element.  ``status`` [1] int32: the word of the call."""
+
+    vec_ptr: torch.Tensor
+    hkl: torch.Tensor
+    qnorm: torch.Tensor
+    vbin: torch.Tensor
+    offsets: np.ndarray
+    n_vectors: int
+    max_vectors: int
+    status: torch.Tensor
+
+
+def reciprocal_vectors(who: str, sel, q_max: float, n_bins: int) -> ReciprocalVectors:
+    """The two calls of ``alignn_order_sq_vectors`` - count, read back, list - for the cells of ``sel`` (an ``Inputs`` of
+    alignn_amd/_trajectory_inputs.py whose ``groups`` have been set), under the caller's device guard: what ``structure_factor``
+    and ``vanhove.intermediate_scattering`` evaluate their sums on.  The half space h0 > 0, or h0 = 0 and h1 > 0, or h0 = h1 = 0
+    and h2 > 0, |h_k| <= floor(q_max |C_k| / 2 pi) <= 32, |q| < q_max, in lexicographic order; a ``ValueError`` beyond 32."""
+    B, dev = len(sel.ns), sel.traj.device
+    lib = _load()
+    words = torch.zeros(B + 1, dtype=torch.int32, device=dev)  # the vectors of every structure, then the status word: one copy back
+    args = SqArgs(n_vec=words.data_ptr(), q_max=q_max, n_bins=n_bins, **sel.fields(SqArgs, words[B:]))
+    _lib.check(lib.alignn_order_sq_vectors(C.byref(args), _lib.stream()), "order_sq_vectors")
+    host = words.cpu().numpy()
+    if int(host[B]) & STATUS_HKL:
+        raise ValueError(f"{who}: q_max = {q_max} needs reciprocal vectors beyond |h| = {MAX_HKL} along an axis of some cell "
+                         "(or a cell is singular): lower q_max or analyse a smaller cell")
+    n_vec = host[:B].astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(n_vec)])
+    V = int(offsets[-1])
+    if V >= 2 ** 31:
+        raise ValueError(f"{who}: {V} reciprocal vectors; a call takes fewer than 2^31")
+    vec_ptr = torch.tensor(offsets, dtype=torch.int32, device=dev)
+    hkl = torch.zeros(max(V, 1), 3, dtype=torch.int32, device=dev)
+    qnorm = torch.zeros(max(V, 1), dtype=torch.float64, device=dev)
+    vbin = torch.zeros(max(V, 1), dtype=torch.int32, device=dev)
+    if V > 0:
+        args.vec_ptr, args.hkl, args.qnorm, args.vbin = vec_ptr.data_ptr(), hkl.data_ptr(), qnorm.data_ptr(), vbin.data_ptr()
+        args.n_vectors, args.max_vectors = V, int(n_vec.max())
+        _lib.check(lib.alignn_order_sq_vectors(C.byref(args), _lib.stream()), "order_sq_vectors")
+    return ReciprocalVectors(vec_ptr=vec_ptr, hkl=hkl, qnorm=qnorm, vbin=vbin, offsets=offsets, n_vectors=V,
+                             max_vectors=int(n_vec.max()), status=words[B:])
 
 
 # --- the call of the angle functions  ----------------------------------------------------------------------------------------------
@@ -201,34 +250,20 @@ def structure_factor(traj: torch.Tensor, lattice: torch.Tensor, ns: Sequence[int
     sel = inputs(who, traj, lattice, ns, start, stop, step, per_frame=False, atom_limit=False)
     B, used, dev = len(sel.ns), sel.n_frames, sel.traj.device
     lib = _load()
-    i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
     with _lib.device_guard(sel.traj):
         S, lists = sel.groups(species)
         P = 1 + S * (S + 1) // 2
-        words = i32(B + 1)  # the vectors of every structure, then the status word: one copy back
-        args = SqArgs(n_vec=words.data_ptr(), q_max=q_max, n_bins=n_bins, **sel.fields(SqArgs, words[B:]))
-        _lib.check(lib.alignn_order_sq_vectors(C.byref(args), _lib.stream()), "order_sq_vectors")
-        host = words.cpu().numpy()
-        if int(host[B]) & STATUS_HKL:
-            raise ValueError(f"{who}: q_max = {q_max} needs reciprocal vectors beyond |h| = {MAX_HKL} along an axis of some cell "
-                             "(or a cell is singular): lower q_max or analyse a smaller cell")
-        n_vec = host[:B].astype(np.int64)
-        offsets = np.concatenate([[0], np.cumsum(n_vec)])
-        V = int(offsets[-1])
-        if V >= 2 ** 31:
-            raise ValueError(f"{who}: {V} reciprocal vectors; a call takes fewer than 2^31")
-        vec_ptr = torch.tensor(offsets, dtype=torch.int32, device=dev)
+        vec = reciprocal_vectors(who, sel, q_max, n_bins)
+        offsets, V, hkl = vec.offsets, vec.n_vectors, vec.hkl
         chunks = max(1, -(-used // SQ_FRAME_CHUNK))
-        hkl, qnorm, vbin = i32(max(V, 1), 3), f64(max(V, 1)), i32(max(V, 1))
         partial, s_vec = f64(chunks, P, max(V, 1)), f64(P, max(V, 1))
         s, n_vectors, centres = f64(B, P, n_bins), torch.zeros(B, n_bins, dtype=torch.int64, device=dev), f64(n_bins)
-        args.vec_ptr, args.hkl, args.qnorm, args.vbin = vec_ptr.data_ptr(), hkl.data_ptr(), qnorm.data_ptr(), vbin.data_ptr()
-        args.partial, args.s_vec, args.s = partial.data_ptr(), s_vec.data_ptr(), s.data_ptr()
-        args.n_vectors_bin, args.centres = n_vectors.data_ptr(), centres.data_ptr()
-        args.n_vectors, args.max_vectors = V, int(n_vec.max())
+        args = SqArgs(vec_ptr=vec.vec_ptr.data_ptr(), hkl=hkl.data_ptr(), qnorm=vec.qnorm.data_ptr(), vbin=vec.vbin.data_ptr(),
+                      partial=partial.data_ptr(), s_vec=s_vec.data_ptr(), s=s.data_ptr(), n_vectors_bin=n_vectors.data_ptr(),
+                      centres=centres.data_ptr(), q_max=q_max, n_bins=n_bins, n_vectors=V, max_vectors=vec.max_vectors,
+                      **sel.fields(SqArgs, vec.status))
         if V > 0:
-            _lib.check(lib.alignn_order_sq_vectors(C.byref(args), _lib.stream()), "order_sq_vectors")
             _lib.check(lib.alignn_order_sq_accumulate(C.byref(args), _lib.stream()), "order_sq_accumulate")
         _lib.check(lib.alignn_order_sq_bin(C.byref(args), _lib.stream()), "order_sq_bin")
     spans = [(int(offsets[b]), int(offsets[b + 1])) for b in range(B)]
