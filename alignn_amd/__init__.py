@@ -27,5 +27,6 @@ from .trajectory import (A2_FS_TO_CM2_S, DiffusionResult, MSDResult, RDFResult, 
                          VDOSResult, analyze_md, diffusion, green_kubo, msd, pair_row, rdf, vacf, vdos)
 from .vanhove import (FqtResult, VanHoveDistinctResult, VanHoveSelfResult, intermediate_scattering,  # noqa: F401
                       van_hove_distinct, van_hove_self)
+from .voronoi import VoronoiResult, voronoi, voronoi_census  # noqa: F401
 
 __version__ = "0.1.0"

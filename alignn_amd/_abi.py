@@ -26,6 +26,8 @@ WORKFLOW_HEADERS = ("alignn_thermo.h", "alignn_neb.h", "alignn_traj.h", "alignn_
 LATER_HEADERS = ("alignn_idpp.h", "alignn_cells.h", "alignn_local.h")
 # the headers of the trajectory analyses added after those, a tuple of their own (the tests of the two above walk them whole)
 ANALYSIS_HEADERS = ("alignn_vanhove.h",)
+# the headers of the per-atom structure analyses added after those, again a tuple of their own (the tests pin the three above)
+STRUCTURE_HEADERS = ("alignn_voronoi.h",)
 
 # the ctypes class of a value of each type (None: there is no such value); behind a `*` every type is c_void_p
 _BASE = {"void": None, "char": C.c_char, "uint8_t": C.c_uint8, "uint64_t": C.c_uint64, "int": C.c_int, "int32_t": C.c_int32,

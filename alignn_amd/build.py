@@ -14,13 +14,13 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-from ._abi import ANALYSIS_HEADERS, LATER_HEADERS, WORKFLOW_HEADERS
+from ._abi import ANALYSIS_HEADERS, LATER_HEADERS, STRUCTURE_HEADERS, WORKFLOW_HEADERS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libalignn_hip.so")
-SOURCES = ["norm.hip", "conv.hip", "gemm_f32.hip", "gemm_x6.hip", "embed.hip", "dual.hip", "knn.hip", "composite.hip", "model.hip", "stage.hip", "radius.hip", "angle.hip", "ff.hip", "convln.hip", "gemm_dw.hip", "relax.hip", "dynamics.hip", "phonon.hip", "defects.hip", "eos.hip", "elastic.hip", "interface.hip", "thermo.hip", "neb.hip", "trajectory.hip", "symmetry.hip", "order.hip", "phonon_sym.hip", "idpp.hip", "cells.hip", "local_order.hip", "vanhove.hip"]
+SOURCES = ["norm.hip", "conv.hip", "gemm_f32.hip", "gemm_x6.hip", "embed.hip", "dual.hip", "knn.hip", "composite.hip", "model.hip", "stage.hip", "radius.hip", "angle.hip", "ff.hip", "convln.hip", "gemm_dw.hip", "relax.hip", "dynamics.hip", "phonon.hip", "defects.hip", "eos.hip", "elastic.hip", "interface.hip", "thermo.hip", "neb.hip", "trajectory.hip", "symmetry.hip", "order.hip", "phonon_sym.hip", "idpp.hip", "cells.hip", "local_order.hip", "vanhove.hip", "voronoi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 DEVICE_FLAGS: list = []
 # Per-file additions: no SLP vectorisation where hipcc 7.2 would otherwise emit the packed-fp32 form that MI355X gets wrong:
@@ -73,7 +73,7 @@ def faulting_packed_forms(lib: str = None) -> list:
 def _headers():
     include = os.path.join(os.path.dirname(HERE), "include")
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
-        os.path.join(include, f) for f in ("alignn_hip.h",) + WORKFLOW_HEADERS + LATER_HEADERS + ANALYSIS_HEADERS]
+        os.path.join(include, f) for f in ("alignn_hip.h",) + WORKFLOW_HEADERS + LATER_HEADERS + ANALYSIS_HEADERS + STRUCTURE_HEADERS]
 
 
 def _stale(target, deps) -> bool:

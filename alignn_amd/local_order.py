@@ -21,8 +21,9 @@ floating-point atomics, every sum in a fixed order over the atom's own list: a s
 batch and at any place of it.  Read back from the device: the status word of each call.  tests/local_ref.py restates the rules
 in numpy; the entry points and every formula are in include/alignn_local.h, read here with the reader of alignn_amd/_abi.py.
 
-Not here: polyhedral template matching, the diamond signatures of CNA, cutoffs per species pair, Voronoi or solid-angle
-neighbours.
+Not here: polyhedral template matching, the diamond signatures of CNA, cutoffs per species pair, solid-angle neighbours.  The
+Voronoi tessellation - atomic volumes, neighbours without a cutoff, the Voronoi index - is ``alignn_amd.voronoi``, on the same
+neighbour list; its neighbours are not fed into ``cna`` or ``bond_order``.
 """
 
 from __future__ import annotations
