@@ -16,14 +16,11 @@ from alignn_amd import find_symmetry, symmetrize_forces, symmetrize_positions, s
 from tests import pair_ref
 from tests import sym_ref as ref
 from tests.sim_gpu import DEV, _t
+from tests.sym_ref import same_as_restated as _same_as_restated, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-MARGIN = 0.05
-# translations modulo 1: the rounding of a three-term integer-weighted sum with |W_ij| <= 17 stays below 60 x 2^-53 = 7e-15; 1e-12
-# leaves two orders above that and sits nine orders below the smallest symprec searched
-T_ATOL = 1e-12
 _CACHE = {}
 
 
@@ -65,25 +62,6 @@ def _batch():
     if "batch" not in _CACHE:
         _CACHE["batch"] = _find(list(_structures()))
     return _CACHE["batch"]
-
-
-def _same_as_restated(res, b, want, what):
-    assert want["margin"] >= MARGIN, (what, want["margin"])  # the precondition: no decision near symprec
-    assert res.n_ops[b] == want["n_ops"] and res.n_translations[b] == want["n_translations"], what
-    assert res.point_group_order[b] == want["point_group_order"] and res.crystal_system[b] == want["crystal_system"], what
-    for got, exp in ((res.rotations[b], want["rotations"]), (res.atom_map[b], want["atom_map"]), (res.shifts[b], want["shifts"]),
-                     (res.orbits[b], want["orbits"])):
-        assert got.dtype == torch.int32 and np.array_equal(got.cpu().numpy(), exp), what
-    dt = res.translations[b].cpu().numpy() - want["translations"]
-    dt = np.abs(dt - np.rint(dt))
-    t = res.translations[b].cpu().numpy()
-    assert ((t >= 0.0) & (t < 1.0)).all() and (dt.max() if dt.size else 0.0) <= T_ATOL, (what, dt.max())
-    return float(dt.max()) if dt.size else 0.0
-
-
-def _same_bits(a, i, b, j):
-    return all(torch.equal(getattr(a, f)[i], getattr(b, f)[j]) for f in ("rotations", "translations", "atom_map", "shifts", "orbits")) and \
-        all(getattr(a, f)[i] == getattr(b, f)[j] for f in ("n_ops", "n_translations", "point_group_order", "crystal_system"))
 
 
 # --- (a) the search --------------------------------------------------------------------------------------------------------------
